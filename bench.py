@@ -2,7 +2,7 @@
 """bench.py -- MPix/s of the L3C encode hot path (net forward + fused logistic-mixture CDF head + HIP range coder) on
 synthetic 768x512 RGB batches, BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config headline|dataset|large]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config headline|dataset|large|files] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -19,7 +19,11 @@ pixels / max-over-ranks time.
 `python bench.py --gpus N` without a launcher (no RANK in the environment) re-executes itself under torch.distributed.run with N
 ranks, one per visible GPU (and fails loudly when fewer than N are visible): the driver's plain command works unattended.
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries (headline config)
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the last timed step
+computed (headline: the `.l3c` files of the batch -- their sizes, image 0's file whole and a seeded sample of every file's bytes) as
+DIR/<name>.npy.  The inputs are seeded: the same arguments give the same inputs in every run.
+
+Prints ONE JSON line (rank 0).  Besides the contract fields it carries, with `--full` (headline config)
   roofline      dominant kernel = conv_wino4_kernel (Winograd F(4x4,3x3) on v_mfma_f32_16x16x4_f32): `achieved` = the FLOPs the
                 matrix pipe EXECUTES (36/144 of the direct convolution's) summed over its launches in the timed region / their
                 summed HIP-event durations; `peak` = 157.3 TFLOP/s dense fp32 MFMA at 2.4 GHz; the direct-convolution
@@ -81,6 +85,11 @@ def parse_args(argv=None):
     ap.add_argument('--no-kernel-events', action='store_true', help='skip the per-launch HIP events of the roofline leg')
     ap.add_argument('--stub-step', action='store_true',
                     help='tests only: no GPU, gloo, a sleep instead of the hot path -- exercises the launch / barrier / max-over-ranks / JSON path')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the secondary legs (headline: roofline HIP events, decode, latency, CPU baseline, parity, worst_case_coder '
+                         'and configs; dataset: the set decode; files: the round trip).  Off: set-up, warm-up, the timed steps, the result line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)')
     a = ap.parse_args(argv)
     if a.gpus is None:      # under torch.distributed.run without --gpus: the launcher's world size is the truth
         a.gpus = int(os.environ.get('WORLD_SIZE', '1')) if 'RANK' in os.environ else 1
@@ -233,6 +242,35 @@ def timed(ranks, step, steps, warmup, before_timed=None):
         res = step()
     ranks.barrier()
     return ranks.max_over_ranks(time.perf_counter() - t0), res
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(args, ranks, arrays):
+    """--dump-outputs DIR: every array as DIR/<name>.npy (float64 where the values are sizes or figures, float32 for bytes); with several
+    ranks every rank writes its own, prefixed rank<r>_."""
+    import numpy as np
+    if not args.dump_outputs:
+        return
+    out = {(name if ranks.world == 1 else 'rank{}_{}'.format(ranks.rank, name)): a for name, a in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values()) and total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
+
+
+def file_arrays(files, sample_bytes=48 << 20):
+    """`.l3c` byte strings -> their sizes, the first file whole and a seeded sample of every file's bytes (the same 0..1 positions
+    of every file, scaled to its length), all within `sample_bytes` of float32."""
+    import numpy as np
+    sizes = np.array([len(f) for f in files], dtype=np.float64)
+    first = np.frombuffer(files[0], dtype=np.uint8).astype(np.float32)
+    k = max(1, min(16384, (sample_bytes - first.nbytes) // 4 // max(1, len(files))))
+    u = np.random.RandomState(0).random_sample(k)
+    sample = np.stack([np.frombuffer(f, dtype=np.uint8)[(u * len(f)).astype(np.int64)] for f in files]).astype(np.float32)
+    return {'file_sizes': sizes, 'file0_bytes': first, 'file_bytes_sample': sample}
 
 
 def contract(args, ranks, value, elapsed, **extra):
@@ -556,9 +594,13 @@ def run_headline(args, ranks):
     cfg, sd, bp, bc, synthetic = build_path('cr', args.coder_cus, args.checkpoint == 'calibrated')
     from l3c_pytorch_amd import _lib, ops
     B = args.batch
-    # synthetic images (seed = global image index), resident in HBM before the timed region
+    # synthetic images (seed = global image index), resident in HBM before the timed region; each image is made from its own seed,
+    # so making them on worker threads gives the same batch
+    import concurrent.futures
     with single_thread():
-        imgs = torch.stack([synthetic.make_image(H, W, ranks.rank * B + i, 'natural') for i in range(B)]).to(ranks.device)
+        with concurrent.futures.ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+            imgs = list(pool.map(lambda i: synthetic.make_image(H, W, ranks.rank * B + i, 'natural'), range(B)))
+        imgs = torch.stack(imgs).to(ranks.device)
     imgs_f = imgs.float().contiguous()
     torch.cuda.synchronize()
     compute_stream = bc.compute_stream if bc.compute_stream is not None else torch.cuda.current_stream()
@@ -568,7 +610,7 @@ def run_headline(args, ranks):
             out = bp.net(imgs_f)
             return bc.encode_batch(imgs_f, out=out)
 
-    want_events = ranks.rank == 0 and not args.no_kernel_events
+    want_events = args.full and ranks.rank == 0 and not args.no_kernel_events
 
     def arm():
         ops.PROFILE = [] if want_events else None
@@ -579,13 +621,15 @@ def run_headline(args, ranks):
 
     with torch.cuda.stream(compute_stream):
         sizes = enc.file_sizes().cpu().numpy()
+        if args.dump_outputs:
+            dump_outputs(args, ranks, file_arrays(enc.to_bytes()))
     bits, subpx = ranks.sum_over_ranks([float(sizes.sum()) * 8, B * 3 * H * W])
     result = None
     if ranks.rank == 0:
         roofline = roofline_leg(records, args, elapsed) if records else None
-        decode = decode_leg(bc, enc, imgs, compute_stream) if ranks.world == 1 and not args.no_decode else None
+        decode = decode_leg(bc, enc, imgs, compute_stream) if args.full and ranks.world == 1 and not args.no_decode else None
         cpu, oracle_file = None, None
-        if ranks.world == 1 and not args.no_cpu_baseline:
+        if args.full and ranks.world == 1 and not args.no_cpu_baseline:
             from oracle import cpu_baseline
             cpu, oracle_file = cpu_baseline.run(sd, imgs[0].cpu())
             elsewhere = (load_json(os.path.join('profiles', 'r04_cpu_reference_build_container_{}.json'.format(args.checkpoint))) or
@@ -593,16 +637,16 @@ def run_headline(args, ranks):
             if elsewhere:     # the UNMODIFIED reference timed where /root/reference exists (python bench.py --cpu-baseline-only)
                 cpu['reference_measured_elsewhere'] = elsewhere
         parity = None
-        if ranks.world == 1 and not args.no_parity:
+        if args.full and ranks.world == 1 and not args.no_parity:
             with torch.cuda.stream(compute_stream):
                 parity = parity_leg(bp, bc, imgs_f, bc.encode_batch(imgs_f[0:1]), sd, oracle_file)
         latency = None
-        if ranks.world == 1 and not args.no_decode:
+        if args.full and ranks.world == 1 and not args.no_decode:
             latency = latency_leg(bp, bc, imgs_f[0:1].contiguous(), compute_stream)
         name, ncu, arch = _lib.device_info()
         peak_gb = round(torch.cuda.max_memory_allocated() / 1e9, 1)
         extra = {}
-        if ranks.world == 1 and not args.no_extra_legs:
+        if args.full and ranks.world == 1 and not args.no_extra_legs:
             del enc
             torch.cuda.empty_cache()
             extra = extra_legs(args)
@@ -621,7 +665,7 @@ def run_headline(args, ranks):
 def _sub_bench(extra_args, timeout=600):
     """Run this script once more in a process of its own (own HIP start-up environment, own memory) and return its JSON line."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--no-extra-legs'] + extra_args
+    cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--full', '--no-extra-legs'] + extra_args
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     try:
         p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
@@ -686,24 +730,34 @@ def run_dataset(args, ranks):
     bits = sum(len(files[i]) for i in mine) * 8
     tot_px, tot_bits = ranks.sum_over_ranks([pixels, bits])
     value = tot_px * args.steps / 1e6 / elapsed
-    # SET DECODE (round 6; outside the encode's timed region): EVERY file of the rank decoded back -- `.l3c` bytes on the host -> uint8 pixels
-    # on the host -- and compared with its input, like the reference's folder evaluation does (multiscale_tester.py:353-381, assert_equal :373);
-    # files of equal padded shape share a batch, the batches stream through Bitcoding.decode_many
-    dec_seconds, lanes = [], int(os.environ.get('L3C_DECODE_LANES', '0')) or None
-    ragged = {'0': False, '1': True}.get(os.environ.get('L3C_DECODE_RAGGED'))      # (development: A/B of the grouped RGB decode; None = the product's choice)
-    if os.environ.get('L3C_RAGGED_GROUP'):      # (development: images per ragged group)
-        bc.RAGGED_GROUP = int(os.environ['L3C_RAGGED_GROUP'])
-    if os.environ.get('L3C_RAGGED_MPIX'):       # (development: pixel budget of a ragged group)
-        bc.RAGGED_GROUP_PIXELS = int(os.environ['L3C_RAGGED_MPIX']) << 20
-    for rep in range(3):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        back = dataset_codec.decode_set(bc, files, mine, max_batch=args.max_batch, lanes=lanes, ragged=ragged)
-        torch.cuda.synchronize()
-        dec_seconds.append(time.perf_counter() - t0)
-    wrong = [i for i in mine if not torch.equal(back[i], imgs[i])]
-    assert not wrong, 'set decode is not lossless for images {}'.format(wrong[:8])
-    dec_best = min(dec_seconds[1:])
+    if args.dump_outputs:
+        import numpy as np
+        dump_outputs(args, ranks, dict(file_arrays([files[i] for i in mine]), image_ids=np.array(mine, dtype=np.float64)))
+    decode = None
+    if args.full:
+        # SET DECODE (round 6; outside the encode's timed region): EVERY file of the rank decoded back -- `.l3c` bytes on the host -> uint8 pixels
+        # on the host -- and compared with its input, like the reference's folder evaluation does (multiscale_tester.py:353-381, assert_equal :373);
+        # files of equal padded shape share a batch, the batches stream through Bitcoding.decode_many
+        dec_seconds, lanes = [], int(os.environ.get('L3C_DECODE_LANES', '0')) or None
+        ragged = {'0': False, '1': True}.get(os.environ.get('L3C_DECODE_RAGGED'))      # (development: A/B of the grouped RGB decode; None = the product's choice)
+        if os.environ.get('L3C_RAGGED_GROUP'):      # (development: images per ragged group)
+            bc.RAGGED_GROUP = int(os.environ['L3C_RAGGED_GROUP'])
+        if os.environ.get('L3C_RAGGED_MPIX'):       # (development: pixel budget of a ragged group)
+            bc.RAGGED_GROUP_PIXELS = int(os.environ['L3C_RAGGED_MPIX']) << 20
+        for rep in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            back = dataset_codec.decode_set(bc, files, mine, max_batch=args.max_batch, lanes=lanes, ragged=ragged)
+            torch.cuda.synchronize()
+            dec_seconds.append(time.perf_counter() - t0)
+        wrong = [i for i in mine if not torch.equal(back[i], imgs[i])]
+        assert not wrong, 'set decode is not lossless for images {}'.format(wrong[:8])
+        dec_best = min(dec_seconds[1:])
+        decode = {'value': round(pixels / 1e6 / dec_best, 2), 'unit': 'MPix/s', 'images_decoded_on_rank0': len(mine), 'lossless': 'every image compared with its input',
+                  'seconds_rank0': [round(t, 4) for t in dec_seconds], 'timing': 'best of the two passes after the first one of the process',
+                  'lanes': lanes or bc.N_DECODE_LANES, 'ragged_rgb': True if ragged is None else ragged,
+                  'note': 'host .l3c bytes -> host uint8 pixels of EVERY file the encode leg wrote (dataset_codec.decode_set): framing parsed on the host, '
+                          'files uploaded as they are, batches of equal padded shape streamed through Bitcoding.decode_many'}
     result = None
     if ranks.rank == 0:
         name, ncu, arch = _lib.device_info()
@@ -717,16 +771,12 @@ def run_dataset(args, ranks):
                     'sharding': 'largest-first greedy on pixel counts (helpers/sharding.shard_balanced), replicas only',
                     'pixels_on_rank0_over_mean': round(pixels * ranks.world / tot_px, 4)},
             bpsp=round(tot_bits / (3 * tot_px), 4), megapixels=round(tot_px / 1e6, 1),
-            decode={'value': round(pixels / 1e6 / dec_best, 2), 'unit': 'MPix/s', 'images_decoded_on_rank0': len(mine), 'lossless': 'every image compared with its input',
-                    'seconds_rank0': [round(t, 4) for t in dec_seconds], 'timing': 'best of the two passes after the first one of the process',
-                    'lanes': lanes or bc.N_DECODE_LANES, 'ragged_rgb': True if ragged is None else ragged,
-                    'note': 'host .l3c bytes -> host uint8 pixels of EVERY file the encode leg wrote (dataset_codec.decode_set): framing parsed on the host, '
-                            'files uploaded as they are, batches of equal padded shape streamed through Bitcoding.decode_many'},
             per_step={'seconds_rank0': [round(t, 4) for t in step_seconds],
                       'mpix_per_s_rank0_best': round(pixels / 1e6 / min(step_seconds), 2),
                       'mpix_per_s_rank0_median': round(pixels / 1e6 / sorted(step_seconds)[len(step_seconds) // 2], 2),
                       'mpix_per_s_rank0_worst': round(pixels / 1e6 / max(step_seconds), 2)},
-            device='{} ({}, {} CUs)'.format(name, arch, ncu), peak_hbm_gb=round(torch.cuda.max_memory_allocated() / 1e9, 1))
+            device='{} ({}, {} CUs)'.format(name, arch, ncu), peak_hbm_gb=round(torch.cuda.max_memory_allocated() / 1e9, 1),
+            **({'decode': decode} if args.full else {}))
     return result
 
 
@@ -739,7 +789,7 @@ def run_files(args, ranks):
     dataloaders/images_loader.py:91-129), measured file to file: N synthetic images are written as PNG files to a temporary
     directory (outside the timed region), then the tester reads and decodes them on worker threads, codes them in windows (encode_set),
     writes the `.l3c` files, reads them back, decodes them (decode_set) and compares every image with its input.  Two figures: encode
-    (PNG files -> `.l3c` files on disk) and the full round trip; the time report names the stages."""
+    (PNG files -> `.l3c` files on disk) and, with --full, the full round trip; the time report names the stages."""
     import concurrent.futures
     import contextlib
     import io
@@ -785,7 +835,7 @@ def run_files(args, ranks):
         testset = Testset(img_dir)
         pixels = sum(sizes[i][0] * sizes[i][1] for i in mine)
         results = {}
-        for name, round_trip in (('encode', False), ('round_trip', True)):
+        for name, round_trip in (('encode', False), ('round_trip', True))[:2 if args.full else 1]:
             tester = make_tester(round_trip)
             secs = []
 
@@ -808,6 +858,15 @@ def run_files(args, ranks):
                              'bpsp': round(res.mean(), 4), 'l3c_bytes_rank0': l3c_bytes,
                              'stage_seconds_last_pass': stages, 'slowest_stage': slowest}
             elapsed_rt = elapsed
+            if name == 'encode' and args.dump_outputs:      # the files of the last encode pass, by name
+                import numpy as np
+                written = sorted(os.listdir(out_dir))
+                blobs = []
+                for f in written:
+                    with open(os.path.join(out_dir, f), 'rb') as fh:
+                        blobs.append(fh.read())
+                bpsp = np.array([res.per_img[k] for k in sorted(res.per_img)], dtype=np.float64)     # per image, by file name
+                dump_outputs(args, ranks, dict(file_arrays(blobs), bpsp=bpsp))
         tot_px, = ranks.sum_over_ranks([pixels])
         result = None
         if ranks.rank == 0:
@@ -820,8 +879,8 @@ def run_files(args, ranks):
                                         args.images, round(png_bytes / 1e6, 1)),
                         'images': args.images, 'images_on_rank0': len(mine), 'max_batch': args.max_batch, 'write_window': args.write_window or 32 * args.max_batch,
                         'io_threads': io_threads, 'temporary_directory': os.path.dirname(root)},
-                megapixels=round(tot_px / 1e6, 1), encode=results['encode'], round_trip=results['round_trip'],
-                device='{} ({}, {} CUs)'.format(name, arch, ncu))
+                megapixels=round(tot_px / 1e6, 1), encode=results['encode'], device='{} ({}, {} CUs)'.format(name, arch, ncu),
+                **({'round_trip': results['round_trip']} if args.full else {}))
             result['ms_per_step'] = round(results['encode']['seconds_rank0'][-1] * 1e3, 3)
         return result
     finally:
@@ -861,6 +920,9 @@ def run_large(args, ranks):
         return bpsps
 
     elapsed, bpsps = timed(ranks, step, args.steps, args.warmup)
+    if args.dump_outputs:
+        import numpy as np
+        dump_outputs(args, ranks, {'bpsp': np.array(bpsps, dtype=np.float64)})
     value = ranks.world * px * args.steps / 1e6 / elapsed
     result = None
     if ranks.rank == 0:

@@ -43,10 +43,10 @@ if [ "$1" == "--bench-only" ]; then
     # the three bench lines only (host-side changes: the kernel sources, hence the committed PMC table and kernel statistics, are unchanged --
     # bench.py checks that by the source stamp); merged into the existing gpurun_out/evidence/ by --collect
     mkdir -p "$E"
-    timeout 900 python bench.py > $E/bench_default.json 2> $E/bench_default.err
-    timeout 900 python bench.py --config dataset > $E/bench_dataset.json 2> $E/bench_dataset.err
-    timeout 600 python bench.py --config large > $E/bench_large.json 2> $E/bench_large.err
-    timeout 900 python bench.py --config files > $E/bench_files.json 2> $E/bench_files.err
+    timeout 900 python bench.py --full > $E/bench_default.json 2> $E/bench_default.err
+    timeout 900 python bench.py --full --config dataset > $E/bench_dataset.json 2> $E/bench_dataset.err
+    timeout 600 python bench.py --full --config large > $E/bench_large.json 2> $E/bench_large.err
+    timeout 900 python bench.py --full --config files > $E/bench_files.json 2> $E/bench_files.err
     tail -c 1200 $E/bench_default.json; cat $E/bench_dataset.json | cut -c1-300
     exit 0
 fi
@@ -58,7 +58,7 @@ timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $E/smoke.log 2>
 cp gpurun_out/parity_768x512_*.json $E/
 # (--no-decode also skips the batch-1 latency leg: the profiled process then launches every encode-side kernel warm-up + steps times and nothing else, so the
 # per-kernel averages of the summary are comparable with the HIP-event averages of the bench line; the decode-side kernels are profiled by the decode trace below)
-timeout 600 rocprofv3 --kernel-trace --stats -d $E/stats -o run -- python bench.py $LIGHT --no-decode > $E/bench_profiled_run.json 2> $E/rocprof_stats.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $E/stats -o run -- python bench.py --full $LIGHT --no-decode > $E/bench_profiled_run.json 2> $E/rocprof_stats.err
 DB=$(find $E/stats -name '*.db' | head -1)
 [ -n "$DB" ] && python tools/rocpd_summary.py "$DB" $E/kernel_stats.csv > $E/kernel_stats.txt
 PMCARGS="--steps 2 --warmup 1 $LIGHT --no-kernel-events --no-decode"
@@ -79,10 +79,10 @@ for ck in calibrated default; do for mode in auto never; do
 done; done > $E/decode_modes.log
 python tools/pmc_bench.py $E/pmc 128 --steps 2 --warmup 1 --decode-root $E/pmcd > $E/pmc_bench.json
 cp $E/pmc_bench.json profiles/${R}_pmc_bench.json      # (the box's copy: the bench line below then reports it as current)
-timeout 900 python bench.py > $E/bench_default.json 2> $E/bench_default.err
-timeout 900 python bench.py --config dataset > $E/bench_dataset.json 2> $E/bench_dataset.err
-timeout 600 python bench.py --config large > $E/bench_large.json 2> $E/bench_large.err
-timeout 900 python bench.py --config files > $E/bench_files.json 2> $E/bench_files.err
+timeout 900 python bench.py --full > $E/bench_default.json 2> $E/bench_default.err
+timeout 900 python bench.py --full --config dataset > $E/bench_dataset.json 2> $E/bench_dataset.err
+timeout 600 python bench.py --full --config large > $E/bench_large.json 2> $E/bench_large.err
+timeout 900 python bench.py --full --config files > $E/bench_files.json 2> $E/bench_files.err
 # L2 hit rates and memory-side bytes per kernel variant (round-5 verdict, next 1): TCC_HIT / TCC_MISS pass, joined with the FETCH / WRITE passes above
 timeout 600 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d $E/pmc_tcc/hm -o run --output-format csv -- python bench.py $PMCARGS > /dev/null 2> $E/pmc_tcc.err
 timeout 600 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_REQ_sum -d $E/pmc_tcc/rd -o run --output-format csv -- python bench.py $PMCARGS > /dev/null 2>> $E/pmc_tcc.err
