@@ -517,6 +517,92 @@ int l3c_container_read(const uint8_t *files, const int64_t *src_offset, const in
 /* symbols -> bottleneck values, to_bn (quantizer.py:44-47): float(S) * bin + x_min, two separately rounded fp32 ops. */
 int l3c_sym_to_bn(const int16_t *sym, int64_t n, float bin_width, float x_min, float *bn, l3c_stream_t stream);
 
+/* ---- the whole network (replaces modules/multiscale_network.py forward / get_P) ------------------------------------ */
+
+/*
+ * MultiscaleNetwork.forward and .get_P (reference modules/multiscale_network.py:226-306, :308-322) as ONE library call each: the
+ * library runs the layer schedule of l3c-pytorch_amd/modules/multiscale_network.py -- the same entry points with the same descriptors
+ * in the same order (l3c_rgb_head, l3c_conv_wino4 for every 3x3 layer, l3c_conv_wino4_stride2 for the 5x5 stride-2 `down` layers,
+ * l3c_conv_pw for the 1x1 192 -> Kp classifier outputs, l3c_to_q_quantize, l3c_dec_head) -- so P is bit-identical to the Python
+ * schedule's and files written through either decode with the other.
+ *
+ * Model families: L3C (EDSRLikeEnc with enc.feed_F and dec.skip, configs/ms/cr.cf) and the RGB / RGB Shared baselines
+ * (BicubicSubsampling, cr_rgb.cf / cr_rgb_shared.cf: no heads and no encoders, q.C == 3, Kp = 12 K at every scale).  l3c_net_forward
+ * covers L3C only (the baselines' bicubic pyramid is driven by tables computed on the host); l3c_net_get_p covers both.
+ * Supported shapes (anything else: L3C_ERR_UNSUPPORTED): Cf == 64, C <= 8, Kp <= 160 at every scale, image sides multiples of
+ * 2^num_scales, H * W * Cf * 4 < 0x7ffffff0 bytes per image, B < 65536 and B * H * W < 2^31.
+ * Every pointer must be 16-byte aligned; all arguments are checked before anything is enqueued.  The only global state read is that
+ * of the convolution entries (l3c_conv_wino4_set_tiles_per_block); two calls on two streams with separate workspaces and outputs may
+ * share one packed buffer.
+ */
+#define L3C_NET_MAX_SCALES 4
+typedef struct {
+    int num_scales;            /* 3 in cr.cf, 1 in cr_rgb_shared.cf */
+    int Cf, C, L, K;           /* Cf, q.C, q.L, prob.K */
+    int enc_blocks, dec_blocks;
+    int rgb_baseline;          /* 1: BicubicSubsampling configs (cr_rgb*.cf): no heads / encoders, Kp = 12 K at every scale */
+    int dec_skip;              /* dec.skip */
+} l3c_net_config;
+
+/* The checkpoint's tensors: name, rank and shape of tensor i in the reference's state-dict order (= modules/schema.param_schema).
+ * name_host receives a NUL-terminated string of at most name_cap bytes; shape_host holds up to 4 entries. */
+int l3c_net_param_count(const l3c_net_config *cfg_host);
+int l3c_net_param(const l3c_net_config *cfg_host, int i, char *name_host, int name_cap, int *ndim_host, int64_t *shape_host);
+
+/*
+ * ONE caller-owned device buffer holding every layer in the form its kernel reads (Winograd / polyphase / sub-pixel-major / pointwise
+ * packings, biases, the small 1x1 weights, the quantiser levels `enc.levels`).  params_host: HOST array of l3c_net_param_count DEVICE
+ * pointers, fp32 contiguous, in l3c_net_param order; read by the enqueued work only (keep them alive until it has run).
+ * The size functions return a negative status for a config outside the supported set.
+ */
+int64_t l3c_net_packed_bytes(const l3c_net_config *cfg_host);
+int64_t l3c_net_pack_workspace_bytes(const l3c_net_config *cfg_host);
+int l3c_net_pack(const l3c_net_config *cfg_host, const float *const *params_host, void *packed, int64_t packed_bytes, void *workspace,
+                 int64_t workspace_bytes, l3c_stream_t stream);
+
+/*
+ * MultiscaleNetwork.forward of the L3C family.  Scale s of the outputs is the reference's Out index s (raw fields of modules/
+ * multiscale_network.Out); h_s = H >> s, w_s = W >> s.  The outputs are also used as scratch before they are written.
+ */
+typedef struct {
+    const l3c_net_config *cfg_host;
+    const void *packed;
+    int64_t packed_bytes;
+    const float *img;                               /* planar fp32 [B][3][H][W], 0..255 */
+    int64_t B;
+    int H, W;
+    int16_t *sym[L3C_NET_MAX_SCALES + 1];           /* [0] image symbols [B][3][H][W] (round half to even); [s] [B][C][h_s][w_s] */
+    float *bn_q[L3C_NET_MAX_SCALES + 1];            /* [s >= 1] planar [B][C][h_s][w_s]; [0] unused */
+    float *P[L3C_NET_MAX_SCALES];                   /* [s] pixel-major [B][h_s][w_s][Kp_s] */
+    float *F_enc[L3C_NET_MAX_SCALES];               /* optional: [s] pixel-major [B][h_(s+1)][w_(s+1)][Cf], encoder features */
+    float *F_dec[L3C_NET_MAX_SCALES];               /* optional: [s] pixel-major [B][h_s][w_s][Cf], decoder features */
+    void *workspace;
+    int64_t workspace_bytes;
+} l3c_net_forward_desc;
+int64_t l3c_net_forward_workspace_bytes(const l3c_net_config *cfg_host, int64_t B, int H, int W);
+int l3c_net_forward(const l3c_net_forward_desc *desc_host, l3c_stream_t stream);
+
+/*
+ * MultiscaleNetwork.get_P: one scale's decoder + probability classifier, both model families.  `net` names the scale whose networks
+ * run (0 .. num_scales - 1; the recursive scales of the RGB Shared baseline map to num_scales - 1: the caller maps them).
+ */
+typedef struct {
+    const l3c_net_config *cfg_host;
+    const void *packed;
+    int64_t packed_bytes;
+    int net;
+    const float *bn_q;                              /* planar [B][C][h][w] */
+    int64_t B;
+    int h, w;
+    const float *fuse;                              /* pixel-major [B][h][w][Cf] coarser decoder features, or NULL (dec_skip == 0: NULL) */
+    float *P;                                       /* pixel-major [B][2h][2w][Kp] */
+    float *F;                                       /* pixel-major [B][2h][2w][Cf], or NULL */
+    void *workspace;
+    int64_t workspace_bytes;
+} l3c_net_get_p_desc;
+int64_t l3c_net_get_p_workspace_bytes(const l3c_net_config *cfg_host, int64_t B, int h, int w);
+int l3c_net_get_p(const l3c_net_get_p_desc *desc_host, l3c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ Layout
   _lib.py        ctypes binding of the C ABI (raw device pointers + hipStream_t)
   torchac.py     reference `torchac` facade (encode/decode_cdf, encode/decode_logistic_mixture)
   modules/       MultiscaleNetwork, Out, EncOut/DecOut, quantizer helpers
+  native_net.py  NativeNet: MultiscaleNetwork.forward / get_P as ONE C-ABI call each (l3c_net_forward / l3c_net_get_p)
   criterion/     DiscretizedMixLogisticLoss, CDFOut
   bitcoding/     Bitcoding (.l3c container), coders, part-suffix helper
   blueprints/    MultiscaleBlueprint

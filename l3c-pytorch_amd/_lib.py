@@ -83,6 +83,30 @@ class RgbRaggedDesc(ctypes.Structure):
                 ('lag', c_int), ('window_mode', c_int), ('workspace', c_vp), ('workspace_bytes', c_i64)]
 
 
+NET_MAX_SCALES = 4    # include/l3c_hip.h: L3C_NET_MAX_SCALES
+
+
+class NetConfig(ctypes.Structure):
+    """l3c_net_config (include/l3c_hip.h)."""
+    _fields_ = [('num_scales', c_int), ('Cf', c_int), ('C', c_int), ('L', c_int), ('K', c_int), ('enc_blocks', c_int),
+                ('dec_blocks', c_int), ('rgb_baseline', c_int), ('dec_skip', c_int)]
+
+
+class NetForwardDesc(ctypes.Structure):
+    """l3c_net_forward_desc (include/l3c_hip.h)."""
+    _fields_ = [('cfg_host', ctypes.POINTER(NetConfig)), ('packed', c_vp), ('packed_bytes', c_i64), ('img', c_vp), ('B', c_i64),
+                ('H', c_int), ('W', c_int), ('sym', c_vp * (NET_MAX_SCALES + 1)), ('bn_q', c_vp * (NET_MAX_SCALES + 1)),
+                ('P', c_vp * NET_MAX_SCALES), ('F_enc', c_vp * NET_MAX_SCALES), ('F_dec', c_vp * NET_MAX_SCALES),
+                ('workspace', c_vp), ('workspace_bytes', c_i64)]
+
+
+class NetGetPDesc(ctypes.Structure):
+    """l3c_net_get_p_desc (include/l3c_hip.h)."""
+    _fields_ = [('cfg_host', ctypes.POINTER(NetConfig)), ('packed', c_vp), ('packed_bytes', c_i64), ('net', c_int), ('bn_q', c_vp),
+                ('B', c_i64), ('h', c_int), ('w', c_int), ('fuse', c_vp), ('P', c_vp), ('F', c_vp), ('workspace', c_vp),
+                ('workspace_bytes', c_i64)]
+
+
 EPI_RELU, EPI_RESIDUAL, EPI_PIXEL_SHUFFLE = 1, 2, 4
 ABI_VERSION = 4      # include/l3c_hip.h: L3C_ABI_VERSION (4: grouped tables, l3c_decode_rgb, l3c_container_read; no canvas batches)
 
@@ -143,6 +167,15 @@ PROTOTYPES = {
     'l3c_resample_u8': (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     'l3c_u8_to_sym_bn': (c_int, [c_vp, ctypes.POINTER(c_f32), c_i64, c_i64, c_vp, c_vp, c_vp]),
     'l3c_sym_to_bn': (c_int, [c_vp, c_i64, c_f32, c_f32, c_vp, c_vp]),
+    'l3c_net_param_count': (c_int, [ctypes.POINTER(NetConfig)]),
+    'l3c_net_param': (c_int, [ctypes.POINTER(NetConfig), c_int, ctypes.c_char_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_i64)]),
+    'l3c_net_packed_bytes': (c_i64, [ctypes.POINTER(NetConfig)]),
+    'l3c_net_pack_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig)]),
+    'l3c_net_pack': (c_int, [ctypes.POINTER(NetConfig), ctypes.POINTER(c_vp), c_vp, c_i64, c_vp, c_i64, c_vp]),
+    'l3c_net_forward_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_i64, c_int, c_int]),
+    'l3c_net_forward': (c_int, [ctypes.POINTER(NetForwardDesc), c_vp]),
+    'l3c_net_get_p_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_i64, c_int, c_int]),
+    'l3c_net_get_p': (c_int, [ctypes.POINTER(NetGetPDesc), c_vp]),
 }
 
 # include/l3c_xcheck.h: the TEST-ONLY cross-check library (round-1/2 Winograd F(2x2,3x3) kernel); see load_xcheck()
