@@ -262,6 +262,35 @@ int64_t l3c_decode_rgb_workspace_bytes(int64_t B, int64_t max_chunk_npix, int n_
 /* byte offset, inside the workspace, of the window statistics int32 [3][n_chunks + 2][B] (slot j + 2 = what chunk j's decoders reported; tests) */
 int64_t l3c_decode_rgb_stats_offset(int64_t B, int64_t max_chunk_npix, int n_chunks, int lag);
 int l3c_decode_rgb(const l3c_rgb_decode_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
+/*
+ * The RGB scale of a batch of BANDED files (see l3c_ac_band_intervals): every band of every image is a stream of its own, and the chunk
+ * pipeline above runs over all of them in lock step -- pipeline step t builds the tables of chunk t - lag * c of channel c for EVERY band
+ * in one launch and resumes every band's decoder in one launch.  Band j of image b is decoded as the ragged entry (pixbase b * HW,
+ * hw HW, chunk k at pixel j * L + k * step_j), so P / sym / window rows are indexed exactly as for the rectangular batch.
+ *   P, targets, sym, B, HW, K, lag, window_mode   as for l3c_rgb_decode_desc
+ *   in / in_offsets / in_nbytes   the B * 3 * n band streams: stream (c, b, j) at index (c * B + b) * n + j, n = ceil(HW / band_len)
+ *   band_len     L, a multiple of 64;  n_chunks  chunks per band (1 .. 64): every band must hold at least 64 * n_chunks symbols when n_chunks > 1
+ * B * n < 65536.  Nothing is read from the host after the call returns; the per-band descriptors live in the workspace and are written by
+ * a kernel on main_stream.
+ */
+typedef struct {
+    const float *P;
+    const float *targets;
+    int16_t *sym;
+    int64_t B, HW;
+    int K;
+    const uint8_t *in;
+    const int64_t *in_offsets;
+    const uint32_t *in_nbytes;
+    int64_t band_len;
+    int n_chunks;
+    int lag;
+    int window_mode;
+    void *workspace;
+    int64_t workspace_bytes;
+} l3c_rgb_banded_desc;
+int64_t l3c_decode_rgb_banded_workspace_bytes(int64_t B, int64_t HW, int64_t band_len, int n_chunks, int lag);
+int l3c_decode_rgb_banded(const l3c_rgb_banded_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
 
 /* ---- logistic-mixture head (replaces torchac_kernel.cu + criterion/logistic_mixture.py on the coding path) --------- */
 
@@ -513,6 +542,39 @@ int l3c_container_write(const l3c_container_scale *scales, int n_scales, int64_t
  */
 int l3c_container_read(const uint8_t *files, const int64_t *src_offset, const int64_t *dst_offset, const uint32_t *nbytes,
                        int64_t n_streams, uint32_t max_nbytes, uint8_t *dst, l3c_stream_t stream);
+
+/*
+ * BANDED files ("Banded .l3c files"): a channel's raster-order stream of H*W symbols is cut into n = ceil(H*W / L) bands of L
+ * consecutive pixels (L % 64 == 0), each coded as a stream of its own -- the same symbols and table rows, n independent chains.
+ *
+ * l3c_ac_band_intervals re-lays the interval buffer of n_streams streams of n_sym symbols (as filled by l3c_dmll_encode_intervals /
+ * l3c_ac_intervals_from_table) into the two groups l3c_ac_encode_groups codes: the FULL bands -- stream (s, j) at index s * (n - 1) + j,
+ * L symbols, l3c_interval_words(n_streams * (n - 1), L) words; NULL when n == 1 -- and the LAST band of every stream -- stream s,
+ * n_sym - (n - 1) * L symbols, l3c_interval_words(n_streams, that) words.  A pure copy of 512-byte runs; `intervals` is not modified.
+ */
+int l3c_ac_band_intervals(const uint32_t *intervals, int64_t n_streams, int64_t n_sym, int64_t band_len, uint32_t *full_out,
+                          uint32_t *last_out, l3c_stream_t stream);
+
+/*
+ * The banded file assembly:  'L3CB' | u8 version 1 | u8 0 | u16 x4 padding | for scale = coarsest .. 0:  u8 C, u16 H, u16 W, u32 L |
+ * for channel c: for band j: u32 nbytes, payload | 46 E2 84 92.   Per scale the coder output of the two groups of l3c_ac_band_intervals;
+ * file b is 14 + sum_scales (9 + 4 * C * n + 4) + its payload bytes long.  `workspace`: l3c_container_write_banded_workspace_bytes(scales,
+ * n_scales, B) bytes (the length fields' positions), 8-byte aligned.
+ */
+typedef struct {
+    const uint8_t *out_full;        /* [B*C*(n-1)][stride_full], NULL when n == 1 */
+    const uint32_t *nbytes_full;    /* [B*C*(n-1)] */
+    int64_t stride_full;
+    const uint8_t *out_last;        /* [B*C][stride_last] */
+    const uint32_t *nbytes_last;    /* [B*C] */
+    int64_t stride_last;
+    int C, H, W;
+    int64_t band_len;               /* L: L % 64 == 0, ceil(H*W / L) <= 1024 */
+} l3c_banded_scale;
+int64_t l3c_container_write_banded_workspace_bytes(const l3c_banded_scale *scales, int n_scales, int64_t B);
+int l3c_container_write_banded(const l3c_banded_scale *scales, int n_scales, int64_t B, const uint16_t *padding,
+                               const int64_t *file_offset, uint8_t *dst, void *workspace, int64_t workspace_bytes,
+                               l3c_stream_t stream);
 
 /* symbols -> bottleneck values, to_bn (quantizer.py:44-47): float(S) * bin + x_min, two separately rounded fp32 ops. */
 int l3c_sym_to_bn(const int16_t *sym, int64_t n, float bin_width, float x_min, float *bn, l3c_stream_t stream);

@@ -83,6 +83,19 @@ class RgbRaggedDesc(ctypes.Structure):
                 ('lag', c_int), ('window_mode', c_int), ('workspace', c_vp), ('workspace_bytes', c_i64)]
 
 
+class BandedScale(ctypes.Structure):
+    """l3c_banded_scale (include/l3c_hip.h)."""
+    _fields_ = [('out_full', c_vp), ('nbytes_full', c_vp), ('stride_full', c_i64), ('out_last', c_vp), ('nbytes_last', c_vp),
+                ('stride_last', c_i64), ('C', c_int), ('H', c_int), ('W', c_int), ('band_len', c_i64)]
+
+
+class RgbBandedDesc(ctypes.Structure):
+    """l3c_rgb_banded_desc (include/l3c_hip.h)."""
+    _fields_ = [('P', c_vp), ('targets', c_vp), ('sym', c_vp), ('B', c_i64), ('HW', c_i64), ('K', c_int),
+                ('in_', c_vp), ('in_offsets', c_vp), ('in_nbytes', c_vp), ('band_len', c_i64), ('n_chunks', c_int),
+                ('lag', c_int), ('window_mode', c_int), ('workspace', c_vp), ('workspace_bytes', c_i64)]
+
+
 NET_MAX_SCALES = 4    # include/l3c_hip.h: L3C_NET_MAX_SCALES
 
 
@@ -128,6 +141,11 @@ PROTOTYPES = {
     'l3c_ac_encode_groups': (c_int, [ctypes.POINTER(AcGroup), c_int, c_vp, c_vp]),
     'l3c_container_write': (c_int, [ctypes.POINTER(ContainerScale), c_int, c_i64, c_vp, c_vp, c_vp, c_vp]),
     'l3c_container_read': (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_uint32, c_vp, c_vp]),
+    'l3c_ac_band_intervals': (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    'l3c_container_write_banded_workspace_bytes': (c_i64, [ctypes.POINTER(BandedScale), c_int, c_i64]),
+    'l3c_container_write_banded': (c_int, [ctypes.POINTER(BandedScale), c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'l3c_decode_rgb_banded_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64, c_int, c_int]),
+    'l3c_decode_rgb_banded': (c_int, [ctypes.POINTER(RgbBandedDesc), c_vp, c_vp]),
     'l3c_dmll_cdf_table_parts': (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, ctypes.POINTER(TablePart), c_int, c_vp]),
     'l3c_decode_rgb_workspace_bytes': (c_i64, [c_i64, c_i64, c_int, c_int]),
     'l3c_decode_rgb_stats_offset': (c_i64, [c_i64, c_i64, c_int, c_int]),

@@ -19,6 +19,8 @@
 
 #include <string.h>
 
+#include <vector>
+
 namespace {
 
 constexpr int C3 = 3;
@@ -293,6 +295,96 @@ int l3c_decode_rgb_ragged(const l3c_rgb_ragged_desc *r, l3c_stream_t main_stream
     d.n_chunks = r->n_chunks;  d.lag = r->lag;  d.window_mode = r->window_mode;
     d.workspace = r->workspace;  d.workspace_bytes = r->workspace_bytes;
     const Ragged rag{r->hw_host, r->chunk_pix0_host, r->chunk_npix_host, r->tables_dev};
+    return decode_rgb_impl(&d, &rag, max_total, main_stream, side_stream);
+}
+}
+
+// ---- banded files: every band a ragged entry ---------------------------------------------------------------------------------------
+//
+// Entry e = b * n + j (band j of image b) is pixels [j L, j L + len_j) of image b: pixbase = b HW and hw = HW (P and sym are the
+// rectangular batch's; no kernel assumes pixbase = the sum of the hw before it), chunk k at j L + k step_j with step_j = len_j / chunks
+// rounded down to 64 symbols, the last chunk taking the rest.  All bands but the last of an image are L long, so chunk k's rows of entry e
+// start at 514 (b T_k + j f_k) bytes of the step's table, T_k = (n - 1) f_k + l_k (f_k / l_k: chunk k's length in a full / the last band).
+namespace {
+
+struct BandPlan {
+    int64_t HW, L, n, chunks;
+    __host__ __device__ int64_t len(int64_t j) const { return j + 1 < n ? L : HW - (n - 1) * L; }
+    __host__ __device__ int64_t step(int64_t j) const { return len(j) / chunks / 64 * 64; }
+    __host__ __device__ int64_t npix(int64_t j, int64_t k) const { return k + 1 < chunks ? step(j) : len(j) - k * step(j); }
+};
+
+// tables: pixbase [S] | hw [S] | pix0 [chunks][S] | npix [chunks][S] | table_off [chunks][S]   (the layout of l3c_rgb_ragged_desc.tables_dev)
+__global__ __launch_bounds__(256) void band_plan_kernel(const BandPlan p, int64_t S, int64_t *__restrict__ tables) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= p.chunks * S) return;
+    const int64_t k = q / S, e = q - k * S;
+    const int64_t b = e / p.n, j = e - b * p.n;
+    const int64_t f = p.npix(0, k), T = (p.n - 1) * f + p.npix(p.n - 1, k);
+    if (k == 0) {
+        tables[e] = b * p.HW;
+        tables[S + e] = p.HW;
+    }
+    tables[2 * S + q] = j * p.L + k * p.step(j);
+    tables[(2 + p.chunks) * S + q] = p.npix(j, k);
+    tables[(2 + 2 * p.chunks) * S + q] = (b * T + j * f) * (int64_t)(LP * 2);
+}
+
+int64_t band_total(const BandPlan &p, int64_t B, int64_t k) { return B * ((p.n - 1) * p.npix(0, k) + p.npix(p.n - 1, k)); }
+
+int64_t banded_max_total(const BandPlan &p, int64_t B) {
+    int64_t m = 0;
+    for (int64_t k = 0; k < p.chunks; ++k) m = band_total(p, B, k) > m ? band_total(p, B, k) : m;
+    return m;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t l3c_decode_rgb_banded_workspace_bytes(int64_t B, int64_t HW, int64_t band_len, int n_chunks, int lag) {
+    if (B <= 0 || HW <= 0 || band_len < 64 || band_len % 64 || n_chunks <= 0 || n_chunks > 64 || (lag != 1 && lag != 2)) return -1;
+    const BandPlan p{HW, band_len, (HW + band_len - 1) / band_len, n_chunks};
+    const int64_t S = B * p.n;
+    return layout(1, banded_max_total(p, B), n_chunks, lag, S).total + up((2 + 3 * (int64_t)n_chunks) * S * 8);
+}
+
+int l3c_decode_rgb_banded(const l3c_rgb_banded_desc *r, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    L3C_REQUIRE(r, "null descriptor");
+    L3C_REQUIRE(r->P && r->targets && r->sym && r->in && r->in_offsets && r->in_nbytes && r->workspace, "null pointer in descriptor");
+    L3C_REQUIRE(r->B > 0 && r->HW > 0 && r->K > 0 && r->K <= 16, "bad shape");
+    L3C_REQUIRE(r->band_len >= 64 && r->band_len % 64 == 0, "band_len must be a positive multiple of 64");
+    L3C_REQUIRE(r->n_chunks > 0 && r->n_chunks <= 64, "1..64 chunks per band");
+    L3C_REQUIRE(r->lag == 1 || r->lag == 2, "lag must be 1 (one stream) or 2 (tables and decoders overlapped on two streams)");
+    L3C_REQUIRE(r->lag == 1 || side_stream != main_stream, "lag 2 needs a side stream that is not the main stream");
+    L3C_REQUIRE(r->window_mode >= 0 && r->window_mode <= 2, "window_mode: 0 never, 1 auto, 2 always");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(r->workspace) & (ALIGN - 1)) == 0, "workspace must be 256-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(r->in) & 3) == 0 && (reinterpret_cast<uintptr_t>(r->sym) & 1) == 0 &&
+                    ((reinterpret_cast<uintptr_t>(r->P) | reinterpret_cast<uintptr_t>(r->targets)) & 3) == 0,
+                "misaligned input (streams 4-byte aligned, l3c_container_read)");
+    const BandPlan p{r->HW, r->band_len, (r->HW + r->band_len - 1) / r->band_len, r->n_chunks};
+    const int64_t S = r->B * p.n;
+    L3C_REQUIRE(p.n <= 1024 && S < 65536, "at most 1024 bands per channel and 65535 bands per call");
+    L3C_REQUIRE(p.chunks == 1 || p.len(p.n - 1) >= 64 * p.chunks, "every band must hold 64 symbols per chunk");
+    const int64_t need = l3c_decode_rgb_banded_workspace_bytes(r->B, r->HW, r->band_len, r->n_chunks, r->lag);
+    L3C_REQUIRE(r->workspace_bytes >= need, "workspace too small (l3c_decode_rgb_banded_workspace_bytes)");
+    const int64_t max_total = banded_max_total(p, r->B);
+    const Layout l = layout(1, max_total, r->n_chunks, r->lag, S);
+    int64_t *tables = reinterpret_cast<int64_t *>(static_cast<uint8_t *>(r->workspace) + l.total);
+    // the host side of the ragged schedule: every entry's hw (only its maximum is used) and chunk lengths (per step: the longest, the total)
+    std::vector<int64_t> hw((size_t)S, r->HW), npix((size_t)(p.chunks * S));
+    for (int64_t k = 0; k < p.chunks; ++k)
+        for (int64_t e = 0; e < S; ++e) npix[(size_t)(k * S + e)] = p.npix(e % p.n, k);
+    const int64_t n_items = p.chunks * S;
+    hipLaunchKernelGGL(band_plan_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, l3c::as_stream(main_stream), p, S, tables);
+    const int rc = l3c::check_launch("band_plan_kernel");
+    if (rc != L3C_OK) return rc;
+    l3c_rgb_decode_desc d{};
+    d.P = r->P;  d.targets = r->targets;  d.sym = r->sym;  d.B = S;  d.HW = r->HW;  d.K = r->K;
+    d.in = r->in;  d.in_offsets = r->in_offsets;  d.in_nbytes = r->in_nbytes;
+    d.n_chunks = r->n_chunks;  d.lag = r->lag;  d.window_mode = r->window_mode;
+    d.workspace = r->workspace;  d.workspace_bytes = l.total;
+    const Ragged rag{hw.data(), nullptr, npix.data(), tables};
     return decode_rgb_impl(&d, &rag, max_total, main_stream, side_stream);
 }
 }

@@ -519,10 +519,88 @@ def decode_z_ragged(P_ragged, targets, sym_ragged, buf, offs, lens, hws, C, K):
     return tabs, tables, flag
 
 
+def decode_z_banded(P_nhwc, targets, sym, buf, offs, lens, B, C, HW, band_len, K):
+    """A bottleneck scale of banded files: every band (b, j) of every channel is a ragged entry (pixbase b HW, hw HW, pixels [j L, j L +
+    len_j)), so ONE ragged table launch (C parts) and ONE ragged decoder launch decode all B C n band streams.  sym int16 (B, C, HW) receives
+    the symbols; streams in (buf, offs, lens) with stream (c, b, j) at index (c B + b) n + j.  -> tensors to keep alive until the stream is done."""
+    import ctypes
+    import numpy as np
+    assert C <= 8
+    n = -(-HW // band_len)
+    S = B * n
+    Lp = targets.shape[0]
+    j = np.tile(np.arange(n, dtype=np.int64), B)
+    b = np.repeat(np.arange(B, dtype=np.int64), n)
+    pix0 = j * band_len
+    npix = np.minimum(band_len, HW - pix0)
+    tables = upload_small(np.concatenate([b * HW, np.full(S, HW, dtype=np.int64), pix0, npix, (b * HW + pix0) * (Lp * 2)]).astype(np.int64))
+    base = tables.data_ptr()
+    flag = torch.zeros(1, dtype=torch.int32, device=P_nhwc.device)
+    tabs = [torch.empty(B * HW * Lp, dtype=torch.int16, device=P_nhwc.device) for _ in range(C)]
+    batch = _lib.RaggedBatch(S, HW, base, base + 8 * S)
+    tparts = (_lib.TablePart * C)()
+    rparts = (_lib.RaggedPart * C)()
+    dparts = (_lib.AcDecodePart * C)()
+    for c in range(C):
+        tparts[c] = _lib.TablePart(c, 0, int(npix.max()), ptr(tabs[c]), ptr(flag, torch.int32), None)
+        rparts[c] = _lib.RaggedPart(base + 16 * S, base + 24 * S, base + 32 * S)
+        d = _lib.AcDecodePart(ptr(tabs[c]), Lp, ptr(buf, torch.uint8), ptr(offs[c * S:(c + 1) * S], torch.int64),
+                              ptr(lens[c * S:(c + 1) * S], torch.int32), S, int(npix.max()), ptr(flag, torch.int32), None, None, 1,
+                              ptr(sym, torch.int16), 0, 0)
+        d.r_npix, d.r_table_off, d.r_pixbase, d.r_hw, d.r_pix0 = base + 24 * S, base + 32 * S, base, base + 8 * S, base + 16 * S
+        d.r_C, d.r_c, d.r_table_bytes = C, c, B * HW * Lp * 2
+        dparts[c] = d
+    call('l3c_dmll_cdf_table_ragged', ptr(P_nhwc, torch.float32), None, ptr(targets, torch.float32), ctypes.byref(batch), C, K, 0, Lp,
+         tparts, rparts, C, stream())
+    call('l3c_ac_decode_chunks', dparts, C, stream())
+    return tabs, tables, flag
+
+
+def decode_rgb_banded(P_nhwc, targets, sym, buf, offs, lens, band_len, n_chunks, K, lag, window_mode, side_stream=None):
+    """An RGB scale of banded files in one host call (l3c_decode_rgb_banded): P (B,H,W,120), sym int16 (B,3,H,W) ZEROED, the band streams in
+    (buf, offs, lens) with stream (c, b, j) at index (c B + b) n + j.  -> workspace tensor; the current stream is ordered after the symbols."""
+    import ctypes
+    lib = _lib.load()
+    B, H, W, _ = P_nhwc.shape
+    HW = H * W
+    nbytes = lib.l3c_decode_rgb_banded_workspace_bytes(B, HW, band_len, n_chunks, lag)
+    if nbytes < 0:
+        raise _lib.L3CError('l3c_decode_rgb_banded_workspace_bytes: bad arguments (B={}, HW={}, L={}, chunks={})'.format(B, HW, band_len, n_chunks))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=P_nhwc.device)
+    desc = _lib.RgbBandedDesc(ptr(P_nhwc, torch.float32), ptr(targets, torch.float32), ptr(sym, torch.int16), B, HW, K,
+                              ptr(buf, torch.uint8), ptr(offs, torch.int64), ptr(lens, torch.int32), band_len, n_chunks, lag, window_mode,
+                              ptr(ws), nbytes)
+    if lag == 2:
+        for t in (P_nhwc, targets, sym, buf, offs, lens, ws):
+            t.record_stream(side_stream)
+    call('l3c_decode_rgb_banded', ctypes.byref(desc), torch.cuda.current_stream().cuda_stream,
+         side_stream.cuda_stream if lag == 2 else None)
+    return ws
+
+
+def band_intervals(iv, n_streams, n_sym, band_len):
+    """l3c_ac_band_intervals: the interval buffer of n_streams streams -> [(iv, n_streams, n_sym)] groups for ac_encode_groups: the full
+    bands (stream s * (n - 1) + j; absent when n == 1), then the last band of every stream."""
+    lib = _lib.load()
+    n = -(-n_sym // band_len)
+    last = n_sym - (n - 1) * band_len
+    full = (torch.empty(lib.l3c_interval_words(n_streams * (n - 1), band_len), dtype=torch.int32, device=iv.device) if n > 1 else None)
+    tail = torch.empty(lib.l3c_interval_words(n_streams, last), dtype=torch.int32, device=iv.device)
+    call('l3c_ac_band_intervals', ptr(iv, torch.int32), n_streams, n_sym, band_len, ptr(full), ptr(tail), stream())
+    return ([(full, n_streams * (n - 1), band_len)] if n > 1 else []) + [(tail, n_streams, last)]
+
+
+CONTAINER_READ_MAX_STREAMS = 65535     # l3c_container_read: one grid row per stream (grid.y)
+
+
 def container_read(files_dev, src_off, dst_off, nbytes, max_nbytes, dst):
-    """l3c_container_read: the streams of many raw `.l3c` files (one device buffer) -> 4-byte aligned, zero padded streams in `dst`."""
-    call('l3c_container_read', ptr(files_dev, torch.uint8), ptr(src_off, torch.int64), ptr(dst_off, torch.int64), ptr(nbytes, torch.int32),
-         nbytes.numel(), int(max_nbytes), ptr(dst, torch.uint8), stream())
+    """l3c_container_read: the streams of many raw `.l3c` files (one device buffer) -> 4-byte aligned, zero padded streams in `dst`;
+    in slices of at most 65 535 streams (a banded batch easily holds more)."""
+    S = nbytes.numel()
+    for a in range(0, S, CONTAINER_READ_MAX_STREAMS):
+        e = min(S, a + CONTAINER_READ_MAX_STREAMS)
+        call('l3c_container_read', ptr(files_dev, torch.uint8), ptr(src_off[a:e], torch.int64), ptr(dst_off[a:e], torch.int64),
+             ptr(nbytes[a:e], torch.int32), e - a, int(max_nbytes), ptr(dst, torch.uint8), stream())
 
 
 def dmll_encode_intervals(P_nhwc, sym, targets, C, K, rgb):

@@ -194,7 +194,7 @@ class MultiscaleTester(object):
         self.file_writer = AsyncFileWriter() if getattr(flags, 'write_to_files', None) else None
         self.bc = Bitcoding(self.blueprint, times=self.times if getattr(flags, 'write_to_files', None) else None,
                             compare_with_theory=bool(getattr(flags, 'compare_theory', False)), auto_recurse=self.recursive,
-                            file_writer=self.file_writer)
+                            file_writer=self.file_writer, bands=int(getattr(flags, 'bands', 0) or 0))
         self.max_batch = int(getattr(flags, 'batch', None) or 8)
         self.io_threads = int(getattr(flags, 'io_threads', None) or 4)
         exp_name = os.path.basename(experiment_dir)

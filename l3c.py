@@ -18,6 +18,9 @@ l3c_pytorch_amd.configure_hip_queues()      # image sets / auto-crops run severa
 from l3c_pytorch_amd import torchac  # noqa: E402
 from l3c_pytorch_amd.test.multiscale_tester import DecodeError, EncodeError, MultiscaleTester  # noqa: E402
 
+# `enc --bands` without a value: the smallest band count within 5 % of the fastest one-image decode (profiles/r07_banded_latency.log)
+DEFAULT_BANDS = 64
+
 
 def parse_device_flag(flag):
     import torch
@@ -47,6 +50,9 @@ def main(argv=None):
     enc.add_argument('img_p')
     enc.add_argument('out_p')
     enc.add_argument('--overwrite', '-f', action='store_true')
+    enc.add_argument('--bands', type=int, nargs='?', const=DEFAULT_BANDS, default=0, metavar='K',
+                     help='write a BANDED file: every channel cut into at most K independently coded bands, for fast one-image '
+                          'encode / decode (1..1024; the flag alone: {}).  Without the flag: the legacy format.'.format(DEFAULT_BANDS))
     dec.add_argument('img_p')
     dec.add_argument('out_p_png')
     flags = p.parse_args(argv)
