@@ -1,10 +1,8 @@
 """Bitcoding -- `.l3c` container encode / decode with the whole data path on the GPU.
 
 Same surface as the reference's bitcoding/bitcoding.py (`Bitcoding(blueprint, times, compare_with_theory)`,
-`encode(img, pout) -> bpsp` :50-123, `decode(pin) -> 1CHW long` :125-161) and the same byte format (:326-375):
-
-    u16 x4  padding (left, right, top, bottom)
-    for scale = coarsest .. 0:   u8 C, u16 H, u16 W;  for each channel: u32 nbytes, payload;  magic 46 E2 84 92
+`encode(img, pout) -> bpsp` :50-123, `decode(pin) -> 1CHW long` :125-161) and the same byte format (:326-375; the host side of the framing,
+and of the opt-in banded files beside it, is container.py).
 
 What changed is WHERE the work happens.  The reference loops over scales and channels in Python, builds one CDF table per
 channel, and range-codes it on one CPU thread (coders.py:38-66 -> torchac.cpp).  Here a batch of B equally sized images
@@ -18,89 +16,15 @@ and only finished byte strings cross PCIe.  `encode_batch` / `decode_batch` are 
 `decode` are the reference's one-image file API on top of them (auto-crop parts included).
 """
 import os
-import struct
 
 import numpy as np
 import torch
 
 from .. import auto_crop, ops
 from ..helpers import pad
-from . import part_suffix_helper
-
-_MAGIC_VALUE_SEP = b'\x46\xE2\x84\x92'
-
-# BANDED files (opt-in, Bitcoding(bands=K); INTEGRATION.md "Banded .l3c files"):
-#     'L3CB' | u8 version = 1 | u8 0 | u16 x4 padding
-#     for scale = coarsest .. 0:  u8 C, u16 H, u16 W, u32 L | for channel c: for band j < n = ceil(H*W / L): u32 nbytes, payload | magic
-# Band j of channel c is pixels [j L, min((j + 1) L, H W)) in raster order, coded as a stream of its own with the legacy format's rows.
-# A legacy file cannot start with the signature: its first u16 is the left padding, below the padding factor ('L3' reads 13132).
-BANDED_SIGNATURE = b'L3CB'
-BANDED_VERSION = 1
-MAX_BANDS = 1024
-
-
-def band_len(hw, bands):
-    """L_s of a scale of hw symbols for the requested band count K: 64 ceil(hw / (64 K)) -- at most K bands of whole 64-symbol blocks."""
-    if not 1 <= int(bands) <= MAX_BANDS:
-        raise ValueError('bands must be in 1..{}, got {}'.format(MAX_BANDS, bands))
-    return 64 * (-(-int(hw) // (64 * int(bands))))
-
-
-def n_bands(hw, L):
-    return -(-int(hw) // int(L))
-
-
-def is_banded(data):
-    return bytes(data[:4]) == BANDED_SIGNATURE
-
-
-class ParsedBanded(object):
-    """Framing of one banded file (`parse_banded`): padding tuple, per scale record (coarsest first) (C, H, W, L) and, as (C, n) int64
-    arrays, where every band's payload lies inside the file (`offset`) and how long it is (`nbytes`)."""
-
-    def __init__(self, padding, scales, offset, nbytes):
-        self.padding, self.scales, self.offset, self.nbytes = padding, scales, offset, nbytes
-
-
-def parse_banded(data):
-    """Walk a banded file by its length fields.  ValueError('invalid file: ...') on an unknown version or reserved byte, C == 0, an empty
-    scale, L == 0 or not a multiple of 64, more than 1024 bands, a length field or payload past the end, a missing magic."""
-    r = _Reader(data)
-    if r.take(4) != BANDED_SIGNATURE:
-        raise ValueError('invalid file: not a banded .l3c file')
-    version, reserved = r.unpack('<BB')
-    if version != BANDED_VERSION:
-        raise ValueError('invalid file: unknown banded format version {}'.format(version))
-    if reserved:
-        raise ValueError('invalid file: reserved byte is {}'.format(reserved))
-    padding = r.unpack('<4H')
-    scales, offset, nbytes = [], [], []
-    while r.p < len(data):
-        C, H, W, L = r.unpack('<BHHI')
-        if C == 0:
-            raise ValueError('invalid file: scale record with C == 0')
-        if H == 0 or W == 0:
-            raise ValueError('invalid file: empty scale {}x{}'.format(H, W))
-        if L == 0 or L % 64:
-            raise ValueError('invalid file: band length {} is not a positive multiple of 64'.format(L))
-        n = n_bands(H * W, L)
-        if n > MAX_BANDS:
-            raise ValueError('invalid file: {} bands per channel (at most {})'.format(n, MAX_BANDS))
-        off = np.zeros((C, n), dtype=np.int64)
-        nb = np.zeros((C, n), dtype=np.int64)
-        for c in range(C):
-            for j in range(n):
-                nb[c, j], = r.unpack('<I')
-                off[c, j] = r.p
-                r.take(int(nb[c, j]))
-        if r.take(4) != _MAGIC_VALUE_SEP:
-            raise ValueError('invalid file: scale separator missing')
-        scales.append((C, H, W, L))
-        offset.append(off)
-        nbytes.append(nb)
-    if len(scales) < 2:
-        raise ValueError('invalid file: {} scale record(s)'.format(len(scales)))
-    return ParsedBanded(padding, scales, offset, nbytes)
+from . import container, part_suffix_helper
+from .container import (_MAGIC_VALUE_SEP, BANDED_SIGNATURE, MAX_BANDS, band_len, count_scale_records, is_banded, n_bands,  # noqa: F401
+                        parse_banded, parse_containers)
 
 
 class _NullTimes(object):
@@ -210,13 +134,9 @@ class EncodedBatch(object):
         return [int(n.to(torch.int64).sum().item()) for _, _, _, _, n in self.scales]
 
     def file_sizes(self):
-        """(B,) file size in bytes incl. the fixed framing: 8 + sum_scales (5 + 4*C + 4) + payload; banded files
-        14 + sum_scales (9 + 4*C*n + 4) + payload."""
-        if self.bands:
-            overhead = 14 + sum(9 + 4 * C * n_bands(H * W, L) + 4 for C, H, W, L, _ in self.banded_scales)
-        else:
-            overhead = 8 + sum(5 + 4 * C + 4 for C, _, _, _, _ in self.scales)
-        return self.total_payload_bytes() + overhead
+        """(B,) file size in bytes incl. the fixed framing (container.framing_bytes)."""
+        scales = [s[:4] for s in self.banded_scales] if self.bands else [s[:3] for s in self.scales]
+        return self.total_payload_bytes() + container.framing_bytes(scales, bool(self.bands))
 
     @staticmethod
     def _checked_nbytes(n):
@@ -324,29 +244,9 @@ class EncodedBatch(object):
     def to_bytes_host_assembled(self, padding_tuples=None):
         """Reference implementation of `to_bytes` on the host (per-scale copies + Python joins); kept for the tests."""
         pl = self.payloads()
-        files = []
-        if self.bands:
-            for b in range(self.B):
-                pt = padding_tuples[b] if padding_tuples else (0, 0, 0, 0)
-                chunks = [BANDED_SIGNATURE, struct.pack('<BB4H', BANDED_VERSION, 0, *pt)]
-                for (C, H, W, L, _), scale_payloads in zip(self.banded_scales, pl):
-                    chunks.append(struct.pack('<BHHI', C, H, W, L))
-                    for bands in scale_payloads[b]:
-                        for p in bands:
-                            chunks += [struct.pack('<I', len(p)), p]
-                    chunks.append(_MAGIC_VALUE_SEP)
-                files.append(b''.join(chunks))
-            return files
-        for b in range(self.B):
-            pt = padding_tuples[b] if padding_tuples else (0, 0, 0, 0)
-            chunks = [struct.pack('<4H', *pt)]
-            for (C, H, W, _, _), scale_payloads in zip(self.scales, pl):
-                chunks.append(struct.pack('<BHH', C, H, W))
-                for p in scale_payloads[b]:
-                    chunks += [struct.pack('<I', len(p)), p]
-                chunks.append(_MAGIC_VALUE_SEP)
-            files.append(b''.join(chunks))
-        return files
+        scales = [s[:4] for s in self.banded_scales] if self.bands else [s[:3] for s in self.scales]
+        return [container.write_file(padding_tuples[b] if padding_tuples else (0, 0, 0, 0), scales, [p[b] for p in pl], bool(self.bands))
+                for b in range(self.B)]
 
 
 class Bitcoding(object):
@@ -613,134 +513,136 @@ class Bitcoding(object):
         0.70 s became 0.87 - 2.98 s with the runtime's four hardware queues (the parts' main and side streams alias and serialise
         each other's long decoder launches) and 0.76 / 1.00 s with 8 or 16 queues -- a decoder wavefront that shares its SIMD
         with MFMA wavefronts runs 2.3x slower, which costs more than the overlap saves; profiles/r02_decode_parts_tried.log.)"""
-        if any(is_banded(f) for f in files):
-            return self._decode_batch_banded(files, out_dtype)
+        return self._decode_batch(files, out_dtype, None)
+
+    # ---- the walk over a file's scale records, coarse -> fine: what decode_batch (legacy and banded files) and the set decoder share -----
+    # The headers are untrusted input: a wrong C / H / W would make the table and decoder kernels index P and the symbol buffers out of
+    # bounds (the reference fails with a shape error here, bitcoding.py:248-266).  What needs only the framing is checked before the first
+    # upload (_n_predicted, _check_coarsest), a predicted record against the network where its P is (_check_header, _get_P).
+
+    def _n_predicted(self, n_records):
+        """Predicted scales of a file of n_records scale records; ValueError when the model codes another number."""
         net = self.blueprint.net
-        rgb_net = bool(net.config_ms.rgb_bicubic_baseline)
-        K = net.config_ms.prob.K
-        B = len(files)
-        parsed = parse_containers(files)
-        n_pred = len(parsed.scales) - 1
-        if n_pred < net.scales or (n_pred != net.scales and not (rgb_net and net.scales == 1)):
+        n_pred = n_records - 1
+        if n_pred < net.scales or (n_pred != net.scales and not (net.config_ms.rgb_bicubic_baseline and net.scales == 1)):
             raise ValueError('invalid file: {} scale records, the model codes {}'.format(n_pred + 1, net.scales + 1))
-        streams = _upload_streams(files, parsed)
-        bn_prev, F_prev, sym, prev_hw = None, None, None, None
+        return n_pred
+
+    def _check_coarsest(self, record, banded, max_nbytes):
+        """The coarsest record (uniform prior): the model's bottleneck channels, and no stream longer than its symbols can be."""
+        C, H, W = record[:3]
+        n_sym = record[3] if banded else H * W                    # symbols per stream: a band of a banded file, else the plane
+        if C != self.blueprint.net.config_ms.q.C or H < 1 or W < 1:
+            raise ValueError('invalid file: coarsest scale header (C={}, H={}, W={})'.format(C, H, W))
+        if max_nbytes > 2 * n_sym + 64:                           # > 16 bits per symbol: not a stream of this coder
+            raise ValueError('invalid file: coarsest scale payload longer than {} symbols can be'.format(n_sym))
+
+    def _check_header(self, scale, dmll, record, prev_hw):
+        """A predicted record's (C, H, W) against what the network will predict from the scale above -> channels of P per pixel."""
+        Cs = 3 if dmll.rgb_scale else self.blueprint.net.config_ms.q.C
+        expect = (Cs, 2 * prev_hw[0], 2 * prev_hw[1])
+        if tuple(record[:3]) != expect:
+            raise ValueError('invalid file: scale {} header (C, H, W) = {} but the network predicts {}'.format(scale, tuple(record[:3]), expect))
+        return (4 if dmll.rgb_scale else 3) * Cs * self.blueprint.net.config_ms.prob.K
+
+    def _get_P(self, scale, n_pred, bn, F, shape):
+        """net.get_P in the pixel-major form the table kernels read, checked against `shape` = (B, H, W, channels of P) -> P, F."""
+        P, F = self.blueprint.net.get_P(scale, bn, F, n_scales_total=n_pred)
+        P = ops.as_pixel_major(P)
+        if tuple(P.shape) != tuple(shape):
+            raise ValueError('invalid file: the network predicts {} at scale {}, the file says {}'.format(tuple(P.shape), scale, tuple(shape)))
+        return P, F
+
+    def _next_input(self, sym, dmll):
+        """Decoded symbols of a scale -> what the decoder of the next finer scale is fed."""
+        bn = ops.sym_to_bn(sym, dmll.bin_width, dmll.x_min)
+        if self.blueprint.net.config_ms.rgb_bicubic_baseline:      # BicubicDownsamplingEnc: the decoder is fed value - mean (net.py:72-80)
+            bn = bn - _rgb_mean_tensor(bn.device)
+        return bn
+
+    def _rgb_schedule(self, n_streams, side):
+        """(lag, window mode, side stream or None) of an RGB chunk pipeline over n_streams streams per channel in lock step.  The two extra
+        steps of lag 2 cost more than the overlap saves while the tables are small (they grow with the batch, a decode step does not):
+        lag 2 from 16 streams on [measured at 128 images: 0.726 s instead of 0.825 s]; the constructor's decode_overlap forces.
+        side: the stream the decoders of lag 2 run on (a lane's, the set decoder's); None = the next of the coder's side streams."""
+        overlap = n_streams >= 16 if self.decode_overlap is None else bool(self.decode_overlap)
+        mode = {'never': 0, 'auto': 1, 'always': 2}[self.rgb_window]
+        return (2 if overlap else 1), mode, ((side or self._side_stream()) if overlap else None)
+
+    def _decode_batch(self, files, out_dtype, side):
+        """decode_batch on the current stream; `side`: see _rgb_schedule."""
+        B = len(files)
+        records, framing, banded = container.parse_batch(files)
+        n_pred = self._n_predicted(len(records))
+        self._check_coarsest(records[0], banded, int(framing.nbytes[0].max()))
+        symbols = self._scale_symbols_banded if banded else self._scale_symbols
+        streams = _upload_streams(files, framing)
+        bn, F, P, hw, keep = None, None, None, None, []
         for k, (scale, dmll, uniform) in enumerate(self.iter_scale_dmll(n_pred)):
-            C, H, W = parsed.scales[k]
-            # the headers are untrusted input: a wrong C / H / W would make the table and decoder kernels index P and the symbol
-            # buffers out of bounds (the reference fails with a shape error here, bitcoding.py:248-266)
-            if uniform:
-                buf, offs, lens = streams.scale(k)
-                if C != net.config_ms.q.C or H < 1 or W < 1:
-                    raise ValueError('invalid file: coarsest scale header (C={}, H={}, W={})'.format(C, H, W))
-                if int(parsed.nbytes[k].max()) > 2 * H * W + 64:      # > 16 bits per symbol: not a stream of this coder
-                    raise ValueError('invalid file: coarsest scale payload longer than {} symbols can be'.format(H * W))
-                sym = ops.ac_decode(self._uniform_row(dmll.L), buf, offs, lens, B * C, H * W, True,
-                                    broadcast_row=True).reshape(B, C, H, W)
-            else:
-                P, F_prev = net.get_P(scale, bn_prev, F_prev, n_scales_total=n_pred)
-                P = ops.as_pixel_major(P)
-                n_params = 4 if dmll.rgb_scale else 3
-                expect = (P.shape[-1] // (n_params * K), 2 * prev_hw[0], 2 * prev_hw[1])
-                if (C, H, W) != expect or tuple(P.shape[1:3]) != (H, W):
-                    raise ValueError('invalid file: scale {} header (C, H, W) = {} but the network predicts {}'.format(
-                        scale, (C, H, W), expect))
-                targets = self._targets(dmll)
-                buf, offs, lens = streams.scale(k)      # (the last record's streams are staged and uploaded HERE: behind the convolutions just enqueued)
-                if dmll.rgb_scale:
-                    sym = self._decode_rgb_pipelined(P, targets, (buf, offs, lens), B, C, K, H, W)
-                else:
-                    sym = self._decode_z_scale(P, targets, (buf, offs, lens), B, C, K, H, W)
-            prev_hw = (H, W)
-            if scale == 0:
-                break                                   # the finest scale's symbols ARE the pixel values (to_bn of the RGB scale: x 1 + 0)
-            bn_prev = ops.sym_to_bn(sym, dmll.bin_width, dmll.x_min)
-            if rgb_net and scale > 0:                  # BicubicDownsamplingEnc: the decoder is fed value - mean (net.py:72-80)
-                bn_prev = bn_prev - _rgb_mean_tensor(bn_prev.device)
-        return sym.to(out_dtype), parsed.padding
+            H, W = records[k][1:3]
+            if not uniform:
+                Kp = self._check_header(scale, dmll, records[k], hw)
+                P, F = self._get_P(scale, n_pred, bn, F, (B, H, W, Kp))
+            sym, hold = symbols(streams, k, records[k], dmll, uniform, P, B, side)    # (the last record's streams are staged and uploaded HERE: behind the convolutions just enqueued)
+            keep.append(hold)                                           # workspaces and tables live until the whole decode is enqueued
+            hw = (H, W)
+            if scale > 0:                                               # the finest scale's symbols ARE the pixel values (to_bn of the RGB scale: x 1 + 0)
+                bn = self._next_input(sym, dmll)
+        return sym.to(out_dtype), framing.padding
+
+    def _scale_symbols(self, streams, k, record, dmll, uniform, P, B, side):
+        """-> (symbols (B, C, H, W) int16 of record k of legacy files, tensors to keep alive); uniform: the coarsest record, no P."""
+        C, H, W = record
+        if uniform:
+            buf, offs, lens = streams.scale(k)
+            return ops.ac_decode(self._uniform_row(dmll.L), buf, offs, lens, B * C, H * W, True, broadcast_row=True).reshape(B, C, H, W), None
+        K = self.blueprint.net.config_ms.prob.K
+        targets = self._targets(dmll)
+        if dmll.rgb_scale:
+            return self._decode_rgb_pipelined(P, targets, streams.scale(k), B, C, K, H, W, side), None
+        return self._decode_z_scale(P, targets, streams.scale(k), B, C, K, H, W), None
 
     RGB_BAND_CHUNKS = 8      # chunks per band of the banded RGB decode (every band must hold 64 symbols per chunk: fewer for short bands)
 
-    def _decode_batch_banded(self, files, out_dtype):
-        """decode_batch of BANDED files (equally sized images, the same band length per scale): per scale every band of every channel
-        and image is a stream of its own --
+    def _scale_symbols_banded(self, streams, k, record, dmll, uniform, P, B, side):
+        """-> (symbols, tensors to keep alive) of record k of BANDED files (the same band length in every file): every band of every channel and image is a stream
+        of its own --
             coarsest scale  the uniform row: one decoder launch over the full bands, one over the last bands
-            bottleneck      one ragged table launch + one ragged decoder launch over all B C n bands (ops.decode_z_banded)
+            bottleneck      one ragged table launch + one ragged decoder launch over all B C n bands (ops.decode_z_entries)
             RGB scale(s)    the chunk pipeline over all B n bands of each channel in lock step (l3c_decode_rgb_banded)."""
-        net = self.blueprint.net
-        rgb_net = bool(net.config_ms.rgb_bicubic_baseline)
-        K = net.config_ms.prob.K
-        B = len(files)
-        if not all(is_banded(f) for f in files):
-            raise ValueError('decode_batch: a batch mixes banded and legacy .l3c files')
-        parsed = [parse_banded(f) for f in files]
-        shapes = parsed[0].scales
-        for p in parsed[1:]:
-            if len(p.scales) != len(shapes) or any(a[:3] != b[:3] for a, b in zip(p.scales, shapes)):
-                raise ValueError('decode_batch needs equally sized images, got scale records {} and {}'.format(
-                    [s[:3] for s in shapes], [s[:3] for s in p.scales]))
-            if any(a[3] != b[3] for a, b in zip(p.scales, shapes)):
-                raise ValueError('decode_batch: banded files of one batch must share the band length of every scale, got {} and {}'.format(
-                    [s[3] for s in shapes], [s[3] for s in p.scales]))
-        n_pred = len(shapes) - 1
-        if n_pred < net.scales or (n_pred != net.scales and not (rgb_net and net.scales == 1)):
-            raise ValueError('invalid file: {} scale records, the model codes {}'.format(n_pred + 1, net.scales + 1))
-        # the legacy uploader with every (channel, band) as a "channel": streams of record k >= 1 then come channel-major, (c n + j) B + b
-        flat = ParsedContainers([p.padding for p in parsed], [(C * n_bands(H * W, L), H, W) for C, H, W, L in shapes],
-                                [np.stack([p.offset[k].reshape(-1) for p in parsed]) for k in range(len(shapes))],
-                                [np.stack([p.nbytes[k].reshape(-1) for p in parsed]) for k in range(len(shapes))])
-        streams = _upload_streams(files, flat)
-        bn_prev, F_prev, sym, prev_hw, keep = None, None, None, None, []
-        for k, (scale, dmll, uniform) in enumerate(self.iter_scale_dmll(n_pred)):
-            C, H, W, L = shapes[k]
-            HW, n = H * W, n_bands(H * W, L)
-            buf, _, _ = streams.scale(k)
-            o_h, l_h = streams.scale_host(k)
-            if uniform:
-                if C != net.config_ms.q.C:
-                    raise ValueError('invalid file: coarsest scale header (C={}, H={}, W={})'.format(C, H, W))
-                if int(l_h.max()) > 2 * L + 64:                 # > 16 bits per symbol: not a stream of this coder
-                    raise ValueError('invalid file: coarsest scale payload longer than {} symbols can be'.format(L))
-                o3, l3 = o_h.reshape(B * C, n), l_h.reshape(B * C, n).astype(np.int32)       # image-major: stream (b C + c) n + j
-                row = self._uniform_row(dmll.L)
-                sym = torch.empty(B * C, HW, dtype=torch.int16, device='cuda')
-                if n > 1:
-                    full = ops.ac_decode(row, buf, ops.upload_small(o3[:, :n - 1].reshape(-1)), ops.upload_small(l3[:, :n - 1].reshape(-1)),
-                                         B * C * (n - 1), L, True, broadcast_row=True)
-                    sym[:, :(n - 1) * L].copy_(full.view(B * C, (n - 1) * L))
-                last = ops.ac_decode(row, buf, ops.upload_small(o3[:, n - 1].copy()), ops.upload_small(l3[:, n - 1].copy()), B * C,
-                                     HW - (n - 1) * L, True, broadcast_row=True)
-                sym[:, (n - 1) * L:].copy_(last)
-                sym = sym.view(B, C, H, W)
-            else:
-                P, F_prev = net.get_P(scale, bn_prev, F_prev, n_scales_total=n_pred)
-                P = ops.as_pixel_major(P)
-                n_params = 4 if dmll.rgb_scale else 3
-                expect = (P.shape[-1] // (n_params * K), 2 * prev_hw[0], 2 * prev_hw[1])
-                if (C, H, W) != expect or tuple(P.shape[1:3]) != (H, W):
-                    raise ValueError('invalid file: scale {} header (C, H, W) = {} but the network predicts {}'.format(
-                        scale, (C, H, W), expect))
-                # (c n + j) B + b  ->  (c B + b) n + j
-                offs = ops.upload_small(o_h.reshape(C, n, B).transpose(0, 2, 1).reshape(-1))
-                lens = ops.upload_small(l_h.reshape(C, n, B).transpose(0, 2, 1).reshape(-1).astype(np.int32))
-                targets = self._targets(dmll)
-                if dmll.rgb_scale:
-                    sym = torch.zeros(B, C, H, W, dtype=torch.int16, device='cuda')
-                    chunks = max(1, min(self.RGB_BAND_CHUNKS, (HW - (n - 1) * L) // 64))
-                    overlap = B * n >= 16 if self.decode_overlap is None else bool(self.decode_overlap)
-                    mode = {'never': 0, 'auto': 1, 'always': 2}[self.rgb_window]
-                    keep.append(ops.decode_rgb_banded(P, targets, sym, buf, offs, lens, L, chunks, K, 2 if overlap else 1, mode,
-                                                      (getattr(self, '_lane_side', None) or self._side_stream()) if overlap else None))
-                else:
-                    sym = torch.empty(B, C, H, W, dtype=torch.int16, device='cuda')
-                    keep.append(ops.decode_z_banded(P, targets, sym, buf, offs, lens, B, C, HW, L, K))
-            prev_hw = (H, W)
-            if scale == 0:
-                break
-            bn_prev = ops.sym_to_bn(sym, dmll.bin_width, dmll.x_min)
-            if rgb_net and scale > 0:                  # BicubicDownsamplingEnc: the decoder is fed value - mean (net.py:72-80)
-                bn_prev = bn_prev - _rgb_mean_tensor(bn_prev.device)
-        return sym.to(out_dtype), [p.padding for p in parsed]
+        C, H, W, L = record
+        HW, n = H * W, n_bands(H * W, L)
+        buf, _, _ = streams.scale(k)
+        o_h, l_h = streams.scale_host(k)
+        if uniform:
+            o3, l3 = o_h.reshape(B * C, n), l_h.reshape(B * C, n).astype(np.int32)       # image-major: stream (b C + c) n + j
+            row = self._uniform_row(dmll.L)
+            sym = torch.empty(B * C, HW, dtype=torch.int16, device='cuda')
+            if n > 1:
+                full = ops.ac_decode(row, buf, ops.upload_small(o3[:, :n - 1].reshape(-1)), ops.upload_small(l3[:, :n - 1].reshape(-1)),
+                                     B * C * (n - 1), L, True, broadcast_row=True)
+                sym[:, :(n - 1) * L].copy_(full.view(B * C, (n - 1) * L))
+            last = ops.ac_decode(row, buf, ops.upload_small(o3[:, n - 1].copy()), ops.upload_small(l3[:, n - 1].copy()), B * C,
+                                 HW - (n - 1) * L, True, broadcast_row=True)
+            sym[:, (n - 1) * L:].copy_(last)
+            return sym.view(B, C, H, W), None
+        K = self.blueprint.net.config_ms.prob.K
+        # (c n + j) B + b  ->  (c B + b) n + j
+        offs = ops.upload_small(o_h.reshape(C, n, B).transpose(0, 2, 1).reshape(-1))
+        lens = ops.upload_small(l_h.reshape(C, n, B).transpose(0, 2, 1).reshape(-1).astype(np.int32))
+        targets = self._targets(dmll)
+        if dmll.rgb_scale:
+            sym = torch.zeros(B, C, H, W, dtype=torch.int16, device='cuda')
+            chunks = max(1, min(self.RGB_BAND_CHUNKS, (HW - (n - 1) * L) // 64))
+            hold = ops.decode_rgb_banded(P, targets, sym, buf, offs, lens, L, chunks, K, *self._rgb_schedule(B * n, side))
+        else:
+            sym = torch.empty(B, C, H, W, dtype=torch.int16, device='cuda')
+            j = np.tile(np.arange(n, dtype=np.int64), B)             # every band (b, j) is an entry: pixels [j L, j L + len_j) of image b
+            pixbase = np.repeat(np.arange(B, dtype=np.int64), n) * HW
+            pix0 = j * L
+            hold = ops.decode_z_entries(P, targets, sym, buf, offs, lens, pixbase, np.full(B * n, HW, dtype=np.int64), pix0,
+                                        np.minimum(L, HW - pix0), B * HW, C, K)
+        return sym, hold
 
     N_DECODE_LANES = 8       # decode_many: lanes when every batch is small (fewer than 64 images: latency-bound chains); large batches run one after the other
 
@@ -816,11 +718,7 @@ class Bitcoding(object):
             for i, files in enumerate(batches):
                 main, side = lane_streams[i % n]
                 with torch.cuda.stream(main):
-                    self._lane_side = side
-                    try:
-                        pixels, padding = self.decode_batch(files, out_dtype)
-                    finally:
-                        self._lane_side = None
+                    pixels, padding = self._decode_batch(files, out_dtype, side)
                     finish(i, pixels, padding, main)
                     done.append(main.record_event())
         else:
@@ -858,17 +756,13 @@ class Bitcoding(object):
             lanes:   P of the next finer scale ...                                                          -- and so on down to scale 0
         An image's serial chains -- 12 ms at scale 1, 60-70 ms at scale 0 for 768x512 -- are thereby paid once per GROUP instead of once
         per image; what is left per image are the decoder-side convolutions of its shape."""
-        import numpy as np
-        net = self.blueprint.net
-        rgb_net = bool(net.config_ms.rgb_bicubic_baseline)
-        K = net.config_ms.prob.K
+        K = self.blueprint.net.config_ms.prob.K
         n = len(lane_streams)
         st = []
         for i, files in group:
             parsed = parse_containers(files)
-            n_pred = len(parsed.scales) - 1
-            if n_pred < net.scales or (n_pred != net.scales and not (rgb_net and net.scales == 1)):
-                raise ValueError('invalid file: {} scale records, the model codes {}'.format(n_pred + 1, net.scales + 1))
+            n_pred = self._n_predicted(len(parsed.scales))
+            self._check_coarsest(parsed.scales[0], False, int(parsed.nbytes[0].max()))
             st.append({'i': i, 'files': files, 'parsed': parsed, 'B': len(files), 'lane': lane_streams[i % n], 'F': None, 'n_pred': n_pred})
         if len({e['n_pred'] for e in st}) != 1:
             raise ValueError('decode_many: the files of a set must come from one model (different numbers of scale records)')
@@ -895,30 +789,19 @@ class Bitcoding(object):
         assert uniform
         for e in st:
             C, H, W = e['parsed'].scales[0]
-            if C != net.config_ms.q.C or H < 1 or W < 1:
-                raise ValueError('invalid file: coarsest scale header (C={}, H={}, W={})'.format(C, H, W))
-            if int(e['parsed'].nbytes[0].max()) > 2 * H * W + 64:
-                raise ValueError('invalid file: coarsest scale payload longer than {} symbols can be'.format(H * W))
-            main, _ = e['lane']
-            with torch.cuda.stream(main):
+            with torch.cuda.stream(e['lane'][0]):
                 e['streams'] = _upload_streams(e['files'], e['parsed'])
-                buf, offs, lens = e['streams'].scale(0)
-                e['sym'] = ops.ac_decode(self._uniform_row(dmll.L), buf, offs, lens, e['B'] * C, H * W, True, broadcast_row=True).reshape(e['B'], C, H, W)
+                e['sym'], _ = self._scale_symbols(e['streams'], 0, (C, H, W), dmll, True, None, e['B'], None)
                 e['hw'] = (H, W)
         prev = dmll
         # ---- every predicted scale, coarse -> fine
         keep = []
         for k in range(1, n_pred + 1):
             scale, dmll, _ = plan[k]
-            n_params = 4 if dmll.rgb_scale else 3
-            Cs = 3 if dmll.rgb_scale else net.config_ms.q.C
-            Kp, Lp = n_params * Cs * K, dmll.L + 1
             hws, pixbase, p = [], [], 0
             for e in st:
-                C, H, W = e['parsed'].scales[k]
-                if (C, H, W) != (Cs, 2 * e['hw'][0], 2 * e['hw'][1]):
-                    raise ValueError('invalid file: scale {} header (C, H, W) = {} but the network predicts {}'.format(
-                        scale, (C, H, W), (Cs, 2 * e['hw'][0], 2 * e['hw'][1])))
+                Cs, H, W = e['parsed'].scales[k]
+                Kp = self._check_header(scale, dmll, (Cs, H, W), e['hw'])
                 pixbase.append(p)
                 p += e['B'] * H * W
                 hws += [H * W] * e['B']
@@ -927,21 +810,11 @@ class Bitcoding(object):
             P_rag, sym_rag, alloc_ev = ragged_buffers(total * Kp, Cs * total)
             rgb_main.wait_event(alloc_ev)
             for g, e in enumerate(st):
-                main, side = e['lane']
+                main = e['lane'][0]
                 main.wait_event(alloc_ev)
                 with torch.cuda.stream(main):
-                    bn = ops.sym_to_bn(e['sym'], prev.bin_width, prev.x_min)
-                    if rgb_net:                                  # BicubicDownsamplingEnc: the decoder is fed value - mean (net.py:72-80)
-                        bn = bn - _rgb_mean_tensor(bn.device)
-                    self._lane_side = side
-                    try:
-                        P, e['F'] = net.get_P(scale, bn, e['F'], n_scales_total=n_pred)
-                    finally:
-                        self._lane_side = None
-                    P = ops.as_pixel_major(P)
                     H, W = e['hw']
-                    if tuple(P.shape) != (e['B'], H, W, Kp):
-                        raise ValueError('invalid file: the network predicts {} at scale {}, the file says {}'.format(tuple(P.shape), scale, (e['B'], H, W, Kp)))
+                    P, e['F'] = self._get_P(scale, n_pred, self._next_input(e['sym'], prev), e['F'], (e['B'], H, W, Kp))
                     P_rag[pixbase[g] * Kp:(pixbase[g] + e['B'] * H * W) * Kp].view(e['B'], H, W, Kp).copy_(P)
                     rgb_main.wait_event(main.record_event())
             # one stream table for the whole group: CHANNEL-major over all images; every entry keeps its own stream buffer, addressed from the lowest one
@@ -965,15 +838,15 @@ class Bitcoding(object):
                 lens_d = ops.upload_small(lens.reshape(-1))
                 if dmll.rgb_scale:
                     min_hw = min(hws)
-                    mode = {'never': 0, 'auto': 1, 'always': 2}[self.rgb_window]
                     probe = self.RGB_PROBE if (self.rgb_window == 'auto' and min_hw >= 16 * self.RGB_PROBE) else 0
                     n_regular = max(1, min(self.RGB_CHUNKS, (min_hw - 2 * probe) // 4096))
                     pix0, npix = ops.ragged_rgb_plan(hws, n_regular, probe)
-                    overlap = Btot >= 16 if self.decode_overlap is None else bool(self.decode_overlap)
                     keep.append(ops.decode_rgb_ragged(P_rag, targets, sym_rag, base_t, offs_d, lens_d, hws, pix0, npix, K,
-                                                      2 if overlap else 1, mode, rgb_side if overlap else None))
+                                                      *self._rgb_schedule(Btot, rgb_side)))
                 else:
-                    keep.append(ops.decode_z_ragged(P_rag, targets, sym_rag, base_t, offs_d, lens_d, hws, Cs, K))
+                    hw = np.asarray(hws, dtype=np.int64)             # every image's whole plane is one entry: pix0 = 0, npix = hw
+                    keep.append(ops.decode_z_entries(P_rag, targets, sym_rag, base_t, offs_d, lens_d, np.cumsum(hw) - hw, hw,
+                                                     np.zeros(Btot, dtype=np.int64), hw, total, Cs, K))
                 done = rgb_main.record_event()
             for g, e in enumerate(st):
                 H, W = e['hw']
@@ -1013,14 +886,14 @@ class Bitcoding(object):
     #                          the host already needs 0.24 s of the 0.35 s to issue them [profiles/r05_decode_chunks_probe.log]
     RGB_CHUNKS_FEW = 32      # ... for a few images: the pipeline's fill (two extra chunk steps) weighs more than a step's launches
 
-    def _decode_rgb_pipelined(self, P, targets, streams, B, C, K, H, W):
+    def _decode_rgb_pipelined(self, P, targets, streams, B, C, K, H, W, side=None):
         """The RGB scale: channel c's means depend on the decoded values of the channels < c AT THE SAME PIXEL
         (logistic_mixture.py:262-272), so R, G and B are three serial chains of H*W symbols that only have to stay a
         chunk of pixels apart.  Pipeline step t: channel c handles chunk t - D c -- its table rows are built straight from P
         and the symbols decoded so far, then ONE grouped launch resumes the range decoders of all active channels side by side.
         Table validity is a device-side flag, nothing synchronises with the host.  Round 6: the whole schedule is ONE call into
         the library (l3c_decode_rgb, csrc/decode_pipeline.hip: a C loop over a workspace -- one grouped table launch and one decoder
-        launch pair per step, a few microseconds of host time each); this method only chooses the chunks, the lag and the row form.
+        launch pair per step, a few microseconds of host time each); this method only chooses the chunks (the lag and the row form: _rgb_schedule).
 
         D = 1 (small batches): everything on the current stream, (chunks + 2) steps of table + decode.
         D = 2 (16 images or more): the channels stay TWO chunks apart, so the tables of step t + 1 need only the symbols of
@@ -1046,12 +919,7 @@ class Bitcoding(object):
             P2 = 2 * self.RGB_PROBE
             bounds = [(0, self.RGB_PROBE), (self.RGB_PROBE, self.RGB_PROBE)] + [(p0, min(step, HW - p0)) for p0 in range(P2, HW, step)]
         sym = torch.zeros(B, C, H, W, dtype=torch.int16, device='cuda')
-        # the two extra steps cost more than the overlap saves while the tables are small (they grow with the batch, a decode
-        # step does not): D = 2 from 16 images on [measured at 128: 0.726 s instead of 0.825 s]; the constructor's decode_overlap forces
-        overlap = B >= 16 if self.decode_overlap is None else bool(self.decode_overlap)
-        mode = {'never': 0, 'auto': 1, 'always': 2}[self.rgb_window]
-        ws, stats = ops.decode_rgb(P, targets, sym, buf, offs, lens, bounds, K, 2 if overlap else 1, mode,
-                                   (getattr(self, '_lane_side', None) or self._side_stream()) if overlap else None)
+        ws, stats = ops.decode_rgb(P, targets, sym, buf, offs, lens, bounds, K, *self._rgb_schedule(B, side))
         self.last_rgb_window_stats = stats      # (development / tests: misses per channel, chunk + 2, image)
         return sym
 
@@ -1143,8 +1011,7 @@ class Bitcoding(object):
         datas = [self._read_file(p) for p in paths]
         groups = {}
         for i, d in enumerate(datas):
-            # the coarsest scale's header (C, H, W) identifies the padded shape; a banded file's header (C, H, W, L) starts at byte 14
-            groups.setdefault(d[:4] + d[14:23] if is_banded(d) else d[8:13], []).append(i)
+            groups.setdefault((is_banded(d), container.padded_shape(d)), []).append(i)
         parts = [None] * len(datas)
         for idxs in groups.values():
             out, padding = self.decode_batch([datas[i] for i in idxs])
@@ -1177,46 +1044,6 @@ def _rgb_mean_tensor(device):
     if key not in _RGB_MEAN_T:
         _RGB_MEAN_T[key] = torch.tensor([float(v) for v in ops.rgb_mean()], dtype=torch.float32, device=device).reshape(1, 3, 1, 1)
     return _RGB_MEAN_T[key]
-
-
-class ParsedContainers(object):
-    """Framing of B `.l3c` files of equally sized images (`parse_containers`): padding tuples, per scale record (coarsest first) its
-    (C, H, W) and, as (B, C) arrays, where every channel's payload lies inside its file (`offset`) and how long it is (`nbytes`)."""
-
-    def __init__(self, padding, scales, offset, nbytes):
-        self.padding, self.scales, self.offset, self.nbytes = padding, scales, offset, nbytes
-
-
-def parse_containers(files):
-    """The byte format of bitcoding.py:326-375 -- u16 x4 padding | per scale (coarsest first): u8 C, u16 H, u16 W | per channel u32 n +
-    payload | 46 E2 84 92 -- walked by its length fields only.  ValueError on broken framing or when the files disagree in shape."""
-    B = len(files)
-    padding, scales, offset, nbytes = [], None, None, None
-    for b, f in enumerate(files):
-        n_rec = count_scale_records(f)
-        if scales is None:
-            scales = [None] * n_rec
-            offset, nbytes = [None] * n_rec, [None] * n_rec
-        elif n_rec != len(scales):
-            raise ValueError('decode_batch needs equally sized images: {} vs {} scale records'.format(n_rec, len(scales)))
-        padding.append(struct.unpack_from('<4H', f, 0))
-        p = 8
-        for k in range(n_rec):
-            shape = struct.unpack_from('<BHH', f, p)
-            p += 5
-            if scales[k] is None:
-                scales[k] = shape
-                offset[k] = np.zeros((B, shape[0]), dtype=np.int64)
-                nbytes[k] = np.zeros((B, shape[0]), dtype=np.int64)
-            elif shape != scales[k]:
-                raise ValueError('decode_batch needs equally sized images, got shapes {}'.format(sorted({shape, scales[k]})))
-            for c in range(shape[0]):
-                n, = struct.unpack_from('<I', f, p)
-                offset[k][b, c] = p + 4
-                nbytes[k][b, c] = n
-                p += 4 + n
-            p += 4                                   # the separator (count_scale_records has checked it)
-    return ParsedContainers(padding, scales, offset, nbytes)
 
 
 class _H2DRing(object):
@@ -1356,28 +1183,6 @@ def _upload_streams(files, parsed):
     return _DeviceStreams(out, dst_d, len_d, first, count, dst, lens, finish)
 
 
-def count_scale_records(data):
-    """Number of scale records of a `.l3c` byte string (u8 C, u16 H, u16 W, C x (u32 n + payload), magic); ValueError if the
-    framing is broken.  An L3C file has num_scales + 1 of them; an RGB Shared file one more per recursion.  A BANDED file is refused
-    here (and so by every reader of the legacy framing: decode_many, dataset_codec.decode_set): `parse_banded` reads those."""
-    if is_banded(data):
-        raise ValueError('banded .l3c file (L3CB format): only Bitcoding.decode_batch / decode read it, not the legacy-format readers')
-    r = _Reader(data)
-    r.take(8)
-    n = 0
-    while r.p < len(data):
-        C, _, _ = r.unpack('<BHH')
-        for _ in range(C):
-            nb, = r.unpack('<I')
-            r.take(nb)
-        if r.take(4) != _MAGIC_VALUE_SEP:
-            raise ValueError('invalid file: scale separator missing')
-        n += 1
-    if n < 2:
-        raise ValueError('invalid file: {} scale record(s)'.format(n))
-    return n
-
-
 class AsyncFileWriter(object):
     """Writes finished `.l3c` byte strings on worker threads (file output is not part of the hot path: reference bitcoding.py:
     326-375 writes from the coding loop).  `wait(path)` blocks until a pending write of `path` is on disk; `close()` drains."""
@@ -1408,18 +1213,3 @@ class AsyncFileWriter(object):
     def close(self):
         self.wait()
         self._pool.shutdown()
-
-
-class _Reader(object):
-    def __init__(self, data):
-        self.d, self.p = data, 0
-
-    def take(self, n):
-        b = self.d[self.p:self.p + n]
-        if len(b) != n:
-            raise ValueError('invalid file: truncated')
-        self.p += n
-        return b
-
-    def unpack(self, fmt):
-        return struct.unpack(fmt, self.take(struct.calcsize(fmt)))

@@ -1,0 +1,217 @@
+"""The host side of the `.l3c` framing, both formats: what a file's bytes mean, and nothing else (no torch, no library call; the device
+reader and writer of the same bytes are csrc/container.hip).
+
+LEGACY files -- the reference's byte format (bitcoding.py:326-375):
+
+    u16 x4  padding (left, right, top, bottom)
+    for scale = coarsest .. 0:   u8 C, u16 H, u16 W;  for each channel: u32 nbytes, payload;  magic 46 E2 84 92
+
+BANDED files (opt-in, Bitcoding(bands=K); INTEGRATION.md "Banded .l3c files"):
+
+    'L3CB' | u8 version = 1 | u8 0 | u16 x4 padding
+    for scale = coarsest .. 0:  u8 C, u16 H, u16 W, u32 L | for channel c: for band j < n = ceil(H*W / L): u32 nbytes, payload | magic
+
+Band j of channel c is pixels [j L, min((j + 1) L, H W)) in raster order, coded as a stream of its own with the legacy format's rows.
+A legacy file cannot start with the signature: its first u16 is the left padding, below the padding factor ('L3' reads 13132).
+An L3C file has num_scales + 1 scale records; an RGB Shared file one more per recursion.  The headers are untrusted input: every reader
+here raises ValueError('invalid file: ...') on broken framing."""
+import struct
+
+import numpy as np
+
+_MAGIC_VALUE_SEP = b'\x46\xE2\x84\x92'
+BANDED_SIGNATURE = b'L3CB'
+BANDED_VERSION = 1
+MAX_BANDS = 1024
+
+
+def band_len(hw, bands):
+    """L_s of a scale of hw symbols for the requested band count K: 64 ceil(hw / (64 K)) -- at most K bands of whole 64-symbol blocks."""
+    if not 1 <= int(bands) <= MAX_BANDS:
+        raise ValueError('bands must be in 1..{}, got {}'.format(MAX_BANDS, bands))
+    return 64 * (-(-int(hw) // (64 * int(bands))))
+
+
+def n_bands(hw, L):
+    return -(-int(hw) // int(L))
+
+
+def is_banded(data):
+    return bytes(data[:4]) == BANDED_SIGNATURE
+
+
+class _Reader(object):
+    def __init__(self, data):
+        self.d, self.p = data, 0
+
+    def take(self, n):
+        b = self.d[self.p:self.p + n]
+        if len(b) != n:
+            raise ValueError('invalid file: truncated')
+        self.p += n
+        return b
+
+    def unpack(self, fmt):
+        return struct.unpack(fmt, self.take(struct.calcsize(fmt)))
+
+
+class ParsedFraming(object):
+    """Where the payloads lie: padding, per scale record (coarsest first) its header (`scales`) and, as int64 arrays, every payload's
+    position inside its file (`offset`) and its length (`nbytes`).
+      parse_containers (B legacy files)   padding: B tuples, scales: (C, H, W),    arrays (B, C)
+      parse_banded (one banded file)      padding: a tuple,  scales: (C, H, W, L), arrays (C, n)
+      parse_batch (B files, either)       padding: B tuples, scales: (S, H, W),    arrays (B, S), S streams per image"""
+
+    def __init__(self, padding, scales, offset, nbytes):
+        self.padding, self.scales, self.offset, self.nbytes = padding, scales, offset, nbytes
+
+
+def count_scale_records(data):
+    """Number of scale records of a legacy `.l3c` byte string; ValueError if the framing is broken.  A BANDED file is refused
+    here (and so by every reader of the legacy framing: decode_many, dataset_codec.decode_set): `parse_banded` reads those."""
+    if is_banded(data):
+        raise ValueError('banded .l3c file (L3CB format): only Bitcoding.decode_batch / decode read it, not the legacy-format readers')
+    r = _Reader(data)
+    r.take(8)
+    n = 0
+    while r.p < len(data):
+        C, _, _ = r.unpack('<BHH')
+        for _ in range(C):
+            nb, = r.unpack('<I')
+            r.take(nb)
+        if r.take(4) != _MAGIC_VALUE_SEP:
+            raise ValueError('invalid file: scale separator missing')
+        n += 1
+    if n < 2:
+        raise ValueError('invalid file: {} scale record(s)'.format(n))
+    return n
+
+
+def parse_containers(files):
+    """B legacy files of equally sized images, walked by their length fields only.  ValueError on broken framing, a record with C == 0,
+    or when the files disagree in shape."""
+    B = len(files)
+    padding, scales, offset, nbytes = [], None, None, None
+    for b, f in enumerate(files):
+        n_rec = count_scale_records(f)
+        if scales is None:
+            scales = [None] * n_rec
+            offset, nbytes = [None] * n_rec, [None] * n_rec
+        elif n_rec != len(scales):
+            raise ValueError('decode_batch needs equally sized images: {} vs {} scale records'.format(n_rec, len(scales)))
+        padding.append(struct.unpack_from('<4H', f, 0))
+        p = 8
+        for k in range(n_rec):
+            shape = struct.unpack_from('<BHH', f, p)
+            p += 5
+            if shape[0] == 0:
+                raise ValueError('invalid file: scale record with C == 0')
+            if scales[k] is None:
+                scales[k] = shape
+                offset[k] = np.zeros((B, shape[0]), dtype=np.int64)
+                nbytes[k] = np.zeros((B, shape[0]), dtype=np.int64)
+            elif shape != scales[k]:
+                raise ValueError('decode_batch needs equally sized images, got shapes {}'.format(sorted({shape, scales[k]})))
+            for c in range(shape[0]):
+                n, = struct.unpack_from('<I', f, p)
+                offset[k][b, c] = p + 4
+                nbytes[k][b, c] = n
+                p += 4 + n
+            p += 4                                   # the separator (count_scale_records has checked it)
+    return ParsedFraming(padding, scales, offset, nbytes)
+
+
+def parse_banded(data):
+    """One banded file, walked by its length fields.  ValueError('invalid file: ...') on an unknown version or reserved byte, C == 0, an empty
+    scale, L == 0 or not a multiple of 64, more than 1024 bands, a length field or payload past the end, a missing magic."""
+    r = _Reader(data)
+    if r.take(4) != BANDED_SIGNATURE:
+        raise ValueError('invalid file: not a banded .l3c file')
+    version, reserved = r.unpack('<BB')
+    if version != BANDED_VERSION:
+        raise ValueError('invalid file: unknown banded format version {}'.format(version))
+    if reserved:
+        raise ValueError('invalid file: reserved byte is {}'.format(reserved))
+    padding = r.unpack('<4H')
+    scales, offset, nbytes = [], [], []
+    while r.p < len(data):
+        C, H, W, L = r.unpack('<BHHI')
+        if C == 0:
+            raise ValueError('invalid file: scale record with C == 0')
+        if H == 0 or W == 0:
+            raise ValueError('invalid file: empty scale {}x{}'.format(H, W))
+        if L == 0 or L % 64:
+            raise ValueError('invalid file: band length {} is not a positive multiple of 64'.format(L))
+        n = n_bands(H * W, L)
+        if n > MAX_BANDS:
+            raise ValueError('invalid file: {} bands per channel (at most {})'.format(n, MAX_BANDS))
+        off = np.zeros((C, n), dtype=np.int64)
+        nb = np.zeros((C, n), dtype=np.int64)
+        for c in range(C):
+            for j in range(n):
+                nb[c, j], = r.unpack('<I')
+                off[c, j] = r.p
+                r.take(int(nb[c, j]))
+        if r.take(4) != _MAGIC_VALUE_SEP:
+            raise ValueError('invalid file: scale separator missing')
+        scales.append((C, H, W, L))
+        offset.append(off)
+        nbytes.append(nb)
+    if len(scales) < 2:
+        raise ValueError('invalid file: {} scale record(s)'.format(len(scales)))
+    return ParsedFraming(padding, scales, offset, nbytes)
+
+
+def parse_batch(files):
+    """The files of one decode_batch call, either format (not mixed) -> (records, streams, banded): `records` the format's own scale
+    headers -- (C, H, W), banded (C, H, W, L) --, the same in every file; `streams` the upload-ready ParsedFraming with every (channel, band) of a
+    banded file as a "channel": S = C n streams per image, stream c n + j."""
+    if not any(is_banded(f) for f in files):
+        streams = parse_containers(files)
+        return streams.scales, streams, False
+    if not all(is_banded(f) for f in files):
+        raise ValueError('decode_batch: a batch mixes banded and legacy .l3c files')
+    parsed = [parse_banded(f) for f in files]
+    records = parsed[0].scales
+    for p in parsed[1:]:
+        if len(p.scales) != len(records) or any(a[:3] != b[:3] for a, b in zip(p.scales, records)):
+            raise ValueError('decode_batch needs equally sized images, got scale records {} and {}'.format(
+                [s[:3] for s in records], [s[:3] for s in p.scales]))
+        if any(a[3] != b[3] for a, b in zip(p.scales, records)):
+            raise ValueError('decode_batch: banded files of one batch must share the band length of every scale, got {} and {}'.format(
+                [s[3] for s in records], [s[3] for s in p.scales]))
+    return records, ParsedFraming([p.padding for p in parsed], [(C * n_bands(H * W, L), H, W) for C, H, W, L in records],
+                                  [np.stack([p.offset[k].reshape(-1) for p in parsed]) for k in range(len(records))],
+                                  [np.stack([p.nbytes[k].reshape(-1) for p in parsed]) for k in range(len(records))]), True
+
+
+def padded_shape(data):
+    """(H, W) of the PADDED image a file of either format holds: 2**(records - 1) times its first (coarsest) scale record's H, W.
+    Cheap: the record count comes from walking the length fields, no payload is touched."""
+    if is_banded(data):
+        scales = parse_banded(data).scales
+        n, (_, H, W, _) = len(scales), scales[0]
+    else:
+        n = count_scale_records(data)
+        _, H, W = struct.unpack_from('<BHH', data, 8)
+    return (H << (n - 1), W << (n - 1))
+
+
+def framing_bytes(scales, banded):
+    """Bytes of a file that are not payload.  scales: the headers (C, H, W), banded (C, H, W, L)."""
+    if banded:
+        return 14 + sum(9 + 4 * C * n_bands(H * W, L) + 4 for C, H, W, L in scales)
+    return 8 + sum(5 + 4 * C + 4 for C, _, _ in scales)
+
+
+def write_file(padding, scales, payloads, banded):
+    """-> the bytes of one file.  scales: (C, H, W) headers for a legacy file, payloads[k][c] the bytes of channel c of record k;
+    (C, H, W, L) headers for a banded file, payloads[k][c] the list of that channel's band payloads."""
+    chunks = [BANDED_SIGNATURE, struct.pack('<BB4H', BANDED_VERSION, 0, *padding)] if banded else [struct.pack('<4H', *padding)]
+    for header, channels in zip(scales, payloads):
+        chunks.append(struct.pack('<BHHI' if banded else '<BHH', *header))
+        for c in channels:
+            for p in (c if banded else [c]):
+                chunks += [struct.pack('<I', len(p)), p]
+        chunks.append(_MAGIC_VALUE_SEP)
+    return b''.join(chunks)

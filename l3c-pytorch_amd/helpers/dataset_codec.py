@@ -186,14 +186,9 @@ def encode_set(bc, imgs, order, max_batch=16, fac=8, marks=None, n_groups=None, 
 
 
 def file_padded_shape(data):
-    """(H, W) of the PADDED image a `.l3c` byte string holds, from its first (coarsest) scale record alone: u16 x4 padding, then
-    u8 C, u16 H, u16 W of the coarsest scale (reference bitcoding.py:326-375) -- the image is 2**(records - 1) times that.  Cheap: the
-    record count comes from walking the length fields, no payload is touched."""
-    import struct
-    from ..bitcoding.bitcoding import count_scale_records
-    n = count_scale_records(data)
-    _, H, W = struct.unpack_from('<BHH', data, 8)
-    return (H << (n - 1), W << (n - 1))
+    """(H, W) of the PADDED image a `.l3c` byte string holds, from its headers alone: no payload is touched (container.padded_shape)."""
+    from ..bitcoding import container
+    return container.padded_shape(data)
 
 
 def plan_decode_set(files, order, max_batch):

@@ -3,6 +3,7 @@ the current stream here; every function enqueues kernels from libl3c_hip.so and 
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -111,6 +112,22 @@ class PackedConv(object):
         return (H + 2 * pad - ext) // self.stride + 1, (W + 2 * pad - ext) // self.stride + 1
 
 
+def _conv_desc(x, layer, out, in_coff, out_coff, packed_w, ks_stride_dilation, bias=None, residual=None, res_coff=0, epilogue=0):
+    """The ConvDesc of one launch of `layer` on x (B,H,W,cstride) into `out`: `packed_w` the weights in the kernel's own form,
+    ks_stride_dilation what that kernel is told it runs (a polyphase launch is not the layer's 5x5 stride 2)."""
+    B, H, W, cstride = x.shape
+    d = ConvDesc()
+    d.inp, d.in_cstride, d.in_coff = ptr(x, torch.float32), cstride, in_coff
+    d.packed_w, d.bias = ptr(packed_w), ptr(layer.bias if bias is None else bias)
+    d.residual = ptr(residual, torch.float32) if residual is not None else None
+    d.res_cstride, d.res_coff = (residual.shape[-1] if residual is not None else 0), res_coff
+    d.out, d.out_cstride, d.out_coff = ptr(out, torch.float32), out.shape[-1], out_coff
+    d.B, d.Hin, d.Win, d.Cin, d.Cout = B, H, W, layer.Cin, layer.Cout
+    d.KS, d.stride, d.dilation = ks_stride_dilation
+    d.epilogue = epilogue
+    return d
+
+
 def conv(x, layer, out=None, in_coff=0, out_coff=0, residual=None, res_coff=0, relu=False, pixel_shuffle=False, impl=None):
     """x: (B,H,W,cstride) pixel-major fp32.  Returns `out` ((B,Ho,Wo,Cout) freshly allocated when None).  impl: None = the
     product's dispatch (see above); a name forces one kernel (tests, probes)."""
@@ -143,33 +160,19 @@ def conv(x, layer, out=None, in_coff=0, out_coff=0, residual=None, res_coff=0, r
         kernel = impl
     if kernel == 'wino4w':      # probe kernel of the test-only library: 3x3 / stride 1 / dilation 1, bias (+ ReLU)
         assert layer.KS == 3 and layer.stride == 1 and layer.dilation == 1 and residual is None and not pixel_shuffle
-        d = ConvDesc()
-        d.inp, d.in_cstride, d.in_coff = ptr(x, torch.float32), cstride, in_coff
-        d.packed_w, d.bias = ptr(layer.packed_wino4w()), ptr(layer.bias)
-        d.out, d.out_cstride, d.out_coff = ptr(out, torch.float32), out.shape[-1], out_coff
-        d.B, d.Hin, d.Win, d.Cin, d.Cout = B, H, W, layer.Cin, layer.Cout
-        d.KS, d.stride, d.dilation = 3, 1, 1
-        d.epilogue = _lib.EPI_RELU if relu else 0
+        d = _conv_desc(x, layer, out, in_coff, out_coff, layer.packed_wino4w(), (3, 1, 1), epilogue=_lib.EPI_RELU if relu else 0)
         _lib.call_xcheck('l3c_conv_wino4w', d, int(os.environ.get('L3C_W4W_TPB', '0')), stream())
         return out
     if kernel in ('wino4', 'wino2'):
         assert wino_ok and (kernel == 'wino2' or layer.packed_wino4 is not None), 'this layer / epilogue has no Winograd form'
     if kernel == 'gemm' and layer.packed is None:
         raise _lib.L3CError('convolution outside every MFMA kernel\'s preconditions (Cin % 16 != 0)')
-    d = ConvDesc()
-    d.inp, d.in_cstride, d.in_coff = ptr(x, torch.float32), cstride, in_coff
-    d.packed_w = ptr({'wino4': layer.packed_wino4_shuffle() if (kernel == 'wino4' and pixel_shuffle) else layer.packed_wino4,
-                      'pw': layer.packed_pw, 'gemm': layer.packed, 'direct': layer.weight}[kernel]
-                     if kernel != 'wino2' else layer.packed_wino2())
-    d.bias = ptr(layer.bias)
-    d.residual = ptr(residual, torch.float32) if residual is not None else None
-    d.res_cstride = residual.shape[-1] if residual is not None else 0
-    d.res_coff = res_coff
-    d.out, d.out_cstride, d.out_coff = ptr(out, torch.float32), out.shape[-1], out_coff
-    d.B, d.Hin, d.Win, d.Cin, d.Cout = B, H, W, layer.Cin, layer.Cout
-    d.KS, d.stride, d.dilation = layer.KS, layer.stride, layer.dilation
-    d.epilogue = ((_lib.EPI_RELU if relu else 0) | (_lib.EPI_RESIDUAL if residual is not None else 0) |
-                  (_lib.EPI_PIXEL_SHUFFLE if pixel_shuffle else 0))
+    packed_w = ({'wino4': layer.packed_wino4_shuffle() if (kernel == 'wino4' and pixel_shuffle) else layer.packed_wino4,
+                 'pw': layer.packed_pw, 'gemm': layer.packed, 'direct': layer.weight}[kernel]
+                if kernel != 'wino2' else layer.packed_wino2())
+    d = _conv_desc(x, layer, out, in_coff, out_coff, packed_w, (layer.KS, layer.stride, layer.dilation), residual=residual, res_coff=res_coff,
+                   epilogue=((_lib.EPI_RELU if relu else 0) | (_lib.EPI_RESIDUAL if residual is not None else 0) |
+                             (_lib.EPI_PIXEL_SHUFFLE if pixel_shuffle else 0)))
     if kernel == 'wino2':
         _lib.call_xcheck('l3c_conv_wino', d, stream())
         return out
@@ -201,24 +204,12 @@ def _conv_poly5(x, layer, out, in_coff, out_coff, fused=True):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
     if fused:
-        d = ConvDesc()
-        d.inp, d.in_cstride, d.in_coff = ptr(x, torch.float32), cstride, in_coff
-        d.packed_w, d.bias, d.residual = ptr(layer.packed_poly_fused), ptr(layer.bias), None
-        d.out, d.out_cstride, d.out_coff = ptr(out, torch.float32), out.shape[-1], out_coff
-        d.B, d.Hin, d.Win, d.Cin, d.Cout = B, H, W, layer.Cin, layer.Cout
-        d.KS, d.stride, d.dilation, d.epilogue = 5, 2, 1, 0
+        d = _conv_desc(x, layer, out, in_coff, out_coff, layer.packed_poly_fused, (5, 2, 1))
         call('l3c_conv_wino4_stride2', d, stream())
     for k, (a, b) in enumerate(() if fused else ((0, 0), (0, 1), (1, 0), (1, 1))):
-        d = ConvDesc()
-        d.inp, d.in_cstride, d.in_coff = ptr(x, torch.float32), cstride, in_coff
-        d.packed_w = ptr(layer.packed_poly()[k])
-        d.bias = ptr(layer.bias if k == 0 else layer._zero_bias)
-        d.residual = ptr(out, torch.float32) if k else None
-        d.res_cstride, d.res_coff = (out.shape[-1], out_coff) if k else (0, 0)
-        d.out, d.out_cstride, d.out_coff = ptr(out, torch.float32), out.shape[-1], out_coff
-        d.B, d.Hin, d.Win, d.Cin, d.Cout = B, H, W, layer.Cin, layer.Cout
-        d.KS, d.stride, d.dilation = 3, 2, 1
-        d.epilogue = _lib.EPI_RESIDUAL if k else 0
+        packed_w = layer.packed_poly()[k]             # (also makes layer._zero_bias)
+        d = _conv_desc(x, layer, out, in_coff, out_coff, packed_w, (3, 2, 1), bias=layer.bias if k == 0 else layer._zero_bias,
+                       residual=out if k else None, res_coff=out_coff if k else 0, epilogue=_lib.EPI_RESIDUAL if k else 0)
         call('l3c_conv_wino4_phase', d, a, b, stream())
     if PROFILE is not None:
         e1.record()
@@ -384,7 +375,6 @@ def decode_rgb(P_nhwc, targets, sym, buf, offs, lens, bounds, K, lag, window_mod
     CHANNEL-major in (buf, offs int64 (3B,), lens int32 (3B,)), bounds = [(pix0, npix)] tiling H*W.  lag 2 decodes on `side_stream` (a
     torch stream) while the current stream builds the next step's tables.  -> (workspace tensor, window statistics view (3, chunks + 2, B)
     or None); the current stream is ordered after the last symbols."""
-    import ctypes
     lib = _lib.load()
     B, H, W, _ = P_nhwc.shape
     n = len(bounds)
@@ -415,7 +405,6 @@ _PINNED_SCRATCH = {'bufs': [None] * 16, 'events': [None] * 16, 'turn': 0}
 def upload_small(array):
     """numpy array -> device tensor of the same dtype through a small ring of page-locked buffers (an H2D copy from pageable memory makes the
     host wait for the stream): descriptor tables of a few KB."""
-    import numpy as np
     a = np.ascontiguousarray(array)
     r = _PINNED_SCRATCH
     k = r['turn'] = (r['turn'] + 1) % len(r['bufs'])
@@ -435,7 +424,6 @@ def ragged_rgb_plan(hws, n_regular, probe):
     """Chunk plan of a RAGGED RGB decode (l3c_decode_rgb_ragged): every image gets the same NUMBER of chunks -- two probe chunks of `probe`
     symbols (0: none) and n_regular regular ones, the image's own chunk length rounded DOWN to a multiple of 64 with the last chunk taking
     the rest -- so that all images step through the pipeline together.  hws: pixels per image.  -> (pix0, npix) int64 arrays (n_chunks, B)."""
-    import numpy as np
     B = len(hws)
     n_chunks = n_regular + (2 if probe else 0)
     pix0 = np.zeros((n_chunks, B), dtype=np.int64)
@@ -457,8 +445,6 @@ def decode_rgb_ragged(P_ragged, targets, sym_ragged, buf, offs, lens, hws, pix0,
     """The RGB scale of B images of DIFFERENT sizes in lock step (l3c_decode_rgb_ragged): P_ragged (sum HW, 120) fp32, sym_ragged int16
     (3 * sum HW,) ZEROED (image b: its three planes from element 3 * pixbase[b]), streams CHANNEL-major in (buf, offs (3B,), lens (3B,)),
     hws = pixels per image, (pix0, npix) = ragged_rgb_plan(...).  -> workspace tensor (kept alive by the caller until the stream is done)."""
-    import ctypes
-    import numpy as np
     lib = _lib.load()
     B, n = len(hws), pix0.shape[0]
     hw = np.asarray(hws, dtype=np.int64)
@@ -483,74 +469,35 @@ def decode_rgb_ragged(P_ragged, targets, sym_ragged, buf, offs, lens, hws, pix0,
     return ws, tables
 
 
-def decode_z_ragged(P_ragged, targets, sym_ragged, buf, offs, lens, hws, C, K):
-    """A bottleneck scale of B images of DIFFERENT sizes: its C channels are independent given P, so ONE ragged table launch
-    (l3c_dmll_cdf_table_ragged, C parts) and ONE ragged decoder launch (l3c_ac_decode_chunks with the r_* fields) decode every image and
-    channel side by side.  P_ragged (sum HW, 3 C K) fp32; sym_ragged int16 (C * sum HW,): image b's C planes from element C * pixbase[b];
-    streams CHANNEL-major in (buf, offs (C B,), lens (C B,)).  -> tensors to keep alive until the stream is done."""
-    import ctypes
-    import numpy as np
-    B = len(hws)
+def decode_z_entries(P, targets, sym, buf, offs, lens, pixbase, hw, pix0, npix, total_pix, C, K):
+    """A bottleneck scale as S ragged ENTRIES: its C channels are independent given P, so ONE ragged table launch (l3c_dmll_cdf_table_ragged,
+    C parts) and ONE ragged decoder launch (l3c_ac_decode_chunks with the r_* fields) decode every entry and channel side by side.  Entry s
+    (int64 arrays of S) is pixels [pix0, pix0 + npix) of an image of hw pixels that starts at pixel pixbase of P ((total_pix, 3 C K) fp32):
+    a whole image of a set of DIFFERENT sizes, or one band of a banded file.  sym int16 (C * total_pix,) receives the symbols, an image's C
+    planes from element C * pixbase; streams in (buf, offs (C S,), lens (C S,)) with stream (c, s) at index c S + s.
+    -> tensors to keep alive until the stream is done."""
     assert C <= 8
-    hw = np.asarray(hws, dtype=np.int64)
-    pixbase = np.concatenate([[0], np.cumsum(hw)[:-1]]).astype(np.int64)
+    S = len(hw)
     Lp = targets.shape[0]
-    table_off = pixbase * (Lp * 2)                    # every image's whole plane is one range: npix = hw, pix0 = 0
-    tables = upload_small(np.concatenate([pixbase, hw, np.zeros(B, dtype=np.int64), hw, table_off]).astype(np.int64))
+    tables = upload_small(np.concatenate([pixbase, hw, pix0, npix, (pixbase + pix0) * (Lp * 2)]).astype(np.int64))
     base = tables.data_ptr()
-    total = int(hw.sum())
-    flag = torch.zeros(1, dtype=torch.int32, device=P_ragged.device)
-    tabs = [torch.empty(total * Lp, dtype=torch.int16, device=P_ragged.device) for _ in range(C)]
-    batch = _lib.RaggedBatch(B, int(hw.max()), base, base + 8 * B)
+    max_hw, max_npix = int(np.max(hw)), int(np.max(npix))
+    flag = torch.zeros(1, dtype=torch.int32, device=P.device)
+    tabs = [torch.empty(total_pix * Lp, dtype=torch.int16, device=P.device) for _ in range(C)]
+    batch = _lib.RaggedBatch(S, max_hw, base, base + 8 * S)
     tparts = (_lib.TablePart * C)()
     rparts = (_lib.RaggedPart * C)()
     dparts = (_lib.AcDecodePart * C)()
     for c in range(C):
-        tparts[c] = _lib.TablePart(c, 0, int(hw.max()), ptr(tabs[c]), ptr(flag, torch.int32), None)
-        rparts[c] = _lib.RaggedPart(base + 16 * B, base + 24 * B, base + 32 * B)
-        d = _lib.AcDecodePart(ptr(tabs[c]), Lp, ptr(buf, torch.uint8), ptr(offs[c * B:(c + 1) * B], torch.int64), ptr(lens[c * B:(c + 1) * B], torch.int32),
-                              B, int(hw.max()), ptr(flag, torch.int32), None, None, 1, ptr(sym_ragged, torch.int16), 0, 0)
-        d.r_npix, d.r_table_off, d.r_pixbase, d.r_hw, d.r_pix0 = base + 24 * B, base + 32 * B, base, base + 8 * B, base + 16 * B
-        d.r_C, d.r_c, d.r_table_bytes = C, c, total * Lp * 2
-        dparts[c] = d
-    call('l3c_dmll_cdf_table_ragged', ptr(P_ragged, torch.float32), None, ptr(targets, torch.float32), ctypes.byref(batch), C, K, 0, Lp,
-         tparts, rparts, C, stream())
-    call('l3c_ac_decode_chunks', dparts, C, stream())
-    return tabs, tables, flag
-
-
-def decode_z_banded(P_nhwc, targets, sym, buf, offs, lens, B, C, HW, band_len, K):
-    """A bottleneck scale of banded files: every band (b, j) of every channel is a ragged entry (pixbase b HW, hw HW, pixels [j L, j L +
-    len_j)), so ONE ragged table launch (C parts) and ONE ragged decoder launch decode all B C n band streams.  sym int16 (B, C, HW) receives
-    the symbols; streams in (buf, offs, lens) with stream (c, b, j) at index (c B + b) n + j.  -> tensors to keep alive until the stream is done."""
-    import ctypes
-    import numpy as np
-    assert C <= 8
-    n = -(-HW // band_len)
-    S = B * n
-    Lp = targets.shape[0]
-    j = np.tile(np.arange(n, dtype=np.int64), B)
-    b = np.repeat(np.arange(B, dtype=np.int64), n)
-    pix0 = j * band_len
-    npix = np.minimum(band_len, HW - pix0)
-    tables = upload_small(np.concatenate([b * HW, np.full(S, HW, dtype=np.int64), pix0, npix, (b * HW + pix0) * (Lp * 2)]).astype(np.int64))
-    base = tables.data_ptr()
-    flag = torch.zeros(1, dtype=torch.int32, device=P_nhwc.device)
-    tabs = [torch.empty(B * HW * Lp, dtype=torch.int16, device=P_nhwc.device) for _ in range(C)]
-    batch = _lib.RaggedBatch(S, HW, base, base + 8 * S)
-    tparts = (_lib.TablePart * C)()
-    rparts = (_lib.RaggedPart * C)()
-    dparts = (_lib.AcDecodePart * C)()
-    for c in range(C):
-        tparts[c] = _lib.TablePart(c, 0, int(npix.max()), ptr(tabs[c]), ptr(flag, torch.int32), None)
+        tparts[c] = _lib.TablePart(c, 0, max_npix, ptr(tabs[c]), ptr(flag, torch.int32), None)
         rparts[c] = _lib.RaggedPart(base + 16 * S, base + 24 * S, base + 32 * S)
         d = _lib.AcDecodePart(ptr(tabs[c]), Lp, ptr(buf, torch.uint8), ptr(offs[c * S:(c + 1) * S], torch.int64),
-                              ptr(lens[c * S:(c + 1) * S], torch.int32), S, int(npix.max()), ptr(flag, torch.int32), None, None, 1,
+                              ptr(lens[c * S:(c + 1) * S], torch.int32), S, max_npix, ptr(flag, torch.int32), None, None, 1,
                               ptr(sym, torch.int16), 0, 0)
         d.r_npix, d.r_table_off, d.r_pixbase, d.r_hw, d.r_pix0 = base + 24 * S, base + 32 * S, base, base + 8 * S, base + 16 * S
-        d.r_C, d.r_c, d.r_table_bytes = C, c, B * HW * Lp * 2
+        d.r_C, d.r_c, d.r_table_bytes = C, c, total_pix * Lp * 2
         dparts[c] = d
-    call('l3c_dmll_cdf_table_ragged', ptr(P_nhwc, torch.float32), None, ptr(targets, torch.float32), ctypes.byref(batch), C, K, 0, Lp,
+    call('l3c_dmll_cdf_table_ragged', ptr(P, torch.float32), None, ptr(targets, torch.float32), ctypes.byref(batch), C, K, 0, Lp,
          tparts, rparts, C, stream())
     call('l3c_ac_decode_chunks', dparts, C, stream())
     return tabs, tables, flag
@@ -559,7 +506,6 @@ def decode_z_banded(P_nhwc, targets, sym, buf, offs, lens, B, C, HW, band_len, K
 def decode_rgb_banded(P_nhwc, targets, sym, buf, offs, lens, band_len, n_chunks, K, lag, window_mode, side_stream=None):
     """An RGB scale of banded files in one host call (l3c_decode_rgb_banded): P (B,H,W,120), sym int16 (B,3,H,W) ZEROED, the band streams in
     (buf, offs, lens) with stream (c, b, j) at index (c B + b) n + j.  -> workspace tensor; the current stream is ordered after the symbols."""
-    import ctypes
     lib = _lib.load()
     B, H, W, _ = P_nhwc.shape
     HW = H * W
@@ -677,7 +623,6 @@ def ac_encode_groups(groups):
 
 def pack_streams(payloads, device='cuda'):
     """list of bytes -> (uint8 buffer with every stream 4-byte aligned and zero padded, offsets int64, nbytes int32)."""
-    import numpy as np
     offs, pos = [], 0
     for p in payloads:
         offs.append(pos)

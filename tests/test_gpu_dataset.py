@@ -246,7 +246,8 @@ def test_set_decoder_rejects_files_that_do_not_fit_the_model_and_survives_them(l
     """The headers of a `.l3c` file are untrusted input (the reference fails with a shape error, bitcoding.py:248-266): a wrong H in a scale
     record, a record missing, a truncated file, a file of the other model family -> ValueError from `decode_batch` AND from the ragged set
     path (before any kernel indexes P with them); payload bytes that are noise decode to SOME pixels of the right shape, like the reference's
-    decoder does; and the same Bitcoding object decodes a good set afterwards (streams, rings and events are left usable)."""
+    decoder does; and the same Bitcoding object decodes a good set afterwards (streams, rings and events are left usable).  The header edits
+    are made in legacy files (both readers) and in banded encodings of the same image (`decode_batch`): the checks are shared by the formats."""
     import struct
     import numpy as np
     from l3c_pytorch_amd.bitcoding.bitcoding import Bitcoding
@@ -286,6 +287,9 @@ def test_set_decoder_rejects_files_that_do_not_fit_the_model_and_survives_them(l
     b = bytearray(good)
     b[recs[0][0]] = 7                                                     # the coarsest record says 7 channels: the framing no longer parses
     bad['wrong C at the coarsest scale'] = bytes(b)
+    b = bytearray(good)
+    b[recs[-1][0]] = 0                                                    # the RGB record says no channels
+    bad['C == 0 at the RGB scale'] = bytes(b)
     bad['truncated'] = good[:len(good) - 37]
     bad['a record missing'] = good[:8] + good[recs[1][0]:]
     cfg_rgb = config_parser.parse_builtin('ms', 'cr_rgb_shared')
@@ -300,6 +304,40 @@ def test_set_decoder_rejects_files_that_do_not_fit_the_model_and_survives_them(l
         with pytest.raises(ValueError):
             dataset_codec.decode_set(bc, {**files, 1: f}, order, max_batch=2)
         torch.cuda.synchronize()
+    # the same header edits in BANDED files of the same image (record header u8 C, u16 H, u16 W, u32 L from byte 14): the shared checks through
+    # the other format
+    from l3c_pytorch_amd.bitcoding.bitcoding import parse_banded
+    bcb = Bitcoding(bp, bands=4)
+    padded = imgs[1].unsqueeze(0).long()                                  # 72 x 88: multiples of the padding factor
+    goodb = bcb.encode_batch(padded).to_bytes()[0]
+    back, _ = bcb.decode_batch([goodb])
+    assert torch.equal(back.cpu(), padded)
+    pb = parse_banded(goodb)
+    hdr = [int(pb.offset[k][0, 0]) - 4 - 9 for k in range(4)]               # offset of every record's header
+    assert [struct.unpack_from('<BHH', goodb, h) for h in hdr] == [r[1:4] for r in recs]
+    badb = {}
+    b = bytearray(goodb)
+    struct.pack_into('<H', b, hdr[-1] + 1, 80)
+    badb['wrong H at the RGB scale'] = bytes(b)
+    b = bytearray(goodb)
+    struct.pack_into('<H', b, hdr[1] + 3, recs[1][3] * 2)
+    badb['wrong W at a bottleneck scale'] = bytes(b)
+    b = bytearray(goodb)
+    b[hdr[0]] = 7
+    badb['wrong C at the coarsest scale'] = bytes(b)
+    b = bytearray(goodb)
+    b[hdr[-1]] = 0
+    badb['C == 0 at the RGB scale'] = bytes(b)
+    badb['truncated'] = goodb[:len(goodb) - 37]
+    badb['a record missing'] = goodb[:14] + goodb[hdr[1]:]
+    badb['a file of the RGB Shared model (five records)'] = Bitcoding(bp_rgb, auto_recurse=3, bands=4).encode_batch(
+        synthetic.make_image(96, 160, 1, 'natural').unsqueeze(0).long()).to_bytes()[0]
+    for name, f in badb.items():
+        with pytest.raises(ValueError):
+            bcb.decode_batch([f])
+        torch.cuda.synchronize()
+    back, _ = bcb.decode_batch([goodb])
+    assert torch.equal(back.cpu(), padded)
     # noise in the payloads, framing intact: decodes to pixels of the right shape (whatever they are), no error, no hang
     rng = np.random.RandomState(5)
     b = bytearray(good)

@@ -456,6 +456,31 @@ def test_container_framing_parser_and_set_decode_plan():
     c = make([(5, 8, 6), (5, 16, 12), (5, 32, 24), (3, 64, 48)], [[1] * 5, [2] * 5, [3] * 5, [4, 5, 6]])
     chunks, padded = dataset_codec.plan_decode_set({0: a, 1: c, 2: b, 3: a, 4: a}, [0, 1, 2, 3, 4], 3)
     assert sorted(map(tuple, chunks)) == [(0, 2, 3), (1,), (4,)] and sorted(padded) == [(32, 48), (32, 48), (64, 48)]
+    # a record that says C == 0 parses as framing (no length fields follow it) but is no scale: the documented ValueError, not an IndexError
+    # from the uploader
+    for zero in (make(sh[:3] + [(0, 32, 48)], [[1] * 5, [2] * 5, [3] * 5, []]), make([(0, 4, 6)] + sh[1:], [[], [2] * 5, [3] * 5, [4, 5, 6]])):
+        with pytest.raises(ValueError, match='invalid file'):
+            parse_containers([zero])
+        with pytest.raises(ValueError, match='invalid file'):
+            parse_containers([a, zero])
+    # the padded shape of either format comes from one place
+    from l3c_pytorch_amd.bitcoding import container
+    from tests.test_banded_format import banded_file
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+    for name, shape in (('hip_l3c_cal_64x96.l3c', (64, 96)), ('hip_rgb_shared_32x48_r3.l3c', (32, 48))):
+        data = open(os.path.join(golden, name), 'rb').read()
+        assert container.padded_shape(data) == dataset_codec.file_padded_shape(data) == shape
+    assert container.padded_shape(a) == (32, 48) and container.padded_shape(c) == (64, 48)
+    banded = banded_file([(5, 3, 5, 64, [[b'ab']] * 5), (5, 6, 10, 64, [[b'c']] * 5), (3, 12, 20, 128, [[b'de', b'f']] * 3)], padding=(0, 2, 0, 1))
+    assert container.padded_shape(banded) == (12, 20)
+
+    # the module describes bytes: a fresh interpreter that imports it has loaded neither torch nor the HIP library's binding
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, {!r}); import l3c_pytorch_amd.bitcoding.container as c; "
+            "assert 'torch' not in sys.modules, 'torch'; assert 'l3c_pytorch_amd._lib' not in sys.modules and 'l3c_pytorch_amd.ops' not in sys.modules; "
+            "assert c.is_banded(c.BANDED_SIGNATURE)").format(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    subprocess.run([sys.executable, '-s', '-c', code], check=True)
 
 
 def test_balanced_cu_sets_hold_every_xcd_equally():

@@ -5,6 +5,8 @@ convolutions, a stream pair per group parity runs the tables and chains), agains
 
 NOT in the product (measured: 143.9 against 142.4 MPix/s, profiles/r06_decode_phase_overlap_probe.log): the probe needs the two-slot form of
 decode_many that profiles/r06_decode_phase_overlap.patch adds (`git apply profiles/r06_decode_phase_overlap.patch`).
+The patch is a record and is not maintained: the last commit it can be tried on is c5ad0a4 (profiles/README.md, "Patches kept as
+records"); this probe only runs on such a checkout.
 
 usage: python tools/decode_phase_overlap_probe.py [B] [n_batches]"""
 import os

@@ -17,7 +17,7 @@ files = bc.encode_batch(imgs.float()).to_bytes()
 del imgs
 torch.cuda.synchronize()
 marks = {}
-orig_upload, orig_parse = bcm._upload_streams, bcm.parse_containers
+orig_upload = bcm._upload_streams
 
 
 def upload(files_, parsed):
