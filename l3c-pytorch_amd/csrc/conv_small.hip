@@ -354,12 +354,16 @@ int l3c_rgb_head(const float *img, const float *w1, const float *b1, const float
     return l3c::check_launch("rgb_head_kernel");
 }
 
+// Contract of the entry (with the limits checked below): `feat` is 16-byte aligned -- the tile kernel AND the direct kernel read a pixel's
+// features with 16-byte loads.  A misaligned `feat` is refused (L3C_ERR_INVALID_ARG, nothing launched); it used to be sent to the direct
+// kernel, whose loads need the alignment just the same.
 int l3c_to_q_quantize(const float *feat, const float *w, const float *b, const float *levels, int64_t B, int64_t HW,
                       int Cf, int C, int L, int16_t *sym, float *bn_q, float *bn, l3c_stream_t stream) {
     L3C_REQUIRE(feat && w && b && levels && sym && bn_q, "null pointer");
     L3C_REQUIRE(B > 0 && HW > 0 && Cf % 4 == 0 && C > 0 && C <= 8 && L > 0 && L <= 32767, "bad shape (C <= 8)");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(feat) & 15) == 0, "feat must be 16-byte aligned (both kernels read it with 16-byte loads)");
 #ifndef L3C_TO_Q_DIRECT
-    if (Cf <= TQ_MAX_CF && (reinterpret_cast<uintptr_t>(feat) & 15) == 0) {
+    if (Cf <= TQ_MAX_CF) {
         int64_t tiles = (B * HW + TQ_PIX - 1) / TQ_PIX;
         if (tiles > L3C_TQ_GRID) tiles = L3C_TQ_GRID;
         hipLaunchKernelGGL(to_q_quantize_tile_kernel, dim3((unsigned)tiles), dim3(TQ_PIX), 0, l3c::as_stream(stream), feat, w, b,

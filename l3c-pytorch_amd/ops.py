@@ -230,7 +230,9 @@ def rgb_head(img, ms1_w, ms1_b, ms2_w, ms2_b, conv_w, conv_b, want_shifted=False
 
 
 def to_q_quantize(feat, w, b, levels, want_bn=False):
-    """feat (B,H,W,Cf) -> sym int16 (B,C,H,W), bn_q fp32 (B,C,H,W) [, bn pre-quantisation]."""
+    """feat (B,H,W,Cf) -> sym int16 (B,C,H,W), bn_q fp32 (B,C,H,W) [, bn pre-quantisation].
+    `feat` must start on a 16-byte boundary (every torch allocation and every whole-pixel slice of one does): the library refuses
+    anything else with L3C_ERR_INVALID_ARG -- its kernels read a pixel's features with 16-byte loads."""
     B, H, W, Cf = feat.shape
     C, L = w.shape[0], levels.shape[0]
     sym = torch.empty(B, C, H, W, dtype=torch.int16, device=feat.device)
