@@ -291,6 +291,40 @@ typedef struct {
 } l3c_rgb_banded_desc;
 int64_t l3c_decode_rgb_banded_workspace_bytes(int64_t B, int64_t HW, int64_t band_len, int n_chunks, int lag);
 int l3c_decode_rgb_banded(const l3c_rgb_banded_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
+/*
+ * The RGB scale of a SET of banded files -- images of different sizes, band lengths that differ from image to image -- as S arbitrary
+ * ENTRIES in lock step: entry e is pixels [pix0_e, pix0_e + len_e) of an image of hw_e pixels that starts at pixel pixbase_e of the ragged
+ * P ([total_pix][120]) and symbol buffers (the image's 3 planes of hw_e symbols from element 3 * pixbase_e; ZEROED by the caller).  Every
+ * entry is cut into n_chunks chunks of step_e = 64 * ceil(len_e / (64 * n_chunks)) symbols: chunk k covers [k step_e, min((k + 1) step_e,
+ * len_e)), the trailing chunks of a short entry are EMPTY (its decoder only carries its state on) and its stream ends with its last
+ * non-empty chunk -- so a 64-symbol band beside a 32 768-symbol one does not pull the whole call down to one chunk.
+ *   entries_dev / entries_host   the same int64 table on the device and on the host: pixbase [S] | hw [S] | pix0 [S] | len [S]; the host copy
+ *                is checked against total_pix and sizes the launches, and is not read after the call returns
+ *   in / in_offsets / in_nbytes   the 3 S streams, CHANNEL-major: stream (c, e) at index c * S + e (4-byte aligned, zero padded)
+ *   K, lag, window_mode   as for l3c_rgb_decode_desc (window rows follow every entry's own statistics two of ITS chunks earlier)
+ * S < 65536 (slice a larger set).  The chunk plan (the layout of l3c_rgb_ragged_desc.tables_dev, then every entry's final chunk) is written
+ * into the workspace by a kernel on main_stream; nothing synchronises with the host.
+ */
+typedef struct {
+    const float *P;
+    const float *targets;
+    int16_t *sym;
+    int64_t S;
+    int64_t total_pix;
+    const int64_t *entries_dev;
+    const int64_t *entries_host;
+    int K;
+    const uint8_t *in;
+    const int64_t *in_offsets;
+    const uint32_t *in_nbytes;
+    int n_chunks;
+    int lag;
+    int window_mode;
+    void *workspace;
+    int64_t workspace_bytes;
+} l3c_rgb_entries_desc;
+int64_t l3c_decode_rgb_entries_workspace_bytes(int64_t S, const int64_t *len_host, int n_chunks, int lag);
+int l3c_decode_rgb_entries(const l3c_rgb_entries_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
 
 /* ---- logistic-mixture head (replaces torchac_kernel.cu + criterion/logistic_mixture.py on the coding path) --------- */
 

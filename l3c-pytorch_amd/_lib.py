@@ -96,6 +96,13 @@ class RgbBandedDesc(ctypes.Structure):
                 ('lag', c_int), ('window_mode', c_int), ('workspace', c_vp), ('workspace_bytes', c_i64)]
 
 
+class RgbEntriesDesc(ctypes.Structure):
+    """l3c_rgb_entries_desc (include/l3c_hip.h)."""
+    _fields_ = [('P', c_vp), ('targets', c_vp), ('sym', c_vp), ('S', c_i64), ('total_pix', c_i64), ('entries_dev', c_vp),
+                ('entries_host', ctypes.POINTER(c_i64)), ('K', c_int), ('in_', c_vp), ('in_offsets', c_vp), ('in_nbytes', c_vp),
+                ('n_chunks', c_int), ('lag', c_int), ('window_mode', c_int), ('workspace', c_vp), ('workspace_bytes', c_i64)]
+
+
 NET_MAX_SCALES = 4    # include/l3c_hip.h: L3C_NET_MAX_SCALES
 
 
@@ -146,6 +153,8 @@ PROTOTYPES = {
     'l3c_container_write_banded': (c_int, [ctypes.POINTER(BandedScale), c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'l3c_decode_rgb_banded_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64, c_int, c_int]),
     'l3c_decode_rgb_banded': (c_int, [ctypes.POINTER(RgbBandedDesc), c_vp, c_vp]),
+    'l3c_decode_rgb_entries_workspace_bytes': (c_i64, [c_i64, ctypes.POINTER(c_i64), c_int, c_int]),
+    'l3c_decode_rgb_entries': (c_int, [ctypes.POINTER(RgbEntriesDesc), c_vp, c_vp]),
     'l3c_dmll_cdf_table_parts': (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, ctypes.POINTER(TablePart), c_int, c_vp]),
     'l3c_decode_rgb_workspace_bytes': (c_i64, [c_i64, c_i64, c_int, c_int]),
     'l3c_decode_rgb_stats_offset': (c_i64, [c_i64, c_i64, c_int, c_int]),

@@ -667,7 +667,9 @@ class Bitcoding(object):
     RAGGED_GROUP = 512               # decode_many: at most this many images are decoded together as one ragged group ...
     RAGGED_GROUP_PIXELS = 128 << 20  # ... and at most this many pixels (P of the RGB scale is 480 bytes per pixel: 64 GB; its tables 8 GB)
 
-    def decode_many(self, batches, on_batch=None, lanes=None, chain_cus=0, out_dtype=torch.int64, ragged=None):
+    ENTRY_LIMIT = ops.ENTRIES_MAX    # decode_many(banded=True): entries (bands) per ragged library call; a larger group goes through in slices
+
+    def decode_many(self, batches, on_batch=None, lanes=None, chain_cus=0, out_dtype=torch.int64, ragged=None, banded=False):
         """batches: list of lists of `.l3c` byte strings; the files of ONE entry are equally sized (padded) images (a forward pass of
         `encode_many`), entries may differ in shape.  -> list, in the order given, of ((B_i,3,H_i,W_i) int64 on the GPU, padding tuples),
         or None per entry when `on_batch(index, pixels, padding)` consumes the results as they are enqueued (called under the stream
@@ -682,8 +684,12 @@ class Bitcoding(object):
             its own while the lanes work on the next group.
         Large batches (>= 64 images) run one after the other: [measured, profiles/r06_decode_lanes_probe.log] batches of 128 on two lanes
         62-146 MPix/s (erratic: the lanes' long decoder launches and convolutions alias on the hardware queues) against 142-144 for one
-        lane; with the chains on 64 CUs of their own 125-147 -- the round-5 verdict's bar for keeping that overlap was 180."""
-        if any(is_banded(f) for files in batches for f in files):
+        lane; with the chains on 64 CUs of their own 125-147 -- the round-5 verdict's bar for keeping that overlap was 180.
+        banded=True: BANDED files (Bitcoding(bands=K)) are accepted too -- an entry is then all banded (one band length per scale: what one
+        `encode_many` pass writes) or all legacy.  Ragged groups are format-pure; in a banded group every BAND of every image is a ragged
+        entry of its own (l3c_decode_rgb_entries, ops.decode_z_entries), so the group's chains are a band long, not an image."""
+        fmt = [any(is_banded(f) for f in files) for files in batches]
+        if any(fmt) and not banded:
             raise ValueError('decode_many reads legacy .l3c files only: a banded file (L3CB format) goes through decode_batch / decode')
         n = self.N_DECODE_LANES if lanes is None else int(lanes)
         if lanes is None and max(len(f) for f in batches) >= 64:
@@ -730,40 +736,71 @@ class Bitcoding(object):
             # groups of 48 / 96 / 160 MPix: 69 / 95 / 32 MPix/s (peak 55 / 96 / 157 GB: two consecutive groups' buffers then no longer fit the
             # allocator's caches and every phase pays hipFree + hipMalloc)
             pix = []
-            for files in batches:
-                _, H, W = parse_containers(files[:1]).scales[-1]
+            for files, b in zip(batches, fmt):
+                H, W = container.padded_shape(files[0]) if b else parse_containers(files[:1]).scales[-1][1:]
                 pix.append(len(files) * H * W)
-            n_groups = max(1, -(-sum(pix) // self.RAGGED_GROUP_PIXELS))
-            target = sum(pix) / float(n_groups)
-            group, n_img, n_pix = [], 0, 0
-            for i, files in enumerate(batches):
-                group.append((i, files))
-                n_img += len(files)
-                n_pix += pix[i]
-                if n_img >= self.RAGGED_GROUP or n_pix >= target or i + 1 == len(batches):
-                    self._decode_group_ragged(group, lane_streams, rgb_main, rgb_side, out_dtype, finish)
-                    group, n_img, n_pix = [], 0, 0
+            for b in (False, True):        # format-pure groups: the legacy entries, then the banded ones
+                idx = [i for i in range(len(batches)) if fmt[i] == b]
+                if not idx:
+                    continue
+                n_groups = max(1, -(-sum(pix[i] for i in idx) // self.RAGGED_GROUP_PIXELS))
+                target = sum(pix[i] for i in idx) / float(n_groups)
+                group, n_img, n_pix = [], 0, 0
+                for i in idx:
+                    group.append((i, batches[i]))
+                    n_img += len(batches[i])
+                    n_pix += pix[i]
+                    if n_img >= self.RAGGED_GROUP or n_pix >= target or i == idx[-1]:
+                        self._decode_group_ragged(group, lane_streams, rgb_main, rgb_side, out_dtype, finish, banded=b)
+                        group, n_img, n_pix = [], 0, 0
             done.append(rgb_main.record_event())
         for ev in done:
             outer.wait_event(ev)
         return result
 
-    def _decode_group_ragged(self, group, lane_streams, rgb_main, rgb_side, out_dtype, finish):
+    @classmethod
+    def ragged_rgb_chunk_plan(cls, hws, rgb_window):
+        """(pix0, npix) of ops.ragged_rgb_plan for images of hws pixels as the legacy ragged group decode chunks them."""
+        min_hw = min(hws)
+        probe = cls.RGB_PROBE if (rgb_window == 'auto' and min_hw >= 16 * cls.RGB_PROBE) else 0
+        n_regular = max(1, min(cls.RGB_CHUNKS, (min_hw - 2 * probe) // 4096))
+        return ops.ragged_rgb_plan(hws, n_regular, probe)
+
+    @classmethod
+    def banded_rgb_chunks(cls, hws, lens, rgb_window, lag_legacy, lag):
+        """Chunks per entry of a banded group's RGB scale (entries of `lens` symbols, lag `lag`): the workspace of l3c_decode_rgb_entries --
+        its tables, above all -- must not exceed what the SAME images (hws pixels each) ask for as legacy files, chunked by
+        ragged_rgb_chunk_plan at the lag the legacy group decode would use.  -> (chunks, fits); fits is False for the groups no chunk
+        count can keep within that bound (ops.rgb_entries_chunks: a few tiny images, kilobytes of plan arrays)."""
+        from .. import _lib
+        pix0, npix = cls.ragged_rgb_chunk_plan(hws, rgb_window)
+        budget = _lib.load().l3c_decode_rgb_ragged_workspace_bytes(len(hws), int(npix.sum(axis=1).max()), pix0.shape[0], lag_legacy)
+        return ops.rgb_entries_chunks(lens, budget, lag)
+
+    def _decode_group_ragged(self, group, lane_streams, rgb_main, rgb_side, out_dtype, finish, banded=False):
         """One group of decode_many's ragged form, in PHASES over all its entries (batches of different shapes):
             lanes:   upload, the coarsest scale (uniform prior), P of the next scale (get_P per shape)      -- small launches, a lane per entry
             ragged:  that scale's symbols of ALL images in lock step (bottleneck scale: one table launch + one decoder launch for every
                      image and channel; RGB scale: the chunk pipeline of l3c_decode_rgb_ragged), on (rgb_main, rgb_side)
             lanes:   P of the next finer scale ...                                                          -- and so on down to scale 0
         An image's serial chains -- 12 ms at scale 1, 60-70 ms at scale 0 for 768x512 -- are thereby paid once per GROUP instead of once
-        per image; what is left per image are the decoder-side convolutions of its shape."""
+        per image; what is left per image are the decoder-side convolutions of its shape.
+        banded: the group's files are BANDED (an entry's files share the band length of every scale).  The phases are the same; a ragged
+        phase then runs over every band of every image as an entry of its own -- pixels [j L, j L + len_j) of its image -- and the chains
+        paid per group are a band long."""
         K = self.blueprint.net.config_ms.prob.K
         n = len(lane_streams)
         st = []
         for i, files in group:
-            parsed = parse_containers(files)
-            n_pred = self._n_predicted(len(parsed.scales))
-            self._check_coarsest(parsed.scales[0], False, int(parsed.nbytes[0].max()))
-            st.append({'i': i, 'files': files, 'parsed': parsed, 'B': len(files), 'lane': lane_streams[i % n], 'F': None, 'n_pred': n_pred})
+            if banded:
+                records, parsed = container.parse_set_entry(files)
+            else:
+                parsed = parse_containers(files)
+                records = parsed.scales
+            n_pred = self._n_predicted(len(records))
+            self._check_coarsest(records[0], banded, int(parsed.nbytes[0].max()))
+            st.append({'i': i, 'files': files, 'parsed': parsed, 'records': records, 'B': len(files), 'lane': lane_streams[i % n], 'F': None,
+                       'n_pred': n_pred})
         if len({e['n_pred'] for e in st}) != 1:
             raise ValueError('decode_many: the files of a set must come from one model (different numbers of scale records)')
         n_pred = st[0]['n_pred']
@@ -788,10 +825,11 @@ class Bitcoding(object):
         scale, dmll, uniform = plan[0]
         assert uniform
         for e in st:
-            C, H, W = e['parsed'].scales[0]
+            H, W = e['records'][0][1:3]
             with torch.cuda.stream(e['lane'][0]):
                 e['streams'] = _upload_streams(e['files'], e['parsed'])
-                e['sym'], _ = self._scale_symbols(e['streams'], 0, (C, H, W), dmll, True, None, e['B'], None)
+                e['sym'], _ = (self._scale_symbols_banded if banded else self._scale_symbols)(e['streams'], 0, e['records'][0], dmll, True, None,
+                                                                                              e['B'], None)
                 e['hw'] = (H, W)
         prev = dmll
         # ---- every predicted scale, coarse -> fine
@@ -800,7 +838,7 @@ class Bitcoding(object):
             scale, dmll, _ = plan[k]
             hws, pixbase, p = [], [], 0
             for e in st:
-                Cs, H, W = e['parsed'].scales[k]
+                Cs, H, W = e['records'][k][:3]
                 Kp = self._check_header(scale, dmll, (Cs, H, W), e['hw'])
                 pixbase.append(p)
                 p += e['B'] * H * W
@@ -819,14 +857,17 @@ class Bitcoding(object):
                     rgb_main.wait_event(main.record_event())
             # one stream table for the whole group: CHANNEL-major over all images; every entry keeps its own stream buffer, addressed from the lowest one
             base_t = min((e['streams'].buf for e in st), key=lambda t: t.data_ptr())
-            offs = np.zeros((Cs, Btot), dtype=np.int64)
-            lens = np.zeros((Cs, Btot), dtype=np.int32)
-            b0 = 0
+            # per channel the streams of the whole group: legacy one per image; banded one per BAND, in the order (entry, image, band)
+            o_all, l_all = [], []
             for e in st:
-                o, l = e['streams'].scale_host(k)                             # (Cs * B,) channel-major within the entry
-                offs[:, b0:b0 + e['B']] = o.reshape(Cs, e['B']) + (e['streams'].buf.data_ptr() - base_t.data_ptr())
-                lens[:, b0:b0 + e['B']] = l.reshape(Cs, e['B'])
-                b0 += e['B']
+                o, l = e['streams'].scale_host(k)                             # channel-major within the entry: (c B + b), banded (c n + j) B + b
+                if banded:
+                    nb = o.shape[0] // (Cs * e['B'])
+                    o, l = (a.reshape(Cs, nb, e['B']).transpose(0, 2, 1).reshape(Cs, -1) for a in (o, l))
+                o_all.append(o.reshape(Cs, -1) + (e['streams'].buf.data_ptr() - base_t.data_ptr()))
+                l_all.append(l.reshape(Cs, -1))
+            offs = np.concatenate(o_all, axis=1).astype(np.int64)
+            lens = np.concatenate(l_all, axis=1).astype(np.int32)
             targets = self._targets(dmll)
             with torch.cuda.stream(rgb_main):
                 for e in st:
@@ -834,19 +875,20 @@ class Bitcoding(object):
                     e['streams'].buf.record_stream(rgb_side)
                     if k == n_pred:
                         e['streams'].finish()       # the bulk of the files (the last record) crosses PCIe here, behind the convolutions just enqueued
-                offs_d = ops.upload_small(offs.reshape(-1))
-                lens_d = ops.upload_small(lens.reshape(-1))
-                if dmll.rgb_scale:
-                    min_hw = min(hws)
-                    probe = self.RGB_PROBE if (self.rgb_window == 'auto' and min_hw >= 16 * self.RGB_PROBE) else 0
-                    n_regular = max(1, min(self.RGB_CHUNKS, (min_hw - 2 * probe) // 4096))
-                    pix0, npix = ops.ragged_rgb_plan(hws, n_regular, probe)
-                    keep.append(ops.decode_rgb_ragged(P_rag, targets, sym_rag, base_t, offs_d, lens_d, hws, pix0, npix, K,
-                                                      *self._rgb_schedule(Btot, rgb_side)))
+                if banded:
+                    offs_d = lens_d = None
+                    keep.append(self._decode_scale_entries(st, k, dmll, pixbase, hws, P_rag, sym_rag, base_t, offs, lens, Cs, K, rgb_side))
                 else:
-                    hw = np.asarray(hws, dtype=np.int64)             # every image's whole plane is one entry: pix0 = 0, npix = hw
-                    keep.append(ops.decode_z_entries(P_rag, targets, sym_rag, base_t, offs_d, lens_d, np.cumsum(hw) - hw, hw,
-                                                     np.zeros(Btot, dtype=np.int64), hw, total, Cs, K))
+                    offs_d = ops.upload_small(offs.reshape(-1))
+                    lens_d = ops.upload_small(lens.reshape(-1))
+                    if dmll.rgb_scale:
+                        pix0, npix = self.ragged_rgb_chunk_plan(hws, self.rgb_window)
+                        keep.append(ops.decode_rgb_ragged(P_rag, targets, sym_rag, base_t, offs_d, lens_d, hws, pix0, npix, K,
+                                                          *self._rgb_schedule(Btot, rgb_side)))
+                    else:
+                        hw = np.asarray(hws, dtype=np.int64)             # every image's whole plane is one entry: pix0 = 0, npix = hw
+                        keep.append(ops.decode_z_entries(P_rag, targets, sym_rag, base_t, offs_d, lens_d, np.cumsum(hw) - hw, hw,
+                                                         np.zeros(Btot, dtype=np.int64), hw, total, Cs, K))
                 done = rgb_main.record_event()
             for g, e in enumerate(st):
                 H, W = e['hw']
@@ -860,6 +902,41 @@ class Bitcoding(object):
             for e in st:
                 finish(e['i'], e['sym'].to(out_dtype), e['parsed'].padding, rgb_main)
         del keep
+
+    def _decode_scale_entries(self, st, k, dmll, pixbase, hws, P_rag, sym_rag, buf, offs, lens, Cs, K, rgb_side):
+        """Record k of a BANDED group on the current stream: every band (entry of `st`, image b, band j) is a ragged entry -- pixels
+        [j L, min((j + 1) L, HW)) of its image --, streams (c, entry) in the numpy tables offs / lens (Cs, S).  Bottleneck scales: one ragged
+        table launch and one ragged decoder launch (ops.decode_z_entries); RGB scales: the chunk pipeline over all entries in lock step
+        (l3c_decode_rgb_entries), the chunk count bounded by the legacy group decode's workspace for the same images (banded_rgb_chunks).
+        More than ENTRY_LIMIT entries go through in slices.  -> tensors to keep alive."""
+        ent = [[], [], [], []]
+        for g, e in enumerate(st):
+            H, W, L = e['records'][k][1:4]
+            HW, nb = H * W, n_bands(H * W, L)
+            j = np.tile(np.arange(nb, dtype=np.int64), e['B'])
+            ent[0].append(pixbase[g] + np.repeat(np.arange(e['B'], dtype=np.int64), nb) * HW)
+            ent[1].append(np.full(e['B'] * nb, HW, dtype=np.int64))
+            ent[2].append(j * L)
+            ent[3].append(np.minimum(L, HW - j * L))
+        base, hw, pix0, length = (np.concatenate(a) for a in ent)
+        S, total = hw.shape[0], int(sum(hws))
+        targets = self._targets(dmll)
+        if dmll.rgb_scale:
+            lag, mode, side = self._rgb_schedule(S, rgb_side)
+            chunks, _ = self.banded_rgb_chunks(hws, length, self.rgb_window, self._rgb_schedule(len(hws), rgb_side)[0], lag)
+            return ops.decode_rgb_entries(P_rag, targets, sym_rag, buf, offs, lens, base, hw, pix0, length, chunks, K, lag, mode, side,
+                                          limit=self.ENTRY_LIMIT)
+        # Every slice's call allocates its Cs tables for the pixels of the WHOLE group (ops.decode_z_entries addresses a table row by its
+        # pixel in the group), and all of them live until the group is done: the bottleneck tables are paid once per SLICE.  A group has at
+        # most RAGGED_GROUP images of at most K bands each, so K = 64 never slices (32 768 bands) and K = 256 slices in three at the most;
+        # tables sized per slice would need slice-relative table offsets in ops.decode_z_entries.
+        keep = []
+        for a, b in ops.entry_slices(S, self.ENTRY_LIMIT):
+            offs_d = ops.upload_small(np.ascontiguousarray(offs[:, a:b]).reshape(-1))
+            lens_d = ops.upload_small(np.ascontiguousarray(lens[:, a:b]).reshape(-1))
+            keep.append((offs_d, lens_d, ops.decode_z_entries(P_rag, targets, sym_rag, buf, offs_d, lens_d, base[a:b], hw[a:b], pix0[a:b],
+                                                              length[a:b], total, Cs, K)))
+        return keep
 
     def _decode_z_scale(self, P, targets, streams, B, C, K, H, W):
         """A bottleneck scale: its C channels are independent given P, so ONE grouped table launch (fused, straight from P) and one

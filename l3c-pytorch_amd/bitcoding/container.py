@@ -185,6 +185,22 @@ def parse_batch(files):
                                   [np.stack([p.nbytes[k].reshape(-1) for p in parsed]) for k in range(len(records))]), True
 
 
+def parse_set_entry(files):
+    """The banded files of ONE entry of a set decode (equally sized images written with one band count: Bitcoding.decode_many(banded=True))
+    -> (records, streams): `records` every scale's (C, H, W, L), the same in every file; `streams` the upload-ready band stream table of
+    parse_batch -- per scale the (B, C n) positions and lengths of every file's band payloads, band j of channel c at column c n + j.
+    ValueError for a legacy file among them, broken framing, or files that disagree in a shape or a band length."""
+    if not all(is_banded(f) for f in files):
+        raise ValueError('decode_many: an entry mixes banded and legacy .l3c files')
+    records, streams, _ = parse_batch(files)
+    return records, streams
+
+
+def band_lengths(data):
+    """(L per scale record, coarsest first) of a banded file, None for a legacy one."""
+    return tuple(s[3] for s in parse_banded(data).scales) if is_banded(data) else None
+
+
 def padded_shape(data):
     """(H, W) of the PADDED image a file of either format holds: 2**(records - 1) times its first (coarsest) scale record's H, W.
     Cheap: the record count comes from walking the length fields, no payload is touched."""

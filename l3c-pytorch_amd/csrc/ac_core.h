@@ -336,6 +336,23 @@ L3C_HD int lean_advance(uint32_t &low, uint32_t &nh, uint32_t &range, uint32_t t
     return c;
 }
 
+// ---- streams decoded chunk by chunk (csrc/ac_kernels.hip: l3c_ac_decode_chunks; csrc/decode_pipeline.hip) -------------------------
+// Between two chunks a stream carries (low, high, value, bits consumed).  The symbol that must not advance the state -- the STREAM's last,
+// torchac.cpp:335-337 -- is the chunk's last one iff the stream ends with this chunk, which is a property of the stream, not of the launch:
+// streams of different lengths in lock step end in different chunks.  An EMPTY chunk (a short stream's trailing chunks) decodes nothing,
+// writes nothing and hands the record on as it is.
+L3C_HD bool chunk_is_empty(uint32_t n_sym) { return n_sym == 0u; }
+L3C_HD uint32_t chunk_no_advance(uint32_t n_sym, bool stream_ends) { return stream_ends && n_sym ? n_sym - 1u : 0xFFFFFFFFu; }
+// Lock-step chunking of an entry of `len` symbols into `chunks` chunks (l3c_decode_rgb_entries): steps of whole 64-symbol blocks,
+// chunk k = [k step, min((k + 1) step, len)) -- empty from some k on when the entry is short -- and the stream ends with its last
+// non-empty chunk.
+L3C_HD int64_t entry_step(int64_t len, int64_t chunks) { return 64 * ((len + 64 * chunks - 1) / (64 * chunks)); }
+L3C_HD int64_t entry_npix(int64_t len, int64_t chunks, int64_t k) {
+    const int64_t st = entry_step(len, chunks), a = k * st;
+    return a >= len ? 0 : (len - a < st ? len - a : st);
+}
+L3C_HD int64_t entry_final_chunk(int64_t len, int64_t chunks) { return (len - 1) / entry_step(len, chunks); }
+
 // Literal (serial) emission of one record -- the definition phase 2 must reproduce; also used for its rare long runs.
 template <class Sink>
 L3C_HD void emit_record(uint32_t rec_lo, uint32_t rec_nm, uint32_t &pending, Sink &sink) {

@@ -845,6 +845,11 @@ struct DecodeArgs {
     // sym_out + r_C * r_pixbase[s] + r_c * r_hw[s] + r_pix0[s]; the window context's P / sym are offset likewise)
     const int64_t *r_npix, *r_table_off, *r_pixbase, *r_hw, *r_pix0;
     int r_C, r_c;
+    // ENTRIES (l3c_decode_rgb_entries: every band of a set of banded files a ragged entry; null = `final_chunk` holds for every stream):
+    // stream s ends with chunk r_final[s] of its own -- a short entry before the long ones, its later chunks are EMPTY (r_npix[s] == 0:
+    // no row, no symbol, no marker, the state record carried from state_in to state_out, the window statistics left alone)
+    const int32_t *r_final;
+    int chunk;                     // the index of this chunk, compared with r_final[s]
 };
 
 // the stream's view of a part: rectangular or ragged
@@ -854,11 +859,14 @@ struct StreamView {
     int16_t *dst;
     WindowCtx win;                 // (P, sym, HW, pix0 of THIS stream's image when ragged; index the image as 0 then)
     int64_t img;                   // image index to hand to the window functions
+    bool final;                    // the stream ends with this chunk: its last symbol does not advance the state (torchac.cpp:335-337)
 };
 __device__ __forceinline__ StreamView stream_view(const DecodeArgs &a, int64_t s) {
     StreamView v;
     v.win = a.win;
+    v.final = a.final_chunk != 0;
     if (a.r_npix) {
+        if (a.r_final) v.final = a.r_final[s] == a.chunk;
         const int64_t pb = a.r_pixbase[s], hw = a.r_hw[s], p0 = a.r_pix0[s];
         v.n_sym = (uint32_t)a.r_npix[s];
         v.rows = reinterpret_cast<uint64_t>(a.cdf) + (uint64_t)a.r_table_off[s];
@@ -905,6 +913,10 @@ __device__ __forceinline__ void ring_decode_body(const DecodeArgs &a, uint8_t *r
     const int64_t s = blockIdx.x;
     const StreamView sv = stream_view(a, s);
     const uint32_t n_sym = sv.n_sym;
+    if (l3c::chunk_is_empty(n_sym)) {   // an empty chunk of a short entry: only the state record moves on (both passes write the same record)
+        if (a.state_in && a.state_out && threadIdx.x == 0) a.state_out[s] = a.state_in[s];
+        return;
+    }
     const int lane = threadIdx.x;
     const int top = Lp - 2;
     const uint32_t row_bytes = (uint32_t)Lp * 2u;
@@ -946,7 +958,7 @@ __device__ __forceinline__ void ring_decode_body(const DecodeArgs &a, uint8_t *r
         src.init(words, a.in_nbytes[s], lane, ring_base + C::NB * C::BLOCK_BYTES);
         value = src.take(32);
     }
-    const uint32_t no_advance = a.final_chunk ? n_sym - 1u : 0xFFFFFFFFu;   // torchac.cpp:335-337
+    const uint32_t no_advance = l3c::chunk_no_advance(n_sym, sv.final);   // torchac.cpp:335-337
 
 #pragma unroll
     for (uint32_t k = 0; k < (uint32_t)C::NB - 1u; ++k)
@@ -1486,6 +1498,10 @@ __device__ __forceinline__ void lean_decode_body(const DecodeArgs &a, uint8_t *r
     const int64_t s = blockIdx.x;
     const StreamView sv = stream_view(a, s);
     const uint32_t n_sym = sv.n_sym;
+    if (l3c::chunk_is_empty(n_sym)) {   // an empty chunk of a short entry: only the state record moves on (both passes write the same record)
+        if (a.state_in && a.state_out && threadIdx.x == 0) a.state_out[s] = a.state_in[s];
+        return;
+    }
     const int lane = threadIdx.x;
     const uint32_t top = (uint32_t)(Lp - 2);
     const uint32_t row_bytes = (uint32_t)Lp * 2u;
@@ -1566,7 +1582,7 @@ __device__ __forceinline__ void lean_decode_body(const DecodeArgs &a, uint8_t *r
         }
         st.range = ~(st.low + st.nh);
     }
-    const uint32_t no_advance = a.final_chunk ? n_sym - 1u : 0xFFFFFFFFu;   // torchac.cpp:335-337
+    const uint32_t no_advance = l3c::chunk_no_advance(n_sym, sv.final);   // torchac.cpp:335-337
 
 #pragma unroll
     for (uint32_t k = 0; k < (uint32_t)C::NB - 1u; ++k)
@@ -1980,7 +1996,15 @@ int l3c_ac_decode(const uint16_t *cdf, int64_t row_stride, int Lp, const uint8_t
 int64_t l3c_ac_decode_state_bytes(void) { return (int64_t)sizeof(DecodeState); }
 
 int l3c_ac_decode_chunks(const l3c_ac_decode_part *parts, int n_parts, l3c_stream_t stream) {
+    return l3c::ac_decode_chunks_entries(parts, n_parts, nullptr, nullptr, stream);
+}
+}   // extern "C"
+
+// l3c_ac_decode_chunks with per-stream finality (l3c_common.h): final_chunk_dev == nullptr is the public call
+int l3c::ac_decode_chunks_entries(const l3c_ac_decode_part *parts, int n_parts, const int32_t *final_chunk_dev, const int *chunk_host,
+                                  l3c_stream_t stream) {
     L3C_REQUIRE(parts && n_parts > 0 && n_parts <= DecodeArgsPack::N, "1..8 parts per call");
+    L3C_REQUIRE(!final_chunk_dev || chunk_host, "per-stream finality needs every part's chunk index");
     DecodeArgsPack pack{};
     for (int i = 0; i < n_parts; ++i) {
         const l3c_ac_decode_part &q = parts[i];
@@ -2002,6 +2026,11 @@ int l3c_ac_decode_chunks(const l3c_ac_decode_part *parts, int n_parts, l3c_strea
         a.table_bytes = ragged ? q.r_table_bytes : q.n_streams * q.n_sym * (int64_t)q.Lp * 2;
         a.r_npix = q.r_npix;  a.r_table_off = q.r_table_off;  a.r_pixbase = q.r_pixbase;  a.r_hw = q.r_hw;  a.r_pix0 = q.r_pix0;
         a.r_C = q.r_C;  a.r_c = q.r_c;
+        if (final_chunk_dev) {
+            L3C_REQUIRE(ragged, "per-stream finality: ragged parts only");
+            a.r_final = final_chunk_dev;
+            a.chunk = chunk_host[i];
+        }
         a.in = q.in;
         a.in_offsets = q.in_offsets;
         a.in_nbytes = q.in_nbytes;
@@ -2028,6 +2057,8 @@ int l3c_ac_decode_chunks(const l3c_ac_decode_part *parts, int n_parts, l3c_strea
             L3C_REQUIRE(!parts[i].window_stats_in || parts[j].Lp == 257, "a call with window rows: every part must code the 256-symbol alphabet (Lp 257)");
     return launch_ring_decode(pack, n_parts, /*fast_pass=*/parts[0].not_monotone_flag != nullptr, l3c::as_stream(stream));
 }
+
+extern "C" {
 
 int l3c_cdf_check_monotone(const uint16_t *cdf, int64_t n_rows, int Lp, int32_t *flag_out, l3c_stream_t stream) {
     L3C_REQUIRE(cdf && flag_out, "null pointer");

@@ -15,6 +15,7 @@
 //   D = 2: the channels stay TWO chunks apart, so the tables of step t + 1 need only the symbols of step t - 1 and are built on `main`
 //          WHILE `side` decodes step t: max(table, decode) per step instead of their sum.  Two table slot sets (step parity): the tables
 //          of step t are written after `main` has waited for the decode of step t - 2, the last reader of that slot set.
+#include "ac_core.h"
 #include "l3c_common.h"
 
 #include <string.h>
@@ -98,6 +99,7 @@ struct Ragged {
     const int64_t *pix0_host;      // [n_chunks][B]
     const int64_t *npix_host;      // [n_chunks][B]
     const int64_t *tables_dev;     // pixbase [B] | hw [B] | pix0 [n_chunks][B] | npix [n_chunks][B] | table_off [n_chunks][B]
+    const int32_t *final_dev;      // [B] the chunk every stream ends with (l3c_decode_rgb_entries; chunks of npix 0 allowed), nullptr: the last one
 };
 
 int decode_rgb_impl(const l3c_rgb_decode_desc *d, const Ragged *rag, int64_t max_npix, l3c_stream_t main_stream, l3c_stream_t side_stream) {
@@ -145,6 +147,7 @@ int decode_rgb_impl(const l3c_rgb_decode_desc *d, const Ragged *rag, int64_t max
         l3c_table_part tp[C3];
         l3c_ragged_part rp[C3];
         l3c_ac_decode_part dp[C3];
+        int chunk_of[C3];
         int n = 0;
         uint8_t *slot = ws + l.tables + (D == 2 ? (t & 1) : 0) * C3 * l.table_bytes;
         for (int c = 0; c < C3; ++c) {
@@ -157,6 +160,7 @@ int decode_rgb_impl(const l3c_rgb_decode_desc *d, const Ragged *rag, int64_t max
                     np = nb > np ? nb : np;
                     total += nb;
                 }
+                if (total == 0) continue;   // (entries: a trailing chunk that is empty in every stream)
             } else {
                 p0 = d->chunk_pix0_host[j];
                 np = d->chunk_npix_host[j];
@@ -204,6 +208,7 @@ int decode_rgb_impl(const l3c_rgb_decode_desc *d, const Ragged *rag, int64_t max
                 q.K = d->K;
                 q.c = c;
             }
+            chunk_of[n] = j;
             dp[n++] = q;
         }
         if (!n) continue;
@@ -219,7 +224,7 @@ int decode_rgb_impl(const l3c_rgb_decode_desc *d, const Ragged *rag, int64_t max
             if (rc == L3C_OK) rc = l3c::check_hip(hipStreamWaitEvent(side, ev_tables, 0), "hipStreamWaitEvent");
             if (rc != L3C_OK) return rc;
         }
-        rc = l3c_ac_decode_chunks(dp, n, side);
+        rc = rag && rag->final_dev ? l3c::ac_decode_chunks_entries(dp, n, rag->final_dev, chunk_of, side) : l3c_ac_decode_chunks(dp, n, side);
         if (rc != L3C_OK) return rc;
         if (D == 2) {
             rc = l3c::check_hip(hipEventRecord(ev_decoded[t % 3], side), "hipEventRecord");
@@ -294,7 +299,7 @@ int l3c_decode_rgb_ragged(const l3c_rgb_ragged_desc *r, l3c_stream_t main_stream
     d.in = r->in;  d.in_offsets = r->in_offsets;  d.in_nbytes = r->in_nbytes;
     d.n_chunks = r->n_chunks;  d.lag = r->lag;  d.window_mode = r->window_mode;
     d.workspace = r->workspace;  d.workspace_bytes = r->workspace_bytes;
-    const Ragged rag{r->hw_host, r->chunk_pix0_host, r->chunk_npix_host, r->tables_dev};
+    const Ragged rag{r->hw_host, r->chunk_pix0_host, r->chunk_npix_host, r->tables_dev, nullptr};
     return decode_rgb_impl(&d, &rag, max_total, main_stream, side_stream);
 }
 }
@@ -384,7 +389,139 @@ int l3c_decode_rgb_banded(const l3c_rgb_banded_desc *r, l3c_stream_t main_stream
     d.in = r->in;  d.in_offsets = r->in_offsets;  d.in_nbytes = r->in_nbytes;
     d.n_chunks = r->n_chunks;  d.lag = r->lag;  d.window_mode = r->window_mode;
     d.workspace = r->workspace;  d.workspace_bytes = l.total;
-    const Ragged rag{hw.data(), nullptr, npix.data(), tables};
+    const Ragged rag{hw.data(), nullptr, npix.data(), tables, nullptr};
+    return decode_rgb_impl(&d, &rag, max_total, main_stream, side_stream);
+}
+}
+
+// ---- a set of banded files: every band of every image an ENTRY ---------------------------------------------------------------------
+//
+// Entry e is pixels [pix0_e, pix0_e + len_e) of an image of hw_e pixels at pixel pixbase_e of the ragged P / symbol buffers: any mix of
+// image sizes and band lengths.  All entries step through n_chunks chunks together, entry e in steps of step_e = 64 ceil(len_e / (64 n_chunks))
+// symbols: chunk k is [k step_e, min((k + 1) step_e, len_e)) -- EMPTY for the trailing chunks of a short entry (a 64-symbol last band has
+// one chunk whatever n_chunks is), and the entry's stream ends with its last non-empty chunk, (len_e - 1) / step_e.
+namespace {
+
+using l3c::entry_final_chunk;   // the chunking rule itself: csrc/ac_core.h (tests/hostsim runs it on the host)
+using l3c::entry_npix;
+using l3c::entry_step;
+
+// One block per chunk k: table_off[k][e] = 514 * (sum of npix[k][e'] over e' < e) needs a scan over the entries -- every thread sums a
+// contiguous run of them, thread 0 scans the 256 sums.  ent: pixbase [S] | hw [S] | pix0 [S] | len [S];  tables: the layout of
+// l3c_rgb_ragged_desc.tables_dev;  final_chunk [S].  An empty chunk's pix0 stays inside the entry (nothing is read or written there).
+__global__ __launch_bounds__(256) void entry_plan_kernel(const int64_t *__restrict__ ent, int64_t S, int64_t chunks,
+                                                         int64_t *__restrict__ tables, int32_t *__restrict__ final_chunk) {
+    __shared__ int64_t run[256];
+    const int64_t k = blockIdx.x;
+    const int t = threadIdx.x;
+    const int64_t per = (S + 255) / 256;
+    const int64_t e0 = t * per < S ? t * per : S, e1 = e0 + per < S ? e0 + per : S;
+    const int64_t *len = ent + 3 * S;
+    int64_t sum = 0;
+    for (int64_t e = e0; e < e1; ++e) sum += entry_npix(len[e], chunks, k);
+    run[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        int64_t acc = 0;
+        for (int i = 0; i < 256; ++i) {
+            const int64_t v = run[i];
+            run[i] = acc;
+            acc += v;
+        }
+    }
+    __syncthreads();
+    int64_t off = run[t];
+    for (int64_t e = e0; e < e1; ++e) {
+        const int64_t n = len[e], st = entry_step(n, chunks), np = entry_npix(n, chunks, k);
+        if (k == 0) {
+            tables[e] = ent[e];
+            tables[S + e] = ent[S + e];
+            final_chunk[e] = (int32_t)entry_final_chunk(n, chunks);
+        }
+        tables[(2 + k) * S + e] = ent[2 * S + e] + (k * st < n ? k * st : n - 1);
+        tables[(2 + chunks + k) * S + e] = np;
+        tables[(2 + 2 * chunks + k) * S + e] = off * (int64_t)(LP * 2);
+        off += np;
+    }
+}
+
+// per step the total over the entries: the largest sizes the table slots
+int64_t entries_max_total(const int64_t *len, int64_t S, int64_t chunks) {
+    int64_t m = 0;
+    for (int64_t k = 0; k < chunks; ++k) {
+        int64_t total = 0;
+        for (int64_t e = 0; e < S; ++e) total += entry_npix(len[e], chunks, k);
+        m = total > m ? total : m;
+    }
+    return m;
+}
+
+// the workspace: the pipeline's own (its tables sized by max_total), then the plan arrays, then every entry's final chunk
+int64_t entries_workspace(int64_t S, int64_t max_total, int n_chunks, int lag) {
+    return layout(1, max_total, n_chunks, lag, S).total + up((2 + 3 * (int64_t)n_chunks) * S * 8) + up(S * 4);
+}
+
+bool entries_shape_ok(int64_t S, const int64_t *len_host, int n_chunks, int lag) {
+    if (S <= 0 || S >= 65536 || !len_host || n_chunks <= 0 || n_chunks > 4096 || (lag != 1 && lag != 2)) return false;
+    for (int64_t e = 0; e < S; ++e)
+        if (len_host[e] <= 0) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t l3c_decode_rgb_entries_workspace_bytes(int64_t S, const int64_t *len_host, int n_chunks, int lag) {
+    if (!entries_shape_ok(S, len_host, n_chunks, lag)) return -1;
+    return entries_workspace(S, entries_max_total(len_host, S, n_chunks), n_chunks, lag);
+}
+
+int l3c_decode_rgb_entries(const l3c_rgb_entries_desc *r, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    L3C_REQUIRE(r, "null descriptor");
+    L3C_REQUIRE(r->P && r->targets && r->sym && r->in && r->in_offsets && r->in_nbytes && r->workspace && r->entries_host && r->entries_dev,
+                "null pointer in descriptor");
+    L3C_REQUIRE(r->S > 0 && r->S < 65536, "1..65535 entries per call (slice a larger set)");
+    L3C_REQUIRE(r->total_pix > 0 && r->K > 0 && r->K <= 16, "bad shape");
+    L3C_REQUIRE(r->n_chunks > 0 && r->n_chunks <= 4096, "1..4096 chunks per entry");
+    L3C_REQUIRE(r->lag == 1 || r->lag == 2, "lag must be 1 (one stream) or 2 (tables and decoders overlapped on two streams)");
+    L3C_REQUIRE(r->lag == 1 || side_stream != main_stream, "lag 2 needs a side stream that is not the main stream");
+    L3C_REQUIRE(r->window_mode >= 0 && r->window_mode <= 2, "window_mode: 0 never, 1 auto, 2 always");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(r->workspace) & (ALIGN - 1)) == 0, "workspace must be 256-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(r->in) & 3) == 0 && (reinterpret_cast<uintptr_t>(r->sym) & 1) == 0 &&
+                    ((reinterpret_cast<uintptr_t>(r->P) | reinterpret_cast<uintptr_t>(r->targets)) & 3) == 0 &&
+                    (reinterpret_cast<uintptr_t>(r->entries_dev) & 7) == 0,
+                "misaligned input (streams 4-byte aligned, l3c_container_read)");
+    const int64_t S = r->S;
+    const int64_t *pixbase = r->entries_host, *hw = pixbase + S, *pix0 = hw + S, *len = pix0 + S;
+    for (int64_t e = 0; e < S; ++e) {
+        L3C_REQUIRE(pixbase[e] >= 0 && hw[e] > 0 && hw[e] <= r->total_pix && pixbase[e] <= r->total_pix - hw[e], "entry: image outside the P / symbol buffers");
+        L3C_REQUIRE(pix0[e] >= 0 && len[e] > 0 && len[e] <= hw[e] && pix0[e] <= hw[e] - len[e], "entry: pixel range outside its image, or empty");
+    }
+    // the host side of the ragged schedule, computed once: every chunk's symbols per entry (the longest sizes a step's launches) and from
+    // them the largest total of a step (the table slots, hence the workspace)
+    const int64_t chunks = r->n_chunks;
+    std::vector<int64_t> npix((size_t)(chunks * S));
+    int64_t max_total = 0;
+    for (int64_t k = 0; k < chunks; ++k) {
+        int64_t total = 0;
+        for (int64_t e = 0; e < S; ++e) total += npix[(size_t)(k * S + e)] = entry_npix(len[e], chunks, k);
+        max_total = total > max_total ? total : max_total;
+    }
+    L3C_REQUIRE(r->workspace_bytes >= entries_workspace(S, max_total, r->n_chunks, r->lag), "workspace too small (l3c_decode_rgb_entries_workspace_bytes)");
+    const Layout l = layout(1, max_total, r->n_chunks, r->lag, S);
+    int64_t *tables = reinterpret_cast<int64_t *>(static_cast<uint8_t *>(r->workspace) + l.total);
+    int32_t *final_chunk = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(tables) + up((2 + 3 * chunks) * S * 8));
+    hipLaunchKernelGGL(entry_plan_kernel, dim3((unsigned)chunks), dim3(256), 0, l3c::as_stream(main_stream), r->entries_dev, S, chunks, tables,
+                       final_chunk);
+    const int rc = l3c::check_launch("entry_plan_kernel");
+    if (rc != L3C_OK) return rc;
+    l3c_rgb_decode_desc d{};
+    d.P = r->P;  d.targets = r->targets;  d.sym = r->sym;  d.B = S;  d.HW = 0;  d.K = r->K;
+    d.in = r->in;  d.in_offsets = r->in_offsets;  d.in_nbytes = r->in_nbytes;
+    d.n_chunks = r->n_chunks;  d.lag = r->lag;  d.window_mode = r->window_mode;
+    d.workspace = r->workspace;  d.workspace_bytes = l.total;
+    const Ragged rag{hw, nullptr, npix.data(), tables, final_chunk};
     return decode_rgb_impl(&d, &rag, max_total, main_stream, side_stream);
 }
 }

@@ -27,6 +27,12 @@ inline int check_launch(const char *kernel) { return check_hip(hipGetLastError()
 
 inline hipStream_t as_stream(l3c_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// l3c_ac_decode_chunks for ragged parts whose streams end in DIFFERENT chunks (csrc/ac_kernels.hip; the caller is l3c_decode_rgb_entries):
+// stream s of every part ends with chunk final_chunk_dev[s] (device int32 [n_streams]), part i is chunk chunk_host[i] of its channel, and
+// a stream with r_npix[s] == 0 only carries its state record on.  parts[i].final_chunk is ignored.
+int ac_decode_chunks_entries(const l3c_ac_decode_part *parts, int n_parts, const int32_t *final_chunk_dev, const int *chunk_host,
+                             l3c_stream_t stream);
+
 }  // namespace l3c
 
 #define L3C_REQUIRE(cond, msg)                                                         \

@@ -193,24 +193,27 @@ def file_padded_shape(data):
 
 def plan_decode_set(files, order, max_batch):
     """Host-side plan of a set decode: files of equal padded shape share a batch of at most max_batch (the mirror of plan_set, from
-    the files' own headers).  -> (chunks: list of index lists, padded shape per chunk)."""
+    the files' own headers) -- and of equal format: banded files only with banded files of the same band length at every scale, which is
+    what one batch decodes.  -> (chunks: list of index lists, padded shape per chunk)."""
+    from ..bitcoding import container
     groups = collections.defaultdict(list)
     for i in order:
-        groups[file_padded_shape(files[i])].append(i)
+        groups[(file_padded_shape(files[i]), container.band_lengths(files[i]))].append(i)
     chunks, padded = [], []
-    for shape, idxs in groups.items():
+    for (shape, _), idxs in groups.items():
         for k in range(0, len(idxs), max_batch):
             chunks.append(idxs[k:k + max_batch])
             padded.append(shape)
     return chunks, padded
 
 
-def decode_set(bc, files, order, max_batch=16, marks=None, lanes=None, chain_cus=0, n_pinned=None, ragged=None):
+def decode_set(bc, files, order, max_batch=16, marks=None, lanes=None, chain_cus=0, n_pinned=None, ragged=None, banded=False):
     """files: {index: `.l3c` bytes} (as `encode_set` returns them); order: the indices to decode.  -> {index: uint8 (3,H,W) HOST tensor},
     the padding undone.  The mirror of `encode_set` for the reference's folder evaluation, which decodes EVERY file it wrote and
     compares it with the input (multiscale_tester.py:353-381, assert_equal at :373): files of equal padded shape share a batch,
     largest batches first, the batches stream through `Bitcoding.decode_many` (batch i + 1's convolutions beside batch i's RGB chains);
-    the decoded pixels leave the device as uint8 through `n_pinned` page-locked buffers while later batches decode."""
+    the decoded pixels leave the device as uint8 through `n_pinned` page-locked buffers while later batches decode.
+    banded=True: the set may hold BANDED files (Bitcoding(bands=K), alone or beside legacy ones); without it such a file is refused."""
     import time
     from . import pad as _pad
 
@@ -255,7 +258,7 @@ def decode_set(bc, files, order, max_batch=16, marks=None, lanes=None, chain_cus
         collect(False)
 
     bc.decode_many([[files[i] for i in chunks[ci]] for ci in by_size], on_batch=on_batch, lanes=lanes, chain_cus=chain_cus,
-                   out_dtype=torch.uint8, ragged=ragged)
+                   out_dtype=torch.uint8, ragged=ragged, banded=banded)
     collect(True)
     mark('parse + H2D + decode + D2H (pipelined)')
     return out

@@ -526,6 +526,104 @@ def decode_rgb_banded(P_nhwc, targets, sym, buf, offs, lens, band_len, n_chunks,
     return ws
 
 
+ENTRIES_MAX = 65535     # l3c_decode_rgb_entries / the ragged table kernel: one grid row per entry (grid.y)
+
+
+def entry_slices(n_entries, limit=ENTRIES_MAX):
+    """[(first, end)] slices of at most `limit` entries that cover n_entries in order."""
+    limit = max(1, min(int(limit), ENTRIES_MAX))
+    return [(a, min(n_entries, a + limit)) for a in range(0, n_entries, limit)]
+
+
+def rgb_entries_plan(lens, n_chunks):
+    """The chunk plan l3c_decode_rgb_entries writes on the device, as a pure function (tests, sizing): entry e of lens[e] symbols steps in
+    step_e = 64 ceil(len_e / (64 n_chunks)); chunk k is [k step_e, min((k + 1) step_e, len_e)), empty past the entry's end.
+    -> (start (n_chunks, S) relative to the entry's pix0, npix (n_chunks, S), final chunk (S,), table_off (n_chunks, S) bytes)."""
+    lens = np.asarray(lens, dtype=np.int64)
+    step = 64 * (-(-lens // (64 * n_chunks)))
+    k = np.arange(n_chunks, dtype=np.int64)[:, None]
+    start = np.minimum(k * step, lens - 1)
+    npix = np.clip(lens - k * step, 0, step)
+    table_off = (np.cumsum(npix, axis=1) - npix) * (257 * 2)
+    return start, npix, (lens - 1) // step, table_off
+
+
+def rgb_entries_workspace_bytes(lens, n_chunks, lag):
+    """l3c_decode_rgb_entries_workspace_bytes of entries of `lens` symbols (no GPU needed)."""
+    lens = np.ascontiguousarray(lens, dtype=np.int64)
+    n = _lib.load().l3c_decode_rgb_entries_workspace_bytes(lens.shape[0], lens.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), int(n_chunks), int(lag))
+    if n < 0:
+        raise _lib.L3CError('l3c_decode_rgb_entries_workspace_bytes: bad arguments (S={}, chunks={}, lag={})'.format(lens.shape[0], n_chunks, lag))
+    return n
+
+
+def rgb_entries_chunks(lens, budget_bytes, lag, lo=8, hi=256):
+    """Chunks per entry of an entries RGB decode: the smallest count from `lo` on whose workspace stays within budget_bytes (the tables of
+    a step shrink with the count; the per-chunk plan arrays, (2 + 3 n) S int64, grow with it).  Fewer chunks = fewer pipeline steps and
+    launches.  -> (count, fits).  fits is False where NO count keeps the workspace within the budget -- a few tiny images, whose plan arrays
+    outweigh their tables: a legacy decode keeps those arrays outside its workspace, an entries decode inside -- and the count is then the
+    one with the smallest workspace, the counts below `lo` included."""
+    best, n = None, lo
+    while n <= hi:
+        ws = rgb_entries_workspace_bytes(lens, n, lag)
+        if ws <= budget_bytes:
+            return n, True
+        if best is None or ws < best[0]:
+            best = (ws, n)
+        n += max(1, n // 8)
+    for n in range(min(lo, hi + 1) - 1, 0, -1):
+        ws = rgb_entries_workspace_bytes(lens, n, lag)
+        if ws <= budget_bytes:
+            return n, True
+        if ws < best[0]:
+            best = (ws, n)
+    return best[1], False
+
+
+def rgb_entries_device_plan(ws, S, n_chunks):
+    """The plan l3c_decode_rgb_entries wrote into its workspace `ws` (uint8 tensor of rgb_entries_workspace_bytes; S entries, n_chunks
+    chunks), once the stream is done: the workspace ends with the plan arrays and, behind them, every entry's final chunk, each rounded up
+    to 256 bytes.  -> (pixbase (S,), hw (S,), pix0 (n_chunks, S), npix (n_chunks, S), table_off (n_chunks, S), final chunk (S,)) numpy."""
+    def up(v):
+        return -(-v // 256) * 256
+    n_tab = (2 + 3 * n_chunks) * S * 8
+    a = ws.numel() - up(4 * S) - up(n_tab)
+    t = ws[a:a + n_tab].view(torch.int64).cpu().numpy()
+    final = ws[ws.numel() - up(4 * S):][:4 * S].view(torch.int32).cpu().numpy()
+    per = n_chunks * S
+    return (t[:S], t[S:2 * S], t[2 * S:2 * S + per].reshape(n_chunks, S), t[2 * S + per:2 * S + 2 * per].reshape(n_chunks, S),
+            t[2 * S + 2 * per:].reshape(n_chunks, S), final)
+
+
+def decode_rgb_entries(P_ragged, targets, sym_ragged, buf, offs_host, lens_host, pixbase, hw, pix0, length, n_chunks, K, lag, window_mode,
+                       side_stream=None, limit=ENTRIES_MAX):
+    """An RGB scale as S arbitrary ENTRIES in lock step (l3c_decode_rgb_entries: every band of every image of a set of banded files):
+    entry e (int64 arrays of S) is pixels [pix0, pix0 + length) of an image of hw pixels at pixel pixbase of P_ragged ((total_pix, 120)
+    fp32) and of sym_ragged (int16 (3 * total_pix,), ZEROED); the streams in `buf` at offs_host / lens_host, numpy (3, S): stream (c, e).
+    More than `limit` entries go through the call in slices.  -> tensors to keep alive until the stream is done."""
+    S = len(hw)
+    total_pix = P_ragged.numel() // (12 * K)
+    ent = np.stack([np.asarray(a, dtype=np.int64) for a in (pixbase, hw, pix0, length)])
+    keep = []
+    for a, e in entry_slices(S, limit):
+        ent_h = np.ascontiguousarray(ent[:, a:e]).reshape(-1)
+        nbytes = rgb_entries_workspace_bytes(ent[3, a:e], n_chunks, lag)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=P_ragged.device)
+        ent_d = upload_small(ent_h)
+        offs = upload_small(np.ascontiguousarray(offs_host[:, a:e], dtype=np.int64).reshape(-1))
+        lens = upload_small(np.ascontiguousarray(lens_host[:, a:e], dtype=np.int32).reshape(-1))
+        desc = _lib.RgbEntriesDesc(ptr(P_ragged, torch.float32), ptr(targets, torch.float32), ptr(sym_ragged, torch.int16), e - a, total_pix,
+                                   ptr(ent_d, torch.int64), ent_h.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), K, ptr(buf, torch.uint8),
+                                   ptr(offs, torch.int64), ptr(lens, torch.int32), n_chunks, lag, window_mode, ptr(ws), nbytes)
+        if lag == 2:
+            for t in (P_ragged, targets, sym_ragged, buf, offs, lens, ws, ent_d):
+                t.record_stream(side_stream)
+        call('l3c_decode_rgb_entries', ctypes.byref(desc), torch.cuda.current_stream().cuda_stream,
+             side_stream.cuda_stream if lag == 2 else None)
+        keep.append((ws, ent_d, offs, lens))
+    return keep
+
+
 def band_intervals(iv, n_streams, n_sym, band_len):
     """l3c_ac_band_intervals: the interval buffer of n_streams streams -> [(iv, n_streams, n_sym)] groups for ac_encode_groups: the full
     bands (stream s * (n - 1) + j; absent when n == 1), then the last band of every stream."""

@@ -3,7 +3,7 @@
 
     python test.py LOG_DIR LOG_DATES IMAGES [--match_filenames F ..] [-m MAX] [--crop N] [--names N,..] [--overwrite_cache]
                    [--reset_entire_cache] [-i ITR,..] [--write_to_files DIR [--compare_theory] [--time_report PATH]]
-                   [--sort_output testset|exp|itr|res] [--batch B]
+                   [--sort_output testset|exp|itr|res] [--batch B] [--bands K]
 
 Prints the mean bpsp of every (test set, experiment, iteration); results are cached in LOG_DIR_test/<experiment>/cache.pkl.
 `--write_to_files` encodes every image to DIR/<name>.l3c with the HIP coder, decodes it again and asserts equality.
@@ -52,6 +52,9 @@ def main(argv=None):
     p.add_argument('--io_threads', type=int, default=4, help='worker threads that read and decode the image files ahead of the GPU')
     p.add_argument('--write_window', type=int, default=None,
                    help='--write_to_files: images coded / decoded as one set (default 32 x --batch; 1 = one image at a time like the reference)')
+    p.add_argument('--bands', type=int, default=0, metavar='K',
+                   help='--write_to_files: write BANDED .l3c files (every channel cut into at most K independently coded bands) and decode '
+                        'them as a set, every band a stream of its own (0: the legacy format)')
     flags = p.parse_args(argv)
 
     if flags.compare_theory and not flags.write_to_files:
