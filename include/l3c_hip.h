@@ -422,6 +422,20 @@ int l3c_dmll_nll(const float *P, const float *x, int64_t B, int64_t HW, int C, i
 int l3c_dmll_sample(const float *P, const float *u_mix, const float *u_logistic, int64_t B, int64_t HW, int C, int K,
                     int rgb, float *x, l3c_stream_t stream);
 
+/*
+ * The mixture's MEAN as symbols: the estimator of the preview decode (INTEGRATION.md "Preview decode"), for a scale whose record is not
+ * decoded.  It stands beside the reference's sampling (logistic_mixture.py:277-323, driven by multiscale_network.py:328-406), which
+ * draws a value per pixel where this takes the expectation.  Per pixel, channels in order c = 0 .. C-1:
+ *   pi_k = softmax_k(logit_c,k)     m_c = sum_k pi_k mu'_c,k     mu' = mu (+ the lambda coupling of l3c_dmll_channel_params, rgb only,
+ *                                                                      evaluated on the ESTIMATED values of the channels below c)
+ *   v = fminf(fmaxf(m_c, x_min), x_max)  (a NaN becomes x_min)     sym_c = clamp(rintf((v - x_min) / bin_width), 0, L-1)  (ties to even)
+ *   value fed on: sym_c * bin_width + x_min (l3c_sym_to_bn)        bin_width = (x_max - x_min) / (L - 1);  log_sigma plays no part
+ *   sym_out    int16 planar [B][C][HW]: the form the range decoders write.  2 <= L <= 32768.
+ * The kernel is pixel-wise: a ragged P [sum_b HW_b][Kp] is B = 1, HW = sum_b HW_b.  Not part of the bitstream.
+ */
+int l3c_dmll_mean(const float *P, int64_t B, int64_t HW, int C, int K, int rgb, float x_min, float x_max, int L,
+                  int16_t *sym_out, l3c_stream_t stream);
+
 /* ---- convolution stack (replaces the cuDNN convs behind modules/{net,edsr,head,prob_clf}.py) ---------------------- */
 
 /*

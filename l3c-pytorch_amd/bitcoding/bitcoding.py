@@ -590,6 +590,54 @@ class Bitcoding(object):
                 bn = self._next_input(sym, dmll)
         return sym.to(out_dtype), framing.padding
 
+    def decode_preview(self, files, records=None, out_dtype=torch.uint8):
+        """A picture from the COARSE records of B files -- whole files or prefixes of them (container.prefix_bytes), legacy or banded, of
+        equally sized images -> ((B,3,H,W) out_dtype on the GPU, list of padding tuples).
+        The first `records` scale records, coarsest first, are decoded as decode_batch decodes them; every finer scale takes the MEAN of the
+        mixture the network predicts for it (ops.dmll_mean: sum_k pi_k mu'_k per pixel and channel, snapped to a symbol) in place of the
+        range decoder's symbols and feeds it on the same way.  records == total is therefore the exact decode.
+        A prefix cannot say how many records its file has: the total is this model's, n_predicted_scales() + 1 (RGB Shared: build Bitcoding
+        with the file's auto_recurse); data holding more complete records than that raises ValueError.  records: 1 .. total, default every
+        complete record present but the finest; more than the data holds raises ValueError.  Only the bytes of the records decoded cross
+        PCIe; nothing synchronises with the host."""
+        B = len(files)
+        total = self.n_predicted_scales() + 1
+        recs, framing, banded, n = container.parse_prefix(files, total + 1)
+        if n > total:
+            raise ValueError('invalid file: more than {} scale records, the model codes {}'.format(total, total))
+        if records is None:
+            records = min(n, total - 1)
+        records = int(records)
+        if not 1 <= records <= total:
+            raise ValueError('records must be in 1..{}, got {}'.format(total, records))
+        if records > n:
+            raise ValueError('{} record(s) asked for, the data holds {} complete one(s)'.format(records, n))
+        self._check_coarsest(recs[0], banded, int(framing.nbytes[0].max()))
+        # the upload path sends "the rest of the file" with its last record: the files cut behind record `records` (prefix_bytes)
+        ends = framing.offset[records - 1][:, -1] + framing.nbytes[records - 1][:, -1] + 4
+        framing = container.ParsedFraming(framing.padding, framing.scales[:records], framing.offset[:records], framing.nbytes[:records])
+        streams = _upload_streams([f[:int(e)] for f, e in zip(files, ends)], framing)
+        symbols = self._scale_symbols_banded if banded else self._scale_symbols
+        K = self.blueprint.net.config_ms.prob.K
+        n_pred = total - 1
+        bn, F, P, hw, keep = None, None, None, None, []
+        for k, (scale, dmll, uniform) in enumerate(self.iter_scale_dmll(n_pred)):
+            Cs = 3 if dmll.rgb_scale else self.blueprint.net.config_ms.q.C
+            record = recs[k] if k < records else (Cs, 2 * hw[0], 2 * hw[1])
+            H, W = record[1:3]
+            if not uniform:
+                Kp = self._check_header(scale, dmll, record, hw)
+                P, F = self._get_P(scale, n_pred, bn, F, (B, H, W, Kp))
+            if k < records:
+                sym, hold = symbols(streams, k, record, dmll, uniform, P, B, None)
+                keep.append(hold)
+            else:
+                sym = ops.dmll_mean(P, Cs, K, dmll.rgb_scale, dmll.x_min, dmll.x_max, dmll.L)
+            hw = (H, W)
+            if scale > 0:
+                bn = self._next_input(sym, dmll)
+        return sym.to(out_dtype), framing.padding
+
     def _scale_symbols(self, streams, k, record, dmll, uniform, P, B, side):
         """-> (symbols (B, C, H, W) int16 of record k of legacy files, tensors to keep alive); uniform: the coarsest record, no P."""
         C, H, W = record
@@ -1111,6 +1159,21 @@ class Bitcoding(object):
             out = pad.undo_pad(out, *padding[0])
         return out
 
+    def preview(self, pin, records=None, max_bytes=None):
+        """-> a preview of the image in file `pin`, 1CHW uint8 (on the GPU), from its first `records` scale records (decode_preview; default:
+        all but the finest of those that lie within the first `max_bytes` bytes -- no more of the file is read)."""
+        if part_suffix_helper.contains_part_suffix(pin):
+            raise NotImplementedError('preview of an auto-cropped image: its .partN files are images of their own, a preview would have to '
+                                      'decode and stitch every part ({})'.format(pin))
+        if self.file_writer is not None:
+            self.file_writer.wait(pin)
+        with open(pin, 'rb') as fin:
+            data = fin.read() if max_bytes is None else fin.read(max(0, int(max_bytes)))
+        out, padding = self.decode_preview([data], records)
+        if any(padding[0]):
+            out = pad.undo_pad(out, *padding[0])
+        return out
+
 
 _RGB_MEAN_T = {}
 
@@ -1243,7 +1306,8 @@ def _upload_streams(files, parsed):
     dst_d = dev[table_at + 8 * S:table_at + 16 * S].view(torch.int64)
     len_d = dev[table_at + 16 * S:table_at + 20 * S].view(torch.int32)
     out = torch.empty(int(padded.sum()), dtype=torch.uint8, device='cuda')
-    ops.container_read(dev, src_d[:S_a], dst_d[:S_a], len_d[:S_a], int(lens[:S_a].max()), out)
+    if S_a:                                          # (a one-record prefix of decode_preview: its only record is the "last" one)
+        ops.container_read(dev, src_d[:S_a], dst_d[:S_a], len_d[:S_a], int(lens[:S_a].max()), out)
 
     def finish():
         k2, stage2 = _UPLOAD_RING.take(b_bytes)

@@ -185,6 +185,110 @@ def parse_batch(files):
                                   [np.stack([p.nbytes[k].reshape(-1) for p in parsed]) for k in range(len(records))]), True
 
 
+# ---- a PREFIX of a file (Bitcoding.decode_preview): the first records of a file that may end anywhere after them ------------------------
+
+
+class _Truncated(Exception):
+    """The data ends inside the record being read: the record is not part of the prefix."""
+
+
+class _PrefixReader(_Reader):
+    def take(self, n):
+        if self.p + n > len(self.d):
+            raise _Truncated()
+        return _Reader.take(self, n)
+
+
+def _walk_prefix(data, max_records=None):
+    """The complete scale records at the start of `data`, either format -> (banded, padding, [(header, offset (C, n), nbytes (C, n), end)]),
+    `end` the position behind the record's separator.  The walk stops, without an error, where the data ends inside a record (or at
+    max_records); what the full parsers reject in a record that IS complete -- and in the file header -- raises as they raise."""
+    banded = is_banded(data)
+    r = _PrefixReader(data)
+    try:
+        if banded:
+            r.take(4)
+            version, reserved = r.unpack('<BB')
+            if version != BANDED_VERSION:
+                raise ValueError('invalid file: unknown banded format version {}'.format(version))
+            if reserved:
+                raise ValueError('invalid file: reserved byte is {}'.format(reserved))
+        padding = r.unpack('<4H')
+    except _Truncated:
+        raise ValueError('invalid file: truncated')
+    found = []
+    while max_records is None or len(found) < max_records:
+        try:
+            if banded:
+                C, H, W, L = header = r.unpack('<BHHI')
+            else:
+                C, H, W = header = r.unpack('<BHH')
+            if C == 0:
+                raise ValueError('invalid file: scale record with C == 0')
+            n = 1
+            if banded:
+                if H == 0 or W == 0:
+                    raise ValueError('invalid file: empty scale {}x{}'.format(H, W))
+                if L == 0 or L % 64:
+                    raise ValueError('invalid file: band length {} is not a positive multiple of 64'.format(L))
+                n = n_bands(H * W, L)
+                if n > MAX_BANDS:
+                    raise ValueError('invalid file: {} bands per channel (at most {})'.format(n, MAX_BANDS))
+            off = np.zeros((C, n), dtype=np.int64)
+            nb = np.zeros((C, n), dtype=np.int64)
+            for c in range(C):
+                for j in range(n):
+                    nb[c, j], = r.unpack('<I')
+                    off[c, j] = r.p
+                    r.take(int(nb[c, j]))
+            if r.take(4) != _MAGIC_VALUE_SEP:
+                raise ValueError('invalid file: scale separator missing')
+        except _Truncated:
+            break
+        found.append((header, off, nb, r.p))
+    return banded, padding, found
+
+
+def prefix_bytes(data, records):
+    """Byte length of the shortest prefix of a file (either format) that holds its first `records` scale records: the file header, the
+    records' headers, payloads and separators.  ValueError when `data` holds fewer complete records."""
+    if records < 1:
+        raise ValueError('records must be at least 1, got {}'.format(records))
+    found = _walk_prefix(data, records)[2]
+    if len(found) < records:
+        raise ValueError('invalid file: {} complete scale record(s), {} asked for'.format(len(found), records))
+    return found[-1][3]
+
+
+def parse_prefix(files, max_records=None):
+    """B files or PREFIXES of files of equally sized images, either format (not mixed) -> (records, streams, banded, n): the first n scale
+    records that are complete in EVERY file (at most max_records), as parse_batch returns them.  The data may end anywhere behind them:
+    a cut inside record n + 1 is not an error.  Inside the kept records everything parse_containers / parse_banded reject raises
+    ValueError('invalid file: ...'), as do files that disagree in format, shape or band length, and data without one complete record."""
+    if max_records is not None and max_records < 1:
+        raise ValueError('max_records must be at least 1, got {}'.format(max_records))
+    if len({is_banded(f) for f in files}) != 1:
+        raise ValueError('decode_preview: a batch mixes banded and legacy .l3c files' if files else 'decode_preview: no files')
+    walked = [_walk_prefix(f, max_records) for f in files]
+    banded = walked[0][0]
+    n = min(len(w[2]) for w in walked)
+    if n < 1:
+        raise ValueError('invalid file: not one complete scale record')
+    records = [h for h, _, _, _ in walked[0][2][:n]]
+    for w in walked[1:]:
+        other = [h for h, _, _, _ in w[2][:n]]
+        if any(a[:3] != b[:3] for a, b in zip(other, records)):
+            raise ValueError('decode_preview needs equally sized images, got scale records {} and {}'.format(
+                [s[:3] for s in records], [s[:3] for s in other]))
+        if other != records:
+            raise ValueError('decode_preview: banded files of one batch must share the band length of every scale, got {} and {}'.format(
+                [s[3] for s in records], [s[3] for s in other]))
+    streams = ParsedFraming([w[1] for w in walked], [(h[0] * (n_bands(h[1] * h[2], h[3]) if banded else 1), h[1], h[2]) for h in records],
+                            [np.stack([w[2][k][1].reshape(-1) for w in walked]) for k in range(n)],
+                            [np.stack([w[2][k][2].reshape(-1) for w in walked]) for k in range(n)])
+    return records, streams, banded, n
+
+
 def parse_set_entry(files):
     """The banded files of ONE entry of a set decode (equally sized images written with one band count: Bitcoding.decode_many(banded=True))
     -> (records, streams): `records` every scale's (C, H, W, L), the same in every file; `streams` the upload-ready band stream table of

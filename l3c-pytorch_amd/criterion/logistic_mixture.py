@@ -91,3 +91,8 @@ class DiscretizedMixLogisticLoss(nn.Module):
                      torch.empty(N, C, H, W, device='cuda').uniform_(1e-5, 1. - 1e-5))
         u_mix, u_log = [u.to('cuda', torch.float32).contiguous() for u in noise]
         return ops.dmll_sample(ops.as_pixel_major(l), u_mix, u_log, C, K, self.rgb_scale)
+
+    def mean_sym(self, l, C):
+        """The mixture's mean as symbols: l (N,Kp,H,W) -> int16 (N,C,H,W), sum_k pi_k mu'_k snapped as `to_sym` snaps, the RGB scale's
+        channels coupled through the estimates of the channels before them (the preview decode's estimator)."""
+        return ops.dmll_mean(ops.as_pixel_major(l), C, self._K(l, C), self.rgb_scale, self.x_min, self.x_max, self.L)

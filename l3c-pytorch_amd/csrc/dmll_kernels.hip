@@ -556,6 +556,78 @@ __global__ __launch_bounds__(256) void sample_kernel(const float *__restrict__ P
     }
 }
 
+// ---- the mixture's mean as symbols (preview decode: a scale whose record is NOT decoded; INTEGRATION.md "Preview decode") ------------
+// Per (pixel, channel)  m_c = sum_k pi_k mu'_k,  mu' the lambda-coupled mean of mix_component on the ESTIMATED values of the channels
+// below c; log_sigma plays no part.  The coupling is linear in those values, so it does not serialise the sums:
+//     m_G = S_1 + x_R A_10,   m_B = S_2 + (x_R A_20 + x_G A_21),   S_c = sum_k pi_k mu_c,k,   A = sum_k pi_k sigmoid(lam_k)
+// Staging as encode_intervals_kernel: a block takes kHeadPix pixels, their P records go coalesced into the [kHeadPix][Kp + 1] tile, every
+// (pixel, channel) item gets a thread for its sums (normalised once: (sum_k e_k mu_k) / sum_k e_k).  Only the last three multiply-adds
+// and roundings of an RGB pixel are ordered, after one barrier.  The snapping is Spec.to_sym's: clamp (a NaN becomes x_min), divide,
+// round half to even; the value fed on is sym_to_bn_kernel's sym * bin_width + x_min.
+struct MeanSnap {
+    float x_min, x_max, bin_width, top;    // top = L - 1
+};
+__device__ __forceinline__ float mean_to_sym(float m, const MeanSnap &s) {
+    const float v = fminf(fmaxf(m, s.x_min), s.x_max);
+    return fminf(fmaxf(rintf((v - s.x_min) / s.bin_width), 0.0f), s.top);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void dmll_mean_kernel(const float *__restrict__ P, int64_t HW, int C, int K, int rgb, MeanSnap snap,
+                                                        int16_t *__restrict__ sym_out, TileDiv dv) {
+    extern __shared__ __attribute__((aligned(16))) float tile[];   // [kHeadPix][Kp + 1], then (RGB scale) S, A0, A1: [3][kHeadPix] each
+    const int Kp = (rgb ? 4 : 3) * C * K;
+    const int CK = C * K;
+    const int ld = Kp + 1;
+    float *s_S = tile + kHeadPix * ld, *s_A0 = s_S + 3 * kHeadPix, *s_A1 = s_A0 + 3 * kHeadPix;
+    const int64_t b = blockIdx.y;
+    const int64_t pix0 = (int64_t)blockIdx.x * kHeadPix;
+    const int npix = (int)((HW - pix0) < kHeadPix ? (HW - pix0) : kHeadPix);
+    const int tid = threadIdx.x;
+    fill_tile<NT>(tile, P + (b * HW + pix0) * Kp, npix, Kp, ld, dv, tid);
+    __syncthreads();
+    for (int w = tid; w < kHeadPix * C; w += NT) {
+        const int p = w % kHeadPix, c = w / kHeadPix;
+        if (p >= npix) continue;
+        const float *px = tile + p * ld;
+        float mx = px[c * K];
+        for (int k = 1; k < K; ++k) mx = fmaxf(mx, px[c * K + k]);
+        float denom = 0.0f, s = 0.0f, a0 = 0.0f, a1 = 0.0f;
+        for (int k = 0; k < K; ++k) {
+            const float e = expf(px[c * K + k] - mx);
+            denom = denom + e;
+            s = s + e * px[CK + c * K + k];
+            if (rgb && c == 1) {
+                a0 = a0 + e * sigmoid_f(px[3 * CK + k]);
+            } else if (rgb && c == 2) {
+                a0 = a0 + e * sigmoid_f(px[3 * CK + K + k]);
+                a1 = a1 + e * sigmoid_f(px[3 * CK + 2 * K + k]);
+            }
+        }
+        if (rgb) {
+            s_S[c * kHeadPix + p] = s / denom;
+            s_A0[c * kHeadPix + p] = a0 / denom;
+            s_A1[c * kHeadPix + p] = a1 / denom;
+        } else {
+            sym_out[(b * C + c) * HW + pix0 + p] = (int16_t)mean_to_sym(s / denom, snap);
+        }
+    }
+    if (!rgb) return;
+    __syncthreads();
+    if (tid < npix) {       // C == 3: R, then G on R's estimate, then B on both
+        const int p = tid;
+        int16_t *out = sym_out + b * 3 * HW + pix0 + p;
+        const float q0 = mean_to_sym(s_S[p], snap);
+        const float x0 = q0 * snap.bin_width + snap.x_min;
+        const float q1 = mean_to_sym(s_S[kHeadPix + p] + x0 * s_A0[kHeadPix + p], snap);
+        const float x1 = q1 * snap.bin_width + snap.x_min;
+        const float q2 = mean_to_sym(s_S[2 * kHeadPix + p] + (x0 * s_A0[2 * kHeadPix + p] + x1 * s_A1[2 * kHeadPix + p]), snap);
+        out[0] = (int16_t)q0;
+        out[HW] = (int16_t)q1;
+        out[2 * HW] = (int16_t)q2;
+    }
+}
+
 int grid_1d(int64_t total, int block) {
     int64_t g = (total + block - 1) / block;
     return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
@@ -712,5 +784,28 @@ int l3c_dmll_sample(const float *P, const float *u_mix, const float *u_logistic,
     const dim3 grid((unsigned)((HW + kHeadPix - 1) / kHeadPix), (unsigned)B);
     hipLaunchKernelGGL(sample_kernel, grid, dim3(256), lds, l3c::as_stream(stream), P, u_mix, u_logistic, HW, C, K, rgb, x);
     return l3c::check_launch("sample_kernel");
+}
+
+int l3c_dmll_mean(const float *P, int64_t B, int64_t HW, int C, int K, int rgb, float x_min, float x_max, int L, int16_t *sym_out,
+                  l3c_stream_t stream) {
+    L3C_REQUIRE(P && sym_out, "null pointer");
+    L3C_REQUIRE(B > 0 && B < 65536 && HW > 0 && HW <= (int64_t)0x7fffffff * kHeadPix && C > 0, "bad shape");
+    L3C_REQUIRE(K > 0 && K <= kMaxK, "K out of range (1..16)");
+    L3C_REQUIRE(!rgb || C == 3, "lambda coupling is only defined for C == 3");
+    L3C_REQUIRE(L >= 2 && L <= 32768 && x_min < x_max, "alphabet out of range (2 <= L <= 32768, x_min < x_max)");
+    const int Kp = (rgb ? 4 : 3) * C * K;
+    const size_t lds = ((size_t)kHeadPix * (Kp + 1) + (rgb ? 9 * kHeadPix : 0)) * sizeof(float);
+    L3C_REQUIRE(lds <= 64 * 1024, "Kp too large for the LDS tile");
+    // the bin width as DiscretizedMixLogisticLoss states it (in double), then to fp32: what l3c_sym_to_bn is handed
+    const MeanSnap snap{x_min, x_max, (float)(((double)x_max - (double)x_min) / (double)(L - 1)), (float)(L - 1)};
+    const dim3 grid((unsigned)((HW + kHeadPix - 1) / kHeadPix), (unsigned)B);
+    // threads per block as l3c_dmll_encode_intervals chooses them: one item each for the bottleneck scales' 320 (pixel, channel) items
+    if (kHeadPix * C == 320)
+        hipLaunchKernelGGL(dmll_mean_kernel<320>, grid, dim3(320), lds, l3c::as_stream(stream), P, HW, C, K, rgb, snap, sym_out,
+                           tile_div(Kp, kHeadPix));
+    else
+        hipLaunchKernelGGL(dmll_mean_kernel<256>, grid, dim3(256), lds, l3c::as_stream(stream), P, HW, C, K, rgb, snap, sym_out,
+                           tile_div(Kp, kHeadPix));
+    return l3c::check_launch("dmll_mean_kernel");
 }
 }

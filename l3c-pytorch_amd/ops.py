@@ -679,6 +679,14 @@ def dmll_sample(P_nhwc, u_mix, u_log, C, K, rgb):
     return out
 
 
+def dmll_mean(P_nhwc, C, K, rgb, x_min, x_max, L):
+    """P (B,H,W,Kp) -> int16 symbols (B,C,H,W) of the mixture's mean, channel by channel (the preview decode's estimator: l3c_dmll_mean)."""
+    B, H, W, _ = P_nhwc.shape
+    out = torch.empty(B, C, H, W, dtype=torch.int16, device=P_nhwc.device)
+    call('l3c_dmll_mean', ptr(P_nhwc, torch.float32), B, H * W, C, K, int(rgb), float(x_min), float(x_max), int(L), ptr(out), stream())
+    return out
+
+
 # ---- arithmetic coder -------------------------------------------------------------------------------------------------
 
 

@@ -522,6 +522,30 @@ class MultiscaleTester(object):
         self._write_img(decoded, png_out_p)
         print('---\nDecoded: {}'.format(png_out_p))
 
+    def preview(self, pin, png_out_p, records=None, max_bytes=None):
+        """A picture from the coarse scale records of `pin` (Bitcoding.preview): `records` of them (default: all but the finest), read from
+        at most the first `max_bytes` bytes of the file."""
+        pout_dir = os.path.dirname(os.path.abspath(png_out_p))
+        if not os.path.isdir(pout_dir):
+            raise DecodeError('png_out_p directory ({}) does not exists!'.format(pout_dir))
+        if not png_out_p.endswith('.png'):
+            raise DecodeError('png_out_p must end in .png, got {}'.format(png_out_p))
+        if not os.path.isfile(pin):
+            raise DecodeError('{} does not exist'.format(pin))
+        from ..bitcoding import container
+        size = os.path.getsize(pin)
+        n_read = size if max_bytes is None else max(0, min(size, int(max_bytes)))
+        total = self.bc.n_predicted_scales() + 1
+        try:
+            if records is None:
+                with open(pin, 'rb') as fin:
+                    records = min(container.parse_prefix([fin.read(n_read)], total)[3], total - 1)
+            decoded = self.bc.preview(pin, records, n_read)
+        except (ValueError, NotImplementedError) as e:
+            raise DecodeError(str(e))
+        self._write_img(decoded, png_out_p)
+        print('---\nPreview: {}  ({} of {} scale records decoded, {} of {} bytes read)'.format(png_out_p, records, total, n_read, size))
+
     @staticmethod
     def _read_img(img_p):
         img = np.array(Image.open(img_p))

@@ -3,6 +3,7 @@
 
     python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] enc IMG_P OUT_P [--overwrite]
     python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] dec IMG_P OUT_P_PNG
+    python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] preview IMG_P OUT_P_PNG [--records R] [--bytes N]
 
 Everything runs on the MI355X path; `--device cpu` is refused (there is no CPU back end in this build).
 """
@@ -55,9 +56,15 @@ def main(argv=None):
                           'encode / decode (1..1024; the flag alone: {}).  Without the flag: the legacy format.'.format(DEFAULT_BANDS))
     dec.add_argument('img_p')
     dec.add_argument('out_p_png')
+    pre = mode.add_parser('preview', help='Picture from the coarse scale records of a file: preview IMG_P OUT_P_PNG [--records R] [--bytes N]')
+    pre.add_argument('img_p')
+    pre.add_argument('out_p_png')
+    pre.add_argument('--records', type=int, default=None, metavar='R',
+                     help='scale records to decode, coarsest first; the finer scales are estimated (default: all but the finest)')
+    pre.add_argument('--bytes', type=int, default=None, metavar='N', help='read at most the first N bytes of the file')
     flags = p.parse_args(argv)
     if flags.mode is None:
-        p.error('mode (enc | dec) required')
+        p.error('mode (enc | dec | preview) required')
     parse_device_flag(flags.device)
     print('Testing {} at {} ---'.format(flags.log_date, flags.restore_itr))
     tester = MultiscaleTester(flags.log_date, flags, flags.restore_itr, l3c=True)
@@ -66,6 +73,12 @@ def main(argv=None):
             tester.encode(flags.img_p, flags.out_p, flags.overwrite)
         except EncodeError as e:
             print('*** EncodeError:', e)
+            return 1
+    elif flags.mode == 'preview':
+        try:
+            tester.preview(flags.img_p, flags.out_p_png, flags.records, flags.bytes)
+        except DecodeError as e:
+            print('*** DecodeError:', e)
             return 1
     else:
         try:
