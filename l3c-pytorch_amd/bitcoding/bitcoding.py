@@ -22,9 +22,10 @@ import torch
 
 from .. import auto_crop, ops
 from ..helpers import pad
-from . import container, part_suffix_helper
+from . import container, part_suffix_helper, upload
 from .container import (_MAGIC_VALUE_SEP, BANDED_SIGNATURE, MAX_BANDS, band_len, count_scale_records, is_banded, n_bands,  # noqa: F401
                         parse_banded, parse_containers)
+from .set_decode import SetDecoder
 
 
 class _NullTimes(object):
@@ -285,7 +286,10 @@ class Bitcoding(object):
         self.compare_with_theory = compare_with_theory
         self.times = times if times is not None else _NullTimes()
         self._const = {}
+        # streams and helpers created on first use (_side_stream, encode_many, set_decoder)
         self._coder_streams = None
+        self._fwd_streams = None
+        self._set_decoder = None
         self.coder_cus = coder_cus
         self.compute_stream = None
         self.N_SIDE_STREAMS = max(1, int(coder_streams))
@@ -450,7 +454,7 @@ class Bitcoding(object):
         main = torch.cuda.current_stream()
         from ..helpers import runtime
         if runtime.forward_streams_allowed(self.N_FORWARD_STREAMS) > 1:
-            if getattr(self, '_fwd_streams', None) is None:
+            if self._fwd_streams is None:
                 self._fwd_streams = [torch.cuda.Stream() for _ in range(self.N_FORWARD_STREAMS)]
             fwd = self._fwd_streams
         else:
@@ -571,24 +575,37 @@ class Bitcoding(object):
 
     def _decode_batch(self, files, out_dtype, side):
         """decode_batch on the current stream; `side`: see _rgb_schedule."""
-        B = len(files)
         records, framing, banded = container.parse_batch(files)
         n_pred = self._n_predicted(len(records))
         self._check_coarsest(records[0], banded, int(framing.nbytes[0].max()))
-        symbols = self._scale_symbols_banded if banded else self._scale_symbols
-        streams = _upload_streams(files, framing)
+        streams = upload._upload_streams(files, framing)
+        return self._walk_records(records, framing, banded, streams, n_pred, len(records), side).to(out_dtype), framing.padding
+
+    def _walk_records(self, records, framing, banded, streams, n_pred, n_decoded, side):
+        """The walk over the n_pred + 1 scale records of B files, coarse -> fine, on the current stream -> the finest scale's symbols
+        (B, 3, H, W) int16.  records / framing / banded: what container.parse_batch or parse_prefix gave, streams: the files on the device
+        (upload._upload_streams).  The first n_decoded records are decoded by the range decoder; every record past them takes the MEAN of
+        the mixture the network predicts for it (ops.dmll_mean) in the shape the network predicts.  side: see _rgb_schedule."""
+        B = len(framing.padding)
+        symbols = self._scale_symbols_of(banded)
+        K = self.blueprint.net.config_ms.prob.K
         bn, F, P, hw, keep = None, None, None, None, []
         for k, (scale, dmll, uniform) in enumerate(self.iter_scale_dmll(n_pred)):
-            H, W = records[k][1:3]
+            Cs = 3 if dmll.rgb_scale else self.blueprint.net.config_ms.q.C
+            record = records[k] if k < n_decoded else (Cs, 2 * hw[0], 2 * hw[1])
+            H, W = record[1:3]
             if not uniform:
-                Kp = self._check_header(scale, dmll, records[k], hw)
+                Kp = self._check_header(scale, dmll, record, hw)
                 P, F = self._get_P(scale, n_pred, bn, F, (B, H, W, Kp))
-            sym, hold = symbols(streams, k, records[k], dmll, uniform, P, B, side)    # (the last record's streams are staged and uploaded HERE: behind the convolutions just enqueued)
-            keep.append(hold)                                           # workspaces and tables live until the whole decode is enqueued
+            if k < n_decoded:
+                sym, hold = symbols(streams, k, record, dmll, uniform, P, B, side)    # (the last record's streams are staged and uploaded HERE: behind the convolutions just enqueued)
+                keep.append(hold)                                       # workspaces and tables live until the whole decode is enqueued
+            else:
+                sym = ops.dmll_mean(P, Cs, K, dmll.rgb_scale, dmll.x_min, dmll.x_max, dmll.L)
             hw = (H, W)
             if scale > 0:                                               # the finest scale's symbols ARE the pixel values (to_bn of the RGB scale: x 1 + 0)
                 bn = self._next_input(sym, dmll)
-        return sym.to(out_dtype), framing.padding
+        return sym
 
     def decode_preview(self, files, records=None, out_dtype=torch.uint8):
         """A picture from the COARSE records of B files -- whole files or prefixes of them (container.prefix_bytes), legacy or banded, of
@@ -600,7 +617,6 @@ class Bitcoding(object):
         with the file's auto_recurse); data holding more complete records than that raises ValueError.  records: 1 .. total, default every
         complete record present but the finest; more than the data holds raises ValueError.  Only the bytes of the records decoded cross
         PCIe; nothing synchronises with the host."""
-        B = len(files)
         total = self.n_predicted_scales() + 1
         recs, framing, banded, n = container.parse_prefix(files, total + 1)
         if n > total:
@@ -616,27 +632,12 @@ class Bitcoding(object):
         # the upload path sends "the rest of the file" with its last record: the files cut behind record `records` (prefix_bytes)
         ends = framing.offset[records - 1][:, -1] + framing.nbytes[records - 1][:, -1] + 4
         framing = container.ParsedFraming(framing.padding, framing.scales[:records], framing.offset[:records], framing.nbytes[:records])
-        streams = _upload_streams([f[:int(e)] for f, e in zip(files, ends)], framing)
-        symbols = self._scale_symbols_banded if banded else self._scale_symbols
-        K = self.blueprint.net.config_ms.prob.K
-        n_pred = total - 1
-        bn, F, P, hw, keep = None, None, None, None, []
-        for k, (scale, dmll, uniform) in enumerate(self.iter_scale_dmll(n_pred)):
-            Cs = 3 if dmll.rgb_scale else self.blueprint.net.config_ms.q.C
-            record = recs[k] if k < records else (Cs, 2 * hw[0], 2 * hw[1])
-            H, W = record[1:3]
-            if not uniform:
-                Kp = self._check_header(scale, dmll, record, hw)
-                P, F = self._get_P(scale, n_pred, bn, F, (B, H, W, Kp))
-            if k < records:
-                sym, hold = symbols(streams, k, record, dmll, uniform, P, B, None)
-                keep.append(hold)
-            else:
-                sym = ops.dmll_mean(P, Cs, K, dmll.rgb_scale, dmll.x_min, dmll.x_max, dmll.L)
-            hw = (H, W)
-            if scale > 0:
-                bn = self._next_input(sym, dmll)
-        return sym.to(out_dtype), framing.padding
+        streams = upload._upload_streams([f[:int(e)] for f, e in zip(files, ends)], framing)
+        return self._walk_records(recs, framing, banded, streams, total - 1, records, None).to(out_dtype), framing.padding
+
+    def _scale_symbols_of(self, banded):
+        """The decoder of one scale record of a batch, by the files' format (the walk and the set decoder's coarsest scale)."""
+        return self._scale_symbols_banded if banded else self._scale_symbols
 
     def _scale_symbols(self, streams, k, record, dmll, uniform, P, B, side):
         """-> (symbols (B, C, H, W) int16 of record k of legacy files, tensors to keep alive); uniform: the coarsest record, no P."""
@@ -661,8 +662,8 @@ class Bitcoding(object):
         C, H, W, L = record
         HW, n = H * W, n_bands(H * W, L)
         buf, _, _ = streams.scale(k)
-        o_h, l_h = streams.scale_host(k)
         if uniform:
+            o_h, l_h = streams.scale_host(k)
             o3, l3 = o_h.reshape(B * C, n), l_h.reshape(B * C, n).astype(np.int32)       # image-major: stream (b C + c) n + j
             row = self._uniform_row(dmll.L)
             sym = torch.empty(B * C, HW, dtype=torch.int16, device='cuda')
@@ -675,9 +676,9 @@ class Bitcoding(object):
             sym[:, (n - 1) * L:].copy_(last)
             return sym.view(B, C, H, W), None
         K = self.blueprint.net.config_ms.prob.K
-        # (c n + j) B + b  ->  (c B + b) n + j
-        offs = ops.upload_small(o_h.reshape(C, n, B).transpose(0, 2, 1).reshape(-1))
-        lens = ops.upload_small(l_h.reshape(C, n, B).transpose(0, 2, 1).reshape(-1).astype(np.int32))
+        o_h, l_h = streams.scale_host_channel_image_band(k, C, B)
+        offs = ops.upload_small(o_h.reshape(-1))
+        lens = ops.upload_small(l_h.reshape(-1).astype(np.int32))
         targets = self._targets(dmll)
         if dmll.rgb_scale:
             sym = torch.zeros(B, C, H, W, dtype=torch.int16, device='cuda')
@@ -685,37 +686,19 @@ class Bitcoding(object):
             hold = ops.decode_rgb_banded(P, targets, sym, buf, offs, lens, L, chunks, K, *self._rgb_schedule(B * n, side))
         else:
             sym = torch.empty(B, C, H, W, dtype=torch.int16, device='cuda')
-            j = np.tile(np.arange(n, dtype=np.int64), B)             # every band (b, j) is an entry: pixels [j L, j L + len_j) of image b
-            pixbase = np.repeat(np.arange(B, dtype=np.int64), n) * HW
-            pix0 = j * L
-            hold = ops.decode_z_entries(P, targets, sym, buf, offs, lens, pixbase, np.full(B * n, HW, dtype=np.int64), pix0,
-                                        np.minimum(L, HW - pix0), B * HW, C, K)
+            # every band (b, j) is an entry: pixels [j L, j L + len_j) of image b
+            hold = ops.decode_z_entries(P, targets, sym, buf, offs, lens, *container.band_entry_table(B, HW, L), B * HW, C, K)
         return sym, hold
 
-    N_DECODE_LANES = 8       # decode_many: lanes when every batch is small (fewer than 64 images: latency-bound chains); large batches run one after the other
+    N_DECODE_LANES = SetDecoder.N_DECODE_LANES      # (read by the benchmark's report and by callers that size their buffers; the knobs of the set decode are SetDecoder's)
 
-    def _lanes(self, n, chain_cus):
-        """`n` pairs (main stream, side stream) for decode_many.  chain_cus > 0: every side stream -- the latency-bound range-decoder
-        chains -- is confined to `chain_cus` compute units (the same number of every XCD, helpers/runtime.balanced_cu_sets) and every main
-        stream -- convolutions, table kernels -- to the others, so that a lane's MFMA wavefronts never take the registers or the issue
-        slots of another lane's chains."""
-        key = (n, chain_cus)
-        if getattr(self, '_lane_key', None) != key:
-            from .. import _lib
-            if chain_cus:
-                from ..helpers import runtime
-                _, n_cu, _ = _lib.device_info()
-                chains, rest = runtime.balanced_cu_sets(n_cu, chain_cus)
-                self._lane_streams = [(_lib.cu_mask_stream(rest), _lib.cu_mask_stream(chains)) for _ in range(n)]
-            else:
-                self._lane_streams = [(torch.cuda.Stream(), torch.cuda.Stream()) for _ in range(n)]
-            self._lane_key = key
-        return self._lane_streams
-
-    RAGGED_GROUP = 512               # decode_many: at most this many images are decoded together as one ragged group ...
-    RAGGED_GROUP_PIXELS = 128 << 20  # ... and at most this many pixels (P of the RGB scale is 480 bytes per pixel: 64 GB; its tables 8 GB)
-
-    ENTRY_LIMIT = ops.ENTRIES_MAX    # decode_many(banded=True): entries (bands) per ragged library call; a larger group goes through in slices
+    @property
+    def set_decoder(self):
+        """The SetDecoder behind decode_many, created on first use: its knobs (N_DECODE_LANES, RAGGED_GROUP, RAGGED_GROUP_PIXELS, ENTRY_LIMIT)
+        are set on it, and it owns the streams of the set decode."""
+        if self._set_decoder is None:
+            self._set_decoder = SetDecoder(self)
+        return self._set_decoder
 
     def decode_many(self, batches, on_batch=None, lanes=None, chain_cus=0, out_dtype=torch.int64, ragged=None, banded=False):
         """batches: list of lists of `.l3c` byte strings; the files of ONE entry are equally sized (padded) images (a forward pass of
@@ -736,75 +719,7 @@ class Bitcoding(object):
         banded=True: BANDED files (Bitcoding(bands=K)) are accepted too -- an entry is then all banded (one band length per scale: what one
         `encode_many` pass writes) or all legacy.  Ragged groups are format-pure; in a banded group every BAND of every image is a ragged
         entry of its own (l3c_decode_rgb_entries, ops.decode_z_entries), so the group's chains are a band long, not an image."""
-        fmt = [any(is_banded(f) for f in files) for files in batches]
-        if any(fmt) and not banded:
-            raise ValueError('decode_many reads legacy .l3c files only: a banded file (L3CB format) goes through decode_batch / decode')
-        n = self.N_DECODE_LANES if lanes is None else int(lanes)
-        if lanes is None and max(len(f) for f in batches) >= 64:
-            n = 1
-        result = [None] * len(batches)
-        if n <= 1 or len(batches) <= 1:
-            for i, files in enumerate(batches):
-                pixels, padding = self.decode_batch(files, out_dtype)
-                if on_batch is not None:
-                    on_batch(i, pixels, padding)
-                else:
-                    result[i] = (pixels, padding)
-            return result
-        self.blueprint.net._prepare()                  # pack the weights before forking streams
-        outer = torch.cuda.current_stream()
-        start = torch.cuda.Event()
-        start.record(outer)
-        lane_streams = self._lanes(n, chain_cus)
-        for main, _ in lane_streams:
-            main.wait_event(start)
-        use_ragged = (ragged is None or ragged) and all(len(f) < 64 for f in batches)
-        done = []
-
-        def finish(i, pixels, padding, stream):
-            if on_batch is not None:
-                on_batch(i, pixels, padding)
-            else:
-                pixels.record_stream(outer)
-                result[i] = (pixels, padding)
-
-        if not use_ragged:
-            for i, files in enumerate(batches):
-                main, side = lane_streams[i % n]
-                with torch.cuda.stream(main):
-                    pixels, padding = self._decode_batch(files, out_dtype, side)
-                    finish(i, pixels, padding, main)
-                    done.append(main.record_event())
-        else:
-            if getattr(self, '_rgb_streams', None) is None:
-                self._rgb_streams = (torch.cuda.Stream(), torch.cuda.Stream())
-            rgb_main, rgb_side = self._rgb_streams
-            rgb_main.wait_event(start)
-            # groups of (nearly) EQUAL pixel counts below the budget: [measured, profiles/r06_set_decode_group_budget.log, 500 images = 312 MPix]
-            # groups of 48 / 96 / 160 MPix: 69 / 95 / 32 MPix/s (peak 55 / 96 / 157 GB: two consecutive groups' buffers then no longer fit the
-            # allocator's caches and every phase pays hipFree + hipMalloc)
-            pix = []
-            for files, b in zip(batches, fmt):
-                H, W = container.padded_shape(files[0]) if b else parse_containers(files[:1]).scales[-1][1:]
-                pix.append(len(files) * H * W)
-            for b in (False, True):        # format-pure groups: the legacy entries, then the banded ones
-                idx = [i for i in range(len(batches)) if fmt[i] == b]
-                if not idx:
-                    continue
-                n_groups = max(1, -(-sum(pix[i] for i in idx) // self.RAGGED_GROUP_PIXELS))
-                target = sum(pix[i] for i in idx) / float(n_groups)
-                group, n_img, n_pix = [], 0, 0
-                for i in idx:
-                    group.append((i, batches[i]))
-                    n_img += len(batches[i])
-                    n_pix += pix[i]
-                    if n_img >= self.RAGGED_GROUP or n_pix >= target or i == idx[-1]:
-                        self._decode_group_ragged(group, lane_streams, rgb_main, rgb_side, out_dtype, finish, banded=b)
-                        group, n_img, n_pix = [], 0, 0
-            done.append(rgb_main.record_event())
-        for ev in done:
-            outer.wait_event(ev)
-        return result
+        return self.set_decoder.decode_many(batches, on_batch, lanes, chain_cus, out_dtype, ragged, banded)
 
     @classmethod
     def ragged_rgb_chunk_plan(cls, hws, rgb_window):
@@ -824,167 +739,6 @@ class Bitcoding(object):
         pix0, npix = cls.ragged_rgb_chunk_plan(hws, rgb_window)
         budget = _lib.load().l3c_decode_rgb_ragged_workspace_bytes(len(hws), int(npix.sum(axis=1).max()), pix0.shape[0], lag_legacy)
         return ops.rgb_entries_chunks(lens, budget, lag)
-
-    def _decode_group_ragged(self, group, lane_streams, rgb_main, rgb_side, out_dtype, finish, banded=False):
-        """One group of decode_many's ragged form, in PHASES over all its entries (batches of different shapes):
-            lanes:   upload, the coarsest scale (uniform prior), P of the next scale (get_P per shape)      -- small launches, a lane per entry
-            ragged:  that scale's symbols of ALL images in lock step (bottleneck scale: one table launch + one decoder launch for every
-                     image and channel; RGB scale: the chunk pipeline of l3c_decode_rgb_ragged), on (rgb_main, rgb_side)
-            lanes:   P of the next finer scale ...                                                          -- and so on down to scale 0
-        An image's serial chains -- 12 ms at scale 1, 60-70 ms at scale 0 for 768x512 -- are thereby paid once per GROUP instead of once
-        per image; what is left per image are the decoder-side convolutions of its shape.
-        banded: the group's files are BANDED (an entry's files share the band length of every scale).  The phases are the same; a ragged
-        phase then runs over every band of every image as an entry of its own -- pixels [j L, j L + len_j) of its image -- and the chains
-        paid per group are a band long."""
-        K = self.blueprint.net.config_ms.prob.K
-        n = len(lane_streams)
-        st = []
-        for i, files in group:
-            if banded:
-                records, parsed = container.parse_set_entry(files)
-            else:
-                parsed = parse_containers(files)
-                records = parsed.scales
-            n_pred = self._n_predicted(len(records))
-            self._check_coarsest(records[0], banded, int(parsed.nbytes[0].max()))
-            st.append({'i': i, 'files': files, 'parsed': parsed, 'records': records, 'B': len(files), 'lane': lane_streams[i % n], 'F': None,
-                       'n_pred': n_pred})
-        if len({e['n_pred'] for e in st}) != 1:
-            raise ValueError('decode_many: the files of a set must come from one model (different numbers of scale records)')
-        n_pred = st[0]['n_pred']
-        plan = list(self.iter_scale_dmll(n_pred))            # record k -> (scale, dmll, uniform), coarse -> fine
-        if getattr(self, '_alloc_stream', None) is None:
-            self._alloc_stream = torch.cuda.Stream()
-        mains = [m for m, _ in lane_streams]
-
-        def ragged_buffers(n_floats, n_sym):
-            # from a stream that runs nothing but the zero fill: allocated under rgb_main they would be ordered behind the previous group's whole
-            # last phase (the allocator reuses a stream's blocks in stream order) and every lane of this group would wait for it
-            with torch.cuda.stream(self._alloc_stream):
-                P_rag = torch.empty(n_floats, dtype=torch.float32, device='cuda')
-                sym_rag = torch.zeros(n_sym, dtype=torch.int16, device='cuda')
-                ev = self._alloc_stream.record_event()
-            for t in (P_rag, sym_rag):
-                for s_ in mains + [rgb_main, rgb_side]:
-                    t.record_stream(s_)
-            return P_rag, sym_rag, ev
-
-        # ---- the coarsest scale: uniform prior, one launch per entry on its lane
-        scale, dmll, uniform = plan[0]
-        assert uniform
-        for e in st:
-            H, W = e['records'][0][1:3]
-            with torch.cuda.stream(e['lane'][0]):
-                e['streams'] = _upload_streams(e['files'], e['parsed'])
-                e['sym'], _ = (self._scale_symbols_banded if banded else self._scale_symbols)(e['streams'], 0, e['records'][0], dmll, True, None,
-                                                                                              e['B'], None)
-                e['hw'] = (H, W)
-        prev = dmll
-        # ---- every predicted scale, coarse -> fine
-        keep = []
-        for k in range(1, n_pred + 1):
-            scale, dmll, _ = plan[k]
-            hws, pixbase, p = [], [], 0
-            for e in st:
-                Cs, H, W = e['records'][k][:3]
-                Kp = self._check_header(scale, dmll, (Cs, H, W), e['hw'])
-                pixbase.append(p)
-                p += e['B'] * H * W
-                hws += [H * W] * e['B']
-                e['hw'] = (H, W)
-            total, Btot = p, len(hws)
-            P_rag, sym_rag, alloc_ev = ragged_buffers(total * Kp, Cs * total)
-            rgb_main.wait_event(alloc_ev)
-            for g, e in enumerate(st):
-                main = e['lane'][0]
-                main.wait_event(alloc_ev)
-                with torch.cuda.stream(main):
-                    H, W = e['hw']
-                    P, e['F'] = self._get_P(scale, n_pred, self._next_input(e['sym'], prev), e['F'], (e['B'], H, W, Kp))
-                    P_rag[pixbase[g] * Kp:(pixbase[g] + e['B'] * H * W) * Kp].view(e['B'], H, W, Kp).copy_(P)
-                    rgb_main.wait_event(main.record_event())
-            # one stream table for the whole group: CHANNEL-major over all images; every entry keeps its own stream buffer, addressed from the lowest one
-            base_t = min((e['streams'].buf for e in st), key=lambda t: t.data_ptr())
-            # per channel the streams of the whole group: legacy one per image; banded one per BAND, in the order (entry, image, band)
-            o_all, l_all = [], []
-            for e in st:
-                o, l = e['streams'].scale_host(k)                             # channel-major within the entry: (c B + b), banded (c n + j) B + b
-                if banded:
-                    nb = o.shape[0] // (Cs * e['B'])
-                    o, l = (a.reshape(Cs, nb, e['B']).transpose(0, 2, 1).reshape(Cs, -1) for a in (o, l))
-                o_all.append(o.reshape(Cs, -1) + (e['streams'].buf.data_ptr() - base_t.data_ptr()))
-                l_all.append(l.reshape(Cs, -1))
-            offs = np.concatenate(o_all, axis=1).astype(np.int64)
-            lens = np.concatenate(l_all, axis=1).astype(np.int32)
-            targets = self._targets(dmll)
-            with torch.cuda.stream(rgb_main):
-                for e in st:
-                    e['streams'].buf.record_stream(rgb_main)
-                    e['streams'].buf.record_stream(rgb_side)
-                    if k == n_pred:
-                        e['streams'].finish()       # the bulk of the files (the last record) crosses PCIe here, behind the convolutions just enqueued
-                if banded:
-                    offs_d = lens_d = None
-                    keep.append(self._decode_scale_entries(st, k, dmll, pixbase, hws, P_rag, sym_rag, base_t, offs, lens, Cs, K, rgb_side))
-                else:
-                    offs_d = ops.upload_small(offs.reshape(-1))
-                    lens_d = ops.upload_small(lens.reshape(-1))
-                    if dmll.rgb_scale:
-                        pix0, npix = self.ragged_rgb_chunk_plan(hws, self.rgb_window)
-                        keep.append(ops.decode_rgb_ragged(P_rag, targets, sym_rag, base_t, offs_d, lens_d, hws, pix0, npix, K,
-                                                          *self._rgb_schedule(Btot, rgb_side)))
-                    else:
-                        hw = np.asarray(hws, dtype=np.int64)             # every image's whole plane is one entry: pix0 = 0, npix = hw
-                        keep.append(ops.decode_z_entries(P_rag, targets, sym_rag, base_t, offs_d, lens_d, np.cumsum(hw) - hw, hw,
-                                                         np.zeros(Btot, dtype=np.int64), hw, total, Cs, K))
-                done = rgb_main.record_event()
-            for g, e in enumerate(st):
-                H, W = e['hw']
-                a = Cs * pixbase[g]
-                e['sym'] = sym_rag[a:a + Cs * e['B'] * H * W].view(e['B'], Cs, H, W)
-                e['lane'][0].wait_event(done)
-            keep.append((sym_rag, offs_d, lens_d))
-            del P_rag          # (its block goes back to the allocator as soon as the streams that touched it have passed this point: a group's three P buffers never pile up)
-            prev = dmll
-        with torch.cuda.stream(rgb_main):
-            for e in st:
-                finish(e['i'], e['sym'].to(out_dtype), e['parsed'].padding, rgb_main)
-        del keep
-
-    def _decode_scale_entries(self, st, k, dmll, pixbase, hws, P_rag, sym_rag, buf, offs, lens, Cs, K, rgb_side):
-        """Record k of a BANDED group on the current stream: every band (entry of `st`, image b, band j) is a ragged entry -- pixels
-        [j L, min((j + 1) L, HW)) of its image --, streams (c, entry) in the numpy tables offs / lens (Cs, S).  Bottleneck scales: one ragged
-        table launch and one ragged decoder launch (ops.decode_z_entries); RGB scales: the chunk pipeline over all entries in lock step
-        (l3c_decode_rgb_entries), the chunk count bounded by the legacy group decode's workspace for the same images (banded_rgb_chunks).
-        More than ENTRY_LIMIT entries go through in slices.  -> tensors to keep alive."""
-        ent = [[], [], [], []]
-        for g, e in enumerate(st):
-            H, W, L = e['records'][k][1:4]
-            HW, nb = H * W, n_bands(H * W, L)
-            j = np.tile(np.arange(nb, dtype=np.int64), e['B'])
-            ent[0].append(pixbase[g] + np.repeat(np.arange(e['B'], dtype=np.int64), nb) * HW)
-            ent[1].append(np.full(e['B'] * nb, HW, dtype=np.int64))
-            ent[2].append(j * L)
-            ent[3].append(np.minimum(L, HW - j * L))
-        base, hw, pix0, length = (np.concatenate(a) for a in ent)
-        S, total = hw.shape[0], int(sum(hws))
-        targets = self._targets(dmll)
-        if dmll.rgb_scale:
-            lag, mode, side = self._rgb_schedule(S, rgb_side)
-            chunks, _ = self.banded_rgb_chunks(hws, length, self.rgb_window, self._rgb_schedule(len(hws), rgb_side)[0], lag)
-            return ops.decode_rgb_entries(P_rag, targets, sym_rag, buf, offs, lens, base, hw, pix0, length, chunks, K, lag, mode, side,
-                                          limit=self.ENTRY_LIMIT)
-        # Every slice's call allocates its Cs tables for the pixels of the WHOLE group (ops.decode_z_entries addresses a table row by its
-        # pixel in the group), and all of them live until the group is done: the bottleneck tables are paid once per SLICE.  A group has at
-        # most RAGGED_GROUP images of at most K bands each, so K = 64 never slices (32 768 bands) and K = 256 slices in three at the most;
-        # tables sized per slice would need slice-relative table offsets in ops.decode_z_entries.
-        keep = []
-        for a, b in ops.entry_slices(S, self.ENTRY_LIMIT):
-            offs_d = ops.upload_small(np.ascontiguousarray(offs[:, a:b]).reshape(-1))
-            lens_d = ops.upload_small(np.ascontiguousarray(lens[:, a:b]).reshape(-1))
-            keep.append((offs_d, lens_d, ops.decode_z_entries(P_rag, targets, sym_rag, buf, offs_d, lens_d, base[a:b], hw[a:b], pix0[a:b],
-                                                              length[a:b], total, Cs, K)))
-        return keep
 
     def _decode_z_scale(self, P, targets, streams, B, C, K, H, W):
         """A bottleneck scale: its C channels are independent given P, so ONE grouped table launch (fused, straight from P) and one
@@ -1184,144 +938,6 @@ def _rgb_mean_tensor(device):
     if key not in _RGB_MEAN_T:
         _RGB_MEAN_T[key] = torch.tensor([float(v) for v in ops.rgb_mean()], dtype=torch.float32, device=device).reshape(1, 3, 1, 1)
     return _RGB_MEAN_T[key]
-
-
-class _H2DRing(object):
-    """Page-locked staging buffers for uploads, round robin; a buffer is reused only after the copy that read it has completed."""
-
-    def __init__(self, n=3):
-        self.bufs, self.events, self.turn = [None] * n, [None] * n, 0
-
-    def take(self, nbytes):
-        k = self.turn = (self.turn + 1) % len(self.bufs)
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-            self.events[k] = None
-        if self.bufs[k] is None or self.bufs[k].numel() < nbytes:
-            self.bufs[k] = torch.empty(max(nbytes, 2 * (self.bufs[k].numel() if self.bufs[k] is not None else 0), 8 << 20),
-                                       dtype=torch.uint8, pin_memory=True)
-        return k, self.bufs[k][:nbytes]
-
-    def sent(self, k):
-        self.events[k] = torch.cuda.Event()
-        self.events[k].record(torch.cuda.current_stream())
-
-
-_UPLOAD_RING = _H2DRing(6)
-_UPLOAD_STREAM = [None]      # the files of a batch cross PCIe on a stream of their own: a lane's upload never queues behind that lane's previous batch
-
-
-class _DeviceStreams(object):
-    """The entropy-coded streams of a batch of files on the device, 4-byte aligned and zero padded, all scales in one buffer.
-    The streams of the LAST scale record (the finest scale: ~95 % of a file's bytes) may still be on the host: `finish()` -- called by
-    `scale(last)`, or by the set decoder before its last phase -- stages, uploads and cuts them out then, under the stream that is current."""
-
-    def __init__(self, buf, offs, lens, first, count, offs_host=None, lens_host=None, pending=None):
-        self.buf, self.offs, self.lens, self.first, self.count = buf, offs, lens, first, count
-        self.offs_host, self.lens_host = offs_host, lens_host       # (numpy: the set decoder merges the tables of several batches on the host)
-        self.pending = pending
-
-    def finish(self):
-        if self.pending is not None:
-            pending, self.pending = self.pending, None
-            pending()
-
-    def scale_host(self, k):
-        a, n = self.first[k], self.count[k]
-        return self.offs_host[a:a + n], self.lens_host[a:a + n]
-
-    def scale(self, k):
-        """(buffer, offsets int64, lengths int32) of scale record k: the coarsest record in image-major order (stream b * C + c, what
-        the uniform-prior decoder writes as (B, C, H, W)), the others channel-major (stream c * B + b: a channel's B streams adjacent)."""
-        if k == len(self.first) - 1:
-            self.finish()
-        a, n = self.first[k], self.count[k]
-        return self.buf, self.offs[a:a + n], self.lens[a:a + n]
-
-
-def _upload_stream():
-    if _UPLOAD_STREAM[0] is None:
-        _UPLOAD_STREAM[0] = torch.cuda.Stream()
-    return _UPLOAD_STREAM[0]
-
-
-def _h2d(stage, k, dev_slice):
-    """One asynchronous copy of a staging buffer of the upload ring on the upload stream; the current stream waits for it."""
-    cur = torch.cuda.current_stream()
-    with torch.cuda.stream(_upload_stream()):
-        dev_slice.copy_(stage, non_blocking=True)
-        _UPLOAD_RING.sent(k)
-        copied = torch.cuda.Event()
-        copied.record(_UPLOAD_STREAM[0])
-    cur.wait_event(copied)
-
-
-def _upload_streams(files, parsed):
-    """Files -> _DeviceStreams on the current stream: page-locked staging, asynchronous H2D copies on the upload stream, l3c_container_read cuts
-    the streams out on the device.  No payload byte is touched by Python.
-    In TWO parts: everything before a file's last scale record (a twentieth of its bytes) and the stream table now, the last record's streams
-    when they are asked for (`_DeviceStreams.finish`): the host's staging copy of the bulk (20 ms for a batch of 128) then runs while the
-    GPU is busy with the coarse scales, not before its first kernel [measured, same box: 0.366 -> see DESIGN 7.2]."""
-    B = len(files)
-    sizes = np.asarray([len(f) for f in files], dtype=np.int64)
-    last = len(parsed.scales) - 1
-    cut = parsed.offset[last][:, 0] - 9                     # the last record's header: u8 C, u16 H, u16 W, then channel 0's u32 length
-    al = lambda n: (n + 3) // 4 * 4                         # noqa: E731 -- file pieces 4-byte aligned in the buffer
-    base_a = np.concatenate([[0], np.cumsum(al(cut))]).astype(np.int64)
-    base_b = np.concatenate([[0], np.cumsum(al(sizes - cut))]).astype(np.int64)
-    src, dst_len, first, count = [], [], [], []
-    for k, (C, H, W) in enumerate(parsed.scales):
-        o = parsed.offset[k] + (base_a[:B, None] if k < last else (base_b[:B] - cut)[:, None])     # (the last record: relative to part B's start, added below)
-        n = parsed.nbytes[k]
-        if k:                                        # channel-major
-            o, n = o.T, n.T
-        first.append(sum(count))
-        count.append(B * C)
-        src.append(o.reshape(-1))
-        dst_len.append(n.reshape(-1))
-    S_a = first[last]
-    lens = np.concatenate(dst_len)
-    padded = (lens + 3) // 4 * 4 + 4
-    dst = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
-    S = lens.shape[0]
-    a_bytes = int(base_a[-1])
-    table_at = (a_bytes + 7) // 8 * 8
-    b_at = table_at + (S * 20 + 7) // 8 * 8
-    b_bytes = int(base_b[-1])
-    src[last] = src[last] + b_at
-    src = np.concatenate(src)
-    k, stage = _UPLOAD_RING.take(b_at)
-    st = stage.numpy()
-    for b, f in enumerate(files):
-        st[base_a[b]:base_a[b] + cut[b]] = np.frombuffer(f, dtype=np.uint8, count=int(cut[b]))
-    st[table_at:table_at + 8 * S] = src.view(np.uint8)
-    st[table_at + 8 * S:table_at + 16 * S] = dst.view(np.uint8)
-    st[table_at + 16 * S:table_at + 20 * S] = lens.astype(np.int32).view(np.uint8)
-    cur = torch.cuda.current_stream()
-    with torch.cuda.stream(_upload_stream()):       # (the upload stream's pool: the copies that fill it are ordered behind that block's previous use)
-        dev = torch.empty(b_at + b_bytes, dtype=torch.uint8, device='cuda')
-    dev.record_stream(cur)
-    _h2d(stage, k, dev[:b_at])
-    src_d = dev[table_at:table_at + 8 * S].view(torch.int64)
-    dst_d = dev[table_at + 8 * S:table_at + 16 * S].view(torch.int64)
-    len_d = dev[table_at + 16 * S:table_at + 20 * S].view(torch.int32)
-    out = torch.empty(int(padded.sum()), dtype=torch.uint8, device='cuda')
-    if S_a:                                          # (a one-record prefix of decode_preview: its only record is the "last" one)
-        ops.container_read(dev, src_d[:S_a], dst_d[:S_a], len_d[:S_a], int(lens[:S_a].max()), out)
-
-    def finish():
-        k2, stage2 = _UPLOAD_RING.take(b_bytes)
-        st2 = stage2.numpy()
-        for b, f in enumerate(files):
-            st2[base_b[b]:base_b[b] + sizes[b] - cut[b]] = np.frombuffer(f, dtype=np.uint8, offset=int(cut[b]))
-        now = torch.cuda.current_stream()
-        if now != cur:
-            dev.record_stream(now)
-            out.record_stream(now)
-        _h2d(stage2, k2, dev[b_at:])
-        ops.container_read(dev, src_d[S_a:], dst_d[S_a:], len_d[S_a:], int(lens[S_a:].max()), out)
-
-    return _DeviceStreams(out, dst_d, len_d, first, count, dst, lens, finish)
 
 
 class AsyncFileWriter(object):

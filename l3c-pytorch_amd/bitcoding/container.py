@@ -124,42 +124,14 @@ def parse_containers(files):
 def parse_banded(data):
     """One banded file, walked by its length fields.  ValueError('invalid file: ...') on an unknown version or reserved byte, C == 0, an empty
     scale, L == 0 or not a multiple of 64, more than 1024 bands, a length field or payload past the end, a missing magic."""
-    r = _Reader(data)
-    if r.take(4) != BANDED_SIGNATURE:
+    if _Reader(data).take(4) != BANDED_SIGNATURE:
         raise ValueError('invalid file: not a banded .l3c file')
-    version, reserved = r.unpack('<BB')
-    if version != BANDED_VERSION:
-        raise ValueError('invalid file: unknown banded format version {}'.format(version))
-    if reserved:
-        raise ValueError('invalid file: reserved byte is {}'.format(reserved))
-    padding = r.unpack('<4H')
-    scales, offset, nbytes = [], [], []
-    while r.p < len(data):
-        C, H, W, L = r.unpack('<BHHI')
-        if C == 0:
-            raise ValueError('invalid file: scale record with C == 0')
-        if H == 0 or W == 0:
-            raise ValueError('invalid file: empty scale {}x{}'.format(H, W))
-        if L == 0 or L % 64:
-            raise ValueError('invalid file: band length {} is not a positive multiple of 64'.format(L))
-        n = n_bands(H * W, L)
-        if n > MAX_BANDS:
-            raise ValueError('invalid file: {} bands per channel (at most {})'.format(n, MAX_BANDS))
-        off = np.zeros((C, n), dtype=np.int64)
-        nb = np.zeros((C, n), dtype=np.int64)
-        for c in range(C):
-            for j in range(n):
-                nb[c, j], = r.unpack('<I')
-                off[c, j] = r.p
-                r.take(int(nb[c, j]))
-        if r.take(4) != _MAGIC_VALUE_SEP:
-            raise ValueError('invalid file: scale separator missing')
-        scales.append((C, H, W, L))
-        offset.append(off)
-        nbytes.append(nb)
-    if len(scales) < 2:
-        raise ValueError('invalid file: {} scale record(s)'.format(len(scales)))
-    return ParsedFraming(padding, scales, offset, nbytes)
+    _, padding, found = _walk_prefix(data)
+    if (found[-1][3] if found else 14) != len(data):       # the walk stopped inside a record: data behind the last complete one (the file header: 14 bytes)
+        raise ValueError('invalid file: truncated')
+    if len(found) < 2:
+        raise ValueError('invalid file: {} scale record(s)'.format(len(found)))
+    return ParsedFraming(padding, [h for h, _, _, _ in found], [o for _, o, _, _ in found], [n for _, _, n, _ in found])
 
 
 def parse_batch(files):
@@ -335,3 +307,21 @@ def write_file(padding, scales, payloads, banded):
                 chunks += [struct.pack('<I', len(p)), p]
         chunks.append(_MAGIC_VALUE_SEP)
     return b''.join(chunks)
+
+
+# ---- ENTRY tables of the ragged decoders (ops.decode_z_entries, ops.decode_rgb_entries): entry e is pixels [pix0, pix0 + length) of an image
+# of hw pixels that starts at pixel pixbase of the group's P and symbol buffers -> (pixbase, hw, pix0, length), int64 arrays of one row per entry
+
+
+def band_entry_table(B, HW, L, pixbase0=0):
+    """Every band of B images of HW pixels, band length L, the first image at pixel pixbase0: B n entries in the order (image, band);
+    band j of image b is pixels [j L, min((j + 1) L, HW)) of the image at pixbase0 + b HW."""
+    n = n_bands(HW, L)
+    pix0 = np.tile(np.arange(n, dtype=np.int64), B) * L
+    return (pixbase0 + np.repeat(np.arange(B, dtype=np.int64), n) * HW, np.full(B * n, HW, dtype=np.int64), pix0, np.minimum(L, HW - pix0))
+
+
+def image_entry_table(hws, pixbase0=0):
+    """Whole images of hws pixels, one after the other from pixel pixbase0: an entry per image, pix0 = 0 and length = hw."""
+    hw = np.asarray(hws, dtype=np.int64)
+    return pixbase0 + np.cumsum(hw) - hw, hw, np.zeros(hw.shape[0], dtype=np.int64), hw

@@ -372,6 +372,16 @@ def dmll_cdf_table_parts(P_nhwc, sym, targets, C, K, rgb, parts):
     return tables
 
 
+def _run_rgb_pipeline(entry_point, desc, lag, side_stream, tensors):
+    """The tail of the decode_rgb* wrappers: one library call runs the whole chunk pipeline of `desc` on (current stream, side stream).
+    lag 2 decodes on `side_stream` (a torch stream) while the current stream builds the next step's tables, so the allocator must know that
+    `tensors` -- everything the descriptor points to -- are in use there; lag 1 runs on the current stream alone."""
+    if lag == 2:
+        for t in tensors:
+            t.record_stream(side_stream)
+    call(entry_point, ctypes.byref(desc), torch.cuda.current_stream().cuda_stream, side_stream.cuda_stream if lag == 2 else None)
+
+
 def decode_rgb(P_nhwc, targets, sym, buf, offs, lens, bounds, K, lag, window_mode, side_stream=None):
     """The whole RGB scale in one host call (l3c_decode_rgb): P (B,H,W,120), sym int16 (B,3,H,W) ZEROED (receives the symbols), the streams
     CHANNEL-major in (buf, offs int64 (3B,), lens int32 (3B,)), bounds = [(pix0, npix)] tiling H*W.  lag 2 decodes on `side_stream` (a
@@ -389,11 +399,7 @@ def decode_rgb(P_nhwc, targets, sym, buf, offs, lens, bounds, K, lag, window_mod
                               ptr(buf, torch.uint8), ptr(offs, torch.int64), ptr(lens, torch.int32), n,
                               ctypes.cast(p0, ctypes.POINTER(_lib.c_i64)), ctypes.cast(np_, ctypes.POINTER(_lib.c_i64)),
                               lag, window_mode, ptr(ws), nbytes)
-    main = torch.cuda.current_stream()
-    if lag == 2:
-        for t in (P_nhwc, targets, sym, buf, offs, lens, ws):
-            t.record_stream(side_stream)
-    call('l3c_decode_rgb', ctypes.byref(desc), main.cuda_stream, side_stream.cuda_stream if lag == 2 else None)
+    _run_rgb_pipeline('l3c_decode_rgb', desc, lag, side_stream, (P_nhwc, targets, sym, buf, offs, lens, ws))
     stats = None
     if window_mode:
         o = lib.l3c_decode_rgb_stats_offset(B, max_npix, n, lag)
@@ -463,11 +469,7 @@ def decode_rgb_ragged(P_ragged, targets, sym_ragged, buf, offs, lens, hws, pix0,
                               ctypes.cast(hw_c, ctypes.POINTER(_lib.c_i64)), K, ptr(buf, torch.uint8), ptr(offs, torch.int64),
                               ptr(lens, torch.int32), n, ctypes.cast(p0_c, ctypes.POINTER(_lib.c_i64)),
                               ctypes.cast(np_c, ctypes.POINTER(_lib.c_i64)), ptr(tables, torch.int64), lag, window_mode, ptr(ws), nbytes)
-    main = torch.cuda.current_stream()
-    if lag == 2:
-        for t in (P_ragged, targets, sym_ragged, buf, offs, lens, ws, tables):
-            t.record_stream(side_stream)
-    call('l3c_decode_rgb_ragged', ctypes.byref(desc), main.cuda_stream, side_stream.cuda_stream if lag == 2 else None)
+    _run_rgb_pipeline('l3c_decode_rgb_ragged', desc, lag, side_stream, (P_ragged, targets, sym_ragged, buf, offs, lens, ws, tables))
     return ws, tables
 
 
@@ -518,11 +520,7 @@ def decode_rgb_banded(P_nhwc, targets, sym, buf, offs, lens, band_len, n_chunks,
     desc = _lib.RgbBandedDesc(ptr(P_nhwc, torch.float32), ptr(targets, torch.float32), ptr(sym, torch.int16), B, HW, K,
                               ptr(buf, torch.uint8), ptr(offs, torch.int64), ptr(lens, torch.int32), band_len, n_chunks, lag, window_mode,
                               ptr(ws), nbytes)
-    if lag == 2:
-        for t in (P_nhwc, targets, sym, buf, offs, lens, ws):
-            t.record_stream(side_stream)
-    call('l3c_decode_rgb_banded', ctypes.byref(desc), torch.cuda.current_stream().cuda_stream,
-         side_stream.cuda_stream if lag == 2 else None)
+    _run_rgb_pipeline('l3c_decode_rgb_banded', desc, lag, side_stream, (P_nhwc, targets, sym, buf, offs, lens, ws))
     return ws
 
 
@@ -615,11 +613,7 @@ def decode_rgb_entries(P_ragged, targets, sym_ragged, buf, offs_host, lens_host,
         desc = _lib.RgbEntriesDesc(ptr(P_ragged, torch.float32), ptr(targets, torch.float32), ptr(sym_ragged, torch.int16), e - a, total_pix,
                                    ptr(ent_d, torch.int64), ent_h.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), K, ptr(buf, torch.uint8),
                                    ptr(offs, torch.int64), ptr(lens, torch.int32), n_chunks, lag, window_mode, ptr(ws), nbytes)
-        if lag == 2:
-            for t in (P_ragged, targets, sym_ragged, buf, offs, lens, ws, ent_d):
-                t.record_stream(side_stream)
-        call('l3c_decode_rgb_entries', ctypes.byref(desc), torch.cuda.current_stream().cuda_stream,
-             side_stream.cuda_stream if lag == 2 else None)
+        _run_rgb_pipeline('l3c_decode_rgb_entries', desc, lag, side_stream, (P_ragged, targets, sym_ragged, buf, offs, lens, ws, ent_d))
         keep.append((ws, ent_d, offs, lens))
     return keep
 

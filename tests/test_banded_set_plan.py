@@ -10,6 +10,7 @@ import l3c_pytorch_amd  # noqa: F401
 from l3c_pytorch_amd import _lib, ops
 from l3c_pytorch_amd.bitcoding import container
 from l3c_pytorch_amd.bitcoding.bitcoding import Bitcoding, band_len, n_bands
+from l3c_pytorch_amd.bitcoding.set_decode import SetDecoder
 from l3c_pytorch_amd.helpers import dataset_codec
 
 # padded image shapes of a mixed set: one band; a 64-symbol last band at K = 64 (L = 128, n = 33); more than 1 MPix; and some in between
@@ -75,7 +76,7 @@ def test_entry_slices_respect_the_limit():
         assert sl[0][0] == 0 and sl[-1][1] == S
         assert all(a[1] == b[0] for a, b in zip(sl, sl[1:]))
         assert all(0 < e - a <= min(limit, 65535) for a, e in sl)
-    assert Bitcoding.ENTRY_LIMIT == 65535
+    assert SetDecoder.ENTRY_LIMIT == 65535
 
 
 def test_entries_entry_point_checks_its_arguments_before_any_launch():

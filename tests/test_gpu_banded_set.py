@@ -48,19 +48,19 @@ class Spy(object):
 
     def __init__(self, monkeypatch):
         from l3c_pytorch_amd import ops
-        from l3c_pytorch_amd.bitcoding.bitcoding import Bitcoding
+        from l3c_pytorch_amd.bitcoding.set_decode import SetDecoder
         self.groups, self.rgb = [], []
-        group, rgb = Bitcoding._decode_group_ragged, ops.decode_rgb_entries
+        group, rgb = SetDecoder.decode_group, ops.decode_rgb_entries
 
-        def spy_group(bc, grp, *a, **kw):
+        def spy_group(dec, grp, *a, **kw):
             self.groups.append((len(grp), kw.get('banded', False)))
-            return group(bc, grp, *a, **kw)
+            return group(dec, grp, *a, **kw)
 
         def spy_rgb(P, targets, sym, buf, offs, lens, pixbase, hw, pix0, length, n_chunks, *a, **kw):
             keep = rgb(P, targets, sym, buf, offs, lens, pixbase, hw, pix0, length, n_chunks, *a, **kw)
             self.rgb.append({'pixbase': pixbase, 'hw': hw, 'pix0': pix0, 'len': length, 'chunks': n_chunks, 'limit': kw.get('limit'), 'keep': keep})
             return keep
-        monkeypatch.setattr(Bitcoding, '_decode_group_ragged', spy_group)
+        monkeypatch.setattr(SetDecoder, 'decode_group', spy_group)
         monkeypatch.setattr(ops, 'decode_rgb_entries', spy_rgb)
 
 
@@ -108,7 +108,7 @@ def _scale_symbols(bp, batches, banded_set, window='auto', **attrs):
         return orig(sym, *a)
     bc = Bitcoding(bp, rgb_window=window)
     for k, v in attrs.items():
-        setattr(bc, k, v)
+        setattr(bc.set_decoder, k, v)
     ops.sym_to_bn = spy
     try:
         if banded_set:
@@ -162,8 +162,8 @@ def test_small_budgets_split_into_groups_and_slices(monkeypatch):
     bp, imgs, files = coded_set('cr', 64)
     spy = Spy(monkeypatch)
     bc = Bitcoding(bp)
-    bc.RAGGED_GROUP_PIXELS = 300 * 1000          # the set is 2.4 MPix: several groups
-    bc.ENTRY_LIMIT = 50                          # and every ragged call in slices of at most 50 bands
+    bc.set_decoder.RAGGED_GROUP_PIXELS = 300 * 1000          # the set is 2.4 MPix: several groups
+    bc.set_decoder.ENTRY_LIMIT = 50               # and every ragged call in slices of at most 50 bands
     back = dataset_codec.decode_set(bc, files, list(imgs), banded=True)
     assert_round_trip(back, imgs)
     assert len(spy.groups) >= 3
@@ -171,7 +171,7 @@ def test_small_budgets_split_into_groups_and_slices(monkeypatch):
     for c in spy.rgb:
         assert len(c['keep']) == -(-len(c['len']) // 50)
     bc2 = Bitcoding(bp)
-    bc2.RAGGED_GROUP = 3                         # groups cut by the image count
+    bc2.set_decoder.RAGGED_GROUP = 3              # groups cut by the image count
     assert_round_trip(dataset_codec.decode_set(bc2, files, list(imgs), banded=True), imgs)
 
 

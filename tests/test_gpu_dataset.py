@@ -235,7 +235,7 @@ def test_decode_set_in_many_small_groups_with_tiny_and_large_images_side_by_side
     order = list(range(len(shapes)))
     files, _, _ = dataset_codec.encode_set(bc, imgs, order, max_batch=2)
     for group, pixels in ((3, 1 << 40), (512, 100 * 1000), (512, 128 << 20)):
-        bc.RAGGED_GROUP, bc.RAGGED_GROUP_PIXELS = group, pixels            # (instance attributes: the class constants stay)
+        bc.set_decoder.RAGGED_GROUP, bc.set_decoder.RAGGED_GROUP_PIXELS = group, pixels            # (instance attributes: the class constants stay)
         for kw in (dict(max_batch=2), dict(max_batch=1, lanes=3)):
             back = dataset_codec.decode_set(bc, files, order, **kw)
             for i in order:

@@ -512,3 +512,50 @@ def test_ragged_rgb_plan_tiles_every_image_in_lock_step():
                 assert npix[0, b] == npix[1, b] == probe
     pix0, npix = ops.ragged_rgb_plan([6, 24, 96], 1, 0)          # the coarsest scales of an RGB Shared file: one chunk each
     assert npix.tolist() == [[6, 24, 96]]
+
+
+@pytest.mark.parametrize('B,HW,L,pixbase0', [(1, 64, 64, 0), (2, 200, 64, 0), (3, 4096, 1024, 0), (2, 200, 64, 1000)])
+def test_band_entry_table_is_every_band_of_every_image(B, HW, L, pixbase0):
+    """One band; four bands, the last 8 symbols; HW a multiple of L (no short band); a base that is not zero."""
+    from l3c_pytorch_amd.bitcoding import container
+    want = []
+    for b in range(B):                                       # (image, band) order, by plain loops
+        p0 = 0
+        while p0 < HW:
+            want.append((pixbase0 + b * HW, HW, p0, min(L, HW - p0)))
+            p0 += L
+    got = container.band_entry_table(B, HW, L, pixbase0)
+    assert len(got) == 4 and all(a.dtype == 'int64' and a.shape == (len(want),) for a in got)
+    assert [tuple(int(a[i]) for a in got) for i in range(len(want))] == want
+    assert len(want) == B * container.n_bands(HW, L)
+    if pixbase0 == 0:
+        assert all((a == b).all() for a, b in zip(got, container.band_entry_table(B, HW, L)))      # the base defaults to 0
+
+
+def test_image_entry_table_is_every_whole_image():
+    from l3c_pytorch_amd.bitcoding import container
+    got = container.image_entry_table([64, 200, 8])
+    assert all(a.dtype == 'int64' for a in got)
+    assert [a.tolist() for a in got] == [[0, 64, 264], [64, 200, 8], [0, 0, 0], [64, 200, 8]]
+    assert container.image_entry_table([64, 200, 8], 1000)[0].tolist() == [1000, 1064, 1264]
+
+
+@pytest.mark.parametrize('C,n,B', [(3, 4, 2), (5, 1, 3)])
+def test_device_streams_host_table_in_channel_image_band_order(C, n, B):
+    """The upload stores a banded record's streams at (c n + j) B + b; the decoders read them at (c B + b) n + j."""
+    import numpy as np
+    from l3c_pytorch_amd.bitcoding.upload import _DeviceStreams
+    S = C * n * B
+    first = 7                                                # the record's streams are a slice of the batch's table
+    offs = np.concatenate([np.full(first, -1), np.arange(S), np.full(3, -1)]).astype(np.int64)
+    lens = np.concatenate([np.full(first, -1), 1000 + np.arange(S), np.full(3, -1)]).astype(np.int64)
+    streams = _DeviceStreams(None, None, None, [0, first], [first, S], offs, lens)
+    o, l = streams.scale_host_channel_image_band(1, C, B)
+    assert o.shape == l.shape == (C, B * n)
+    for c in range(C):
+        for b in range(B):
+            for j in range(n):
+                assert o[c, b * n + j] == (c * n + j) * B + b
+                assert l[c, b * n + j] == 1000 + (c * n + j) * B + b
+    if n == 1:                                               # a legacy record: the plain channel-major reshape
+        assert (o == np.arange(S).reshape(C, -1)).all() and (l == 1000 + np.arange(S).reshape(C, -1)).all()

@@ -8,7 +8,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import bench  # noqa: E402
-from l3c_pytorch_amd.bitcoding import bitcoding as bcm  # noqa: E402
+from l3c_pytorch_amd.bitcoding import upload as upm  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 cfg, sd, bp, bc, synthetic = bench.build_path('cr', 0, True)
@@ -17,7 +17,7 @@ files = bc.encode_batch(imgs.float()).to_bytes()
 del imgs
 torch.cuda.synchronize()
 marks = {}
-orig_upload = bcm._upload_streams
+orig_upload = upm._upload_streams
 
 
 def upload(files_, parsed):
@@ -38,7 +38,7 @@ def upload(files_, parsed):
     return r
 
 
-bcm._upload_streams = upload
+upm._upload_streams = upload
 orig_get_P = bp.net.get_P
 
 
