@@ -127,6 +127,81 @@ def test_argument_validation_of_every_family_precedes_any_launch():
     del ctypes
 
 
+def test_conv_entries_refuse_bad_channel_slices():
+    """The channel-slice preconditions of every conv entry (input / residual / output read or written as channels coff .. coff + C of a
+    tensor with cstride channels per pixel), as refusals with their messages, WITHOUT a GPU.  Every descriptor handed in here must be
+    refused: its pointers are fake.  As a second line of defence its shape (2^45 pixels) is one every entry refuses further down --
+    'grid too large' / 'below 2 GB' -- should a slice check ever go missing: the assertion on the message then fails, and nothing is
+    launched.  (l3c_conv_mfma checks the input slice only and l3c_conv_wino4w the input's multiples of 4 only: nothing else to assert
+    there today.)"""
+    import ctypes
+    lib = _lib.load()
+    xlib = _lib.load_xcheck()
+    fake = 0x1000
+    RES = _lib.EPI_RESIDUAL
+
+    def desc(KS=3, stride=1, epilogue=RES, **over):
+        d = _lib.ConvDesc()
+        d.inp = d.packed_w = d.bias = d.out = d.residual = fake
+        d.B = d.Hin = d.Win = 32768
+        d.Cin, d.Cout, d.KS, d.stride, d.dilation, d.epilogue = 64, 64, KS, stride, 1, epilogue
+        d.in_cstride, d.in_coff = 76, 8              # the layouts of tests/test_gpu_conv_slices.py
+        d.res_cstride, d.res_coff = 84, 12
+        d.out_cstride, d.out_coff = 72, 4
+        for k, v in over.items():
+            setattr(d, k, v)
+        return d
+
+    def refused(fn, d, message, *extra, **kw):
+        err = (xlib if kw.get('x') else lib).l3c_last_error
+        rc = fn(ctypes.byref(d), *(extra + (None,)))
+        assert rc == -1 and message in err().decode(), (fn.__name__, rc, err().decode(), message)
+
+    IN4, OUT4, RES4 = 'input channel stride/offset must be multiples of 4', 'output channel stride/offset must be multiples of 4', \
+        'residual channel stride/offset must be multiples of 4'
+    IN_R, OUT_R, RES_R = 'input channel slice out of range', 'output channel slice out of range', 'residual channel slice out of range'
+    # the three entries of the F(4x4,3x3) kernel and the F(2x2,3x3) kernel of the cross-check library: 16-byte loads and stores
+    # (safety net behind the slice checks: 'grid too large', then 'one image of the input must stay below 2 GB' -- conv_wino4_launch in
+    # csrc/conv_wino4.hip, l3c_conv_wino in csrc/conv_wino.hip)
+    wino = [(lib.l3c_conv_wino4, dict(), (), False), (lib.l3c_conv_wino4_phase, dict(stride=2), (1, 0), False),
+            (lib.l3c_conv_wino4_stride2, dict(KS=5, stride=2, epilogue=0), (), False), (xlib.l3c_conv_wino, dict(), (), True)]
+    for fn, base, extra, x in wino:
+        refused(fn, desc(in_coff=16, **base), IN_R, *extra, x=x)                    # 16 + 64 > 76
+        refused(fn, desc(in_cstride=68, **base), IN_R, *extra, x=x)
+        refused(fn, desc(in_cstride=78, **base), IN4, *extra, x=x)
+        refused(fn, desc(in_coff=6, **base), IN4, *extra, x=x)
+        refused(fn, desc(out_coff=3, **base), OUT4, *extra, x=x)
+        refused(fn, desc(out_cstride=70, **base), OUT4, *extra, x=x)
+        refused(fn, desc(out_coff=12, **base), OUT_R, *extra, x=x)                  # 12 + 64 > 72
+        refused(fn, desc(out_cstride=60, out_coff=0, **base), OUT_R, *extra, x=x)
+        if base.get('epilogue', RES) & RES:
+            refused(fn, desc(res_coff=5, **base), RES4, *extra, x=x)
+            refused(fn, desc(res_cstride=82, **base), RES4, *extra, x=x)
+            refused(fn, desc(res_coff=24, **base), RES_R, *extra, x=x)              # 24 + 64 > 84
+            refused(fn, desc(res_cstride=72, **base), RES_R, *extra, x=x)
+    # pixel shuffle: the slice holds Cout / 4 channels
+    refused(lib.l3c_conv_wino4, desc(Cout=256, epilogue=_lib.EPI_PIXEL_SHUFFLE, out_cstride=64, out_coff=4), OUT_R)
+    refused(xlib.l3c_conv_wino, desc(Cout=256, epilogue=_lib.EPI_PIXEL_SHUFFLE, out_cstride=64, out_coff=4), OUT_R, x=True)
+    # pointwise kernel: 16-byte loads, 4-byte stores (any output offset)
+    # (safety net: 'grid too large' in l3c_conv_pw, csrc/conv_pw.hip -- 2^45 pixels are 2^38 tiles)
+    pw = dict(KS=1, epilogue=0, Cin=192, Cout=120, in_cstride=204, out_cstride=125, out_coff=3)
+    refused(lib.l3c_conv_pw, desc(**dict(pw, in_coff=16)), 'channel slice out of range')
+    refused(lib.l3c_conv_pw, desc(**dict(pw, out_coff=6)), 'channel slice out of range')
+    refused(lib.l3c_conv_pw, desc(**dict(pw, in_coff=6)), IN4)
+    refused(lib.l3c_conv_pw, desc(**dict(pw, in_cstride=206)), IN4)
+    # implicit GEMM: 16-byte loads of the input
+    # (safety net: 'grid too large' in launch / launch_lds, csrc/conv_mfma.hip, ahead of every HIP call)
+    for base in (dict(), dict(KS=5, stride=2, epilogue=0), dict(KS=1, epilogue=0)):
+        refused(lib.l3c_conv_mfma, desc(in_coff=16, **base), IN_R)
+        refused(lib.l3c_conv_mfma, desc(in_cstride=68, **base), IN_R)
+        refused(lib.l3c_conv_mfma, desc(in_coff=6, **base), IN4)
+        refused(lib.l3c_conv_mfma, desc(in_cstride=78, **base), IN4)
+    # the 32x32x2 probe kernel of the cross-check library
+    # (safety net: 'one image of the input must stay below 2 GB' in l3c_conv_wino4w, csrc/conv_wino4w.hip, right behind this check)
+    refused(xlib.l3c_conv_wino4w, desc(epilogue=0, in_coff=6), IN4, 0, x=True)
+    refused(xlib.l3c_conv_wino4w, desc(epilogue=0, in_cstride=78), IN4, 0, x=True)
+
+
 def test_no_cpu_fallback():
     import torch
     with pytest.raises(_lib.L3CError):
