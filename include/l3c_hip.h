@@ -713,6 +713,107 @@ typedef struct {
 int64_t l3c_net_get_p_workspace_bytes(const l3c_net_config *cfg_host, int64_t B, int h, int w);
 int l3c_net_get_p(const l3c_net_get_p_desc *desc_host, l3c_stream_t stream);
 
+/* ---- the whole codec: pixels in, `.l3c` bytes out, and back (replaces bitcoding/bitcoding.py encode / decode) ------------------ */
+
+/*
+ * Bitcoding.encode_batch(...).to_bytes() and Bitcoding.decode_batch (reference bitcoding.py:50-123, :125-161) as ONE library call each,
+ * for the L3C family (configs/ms/cr.cf: what l3c_net_forward supports), batches of equally sized, already padded images, and the LEGACY
+ * `.l3c` format.  The library runs the schedule of l3c-pytorch_amd/bitcoding/bitcoding.py over the entry points above, so a file equals
+ * the Python path's byte for byte and either side reads the other's.  Outside the scope -- L3C_ERR_UNSUPPORTED, with a message naming it,
+ * before anything is enqueued: banded files, the RGB / RGB Shared baselines and auto_recurse; sets of differently sized images, auto-crop
+ * parts and preview decode have no entry here.
+ * Conventions as for l3c_net_forward: device pointers 16-byte aligned, every argument checked before anything is enqueued, no allocation,
+ * no host synchronisation, no copy from pageable memory; workspaces are caller-owned, sized by a pure host function, and their contents
+ * are garbage on entry.  Two calls on two streams with separate workspaces and outputs may share one model.
+ *
+ * The three tables of the model are INPUTS: their host rounding (torch.linspace, torch.cumsum) is part of the bitstream contract
+ * (criterion/logistic_mixture.py: coding_targets; bitcoding.uniform_cdf_row), and a restatement in C differs in a few entries.
+ */
+typedef struct {
+    const l3c_net_config *cfg_host;
+    const void *packed;             /* l3c_net_pack */
+    int64_t packed_bytes;
+    const float *targets_rgb;       /* fp32 [257]:   DiscretizedMixLogisticLoss.coding_targets of the RGB scale */
+    const float *targets_z;         /* fp32 [L + 1]: ... of the bottleneck scales */
+    const uint16_t *uniform_row;    /* [L + 1]: bitcoding.uniform_cdf_row(L), the coarsest scale's prior */
+    float z_x_min, z_bin_width;     /* l3c_sym_to_bn of the bottleneck symbols */
+} l3c_codec_model;
+
+/*
+ * File sizes and offsets of a batch on the device (the sums of EncodedBatch.file_sizes): one thread per file.
+ *   scales       as for l3c_container_write (only nbytes and C are read), coarsest first, HOST array
+ *   file_offset  int64 [B] = b * file_stride        file_bytes  int64 [B] = 8 + sum_scales (5 + 4 C + 4) + the file's payload bytes,
+ *                or -1 when one of its streams reported L3C_AC_OVERRUN (the other files of the batch are not affected)
+ * B < 65536, file_stride a positive multiple of 16.
+ */
+int l3c_container_layout(const l3c_container_scale *scales, int n_scales, int64_t B, int64_t file_stride, int64_t *file_offset,
+                         int64_t *file_bytes, l3c_stream_t stream);
+
+/* int16 symbols -> uint8 (the low byte): the decoded RGB symbols as pixels.  n elements, both pointers 16-byte aligned. */
+int l3c_sym_to_u8(const int16_t *sym, int64_t n, uint8_t *out, l3c_stream_t stream);
+
+/*
+ * Encode.  File b of the batch is written to files + b * file_stride, file_bytes[b] bytes of it; file_bytes[b] == -1: a stream of the
+ * file reported L3C_AC_OVERRUN (table rows not strictly increasing: the marker EncodedBatch._checked_nbytes turns into an error), the
+ * slot's contents are then undefined.  Everything runs on `stream`; overlapping the coder with the next batch's convolutions is the caller's
+ * business (two calls on two streams).
+ *   l3c_encode_file_stride   8 + sum_scales (5 + 4 C_s + 4) + sum_scales C_s * l3c_ac_max_bytes(h_s * w_s), rounded up to 16: the
+ *                            smallest slot that holds any file of that shape
+ */
+typedef struct {
+    const l3c_codec_model *model_host;
+    const uint8_t *img;             /* uint8 planar [B][3][H][W] */
+    int64_t B;
+    int H, W;                       /* multiples of 2^num_scales, below 65536 */
+    const uint16_t *padding;        /* uint16 [B][4] left, right, top, bottom -- or NULL: zeros */
+    uint8_t *files;                 /* [B][file_stride] */
+    int64_t file_stride;            /* a multiple of 16, >= l3c_encode_file_stride */
+    int64_t *file_bytes;            /* int64 [B] */
+    void *workspace;
+    int64_t workspace_bytes;
+} l3c_encode_batch_desc;
+int64_t l3c_encode_file_stride(const l3c_net_config *cfg_host, int H, int W);
+int64_t l3c_encode_batch_workspace_bytes(const l3c_net_config *cfg_host, int64_t B, int H, int W);
+int l3c_encode_batch(const l3c_encode_batch_desc *desc_host, l3c_stream_t stream);
+
+/*
+ * Decode, in two steps so that the half that reads untrusted bytes is pure host code (csrc/codec_plan.h: no HIP, compiles stand-alone).
+ *
+ * l3c_decode_plan touches no GPU and reads only framing bytes of the B files files_host + file_offset_host[b] .. file_offset_host[b + 1].
+ * It rejects -- L3C_ERR_INVALID_ARG, "invalid file: ..." -- what container.parse_containers, count_scale_records and Bitcoding._n_predicted /
+ * _check_coarsest / _check_header reject: truncation, a length field or payload past the end of its file, a missing separator, trailing
+ * bytes, C == 0, a record count other than num_scales + 1, a coarsest header whose C is not the model's or whose H or W is 0, a coarsest
+ * payload longer than 2 H W + 64 bytes, a predicted record that is not (C_s, 2 h, 2 w) of the one above, files that disagree, sizes the
+ * network schedule does not support; a banded file is L3C_ERR_UNSUPPORTED.  It writes ONE self-describing blob (layout: codec_plan.h)
+ * holding the records, per stream the src_offset / dst_offset / nbytes of l3c_container_read, and the RGB chunk list; the caller copies
+ * the blob to the device as it is (the entries_dev / entries_host precedent of l3c_decode_rgb_entries).
+ *   plan_host         l3c_decode_plan_bytes(cfg, B) bytes, 8-byte aligned           padding_host_out  uint16 [B][4], may be NULL
+ *
+ * l3c_decode_batch: the walk over the records.  The RGB chunk policy is Bitcoding._decode_rgb_pipelined's default (32 chunks, two
+ * 1024-symbol probes from 16384 pixels on, window mode 1); from 16 images on the decoders run on `side_stream` (lag 2), which must
+ * then be a stream of its own -- otherwise it is not used and may be NULL.  main_stream is ordered after the last pixel.
+ *   files             the files' bytes on the device at the offsets the plan was made with; 16-byte aligned, readable up to the next
+ *                     multiple of 4 of their size
+ *   plan_host / plan  the blob and the caller's device copy of it; plan_bytes: the size of either
+ *   pixels            uint8 planar [B][3][H][W]           sym   optional: int16 [B][3][H][W], the same values
+ */
+typedef struct {
+    const l3c_codec_model *model_host;
+    const uint8_t *files;
+    const void *plan_host;
+    const void *plan;
+    int64_t plan_bytes;
+    uint8_t *pixels;
+    int16_t *sym;
+    void *workspace;
+    int64_t workspace_bytes;
+} l3c_decode_batch_desc;
+int64_t l3c_decode_plan_bytes(const l3c_net_config *cfg_host, int64_t B);
+int l3c_decode_plan(const l3c_net_config *cfg_host, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B, void *plan_host,
+                    int64_t plan_bytes, int *H_out, int *W_out, uint16_t *padding_host_out);
+int64_t l3c_decode_batch_workspace_bytes(const l3c_net_config *cfg_host, const void *plan_host);
+int l3c_decode_batch(const l3c_decode_batch_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ Layout
   torchac.py     reference `torchac` facade (encode/decode_cdf, encode/decode_logistic_mixture)
   modules/       MultiscaleNetwork, Out, EncOut/DecOut, quantizer helpers
   native_net.py  NativeNet: MultiscaleNetwork.forward / get_P as ONE C-ABI call each (l3c_net_forward / l3c_net_get_p)
+  native_codec.py NativeCodec: Bitcoding.encode_batch(...).to_bytes() / decode_batch as ONE C-ABI call each (l3c_encode_batch / l3c_decode_batch)
   criterion/     DiscretizedMixLogisticLoss, CDFOut
   bitcoding/     Bitcoding (.l3c container), coders, part-suffix helper
   blueprints/    MultiscaleBlueprint

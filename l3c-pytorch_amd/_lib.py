@@ -127,6 +127,24 @@ class NetGetPDesc(ctypes.Structure):
                 ('workspace_bytes', c_i64)]
 
 
+class CodecModel(ctypes.Structure):
+    """l3c_codec_model (include/l3c_hip.h)."""
+    _fields_ = [('cfg_host', ctypes.POINTER(NetConfig)), ('packed', c_vp), ('packed_bytes', c_i64), ('targets_rgb', c_vp),
+                ('targets_z', c_vp), ('uniform_row', c_vp), ('z_x_min', c_f32), ('z_bin_width', c_f32)]
+
+
+class EncodeBatchDesc(ctypes.Structure):
+    """l3c_encode_batch_desc (include/l3c_hip.h)."""
+    _fields_ = [('model_host', ctypes.POINTER(CodecModel)), ('img', c_vp), ('B', c_i64), ('H', c_int), ('W', c_int), ('padding', c_vp),
+                ('files', c_vp), ('file_stride', c_i64), ('file_bytes', c_vp), ('workspace', c_vp), ('workspace_bytes', c_i64)]
+
+
+class DecodeBatchDesc(ctypes.Structure):
+    """l3c_decode_batch_desc (include/l3c_hip.h)."""
+    _fields_ = [('model_host', ctypes.POINTER(CodecModel)), ('files', c_vp), ('plan_host', c_vp), ('plan', c_vp), ('plan_bytes', c_i64),
+                ('pixels', c_vp), ('sym', c_vp), ('workspace', c_vp), ('workspace_bytes', c_i64)]
+
+
 EPI_RELU, EPI_RESIDUAL, EPI_PIXEL_SHUFFLE = 1, 2, 4
 ABI_VERSION = 4      # include/l3c_hip.h: L3C_ABI_VERSION (4: grouped tables, l3c_decode_rgb, l3c_container_read; no canvas batches)
 
@@ -204,6 +222,16 @@ PROTOTYPES = {
     'l3c_net_forward': (c_int, [ctypes.POINTER(NetForwardDesc), c_vp]),
     'l3c_net_get_p_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_i64, c_int, c_int]),
     'l3c_net_get_p': (c_int, [ctypes.POINTER(NetGetPDesc), c_vp]),
+    'l3c_container_layout': (c_int, [ctypes.POINTER(ContainerScale), c_int, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    'l3c_sym_to_u8': (c_int, [c_vp, c_i64, c_vp, c_vp]),
+    'l3c_encode_file_stride': (c_i64, [ctypes.POINTER(NetConfig), c_int, c_int]),
+    'l3c_encode_batch_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_i64, c_int, c_int]),
+    'l3c_encode_batch': (c_int, [ctypes.POINTER(EncodeBatchDesc), c_vp]),
+    'l3c_decode_plan_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_i64]),
+    'l3c_decode_plan': (c_int, [ctypes.POINTER(NetConfig), c_vp, ctypes.POINTER(c_i64), c_i64, c_vp, c_i64, ctypes.POINTER(c_int),
+                                ctypes.POINTER(c_int), c_vp]),
+    'l3c_decode_batch_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
+    'l3c_decode_batch': (c_int, [ctypes.POINTER(DecodeBatchDesc), c_vp, c_vp]),
 }
 
 # include/l3c_xcheck.h: the TEST-ONLY cross-check library (round-1/2 Winograd F(2x2,3x3) kernel); see load_xcheck()

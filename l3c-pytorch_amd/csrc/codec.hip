@@ -1,0 +1,521 @@
+// codec.hip -- the whole codec behind the C ABI: l3c_encode_batch / l3c_decode_batch (include/l3c_hip.h).
+//
+// Two host loops over entry points the library already has, in the order the Python schedule calls them:
+//     encode   Bitcoding.prepare_batch + code + EncodedBatch._write_container (bitcoding/bitcoding.py): image -> l3c_net_forward -> per scale
+//              the interval head -> ONE grouped coder launch -> file sizes -> l3c_container_write
+//     decode   Bitcoding._walk_records for legacy files: l3c_container_read -> the coarsest record on the uniform row -> per finer record
+//              l3c_sym_to_bn, l3c_net_get_p, tables + range decoders (the RGB scale: l3c_decode_rgb) -> pixels
+// so the files equal the Python path's byte for byte and either side decodes the other's.  Every buffer lives in ONE caller-owned workspace
+// whose contents are garbage on entry; nothing is allocated, nothing synchronises with the host.  The framing of an untrusted file is
+// parsed by the HIP-free codec_plan.h.
+//
+// Two small kernels of its own, both element-wise: the file sizes and offsets of a batch (what EncodedBatch.file_sizes sums with torch
+// ops) and int16 symbols -> uint8 pixels.
+#include <string.h>
+
+#include "codec_plan.h"
+#include "l3c_common.h"
+
+#define CODEC_FAIL(code, ...) (snprintf(l3c::error_buffer(), 512, __VA_ARGS__), (code))
+#define CODEC_TRY(x)                        \
+    do {                                    \
+        const int rc_ = (int)(x);           \
+        if (rc_ != L3C_OK) return rc_;      \
+    } while (0)
+
+namespace {
+
+constexpr int64_t ALIGN = 256;
+constexpr int MAX_REC = l3c_plan::MAX_RECORDS;
+inline int64_t up(int64_t n) { return (n + ALIGN - 1) / ALIGN * ALIGN; }
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline char *base256(void *ws) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + ALIGN - 1) / ALIGN * ALIGN); }
+
+// ---- kernels -----------------------------------------------------------------------------------------------------------------
+
+struct LayoutArgs {
+    static constexpr int MAX_SCALES = 8;
+    const uint32_t *nbytes[MAX_SCALES];   // [B * C] per scale, as the coder wrote them
+    uint32_t *clean[MAX_SCALES];          // optional copies with L3C_AC_OVERRUN replaced by 0 (what the file writer may safely copy)
+    int C[MAX_SCALES];
+    int n_scales;
+    int64_t B, file_stride;
+    int64_t *file_offset, *file_bytes;
+};
+
+// one thread per file: 8 + sum over scales (5 + 4 C + 4) + the payload bytes; -1 when a stream of the file overran
+__global__ __launch_bounds__(256) void container_layout_kernel(const LayoutArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= a.B) return;
+    int64_t total = 8;
+    bool overrun = false;
+#pragma unroll
+    for (int k = 0; k < LayoutArgs::MAX_SCALES; ++k) {
+        if (k < a.n_scales) {
+            const int C = a.C[k];
+            total += 9 + 4 * C;
+            for (int c = 0; c < C; ++c) {
+                const uint32_t n = a.nbytes[k][b * C + c];
+                const bool bad = n == L3C_AC_OVERRUN;
+                overrun = overrun || bad;
+                total += bad ? 0 : (int64_t)n;
+                if (a.clean[k]) a.clean[k][b * C + c] = bad ? 0u : n;
+            }
+        }
+    }
+    a.file_offset[b] = b * a.file_stride;
+    a.file_bytes[b] = overrun ? -1 : total;
+}
+
+// 16 symbols per thread and step: two 16-byte loads, one 16-byte store; the last n % 16 symbols one by one
+__device__ __forceinline__ uint32_t pack4(uint32_t lo, uint32_t hi) {
+    return (lo & 0xffu) | ((lo >> 8) & 0xff00u) | ((hi & 0xffu) << 16) | ((hi << 8) & 0xff000000u);
+}
+
+__global__ __launch_bounds__(256) void sym_to_u8_kernel(const int16_t *__restrict__ sym, int64_t n, uint8_t *__restrict__ out) {
+    const int64_t n_vec = n >> 4;
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    const uint4 *in4 = reinterpret_cast<const uint4 *>(sym);
+    uint4 *out4 = reinterpret_cast<uint4 *>(out);
+    for (int64_t i = tid; i < n_vec; i += stride) {
+        const uint4 a = in4[2 * i], b = in4[2 * i + 1];
+        out4[i] = make_uint4(pack4(a.x, a.y), pack4(a.z, a.w), pack4(b.x, b.y), pack4(b.z, b.w));
+    }
+    for (int64_t i = (n_vec << 4) + tid; i < n; i += stride) out[i] = (uint8_t)sym[i];
+}
+
+int launch_layout(const LayoutArgs &a, l3c_stream_t stream) {
+    hipLaunchKernelGGL(container_layout_kernel, dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, l3c::as_stream(stream), a);
+    return l3c::check_launch("container_layout_kernel");
+}
+
+// ---- the model ---------------------------------------------------------------------------------------------------------------
+
+int kp_of(const l3c_net_config &c, int s) {
+    const int Cp = s == 0 ? 3 : c.C;
+    return (Cp == 3 ? 4 : 3) * Cp * c.K;
+}
+
+// the L3C family within what the network schedule supports; the message names what is outside
+int codec_config(const l3c_net_config *cfg) {
+    CODEC_TRY(l3c_plan::check_config(cfg, l3c::error_buffer(), 512));
+    const int64_t n = l3c_net_packed_bytes(cfg);
+    return n < 0 ? (int)n : L3C_OK;
+}
+
+int check_model(const l3c_codec_model *m) {
+    L3C_REQUIRE(m, "null pointer: model_host");
+    CODEC_TRY(codec_config(m->cfg_host));
+    L3C_REQUIRE(m->packed && m->targets_rgb && m->targets_z && m->uniform_row, "null pointer in the model");
+    L3C_REQUIRE(aligned16(m->packed) && aligned16(m->targets_rgb) && aligned16(m->targets_z) && aligned16(m->uniform_row),
+                "every pointer must be 16-byte aligned (model)");
+    const int64_t n = l3c_net_packed_bytes(m->cfg_host);
+    if (m->packed_bytes != n)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "packed_bytes %lld != l3c_net_packed_bytes %lld (packed for another config?)",
+                          (long long)m->packed_bytes, (long long)n);
+    return L3C_OK;
+}
+
+int check_sides(const l3c_net_config &c, int H, int W) {
+    if (H <= 0 || W <= 0 || H >= 65536 || W >= 65536)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "bad shape: %d x %d, H and W must be 1 .. 65535 (u16 fields of the file)", H, W);
+    if (H % (1 << c.num_scales) || W % (1 << c.num_scales))
+        return CODEC_FAIL(L3C_ERR_UNSUPPORTED, "unsupported shape: %d x %d, H and W must be multiples of 2^num_scales = %d (pad first)", H, W,
+                          1 << c.num_scales);
+    return L3C_OK;
+}
+
+// ---- encode ------------------------------------------------------------------------------------------------------------------
+
+struct EncPlan {
+    int S;
+    int Cs[MAX_REC];
+    int64_t hw[MAX_REC];
+    int64_t img, sym[MAX_REC], bn_q[MAX_REC], P[MAX_REC], nb[MAX_REC], clean[MAX_REC], file_offset, zero_pad;
+    int64_t scratch;                               // the forward's workspace, then the coder's buffers
+    int64_t net_ws, iv[MAX_REC], out[MAX_REC], out_stride[MAX_REC], ac_ws;
+    int64_t bytes;
+};
+
+int64_t file_stride_of(const l3c_net_config &c, int H, int W) {
+    int64_t n = 8;
+    for (int s = 0; s <= c.num_scales; ++s) {
+        const int Cs = s == 0 ? 3 : c.C;
+        n += 5 + 4 * Cs + 4 + Cs * l3c_ac_max_bytes((int64_t)(H >> s) * (W >> s));
+    }
+    return (n + 15) / 16 * 16;
+}
+
+int enc_plan(const l3c_net_config &c, int64_t B, int H, int W, EncPlan *out) {
+    EncPlan p{};
+    p.S = c.num_scales;
+    p.net_ws = l3c_net_forward_workspace_bytes(&c, B, H, W);     // (checks the image against the schedule's limits)
+    if (p.net_ws < 0) return (int)p.net_ws;
+    int64_t at = 0, total_streams = 0;
+    auto take = [&at](int64_t n) { const int64_t o = at; at += up(n); return o; };
+    p.img = take(B * 3 * (int64_t)H * W * 4);
+    for (int s = 0; s <= p.S; ++s) {
+        p.Cs[s] = s == 0 ? 3 : c.C;
+        p.hw[s] = (int64_t)(H >> s) * (W >> s);
+        const int64_t n = B * p.Cs[s] * p.hw[s];
+        p.sym[s] = take(n * 2);
+        if (s) p.bn_q[s] = take(n * 4);
+        if (s < p.S) p.P[s] = take(B * p.hw[s] * kp_of(c, s) * 4);
+        p.nb[s] = take(B * p.Cs[s] * 4);
+        p.clean[s] = take(B * p.Cs[s] * 4);
+        total_streams += B * p.Cs[s];
+    }
+    p.file_offset = take(B * 8);
+    p.zero_pad = take(B * 8);
+    p.scratch = at;
+    int64_t coder = 0;
+    auto take_c = [&coder](int64_t n) { const int64_t o = coder; coder += up(n); return o; };
+    for (int s = 0; s <= p.S; ++s) {
+        p.iv[s] = take_c(l3c_interval_words(B * p.Cs[s], p.hw[s]) * 4);
+        p.out_stride[s] = l3c_ac_max_bytes(p.hw[s]);
+        p.out[s] = take_c(B * p.Cs[s] * p.out_stride[s]);
+    }
+    p.ac_ws = take_c(l3c_ac_encode_groups_workspace_bytes(p.S + 1, total_streams));
+    p.bytes = p.scratch + (coder > up(p.net_ws) ? coder : up(p.net_ws)) + ALIGN;   // + ALIGN: the caller's pointer is 16-byte aligned
+    *out = p;
+    return L3C_OK;
+}
+
+// ---- decode ------------------------------------------------------------------------------------------------------------------
+
+struct DecPlan {
+    int64_t streams, sym[MAX_REC], bn, F[MAX_REC], P, flags, scratch, table_bytes[MAX_REC], getp_ws, rgb_ws;
+    int64_t bytes;
+};
+
+int dec_plan(const l3c_net_config &c, const l3c_plan::Header &h, DecPlan *out) {
+    DecPlan p{};
+    const int n_rec = (int)h.n_records, S = c.num_scales;
+    const int64_t B = h.B;
+    int64_t at = 0, scratch = 0;
+    auto take = [&at](int64_t n) { const int64_t o = at; at += up(n); return o; };
+    p.streams = take(h.dst_bytes);
+    int64_t bn = 0, P = 0;
+    for (int k = 0; k < n_rec; ++k) {
+        const l3c_plan::Record &r = h.rec[k];
+        const int64_t hw = r.H * r.W;
+        if (r.H < 1 || r.W < 1 || r.C < 1 || r.C > 8 || (k && (r.H != 2 * h.rec[k - 1].H || r.W != 2 * h.rec[k - 1].W)))
+            return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent record %d", k);
+        p.sym[k] = take(B * r.C * hw * 2);             // (the finest record's: unused when the caller takes the symbols)
+        if (k + 1 < n_rec) bn = B * r.C * hw * 4 > bn ? B * r.C * hw * 4 : bn;
+        if (k) {
+            const int s = S - k;                       // the network that predicts this record
+            const int64_t ws = l3c_net_get_p_workspace_bytes(&c, B, (int)h.rec[k - 1].H, (int)h.rec[k - 1].W);
+            if (ws < 0) return (int)ws;
+            p.getp_ws = ws > p.getp_ws ? ws : p.getp_ws;
+            const int64_t Pk = B * hw * kp_of(c, s) * 4;
+            P = Pk > P ? Pk : P;
+            if (s > 0) {
+                p.F[k] = take(B * hw * c.Cf * 4);
+                p.table_bytes[k] = up(B * hw * (c.L + 1) * 2);
+                scratch = r.C * p.table_bytes[k] > scratch ? r.C * p.table_bytes[k] : scratch;
+            }
+        }
+    }
+    if (h.rec[n_rec - 1].H != h.H || h.rec[n_rec - 1].W != h.W) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent image size");
+    p.bn = take(bn);
+    p.P = take(P);
+    p.flags = take(MAX_REC * 4);
+    p.rgb_ws = l3c_decode_rgb_workspace_bytes(B, h.max_chunk_npix, (int)h.n_chunks, (int)h.lag);
+    if (p.rgb_ws < 0) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: bad chunk list");
+    scratch = p.getp_ws > scratch ? p.getp_ws : scratch;
+    scratch = p.rgb_ws > scratch ? p.rgb_ws : scratch;
+    p.scratch = at;                                    // get_p's workspace, then the scale's tables / the RGB pipeline's workspace
+    p.bytes = at + up(scratch) + ALIGN;
+    *out = p;
+    return L3C_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int l3c_container_layout(const l3c_container_scale *scales, int n_scales, int64_t B, int64_t file_stride, int64_t *file_offset,
+                         int64_t *file_bytes, l3c_stream_t stream) {
+    L3C_REQUIRE(scales && file_offset && file_bytes, "null pointer");
+    L3C_REQUIRE(n_scales > 0 && n_scales <= LayoutArgs::MAX_SCALES, "1..8 scales");
+    L3C_REQUIRE(B > 0 && B < 65536, "bad batch size (1 .. 65535)");
+    const bool stride_ok = file_stride > 0 && file_stride % 16 == 0;
+    L3C_REQUIRE(stride_ok, "file_stride must be a positive multiple of 16");
+    L3C_REQUIRE(aligned16(file_offset) && aligned16(file_bytes), "every pointer must be 16-byte aligned");
+    LayoutArgs a{};
+    a.n_scales = n_scales;
+    a.B = B;
+    a.file_stride = file_stride;
+    a.file_offset = file_offset;
+    a.file_bytes = file_bytes;
+    for (int k = 0; k < n_scales; ++k) {
+        L3C_REQUIRE(scales[k].nbytes && scales[k].C > 0 && scales[k].C < 256, "bad scale descriptor");
+        L3C_REQUIRE((reinterpret_cast<uintptr_t>(scales[k].nbytes) & 3) == 0, "nbytes arrays must be 4-byte aligned");
+        a.nbytes[k] = scales[k].nbytes;
+        a.C[k] = scales[k].C;
+    }
+    return launch_layout(a, stream);
+}
+
+int l3c_sym_to_u8(const int16_t *sym, int64_t n, uint8_t *out, l3c_stream_t stream) {
+    L3C_REQUIRE(sym && out, "null pointer");
+    L3C_REQUIRE(n > 0, "empty input");
+    L3C_REQUIRE(aligned16(sym) && aligned16(out), "every pointer must be 16-byte aligned");
+    const int64_t blocks = ((n >> 4) + 255) / 256;
+    hipLaunchKernelGGL(sym_to_u8_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks))), dim3(256), 0,
+                       l3c::as_stream(stream), sym, n, out);
+    return l3c::check_launch("sym_to_u8_kernel");
+}
+
+int64_t l3c_encode_file_stride(const l3c_net_config *cfg, int H, int W) {
+    CODEC_TRY(codec_config(cfg));
+    CODEC_TRY(check_sides(*cfg, H, W));
+    return file_stride_of(*cfg, H, W);
+}
+
+int64_t l3c_encode_batch_workspace_bytes(const l3c_net_config *cfg, int64_t B, int H, int W) {
+    CODEC_TRY(codec_config(cfg));
+    CODEC_TRY(check_sides(*cfg, H, W));
+    EncPlan p;
+    CODEC_TRY(enc_plan(*cfg, B, H, W, &p));
+    return p.bytes;
+}
+
+int l3c_encode_batch(const l3c_encode_batch_desc *d, l3c_stream_t stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    CODEC_TRY(check_model(d->model_host));
+    const l3c_codec_model &m = *d->model_host;
+    const l3c_net_config &c = *m.cfg_host;
+    L3C_REQUIRE(d->img && d->files && d->file_bytes && d->workspace, "null pointer");
+    L3C_REQUIRE(aligned16(d->img) && aligned16(d->padding) && aligned16(d->files) && aligned16(d->file_bytes) && aligned16(d->workspace),
+                "every pointer must be 16-byte aligned");
+    L3C_REQUIRE(d->B > 0 && d->B < 65536, "bad batch size (1 .. 65535)");
+    CODEC_TRY(check_sides(c, d->H, d->W));
+    EncPlan p;
+    CODEC_TRY(enc_plan(c, d->B, d->H, d->W, &p));
+    const int64_t stride = file_stride_of(c, d->H, d->W);
+    if (d->file_stride < stride || d->file_stride % 16)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "file_stride %lld: must be a multiple of 16 and at least l3c_encode_file_stride = %lld",
+                          (long long)d->file_stride, (long long)stride);
+    if (d->workspace_bytes < p.bytes)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
+
+    // ---- everything checked: enqueue
+    const int64_t B = d->B;
+    const int S = p.S;
+    char *ws = base256(d->workspace);
+    const hipStream_t st = l3c::as_stream(stream);
+    const uint16_t *padding = d->padding;
+    if (!padding) {
+        CODEC_TRY(l3c::check_hip(hipMemsetAsync(ws + p.zero_pad, 0, (size_t)B * 8, st), "hipMemsetAsync"));
+        padding = reinterpret_cast<const uint16_t *>(ws + p.zero_pad);
+    }
+    const float zero_mean[3] = {0.f, 0.f, 0.f};
+    float *img = reinterpret_cast<float *>(ws + p.img);
+    CODEC_TRY(l3c_u8_to_sym_bn(d->img, zero_mean, B, p.hw[0], reinterpret_cast<int16_t *>(ws + p.sym[0]), img, stream));
+    l3c_net_forward_desc f;
+    memset(&f, 0, sizeof(f));
+    f.cfg_host = &c;
+    f.packed = m.packed;
+    f.packed_bytes = m.packed_bytes;
+    f.img = img;
+    f.B = B;
+    f.H = d->H;
+    f.W = d->W;
+    for (int s = 0; s <= S; ++s) {
+        f.sym[s] = reinterpret_cast<int16_t *>(ws + p.sym[s]);
+        if (s) f.bn_q[s] = reinterpret_cast<float *>(ws + p.bn_q[s]);
+        if (s < S) f.P[s] = reinterpret_cast<float *>(ws + p.P[s]);
+    }
+    f.workspace = ws + p.scratch;
+    f.workspace_bytes = p.net_ws;
+    CODEC_TRY(l3c_net_forward(&f, stream));
+
+    // the forward's workspace is dead: the coder's intervals and output rows take its place.  Scales coarsest first: file order.
+    char *cs = ws + p.scratch;
+    l3c_ac_group groups[MAX_REC];
+    l3c_container_scale scales[MAX_REC];
+    LayoutArgs la{};
+    for (int k = 0; k <= S; ++k) {
+        const int s = S - k;
+        uint32_t *iv = reinterpret_cast<uint32_t *>(cs + p.iv[s]);
+        if (s == S)
+            CODEC_TRY(l3c_ac_intervals_from_table(m.uniform_row, 0, c.L + 1, f.sym[s], B * p.Cs[s], p.hw[s], iv, stream));
+        else
+            CODEC_TRY(l3c_dmll_encode_intervals(f.P[s], f.sym[s], s == 0 ? m.targets_rgb : m.targets_z, B, p.hw[s], p.Cs[s], c.K, s == 0,
+                                                s == 0 ? 257 : c.L + 1, iv, stream));
+        uint8_t *out = reinterpret_cast<uint8_t *>(cs + p.out[s]);
+        uint32_t *nb = reinterpret_cast<uint32_t *>(ws + p.nb[s]), *clean = reinterpret_cast<uint32_t *>(ws + p.clean[s]);
+        groups[k] = l3c_ac_group{iv, out, nb, B * p.Cs[s], p.hw[s], p.out_stride[s]};
+        scales[k] = l3c_container_scale{out, clean, p.out_stride[s], p.Cs[s], d->H >> s, d->W >> s};
+        la.nbytes[k] = nb;
+        la.clean[k] = clean;
+        la.C[k] = p.Cs[s];
+    }
+    CODEC_TRY(l3c_ac_encode_groups(groups, S + 1, cs + p.ac_ws, stream));
+    // file sizes and offsets; a stream that overran (L3C_AC_OVERRUN) marks its file -1 and is written as an empty payload, so that
+    // the writer below stays inside the file's slot whatever the coder reported
+    int64_t *file_offset = reinterpret_cast<int64_t *>(ws + p.file_offset);
+    la.n_scales = S + 1;
+    la.B = B;
+    la.file_stride = d->file_stride;
+    la.file_offset = file_offset;
+    la.file_bytes = d->file_bytes;
+    CODEC_TRY(launch_layout(la, stream));
+    return l3c_container_write(scales, S + 1, B, padding, file_offset, d->files, stream);
+}
+
+int64_t l3c_decode_plan_bytes(const l3c_net_config *cfg, int64_t B) {
+    CODEC_TRY(codec_config(cfg));
+    if (B < 1 || B >= 65536) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "bad batch size: B = %lld, must be 1 .. 65535", (long long)B);
+    return l3c_plan::plan_bytes(*cfg, B);
+}
+
+int l3c_decode_plan(const l3c_net_config *cfg, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B, void *plan_host,
+                    int64_t plan_bytes, int *H_out, int *W_out, uint16_t *padding_host_out) {
+    CODEC_TRY(codec_config(cfg));
+    CODEC_TRY(l3c_plan::make_plan(cfg, files_host, file_offset_host, B, plan_host, plan_bytes, H_out, W_out, padding_host_out,
+                                  l3c::error_buffer(), 512));
+    // the header's sizes against the network schedule itself (codec_plan.h restates its limits; this is the schedule's own answer)
+    l3c_plan::Header h;
+    memcpy(&h, plan_host, sizeof(h));
+    DecPlan p;
+    const int rc = dec_plan(*cfg, h, &p);
+    if (rc != L3C_OK) {
+        char why[400];
+        snprintf(why, sizeof(why), "%s", l3c::error_buffer());
+        memset(plan_host, 0, sizeof(int64_t));     // no plan
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "invalid file: %lld x %lld pixels: %s", (long long)h.H, (long long)h.W, why);
+    }
+    return L3C_OK;
+}
+
+int64_t l3c_decode_batch_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) {
+    CODEC_TRY(codec_config(cfg));
+    l3c_plan::Header h;
+    CODEC_TRY(l3c_plan::check_blob(*cfg, plan_host, -1, &h, l3c::error_buffer(), 512));
+    DecPlan p;
+    CODEC_TRY(dec_plan(*cfg, h, &p));
+    return p.bytes;
+}
+
+int l3c_decode_batch(const l3c_decode_batch_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    CODEC_TRY(check_model(d->model_host));
+    const l3c_codec_model &m = *d->model_host;
+    const l3c_net_config &c = *m.cfg_host;
+    L3C_REQUIRE(d->files && d->plan_host && d->plan && d->pixels && d->workspace, "null pointer");
+    L3C_REQUIRE(aligned16(d->files) && aligned16(d->plan) && aligned16(d->pixels) && aligned16(d->sym) && aligned16(d->workspace),
+                "every pointer must be 16-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(d->plan_host) & 7) == 0, "plan_host must be 8-byte aligned");
+    l3c_plan::Header h;
+    CODEC_TRY(l3c_plan::check_blob(c, d->plan_host, d->plan_bytes, &h, l3c::error_buffer(), 512));
+    L3C_REQUIRE(h.lag == 1 || (side_stream && side_stream != main_stream),
+                "a batch of 16 images or more decodes on two streams (lag 2): side_stream must be a stream of its own");
+    DecPlan p;
+    CODEC_TRY(dec_plan(c, h, &p));
+    if (d->workspace_bytes < p.bytes)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
+
+    // ---- everything checked: enqueue
+    const int64_t B = h.B;
+    const int n_rec = (int)h.n_records, S = c.num_scales;
+    char *ws = base256(d->workspace);
+    const hipStream_t st = l3c::as_stream(main_stream);
+    const char *plan = static_cast<const char *>(d->plan);
+    const int64_t *src_off = reinterpret_cast<const int64_t *>(plan + h.src_off), *dst_off = reinterpret_cast<const int64_t *>(plan + h.dst_off);
+    const uint32_t *nbytes = reinterpret_cast<const uint32_t *>(plan + h.nbytes_off);
+    const char *plan_h = static_cast<const char *>(d->plan_host);
+    uint8_t *streams = reinterpret_cast<uint8_t *>(ws + p.streams);
+    int32_t *flags = reinterpret_cast<int32_t *>(ws + p.flags);
+    CODEC_TRY(l3c::check_hip(hipMemsetAsync(flags, 0, MAX_REC * 4, st), "hipMemsetAsync"));
+    for (int k = 0; k < n_rec; ++k)
+        for (int64_t a = h.rec[k].first, e = a + h.rec[k].n_streams; a < e; a += 65535) {
+            const int64_t n = e - a < 65535 ? e - a : 65535;
+            CODEC_TRY(l3c_container_read(d->files, src_off + a, dst_off + a, nbytes + a, n, (uint32_t)h.rec[k].max_nbytes, streams, main_stream));
+        }
+    int16_t *sym[MAX_REC];
+    for (int k = 0; k < n_rec; ++k) sym[k] = reinterpret_cast<int16_t *>(ws + p.sym[k]);
+    if (d->sym) sym[n_rec - 1] = d->sym;
+    float *bn = reinterpret_cast<float *>(ws + p.bn), *P = reinterpret_cast<float *>(ws + p.P);
+    char *scratch = ws + p.scratch;
+    {   // the coarsest record: the uniform prior
+        const l3c_plan::Record &r = h.rec[0];
+        CODEC_TRY(l3c_ac_decode(m.uniform_row, 0, c.L + 1, streams, dst_off + r.first, nbytes + r.first, B * r.C, r.H * r.W, 1, sym[0], main_stream));
+    }
+    for (int k = 1; k < n_rec; ++k) {
+        const l3c_plan::Record &r = h.rec[k], &above = h.rec[k - 1];
+        const int s = S - k;
+        const int64_t hw = r.H * r.W;
+        CODEC_TRY(l3c_sym_to_bn(sym[k - 1], B * above.C * above.H * above.W, m.z_bin_width, m.z_x_min, bn, main_stream));
+        l3c_net_get_p_desc g;
+        memset(&g, 0, sizeof(g));
+        g.cfg_host = &c;
+        g.packed = m.packed;
+        g.packed_bytes = m.packed_bytes;
+        g.net = s;
+        g.bn_q = bn;
+        g.B = B;
+        g.h = (int)above.H;
+        g.w = (int)above.W;
+        g.fuse = k == 1 ? nullptr : reinterpret_cast<const float *>(ws + p.F[k - 1]);
+        g.P = P;
+        g.F = s > 0 ? reinterpret_cast<float *>(ws + p.F[k]) : nullptr;      // the finest scale's features feed nothing
+        g.workspace = scratch;
+        g.workspace_bytes = p.getp_ws;
+        CODEC_TRY(l3c_net_get_p(&g, main_stream));
+        // P is complete: get_p's workspace is dead and holds this scale's tables from here on
+        if (s > 0) {     // a bottleneck scale: its channels are independent given P
+            for (int c0 = 0; c0 < (int)r.C; c0 += 8) {
+                const int n = (int)r.C - c0 < 8 ? (int)r.C - c0 : 8;
+                l3c_table_part tp[8];
+                l3c_ac_decode_part dp[8];
+                memset(dp, 0, sizeof(dp));
+                for (int i = 0; i < n; ++i) {
+                    const int ch = c0 + i;
+                    uint16_t *table = reinterpret_cast<uint16_t *>(scratch + ch * p.table_bytes[k]);
+                    tp[i] = l3c_table_part{ch, 0, hw, table, flags + k, nullptr};
+                    l3c_ac_decode_part &q = dp[i];
+                    q.cdf = table;
+                    q.Lp = c.L + 1;
+                    q.in = streams;
+                    q.in_offsets = dst_off + r.first + ch * B;
+                    q.in_nbytes = nbytes + r.first + ch * B;
+                    q.n_streams = B;
+                    q.n_sym = hw;
+                    q.not_monotone_flag = flags + k;
+                    q.final_chunk = 1;
+                    q.sym_out = sym[k];
+                    q.sym_stride = r.C * hw;
+                    q.sym_offset = ch * hw;
+                }
+                CODEC_TRY(l3c_dmll_cdf_table_parts(P, nullptr, m.targets_z, B, hw, (int)r.C, c.K, 0, c.L + 1, tp, n, main_stream));
+                CODEC_TRY(l3c_ac_decode_chunks(dp, n, main_stream));
+            }
+        } else {         // the RGB scale: the chunk pipeline
+            CODEC_TRY(l3c::check_hip(hipMemsetAsync(sym[k], 0, (size_t)(B * 3 * hw * 2), st), "hipMemsetAsync"));
+            l3c_rgb_decode_desc q;
+            memset(&q, 0, sizeof(q));
+            q.P = P;
+            q.targets = m.targets_rgb;
+            q.sym = sym[k];
+            q.B = B;
+            q.HW = hw;
+            q.K = c.K;
+            q.in = streams;
+            q.in_offsets = dst_off + r.first;
+            q.in_nbytes = nbytes + r.first;
+            q.n_chunks = (int)h.n_chunks;
+            q.chunk_pix0_host = reinterpret_cast<const int64_t *>(plan_h + h.chunk_pix0_off);
+            q.chunk_npix_host = reinterpret_cast<const int64_t *>(plan_h + h.chunk_npix_off);
+            q.lag = (int)h.lag;
+            q.window_mode = 1;
+            q.workspace = scratch;
+            q.workspace_bytes = p.rgb_ws;
+            CODEC_TRY(l3c_decode_rgb(&q, main_stream, h.lag == 2 ? side_stream : nullptr));
+        }
+    }
+    return l3c_sym_to_u8(sym[n_rec - 1], B * 3 * h.H * h.W, d->pixels, main_stream);
+}
+}

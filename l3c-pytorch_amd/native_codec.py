@@ -1,0 +1,172 @@
+"""The codec as one library call per direction (include/l3c_hip.h: l3c_encode_batch / l3c_decode_plan + l3c_decode_batch).
+
+`NativeCodec(blueprint)` stands next to `Bitcoding` as `NativeNet` stands next to `MultiscaleNetwork`: the library runs the schedule of
+bitcoding/bitcoding.py -- the same entry points in the same order -- so the files equal `Bitcoding(bp).encode_batch(img).to_bytes(paddings)`
+byte for byte and either side decodes the other's.  L3C family, equally sized padded images, the legacy `.l3c` format; torch owns the
+memory and the streams, nothing else.  It has no knobs, and no product path (Bitcoding, l3c.py, test.py, bench.py) reads it.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import CodecModel, DecodeBatchDesc, EncodeBatchDesc, ptr, stream
+from .bitcoding import upload
+from .bitcoding.bitcoding import Bitcoding, _staging
+from .native_net import NativeNet, _bytes, _size
+
+PLAN_MAGIC = int.from_bytes(b'L3C_PLAN', 'little')
+_PLAN_HEADER_WORDS = 26          # csrc/codec_plan.h: Header up to its records
+_PLAN_MAX_RECORDS = _lib.NET_MAX_SCALES + 1
+_RING = upload._H2DRing(3)
+
+
+def parse_plan(blob):
+    """The blob l3c_decode_plan writes (layout: csrc/codec_plan.h) as a dict: the header's numbers, `records` = [(C, H, W, first, n_streams,
+    max_nbytes)], and the arrays src_offset / dst_offset / nbytes (per stream) and chunks = [(pix0, npix)]."""
+    raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+    w = raw[:8 * (_PLAN_HEADER_WORDS + 6 * _PLAN_MAX_RECORDS)].view(np.int64)
+    names = ['magic', 'bytes', 'B', 'n_records', 'H', 'W', 'n_streams', 'files_bytes', 'dst_bytes', 'n_chunks', 'max_chunk_npix', 'lag']
+    plan = {n: int(w[i]) for i, n in enumerate(names)}
+    plan['cfg'] = [int(v) for v in w[12:21]]
+    src_off, dst_off, nb_off, p0_off, np_off = (int(v) for v in w[21:26])
+    plan['records'] = [tuple(int(v) for v in w[26 + 6 * k:32 + 6 * k]) for k in range(plan['n_records'])]
+    S, n = plan['n_streams'], plan['n_chunks']
+    plan['src_offset'] = raw[src_off:src_off + 8 * S].view(np.int64).copy()
+    plan['dst_offset'] = raw[dst_off:dst_off + 8 * S].view(np.int64).copy()
+    plan['nbytes'] = raw[nb_off:nb_off + 4 * S].view(np.uint32).copy()
+    pix0, npix = raw[p0_off:p0_off + 8 * n].view(np.int64), raw[np_off:np_off + 8 * n].view(np.int64)
+    plan['chunks'] = [(int(a), int(b)) for a, b in zip(pix0, npix)]
+    return plan
+
+
+def decode_plan(cfg, files):
+    """l3c_decode_plan on host byte strings -> (blob bytes, H, W, paddings).  ValueError with the library's message for an invalid file,
+    L3CError for a file outside the native codec's scope (banded)."""
+    lib = _lib.load()
+    B = len(files)
+    n_plan = lib.l3c_decode_plan_bytes(ctypes.byref(cfg), B)
+    _lib.check(min(n_plan, 0))
+    sizes = np.asarray([len(f) for f in files], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    data = np.frombuffer(b''.join(bytes(f) for f in files) + b'\0' * 8, dtype=np.uint8)
+    blob = np.zeros(n_plan // 8, dtype=np.int64)
+    H, W, pads = ctypes.c_int(), ctypes.c_int(), np.zeros((B, 4), dtype=np.uint16)
+    _check_plan(lib.l3c_decode_plan(ctypes.byref(cfg), data.ctypes.data, offs.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), B, blob.ctypes.data,
+                                    n_plan, ctypes.byref(H), ctypes.byref(W), pads.ctypes.data))
+    return blob.tobytes(), H.value, W.value, [tuple(int(v) for v in p) for p in pads]
+
+
+def _check_plan(rc):
+    if rc == 0:
+        return
+    msg = _lib.load().l3c_last_error().decode()
+    if rc == -1:
+        raise ValueError(msg)
+    raise _lib.L3CError('libl3c_hip: {} (status {})'.format(msg, rc))
+
+
+class NativeCodec(object):
+    def __init__(self, blueprint):
+        _lib.require_gpu()
+        self.net = NativeNet(blueprint.net)
+        self.cfg = self.net.cfg
+        self._cfg_ref = ctypes.byref(self.cfg)
+        bc = Bitcoding(blueprint)
+        losses = blueprint.losses
+        dz = losses.loss_dmol_n
+        # the very tensors Bitcoding codes with: their host rounding is part of the bitstream contract
+        self.targets_rgb = bc._targets(losses.loss_dmol_rgb)
+        self.targets_z = bc._targets(dz)
+        self.uniform_row = bc._uniform_row(dz.L)
+        self.model = CodecModel(ctypes.pointer(self.cfg), ptr(self.net.packed), self.net.packed_bytes, ptr(self.targets_rgb, torch.float32),
+                                ptr(self.targets_z, torch.float32), ptr(self.uniform_row, torch.int16), float(dz.x_min), float(dz.bin_width))
+        self._side = None
+
+    # ---- sizes ---------------------------------------------------------------------------------------------------------------
+
+    def file_stride(self, H, W):
+        return _size(_lib.load().l3c_encode_file_stride(self._cfg_ref, H, W))
+
+    def encode_workspace_bytes(self, B, H, W):
+        return _size(_lib.load().l3c_encode_batch_workspace_bytes(self._cfg_ref, B, H, W))
+
+    def decode_workspace_bytes(self, blob):
+        buf = np.frombuffer(bytes(blob), dtype=np.int64)
+        return _size(_lib.load().l3c_decode_batch_workspace_bytes(self._cfg_ref, buf.ctypes.data))
+
+    # ---- encode --------------------------------------------------------------------------------------------------------------
+
+    def encode_device(self, imgs, paddings=None, workspace=None):
+        """Enqueue the encode on the current stream -> (files uint8 (B, file_stride), file_bytes int64 (B,)) on the device; no host sync."""
+        if imgs.dim() != 4 or imgs.shape[1] != 3 or imgs.dtype != torch.uint8:
+            raise ValueError('Expected a uint8 B3HW image batch, got {} {}'.format(imgs.dtype, tuple(imgs.shape)))
+        imgs = imgs.to('cuda').contiguous()
+        B, _, H, W = imgs.shape
+        stride = self.file_stride(H, W)
+        ws = _bytes(self.encode_workspace_bytes(B, H, W)) if workspace is None else workspace
+        files = torch.empty(B, stride, dtype=torch.uint8, device='cuda')
+        file_bytes = torch.empty(B, dtype=torch.int64, device='cuda')
+        pads = None
+        if paddings is not None:
+            pads = ops.upload_small(np.ascontiguousarray(np.asarray(paddings, dtype=np.uint16).reshape(B, 4)).view(np.int16))
+        d = EncodeBatchDesc(ctypes.pointer(self.model), ptr(imgs), B, H, W, ptr(pads), ptr(files), stride, ptr(file_bytes), ptr(ws), ws.numel())
+        _lib.call('l3c_encode_batch', ctypes.byref(d), stream())
+        return files, file_bytes
+
+    def encode_batch(self, imgs, paddings=None):
+        """imgs: (B,3,H,W) uint8, H and W multiples of 2**num_scales; paddings: B tuples (left, right, top, bottom) or None
+        -> list of B `.l3c` byte strings.  One D2H of the file sizes, then one of the slots."""
+        return self.to_bytes(*self.encode_device(imgs, paddings))
+
+    @staticmethod
+    def to_bytes(files, file_bytes):
+        """The result of encode_device on the host: one D2H of the file sizes (the synchronisation), then one of the slots' used part."""
+        sizes = file_bytes.cpu().numpy()
+        if (sizes < 0).any():
+            raise _lib.L3CError('range coder overrun: a stream asked for more than 16 bits per symbol (table rows not strictly increasing)')
+        B, mx = files.shape[0], int(sizes.max())
+        host = _staging(B * mx).view(B, mx)
+        host.copy_(files[:, :mx])
+        torch.cuda.current_stream().synchronize()
+        h = host.numpy()
+        return [h[b, :sizes[b]].tobytes() for b in range(B)]
+
+    # ---- decode --------------------------------------------------------------------------------------------------------------
+
+    def decode_batch(self, files, workspace=None):
+        """files: list of B legacy `.l3c` byte strings of equally sized (padded) images -> ((B,3,H,W) uint8 on the GPU, padding tuples).
+        The framing is parsed on the host by the library (ValueError with its message for an invalid file, L3CError for a banded one);
+        files and plan cross PCIe in one copy from page-locked memory."""
+        lib = _lib.load()
+        B = len(files)
+        n_plan = _size(lib.l3c_decode_plan_bytes(self._cfg_ref, B))
+        sizes = np.asarray([len(f) for f in files], dtype=np.int64)
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        plan_at = (int(offs[-1]) + 4 + 15) // 16 * 16
+        k, stage = _RING.take(plan_at + n_plan)
+        st = stage.numpy()
+        for b, f in enumerate(files):
+            st[offs[b]:offs[b + 1]] = np.frombuffer(f, dtype=np.uint8)
+        st[offs[-1]:plan_at] = 0
+        H, W, pads = ctypes.c_int(), ctypes.c_int(), np.zeros((B, 4), dtype=np.uint16)
+        plan_host = stage.data_ptr() + plan_at
+        _check_plan(lib.l3c_decode_plan(self._cfg_ref, stage.data_ptr(), offs.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), B, plan_host, n_plan,
+                                        ctypes.byref(H), ctypes.byref(W), pads.ctypes.data))
+        dev = torch.empty(plan_at + n_plan, dtype=torch.uint8, device='cuda')
+        dev.copy_(stage, non_blocking=True)
+        _RING.sent(k)
+        ws_bytes = _size(lib.l3c_decode_batch_workspace_bytes(self._cfg_ref, plan_host))
+        ws = _bytes(ws_bytes) if workspace is None else workspace
+        pixels = torch.empty(B, 3, H.value, W.value, dtype=torch.uint8, device='cuda')
+        side = None
+        if B >= 16:
+            if self._side is None:
+                self._side = torch.cuda.Stream()
+            side = self._side
+            for t in (dev, ws, pixels, self.net.packed, self.targets_rgb):
+                t.record_stream(side)
+        d = DecodeBatchDesc(ctypes.pointer(self.model), ptr(dev), plan_host, ptr(dev) + plan_at, n_plan, ptr(pixels), None, ptr(ws), ws.numel())
+        _lib.call('l3c_decode_batch', ctypes.byref(d), stream(), side.cuda_stream if side is not None else None)
+        return pixels, [tuple(int(v) for v in p) for p in pads]
