@@ -88,7 +88,8 @@ def ac_cases():
     cases['all_zero_symbol_Lp26'] = (tab.copy(), np.zeros(400, dtype=np.int16))
     tab = _random_table(rng, 1, 257)
     cases['single_symbol'] = (tab, np.array([200], dtype=np.int16))
-    # interval straddling the midpoint for a long time -> many pending (underflow) bits
+    # split one count off the midpoint, symbols alternating: short underflow runs (tests/ac_trace.describe: longest pending run 5, at most
+    # 6 bits emitted by one symbol).  Long runs are built by tests/ac_adversarial.py, which follows the coder state.
     tab = np.zeros((600, 3), dtype=np.uint16)
     tab[:, 1] = 32768
     tab[::2, 1] = 32767

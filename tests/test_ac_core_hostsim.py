@@ -1,6 +1,7 @@
 """The product's coder state machine (csrc/ac_core.h -- the exact code the HIP kernels instantiate) executed on the host
 CPU and checked bit-for-bit against the reference KATs and the oracle.  Covers the integer logic without a GPU."""
 import numpy as np
+import pytest
 
 from oracle import ac
 from tests.hostsim import ac_hostsim as hs
@@ -21,6 +22,26 @@ def test_hostsim_kats(golden):
         assert (hs.decode(tab, ref, len(sym), 2) == sym).all(), n
         assert (hs.decode(tab, ref, len(sym), 3) == sym).all(), (n, 'lean')
         assert (hs.decode(tab, ref, len(sym), False) == sym).all(), n
+
+
+def _adversarial():
+    from tests import ac_adversarial as A
+    return A.CASES + [('constant_row', 3)]
+
+
+@pytest.mark.parametrize('name,Lp', _adversarial())
+def test_hostsim_adversarial_streams_vs_oracle(name, Lp):
+    """The streams of tests/ac_adversarial.py (pending runs in the hundreds, resolvers that emit 32 .. 400 bits, streams that end
+    inside a run) through every form of the state machine in ac_core.h, bit for bit against the oracle."""
+    from tests import ac_adversarial as A
+    c = A.constant_row_case() if name == 'constant_row' else A.case(name, Lp)
+    tab = np.tile(c.tab, (len(c.sym), 1)) if c.tab.ndim == 1 else c.tab
+    ref = ac.encode(c.tab, c.sym)
+    for fast in (True, 2, False):
+        assert hs.encode(tab, c.sym, fast=fast) == ref, fast
+    for mode in (True, 2, 3, False):
+        assert (hs.decode(tab, ref, len(c.sym), mode) == c.sym).all(), mode
+    assert (ac.decode(c.tab, ref, len(c.sym)) == c.sym).all()
 
 
 def test_hostsim_truncated_stream_matches_reference(golden):
@@ -72,7 +93,9 @@ def test_hostsim_random_vs_oracle():
 
 
 def test_hostsim_degenerate_intervals():
-    """Width-1 intervals force n == 32 (low == high) and long pending runs."""
+    """Width-1 intervals from the full range: n == 16 symbol after symbol and the full range again (symbols 0 and 1), or n == 0 and
+    m == 0 throughout (the near-certain top symbol); with the split at 2^15, n up to 17 and a longest pending run of 2 (figures of
+    tests/ac_trace.describe).  Nothing here is a long run: those are test_hostsim_adversarial_streams_vs_oracle's."""
     N = 300
     tab = np.zeros((N, 4), dtype=np.uint16)
     tab[:, 1] = 1
