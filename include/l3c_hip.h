@@ -718,7 +718,7 @@ int l3c_net_get_p(const l3c_net_get_p_desc *desc_host, l3c_stream_t stream);
 /*
  * Bitcoding.encode_batch(...).to_bytes() and Bitcoding.decode_batch (reference bitcoding.py:50-123, :125-161) as ONE library call each,
  * for the L3C family (configs/ms/cr.cf: what l3c_net_forward supports), batches of equally sized, already padded images, and the LEGACY
- * `.l3c` format.  The library runs the schedule of l3c-pytorch_amd/bitcoding/bitcoding.py over the entry points above, so a file equals
+ * `.l3c` format (banded files: the l3c_*_banded entry points at the end of this header).  The library runs the schedule of l3c-pytorch_amd/bitcoding/bitcoding.py over the entry points above, so a file equals
  * the Python path's byte for byte and either side reads the other's.  Outside the scope -- L3C_ERR_UNSUPPORTED, with a message naming it,
  * before anything is enqueued: banded files, the RGB / RGB Shared baselines and auto_recurse; sets of differently sized images, auto-crop
  * parts and preview decode have no entry here.
@@ -813,6 +813,69 @@ int l3c_decode_plan(const l3c_net_config *cfg_host, const uint8_t *files_host, c
                     int64_t plan_bytes, int *H_out, int *W_out, uint16_t *padding_host_out);
 int64_t l3c_decode_batch_workspace_bytes(const l3c_net_config *cfg_host, const void *plan_host);
 int l3c_decode_batch(const l3c_decode_batch_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
+
+/* ---- the whole codec on BANDED files (Bitcoding(bands=K): signature 'L3CB', see l3c_ac_band_intervals) ------------------------------- */
+
+/*
+ * The same two directions for the banded format: one library call each, the schedule of Bitcoding.code with enc.bands and of
+ * _walk_records with _scale_symbols_banded, so a file equals Bitcoding(bp, bands=K).encode_batch(x).to_bytes(paddings) byte for byte and
+ * either side reads the other's.  Scope, conventions, model and descriptors as above; the legacy entry points are unchanged (l3c_decode_plan
+ * keeps refusing a banded file, the planner here refuses a legacy one).
+ *
+ * l3c_ac_decode_bands: the uniform-prior decode of every band of every plane in ONE launch, straight into the planes (the coarsest record;
+ * the row_stride == 0 case of l3c_ac_decode, one wavefront per band).  With n = ceil(n_sym / band_len), stream (p, j) is index p * n + j of
+ * in_offsets / in_nbytes; it decodes min(band_len, n_sym - j * band_len) symbols -- a complete stream: its last symbol skips the state update
+ * -- and stores them at sym_out + p * n_sym + j * band_len: bit for bit what l3c_ac_decode gives for that band alone.
+ *   cdf_row   uint16 [Lp], 2 <= Lp <= 257      band_len  a positive multiple of 64      n_planes * n < 2^31      in  4-byte aligned
+ */
+int l3c_ac_decode_bands(const uint16_t *cdf_row, int Lp, const uint8_t *in, const int64_t *in_offsets, const uint32_t *in_nbytes,
+                        int64_t n_planes, int64_t n_sym, int64_t band_len, int monotone, int16_t *sym_out, l3c_stream_t stream);
+
+/*
+ * File sizes and offsets of a banded batch on the device, the banded counterpart of l3c_container_layout: a block per file, a wave
+ * reduction over its up to C * n length fields per scale.
+ *   scales       as for l3c_container_write_banded (only the nbytes arrays, C, H, W and band_len are read), coarsest first, HOST array
+ *   file_offset  int64 [B] = b * file_stride      file_bytes  int64 [B] = 14 + sum_scales (9 + 4 C n + 4) + the file's payload bytes, or -1
+ *                when one of its bands reported L3C_AC_OVERRUN (the other files of the batch are not affected)
+ * B < 65536, file_stride a positive multiple of 16, file_offset / file_bytes 16-byte aligned.
+ */
+int l3c_container_layout_banded(const l3c_banded_scale *scales, int n_scales, int64_t B, int64_t file_stride, int64_t *file_offset,
+                                int64_t *file_bytes, l3c_stream_t stream);
+
+/*
+ * Encode: l3c_encode_batch_desc as for l3c_encode_batch, plus the band count K = `bands` (1 .. 1024): every channel of scale s is cut into
+ * bands of L_s = 64 ceil(h_s w_s / (64 K)) symbols (container.band_len).  Per scale the interval head, l3c_ac_band_intervals (a full-bands
+ * group, absent when n == 1, and a last-bands group), ONE l3c_ac_encode_groups over all groups of all scales, l3c_container_layout_banded,
+ * l3c_container_write_banded.  A band that overran marks its file -1 and is written as an empty payload.
+ *   l3c_encode_banded_file_stride   14 + sum_scales (9 + 4 C_s n_s + 4) + every band at l3c_ac_max_bytes of its length, rounded up to 16
+ */
+int64_t l3c_encode_banded_file_stride(const l3c_net_config *cfg_host, int H, int W, int bands);
+int64_t l3c_encode_batch_banded_workspace_bytes(const l3c_net_config *cfg_host, int64_t B, int H, int W, int bands);
+int l3c_encode_batch_banded(const l3c_encode_batch_desc *desc_host, int bands, l3c_stream_t stream);
+
+/*
+ * Decode.  The planner (csrc/codec_plan_banded.h: pure host code, reads framing bytes only) rejects -- L3C_ERR_INVALID_ARG, "invalid file:
+ * ..." -- what container.parse_banded rejects (version or reserved byte, C == 0, an empty scale, L == 0 or not a multiple of 64, more than
+ * 1024 bands, a length field or payload past the end, a missing separator, trailing bytes), what Bitcoding._n_predicted / _check_coarsest
+ * (a coarsest band payload longer than 2 L + 64 bytes) / _check_header reject, and files of a batch that disagree in any (C, H, W, L).
+ * L3C_ERR_UNSUPPORTED: a legacy file (l3c_decode_plan reads those), a mix of both formats, a scale with B * n > 65535 bands (slice the batch).
+ * The number of bands is a property of the FILES: l3c_decode_plan_banded_bytes walks file 0's framing, validating as it goes, and returns
+ * the blob size or a negative status.  The blob (its own magic word; layout: codec_plan_banded.h) holds the records (C, H, W, L, n, first
+ * stream, stream count, longest payload), per band stream the src_offset / dst_offset / nbytes of l3c_container_read -- coarsest record
+ * image-major (b C + c) n + j, every other record channel-major (c B + b) n + j --, for every bottleneck record the entry table
+ * pixbase | hw | pix0 | npix | table_off of its B n bands (read by the ragged kernels from the DEVICE copy of the blob), and for the RGB
+ * record the band length, the chunk count max(1, min(8, last band's symbols / 64)) and the lag (2 when B * n >= 16, else 1).
+ *
+ * l3c_decode_batch_banded: l3c_container_read in slices of 65535 streams; coarsest record l3c_ac_decode_bands; every bottleneck record
+ * l3c_sym_to_bn, l3c_net_get_p, l3c_dmll_cdf_table_ragged + l3c_ac_decode_chunks (ragged) over all B n bands, up to 8 channels per call;
+ * the RGB record l3c_decode_rgb_banded on zeroed symbols, window mode 1; l3c_sym_to_u8.  side_stream must be a stream of its own whenever
+ * the plan says lag 2; main_stream is ordered after the last pixel.
+ */
+int64_t l3c_decode_plan_banded_bytes(const l3c_net_config *cfg_host, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B);
+int l3c_decode_plan_banded(const l3c_net_config *cfg_host, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B,
+                           void *plan_host, int64_t plan_bytes, int *H_out, int *W_out, uint16_t *padding_host_out);
+int64_t l3c_decode_batch_banded_workspace_bytes(const l3c_net_config *cfg_host, const void *plan_host);
+int l3c_decode_batch_banded(const l3c_decode_batch_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
 
 #ifdef __cplusplus
 }

@@ -232,6 +232,16 @@ PROTOTYPES = {
                                 ctypes.POINTER(c_int), c_vp]),
     'l3c_decode_batch_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
     'l3c_decode_batch': (c_int, [ctypes.POINTER(DecodeBatchDesc), c_vp, c_vp]),
+    'l3c_ac_decode_bands': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp]),
+    'l3c_container_layout_banded': (c_int, [ctypes.POINTER(BandedScale), c_int, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    'l3c_encode_banded_file_stride': (c_i64, [ctypes.POINTER(NetConfig), c_int, c_int, c_int]),
+    'l3c_encode_batch_banded_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_i64, c_int, c_int, c_int]),
+    'l3c_encode_batch_banded': (c_int, [ctypes.POINTER(EncodeBatchDesc), c_int, c_vp]),
+    'l3c_decode_plan_banded_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp, ctypes.POINTER(c_i64), c_i64]),
+    'l3c_decode_plan_banded': (c_int, [ctypes.POINTER(NetConfig), c_vp, ctypes.POINTER(c_i64), c_i64, c_vp, c_i64, ctypes.POINTER(c_int),
+                                       ctypes.POINTER(c_int), c_vp]),
+    'l3c_decode_batch_banded_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
+    'l3c_decode_batch_banded': (c_int, [ctypes.POINTER(DecodeBatchDesc), c_vp, c_vp]),
 }
 
 # include/l3c_xcheck.h: the TEST-ONLY cross-check library (round-1/2 Winograd F(2x2,3x3) kernel); see load_xcheck()

@@ -13,6 +13,7 @@
 //   ac_decode_ring_kernel         the generic decoder on the same ring (streams the fast pass gave up on, tables not known
 //                                 to be monotone): the reference's literal binary search over v_readlane
 //   ac_decode_const_row_kernel    the same for one row shared by all symbols (the uniform prior of the coarsest scale)
+//   ac_decode_bands_kernel        ... for every band of every plane of banded files in one launch, straight into the planes
 //   check_monotone_kernel         flags tables that are not strictly increasing (selects the decode path)
 #include <vector>
 
@@ -700,6 +701,36 @@ __global__ __launch_bounds__(64) void ac_decode_const_row_kernel(const uint16_t 
     for (uint32_t i = 0; i < n_sym; ++i) {
         const uint32_t x = decode_symbol<NJ>(row, low, high, value, src, top, monotone != 0, i != n_sym - 1u);
         keep_symbol(dst, i, n_sym, x, lane, kept);
+    }
+}
+
+// The same for the BANDS of banded files (l3c_ac_decode_bands): block p * n + j is band j of plane p -- a complete stream of its own, of
+// min(band_len, n_sym - j * band_len) symbols -- and writes straight into the plane.  band_len % 64 == 0 keeps keep_symbol's 64-symbol
+// store blocks inside the band.
+template <int NJ>
+__global__ __launch_bounds__(64) void ac_decode_bands_kernel(const uint16_t *__restrict__ cdf, int Lp, const uint8_t *__restrict__ in,
+                                                             const int64_t *__restrict__ in_offsets,
+                                                             const uint32_t *__restrict__ in_nbytes, int64_t n_sym, int64_t band_len,
+                                                             uint32_t n_bands, int monotone, int16_t *__restrict__ sym_out) {
+    const int64_t s = blockIdx.x;
+    const int64_t p = s / n_bands, j = s - p * n_bands;
+    const int lane = threadIdx.x;
+    const int top = Lp - 2;
+    const int64_t left = n_sym - j * band_len;
+    const uint32_t n = (uint32_t)(left < band_len ? left : band_len);
+    int16_t *dst = sym_out + p * n_sym + j * band_len;
+    __shared__ __attribute__((aligned(16))) uint8_t window[512];
+    Regs<NJ> row;
+    regs_load_into(row, cdf, lane, top);
+    WaveBits src;
+    src.init(reinterpret_cast<const uint32_t *>(in + in_offsets[s]), in_nbytes[s], lane,
+             (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)window);
+    uint32_t low = 0, high = 0xFFFFFFFFu;
+    uint32_t value = src.take(32);
+    int kept = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t x = decode_symbol<NJ>(row, low, high, value, src, top, monotone != 0, i != n - 1u);
+        keep_symbol(dst, i, n, x, lane, kept);
     }
 }
 
@@ -1991,6 +2022,27 @@ int l3c_ac_decode(const uint16_t *cdf, int64_t row_stride, int Lp, const uint8_t
     DecodeArgsPack pack{};
     pack.part[0] = a;
     return launch_ring_decode(pack, 1, /*fast_pass=*/monotone != 0, st);
+}
+
+int l3c_ac_decode_bands(const uint16_t *cdf_row, int Lp, const uint8_t *in, const int64_t *in_offsets, const uint32_t *in_nbytes,
+                        int64_t n_planes, int64_t n_sym, int64_t band_len, int monotone, int16_t *sym_out, l3c_stream_t stream) {
+    L3C_REQUIRE(cdf_row && in && in_offsets && in_nbytes && sym_out, "null pointer");
+    L3C_REQUIRE(Lp >= 2 && Lp <= 257, "Lp out of range (2..257)");
+    L3C_REQUIRE(n_planes > 0 && n_sym > 0 && n_sym < (1ll << 31), "bad shape");
+    L3C_REQUIRE(band_len >= 64 && band_len % 64 == 0 && band_len < (1ll << 32), "band_len must be a positive multiple of 64");
+    const int64_t n = (n_sym + band_len - 1) / band_len;
+    L3C_REQUIRE(n_planes < (1ll << 31) && n_planes * n < (1ll << 31), "too many band streams (n_planes * n < 2^31)");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(in) & 3) == 0, "input must be 4-byte aligned (and every offset a multiple of 4)");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(cdf_row) & 1) == 0 && (reinterpret_cast<uintptr_t>(sym_out) & 1) == 0, "table and symbols must be 2-byte aligned");
+    const dim3 grid((unsigned)(n_planes * n)), block(64);
+    const hipStream_t st = l3c::as_stream(stream);
+    if (Lp - 1 <= 64)
+        hipLaunchKernelGGL(ac_decode_bands_kernel<1>, grid, block, 0, st, cdf_row, Lp, in, in_offsets, in_nbytes, n_sym, band_len, (uint32_t)n,
+                           monotone, sym_out);
+    else
+        hipLaunchKernelGGL(ac_decode_bands_kernel<4>, grid, block, 0, st, cdf_row, Lp, in, in_offsets, in_nbytes, n_sym, band_len, (uint32_t)n,
+                           monotone, sym_out);
+    return l3c::check_launch("ac_decode_bands_kernel");
 }
 
 int64_t l3c_ac_decode_state_bytes(void) { return (int64_t)sizeof(DecodeState); }

@@ -9,11 +9,16 @@
 // whose contents are garbage on entry; nothing is allocated, nothing synchronises with the host.  The framing of an untrusted file is
 // parsed by the HIP-free codec_plan.h.
 //
-// Two small kernels of its own, both element-wise: the file sizes and offsets of a batch (what EncodedBatch.file_sizes sums with torch
-// ops) and int16 symbols -> uint8 pixels.
+// The same two loops for BANDED files (l3c_encode_batch_banded / l3c_decode_batch_banded: Bitcoding.code with enc.bands and _walk_records
+// with _scale_symbols_banded; framing parser: codec_plan_banded.h): per scale l3c_ac_band_intervals cuts the intervals into band groups, and
+// every band of a record decodes as a stream of its own -- l3c_ac_decode_bands, the ragged table / decoder launches, l3c_decode_rgb_banded.
+//
+// Three small kernels of its own: the file sizes and offsets of a batch (what EncodedBatch.file_sizes sums with torch ops) for either
+// format -- a thread per legacy file, a block with a wave reduction per banded file -- and int16 symbols -> uint8 pixels.
 #include <string.h>
 
 #include "codec_plan.h"
+#include "codec_plan_banded.h"
 #include "l3c_common.h"
 
 #define CODEC_FAIL(code, ...) (snprintf(l3c::error_buffer(), 512, __VA_ARGS__), (code))
@@ -67,6 +72,59 @@ __global__ __launch_bounds__(256) void container_layout_kernel(const LayoutArgs 
     a.file_bytes[b] = overrun ? -1 : total;
 }
 
+struct BandedLayoutArgs {
+    static constexpr int MAX_SCALES = 8;
+    const uint32_t *nb_full[MAX_SCALES], *nb_last[MAX_SCALES];   // [B * C * (n - 1)] (null when n == 1), [B * C] per scale, as the coder wrote them
+    uint32_t *clean_full[MAX_SCALES], *clean_last[MAX_SCALES];   // optional copies with L3C_AC_OVERRUN replaced by 0
+    int C[MAX_SCALES];
+    int64_t n[MAX_SCALES];
+    int n_scales;
+    int64_t framing;                                             // 14 + sum over scales (9 + 4 C n + 4)
+    int64_t B, file_stride;
+    int64_t *file_offset, *file_bytes;
+};
+
+// one block per file: its C (n - 1) full-band and C last-band length fields of every scale are two contiguous runs; the four wavefronts
+// stride over them, then a wave reduction and one LDS step.  -1 when a band of the file overran.
+__global__ __launch_bounds__(256) void container_layout_banded_kernel(const BandedLayoutArgs a) {
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    int64_t total = 0;
+    int overrun = 0;
+    for (int k = 0; k < a.n_scales; ++k) {
+        const int64_t nf = a.C[k] * (a.n[k] - 1), nl = a.C[k];
+        for (int64_t i = tid; i < nf; i += 256) {
+            const uint32_t v = a.nb_full[k][b * nf + i];
+            const bool bad = v == L3C_AC_OVERRUN;
+            overrun |= bad ? 1 : 0;
+            total += bad ? 0 : (int64_t)v;
+            if (a.clean_full[k]) a.clean_full[k][b * nf + i] = bad ? 0u : v;
+        }
+        for (int64_t i = tid; i < nl; i += 256) {
+            const uint32_t v = a.nb_last[k][b * nl + i];
+            const bool bad = v == L3C_AC_OVERRUN;
+            overrun |= bad ? 1 : 0;
+            total += bad ? 0 : (int64_t)v;
+            if (a.clean_last[k]) a.clean_last[k][b * nl + i] = bad ? 0u : v;
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        total += __shfl_xor(total, d, 64);
+        overrun |= __shfl_xor(overrun, d, 64);
+    }
+    __shared__ int64_t part[4];
+    __shared__ int part_bad[4];
+    if ((tid & 63) == 0) {
+        part[tid >> 6] = total;
+        part_bad[tid >> 6] = overrun;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        a.file_offset[b] = b * a.file_stride;
+        a.file_bytes[b] = (part_bad[0] | part_bad[1] | part_bad[2] | part_bad[3]) ? -1 : a.framing + part[0] + part[1] + part[2] + part[3];
+    }
+}
+
 // 16 symbols per thread and step: two 16-byte loads, one 16-byte store; the last n % 16 symbols one by one
 __device__ __forceinline__ uint32_t pack4(uint32_t lo, uint32_t hi) {
     return (lo & 0xffu) | ((lo >> 8) & 0xff00u) | ((hi & 0xffu) << 16) | ((hi << 8) & 0xff000000u);
@@ -87,6 +145,11 @@ __global__ __launch_bounds__(256) void sym_to_u8_kernel(const int16_t *__restric
 int launch_layout(const LayoutArgs &a, l3c_stream_t stream) {
     hipLaunchKernelGGL(container_layout_kernel, dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, l3c::as_stream(stream), a);
     return l3c::check_launch("container_layout_kernel");
+}
+
+int launch_layout_banded(const BandedLayoutArgs &a, l3c_stream_t stream) {
+    hipLaunchKernelGGL(container_layout_banded_kernel, dim3((unsigned)a.B), dim3(256), 0, l3c::as_stream(stream), a);
+    return l3c::check_launch("container_layout_banded_kernel");
 }
 
 // ---- the model ---------------------------------------------------------------------------------------------------------------
@@ -188,24 +251,30 @@ struct DecPlan {
     int64_t bytes;
 };
 
-int dec_plan(const l3c_net_config &c, const l3c_plan::Header &h, DecPlan *out) {
+// the records of either plan as the workspace layout reads them
+struct RecShape {
+    int64_t C, H, W;
+};
+
+// rgb_ws: the workspace of the RGB record's pipeline (l3c_decode_rgb or l3c_decode_rgb_banded), negative: a bad plan
+int dec_plan_of(const l3c_net_config &c, int64_t B, int n_rec, const RecShape *rec, int64_t H, int64_t W, int64_t dst_bytes, int64_t rgb_ws,
+                DecPlan *out) {
     DecPlan p{};
-    const int n_rec = (int)h.n_records, S = c.num_scales;
-    const int64_t B = h.B;
+    const int S = c.num_scales;
     int64_t at = 0, scratch = 0;
     auto take = [&at](int64_t n) { const int64_t o = at; at += up(n); return o; };
-    p.streams = take(h.dst_bytes);
+    p.streams = take(dst_bytes);
     int64_t bn = 0, P = 0;
     for (int k = 0; k < n_rec; ++k) {
-        const l3c_plan::Record &r = h.rec[k];
+        const RecShape &r = rec[k];
         const int64_t hw = r.H * r.W;
-        if (r.H < 1 || r.W < 1 || r.C < 1 || r.C > 8 || (k && (r.H != 2 * h.rec[k - 1].H || r.W != 2 * h.rec[k - 1].W)))
+        if (r.H < 1 || r.W < 1 || r.C < 1 || r.C > 8 || (k && (r.H != 2 * rec[k - 1].H || r.W != 2 * rec[k - 1].W)))
             return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent record %d", k);
         p.sym[k] = take(B * r.C * hw * 2);             // (the finest record's: unused when the caller takes the symbols)
         if (k + 1 < n_rec) bn = B * r.C * hw * 4 > bn ? B * r.C * hw * 4 : bn;
         if (k) {
             const int s = S - k;                       // the network that predicts this record
-            const int64_t ws = l3c_net_get_p_workspace_bytes(&c, B, (int)h.rec[k - 1].H, (int)h.rec[k - 1].W);
+            const int64_t ws = l3c_net_get_p_workspace_bytes(&c, B, (int)rec[k - 1].H, (int)rec[k - 1].W);
             if (ws < 0) return (int)ws;
             p.getp_ws = ws > p.getp_ws ? ws : p.getp_ws;
             const int64_t Pk = B * hw * kp_of(c, s) * 4;
@@ -217,16 +286,120 @@ int dec_plan(const l3c_net_config &c, const l3c_plan::Header &h, DecPlan *out) {
             }
         }
     }
-    if (h.rec[n_rec - 1].H != h.H || h.rec[n_rec - 1].W != h.W) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent image size");
+    if (rec[n_rec - 1].H != H || rec[n_rec - 1].W != W) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent image size");
     p.bn = take(bn);
     p.P = take(P);
     p.flags = take(MAX_REC * 4);
-    p.rgb_ws = l3c_decode_rgb_workspace_bytes(B, h.max_chunk_npix, (int)h.n_chunks, (int)h.lag);
+    p.rgb_ws = rgb_ws;
     if (p.rgb_ws < 0) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: bad chunk list");
     scratch = p.getp_ws > scratch ? p.getp_ws : scratch;
     scratch = p.rgb_ws > scratch ? p.rgb_ws : scratch;
     p.scratch = at;                                    // get_p's workspace, then the scale's tables / the RGB pipeline's workspace
     p.bytes = at + up(scratch) + ALIGN;
+    *out = p;
+    return L3C_OK;
+}
+
+int dec_plan(const l3c_net_config &c, const l3c_plan::Header &h, DecPlan *out) {
+    RecShape rec[MAX_REC];
+    const int n_rec = (int)h.n_records;
+    for (int k = 0; k < n_rec; ++k) rec[k] = RecShape{h.rec[k].C, h.rec[k].H, h.rec[k].W};
+    return dec_plan_of(c, h.B, n_rec, rec, h.H, h.W, h.dst_bytes, l3c_decode_rgb_workspace_bytes(h.B, h.max_chunk_npix, (int)h.n_chunks, (int)h.lag),
+                       out);
+}
+
+int dec_plan_banded(const l3c_net_config &c, const l3c_plan::BandedHeader &h, DecPlan *out) {
+    RecShape rec[MAX_REC];
+    const int n_rec = (int)h.n_records;
+    for (int k = 0; k < n_rec; ++k) rec[k] = RecShape{h.rec[k].C, h.rec[k].H, h.rec[k].W};
+    return dec_plan_of(c, h.B, n_rec, rec, h.H, h.W, h.dst_bytes,
+                       l3c_decode_rgb_banded_workspace_bytes(h.B, h.H * h.W, h.rgb_band_len, (int)h.rgb_chunks, (int)h.lag), out);
+}
+
+// ---- banded encode -----------------------------------------------------------------------------------------------------------
+
+struct EncBandPlan {
+    int S;
+    int Cs[MAX_REC];
+    int64_t hw[MAX_REC], L[MAX_REC], n[MAX_REC], last[MAX_REC];         // per scale: band length, bands per channel, symbols of the last band
+    int64_t img, sym[MAX_REC], bn_q[MAX_REC], P[MAX_REC], file_offset, zero_pad;
+    int64_t nb_f[MAX_REC], nb_l[MAX_REC], clean_f[MAX_REC], clean_l[MAX_REC];
+    int64_t scratch;                                                     // the forward's workspace, then the coder's buffers
+    int64_t net_ws, iv, iv_f[MAX_REC], iv_l[MAX_REC], out_f[MAX_REC], out_l[MAX_REC], stride_f[MAX_REC], stride_l[MAX_REC], ac_ws, pos;
+    int64_t streams_per_image, framing;
+    int64_t bytes;
+};
+
+inline int64_t band_len_of(int64_t hw, int bands) { return 64 * ((hw + 64 * (int64_t)bands - 1) / (64 * (int64_t)bands)); }
+
+int check_bands(int bands) {
+    if (bands < 1 || bands > l3c_plan::MAX_BANDS) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "bands = %d: must be 1 .. 1024", bands);
+    return L3C_OK;
+}
+
+int64_t banded_file_stride_of(const l3c_net_config &c, int H, int W, int bands) {
+    int64_t total = 14;
+    for (int s = 0; s <= c.num_scales; ++s) {
+        const int64_t Cs = s == 0 ? 3 : c.C, hw = (int64_t)(H >> s) * (W >> s), L = band_len_of(hw, bands), n = (hw + L - 1) / L;
+        total += 9 + 4 * Cs * n + 4 + Cs * ((n - 1) * l3c_ac_max_bytes(L) + l3c_ac_max_bytes(hw - (n - 1) * L));
+    }
+    return (total + 15) / 16 * 16;
+}
+
+int enc_band_plan(const l3c_net_config &c, int64_t B, int H, int W, int bands, EncBandPlan *out) {
+    EncBandPlan p{};
+    p.S = c.num_scales;
+    p.net_ws = l3c_net_forward_workspace_bytes(&c, B, H, W);     // (checks the image against the schedule's limits)
+    if (p.net_ws < 0) return (int)p.net_ws;
+    int64_t at = 0, total_streams = 0, iv_words = 0;
+    int n_groups = 0;
+    auto take = [&at](int64_t n) { const int64_t o = at; at += up(n); return o; };
+    p.img = take(B * 3 * (int64_t)H * W * 4);
+    p.framing = 14;
+    for (int s = 0; s <= p.S; ++s) {
+        p.Cs[s] = s == 0 ? 3 : c.C;
+        p.hw[s] = (int64_t)(H >> s) * (W >> s);
+        p.L[s] = band_len_of(p.hw[s], bands);
+        p.n[s] = (p.hw[s] + p.L[s] - 1) / p.L[s];
+        p.last[s] = p.hw[s] - (p.n[s] - 1) * p.L[s];
+        const int64_t streams = B * p.Cs[s], n = streams * p.hw[s];
+        if (B * p.n[s] > l3c_plan::MAX_BAND_STREAMS)
+            return CODEC_FAIL(L3C_ERR_UNSUPPORTED, "unsupported batch: %lld images x %lld bands at scale %d, more than 65535 band streams per channel "
+                              "in one call: slice the batch", (long long)B, (long long)p.n[s], s);
+        p.sym[s] = take(n * 2);
+        if (s) p.bn_q[s] = take(n * 4);
+        if (s < p.S) p.P[s] = take(B * p.hw[s] * kp_of(c, s) * 4);
+        p.nb_f[s] = take(streams * (p.n[s] - 1) * 4);
+        p.clean_f[s] = take(streams * (p.n[s] - 1) * 4);
+        p.nb_l[s] = take(streams * 4);
+        p.clean_l[s] = take(streams * 4);
+        total_streams += streams * p.n[s];
+        n_groups += p.n[s] > 1 ? 2 : 1;
+        p.streams_per_image += p.Cs[s] * p.n[s];
+        p.framing += 9 + 4 * p.Cs[s] * p.n[s] + 4;
+        const int64_t w = l3c_interval_words(streams, p.hw[s]);
+        iv_words = w > iv_words ? w : iv_words;
+    }
+    p.file_offset = take(B * 8);
+    p.zero_pad = take(B * 8);
+    p.scratch = at;
+    int64_t coder = 0;
+    auto take_c = [&coder](int64_t n) { const int64_t o = coder; coder += up(n); return o; };
+    p.iv = take_c(iv_words * 4);                                  // one scale's intervals at a time: l3c_ac_band_intervals copies them out
+    for (int s = 0; s <= p.S; ++s) {
+        const int64_t streams = B * p.Cs[s];
+        if (p.n[s] > 1) {
+            p.iv_f[s] = take_c(l3c_interval_words(streams * (p.n[s] - 1), p.L[s]) * 4);
+            p.stride_f[s] = l3c_ac_max_bytes(p.L[s]);
+            p.out_f[s] = take_c(streams * (p.n[s] - 1) * p.stride_f[s]);
+        }
+        p.iv_l[s] = take_c(l3c_interval_words(streams, p.last[s]) * 4);
+        p.stride_l[s] = l3c_ac_max_bytes(p.last[s]);
+        p.out_l[s] = take_c(streams * p.stride_l[s]);
+    }
+    p.ac_ws = take_c(l3c_ac_encode_groups_workspace_bytes(n_groups, total_streams));
+    p.pos = take_c(B * p.streams_per_image * 8);
+    p.bytes = p.scratch + (coder > up(p.net_ws) ? coder : up(p.net_ws)) + ALIGN;   // + ALIGN: the caller's pointer is 16-byte aligned
     *out = p;
     return L3C_OK;
 }
@@ -514,6 +687,316 @@ int l3c_decode_batch(const l3c_decode_batch_desc *d, l3c_stream_t main_stream, l
             q.workspace = scratch;
             q.workspace_bytes = p.rgb_ws;
             CODEC_TRY(l3c_decode_rgb(&q, main_stream, h.lag == 2 ? side_stream : nullptr));
+        }
+    }
+    return l3c_sym_to_u8(sym[n_rec - 1], B * 3 * h.H * h.W, d->pixels, main_stream);
+}
+
+// ---- banded files ------------------------------------------------------------------------------------------------------------
+
+int l3c_container_layout_banded(const l3c_banded_scale *scales, int n_scales, int64_t B, int64_t file_stride, int64_t *file_offset,
+                                int64_t *file_bytes, l3c_stream_t stream) {
+    L3C_REQUIRE(scales && file_offset && file_bytes, "null pointer");
+    L3C_REQUIRE(n_scales > 0 && n_scales <= BandedLayoutArgs::MAX_SCALES, "1..8 scales");
+    L3C_REQUIRE(B > 0 && B < 65536, "bad batch size (1 .. 65535)");
+    const bool stride_ok = file_stride > 0 && file_stride % 16 == 0;
+    L3C_REQUIRE(stride_ok, "file_stride must be a positive multiple of 16");
+    L3C_REQUIRE(aligned16(file_offset) && aligned16(file_bytes), "every pointer must be 16-byte aligned");
+    BandedLayoutArgs a{};
+    a.n_scales = n_scales;
+    a.B = B;
+    a.file_stride = file_stride;
+    a.file_offset = file_offset;
+    a.file_bytes = file_bytes;
+    a.framing = 14;
+    for (int k = 0; k < n_scales; ++k) {
+        const l3c_banded_scale &q = scales[k];
+        L3C_REQUIRE(q.C > 0 && q.C < 256 && q.H > 0 && q.H < 65536 && q.W > 0 && q.W < 65536, "bad scale descriptor (C < 256, H and W fit u16)");
+        L3C_REQUIRE(q.band_len >= 64 && q.band_len % 64 == 0, "band_len must be a positive multiple of 64");
+        const int64_t n = ((int64_t)q.H * q.W + q.band_len - 1) / q.band_len;
+        L3C_REQUIRE(n <= l3c_plan::MAX_BANDS, "more than 1024 bands per channel");
+        L3C_REQUIRE(q.nbytes_last && (n == 1 || q.nbytes_full), "bad scale descriptor (null nbytes array)");
+        L3C_REQUIRE(((reinterpret_cast<uintptr_t>(q.nbytes_last) | (n == 1 ? 0 : reinterpret_cast<uintptr_t>(q.nbytes_full))) & 3) == 0,
+                    "nbytes arrays must be 4-byte aligned");
+        a.nb_full[k] = n == 1 ? nullptr : q.nbytes_full;
+        a.nb_last[k] = q.nbytes_last;
+        a.C[k] = q.C;
+        a.n[k] = n;
+        a.framing += 9 + 4 * q.C * n + 4;
+    }
+    return launch_layout_banded(a, stream);
+}
+
+int64_t l3c_encode_banded_file_stride(const l3c_net_config *cfg, int H, int W, int bands) {
+    CODEC_TRY(codec_config(cfg));
+    CODEC_TRY(check_sides(*cfg, H, W));
+    CODEC_TRY(check_bands(bands));
+    return banded_file_stride_of(*cfg, H, W, bands);
+}
+
+int64_t l3c_encode_batch_banded_workspace_bytes(const l3c_net_config *cfg, int64_t B, int H, int W, int bands) {
+    CODEC_TRY(codec_config(cfg));
+    CODEC_TRY(check_sides(*cfg, H, W));
+    CODEC_TRY(check_bands(bands));
+    EncBandPlan p;
+    CODEC_TRY(enc_band_plan(*cfg, B, H, W, bands, &p));
+    return p.bytes;
+}
+
+int l3c_encode_batch_banded(const l3c_encode_batch_desc *d, int bands, l3c_stream_t stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    CODEC_TRY(check_model(d->model_host));
+    const l3c_codec_model &m = *d->model_host;
+    const l3c_net_config &c = *m.cfg_host;
+    L3C_REQUIRE(d->img && d->files && d->file_bytes && d->workspace, "null pointer");
+    L3C_REQUIRE(aligned16(d->img) && aligned16(d->padding) && aligned16(d->files) && aligned16(d->file_bytes) && aligned16(d->workspace),
+                "every pointer must be 16-byte aligned");
+    L3C_REQUIRE(d->B > 0 && d->B < 65536, "bad batch size (1 .. 65535)");
+    CODEC_TRY(check_sides(c, d->H, d->W));
+    CODEC_TRY(check_bands(bands));
+    EncBandPlan p;
+    CODEC_TRY(enc_band_plan(c, d->B, d->H, d->W, bands, &p));
+    const int64_t stride = banded_file_stride_of(c, d->H, d->W, bands);
+    if (d->file_stride < stride || d->file_stride % 16)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "file_stride %lld: must be a multiple of 16 and at least l3c_encode_banded_file_stride = %lld",
+                          (long long)d->file_stride, (long long)stride);
+    if (d->workspace_bytes < p.bytes)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
+
+    // ---- everything checked: enqueue
+    const int64_t B = d->B;
+    const int S = p.S;
+    char *ws = base256(d->workspace);
+    const hipStream_t st = l3c::as_stream(stream);
+    const uint16_t *padding = d->padding;
+    if (!padding) {
+        CODEC_TRY(l3c::check_hip(hipMemsetAsync(ws + p.zero_pad, 0, (size_t)B * 8, st), "hipMemsetAsync"));
+        padding = reinterpret_cast<const uint16_t *>(ws + p.zero_pad);
+    }
+    const float zero_mean[3] = {0.f, 0.f, 0.f};
+    float *img = reinterpret_cast<float *>(ws + p.img);
+    CODEC_TRY(l3c_u8_to_sym_bn(d->img, zero_mean, B, p.hw[0], reinterpret_cast<int16_t *>(ws + p.sym[0]), img, stream));
+    l3c_net_forward_desc f;
+    memset(&f, 0, sizeof(f));
+    f.cfg_host = &c;
+    f.packed = m.packed;
+    f.packed_bytes = m.packed_bytes;
+    f.img = img;
+    f.B = B;
+    f.H = d->H;
+    f.W = d->W;
+    for (int s = 0; s <= S; ++s) {
+        f.sym[s] = reinterpret_cast<int16_t *>(ws + p.sym[s]);
+        if (s) f.bn_q[s] = reinterpret_cast<float *>(ws + p.bn_q[s]);
+        if (s < S) f.P[s] = reinterpret_cast<float *>(ws + p.P[s]);
+    }
+    f.workspace = ws + p.scratch;
+    f.workspace_bytes = p.net_ws;
+    CODEC_TRY(l3c_net_forward(&f, stream));
+
+    // the forward's workspace is dead.  Scales coarsest first (file order): the interval head into the one interval buffer, then its bands
+    // re-laid into the scale's two coder groups -- the full bands (absent when n == 1) and the last bands
+    char *cs = ws + p.scratch;
+    l3c_ac_group groups[2 * MAX_REC];
+    l3c_banded_scale scales[MAX_REC];
+    BandedLayoutArgs la{};
+    int n_groups = 0;
+    uint32_t *iv = reinterpret_cast<uint32_t *>(cs + p.iv);
+    for (int k = 0; k <= S; ++k) {
+        const int s = S - k;
+        const int64_t streams = B * p.Cs[s];
+        if (s == S)
+            CODEC_TRY(l3c_ac_intervals_from_table(m.uniform_row, 0, c.L + 1, f.sym[s], streams, p.hw[s], iv, stream));
+        else
+            CODEC_TRY(l3c_dmll_encode_intervals(f.P[s], f.sym[s], s == 0 ? m.targets_rgb : m.targets_z, B, p.hw[s], p.Cs[s], c.K, s == 0,
+                                                s == 0 ? 257 : c.L + 1, iv, stream));
+        const bool full = p.n[s] > 1;
+        uint32_t *iv_f = full ? reinterpret_cast<uint32_t *>(cs + p.iv_f[s]) : nullptr, *iv_l = reinterpret_cast<uint32_t *>(cs + p.iv_l[s]);
+        CODEC_TRY(l3c_ac_band_intervals(iv, streams, p.hw[s], p.L[s], iv_f, iv_l, stream));
+        uint8_t *out_f = full ? reinterpret_cast<uint8_t *>(cs + p.out_f[s]) : nullptr, *out_l = reinterpret_cast<uint8_t *>(cs + p.out_l[s]);
+        uint32_t *nb_f = full ? reinterpret_cast<uint32_t *>(ws + p.nb_f[s]) : nullptr, *nb_l = reinterpret_cast<uint32_t *>(ws + p.nb_l[s]);
+        uint32_t *clean_f = full ? reinterpret_cast<uint32_t *>(ws + p.clean_f[s]) : nullptr, *clean_l = reinterpret_cast<uint32_t *>(ws + p.clean_l[s]);
+        if (full) groups[n_groups++] = l3c_ac_group{iv_f, out_f, nb_f, streams * (p.n[s] - 1), p.L[s], p.stride_f[s]};
+        groups[n_groups++] = l3c_ac_group{iv_l, out_l, nb_l, streams, p.last[s], p.stride_l[s]};
+        scales[k] = l3c_banded_scale{out_f, clean_f, p.stride_f[s], out_l, clean_l, p.stride_l[s], p.Cs[s], d->H >> s, d->W >> s, p.L[s]};
+        la.nb_full[k] = nb_f;
+        la.nb_last[k] = nb_l;
+        la.clean_full[k] = clean_f;
+        la.clean_last[k] = clean_l;
+        la.C[k] = p.Cs[s];
+        la.n[k] = p.n[s];
+    }
+    CODEC_TRY(l3c_ac_encode_groups(groups, n_groups, cs + p.ac_ws, stream));
+    // file sizes and offsets; a band that overran (L3C_AC_OVERRUN) marks its file -1 and is written as an empty payload, so that the
+    // writer below stays inside the file's slot whatever the coder reported
+    int64_t *file_offset = reinterpret_cast<int64_t *>(ws + p.file_offset);
+    la.n_scales = S + 1;
+    la.framing = p.framing;
+    la.B = B;
+    la.file_stride = d->file_stride;
+    la.file_offset = file_offset;
+    la.file_bytes = d->file_bytes;
+    CODEC_TRY(launch_layout_banded(la, stream));
+    return l3c_container_write_banded(scales, S + 1, B, padding, file_offset, d->files, cs + p.pos, B * p.streams_per_image * 8, stream);
+}
+
+int64_t l3c_decode_plan_banded_bytes(const l3c_net_config *cfg, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B) {
+    CODEC_TRY(codec_config(cfg));
+    return l3c_plan::plan_banded_bytes(cfg, files_host, file_offset_host, B, l3c::error_buffer(), 512);
+}
+
+int l3c_decode_plan_banded(const l3c_net_config *cfg, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B, void *plan_host,
+                           int64_t plan_bytes, int *H_out, int *W_out, uint16_t *padding_host_out) {
+    CODEC_TRY(codec_config(cfg));
+    CODEC_TRY(l3c_plan::make_plan_banded(cfg, files_host, file_offset_host, B, plan_host, plan_bytes, H_out, W_out, padding_host_out,
+                                         l3c::error_buffer(), 512));
+    // the header's sizes against the network schedule itself, as l3c_decode_plan does
+    l3c_plan::BandedHeader h;
+    memcpy(&h, plan_host, sizeof(h));
+    DecPlan p;
+    const int rc = dec_plan_banded(*cfg, h, &p);
+    if (rc != L3C_OK) {
+        char why[400];
+        snprintf(why, sizeof(why), "%s", l3c::error_buffer());
+        memset(plan_host, 0, sizeof(int64_t));     // no plan
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "invalid file: %lld x %lld pixels: %s", (long long)h.H, (long long)h.W, why);
+    }
+    return L3C_OK;
+}
+
+int64_t l3c_decode_batch_banded_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) {
+    CODEC_TRY(codec_config(cfg));
+    l3c_plan::BandedHeader h;
+    CODEC_TRY(l3c_plan::check_blob_banded(*cfg, plan_host, -1, &h, l3c::error_buffer(), 512));
+    DecPlan p;
+    CODEC_TRY(dec_plan_banded(*cfg, h, &p));
+    return p.bytes;
+}
+
+int l3c_decode_batch_banded(const l3c_decode_batch_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    CODEC_TRY(check_model(d->model_host));
+    const l3c_codec_model &m = *d->model_host;
+    const l3c_net_config &c = *m.cfg_host;
+    L3C_REQUIRE(d->files && d->plan_host && d->plan && d->pixels && d->workspace, "null pointer");
+    L3C_REQUIRE(aligned16(d->files) && aligned16(d->plan) && aligned16(d->pixels) && aligned16(d->sym) && aligned16(d->workspace),
+                "every pointer must be 16-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(d->plan_host) & 7) == 0, "plan_host must be 8-byte aligned");
+    l3c_plan::BandedHeader h;
+    CODEC_TRY(l3c_plan::check_blob_banded(c, d->plan_host, d->plan_bytes, &h, l3c::error_buffer(), 512));
+    L3C_REQUIRE(h.lag == 1 || (side_stream && side_stream != main_stream),
+                "16 bands per channel or more decode on two streams (lag 2): side_stream must be a stream of its own");
+    DecPlan p;
+    CODEC_TRY(dec_plan_banded(c, h, &p));
+    if (d->workspace_bytes < p.bytes)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
+
+    // ---- everything checked: enqueue
+    const int64_t B = h.B;
+    const int n_rec = (int)h.n_records, S = c.num_scales, Lp = c.L + 1;
+    char *ws = base256(d->workspace);
+    const hipStream_t st = l3c::as_stream(main_stream);
+    const char *plan = static_cast<const char *>(d->plan);
+    const int64_t *src_off = reinterpret_cast<const int64_t *>(plan + h.src_off), *dst_off = reinterpret_cast<const int64_t *>(plan + h.dst_off);
+    const uint32_t *nbytes = reinterpret_cast<const uint32_t *>(plan + h.nbytes_off);
+    uint8_t *streams = reinterpret_cast<uint8_t *>(ws + p.streams);
+    int32_t *flags = reinterpret_cast<int32_t *>(ws + p.flags);
+    CODEC_TRY(l3c::check_hip(hipMemsetAsync(flags, 0, MAX_REC * 4, st), "hipMemsetAsync"));
+    for (int k = 0; k < n_rec; ++k)
+        for (int64_t a = h.rec[k].first, e = a + h.rec[k].n_streams; a < e; a += 65535) {
+            const int64_t n = e - a < 65535 ? e - a : 65535;
+            CODEC_TRY(l3c_container_read(d->files, src_off + a, dst_off + a, nbytes + a, n, (uint32_t)h.rec[k].max_nbytes, streams, main_stream));
+        }
+    int16_t *sym[MAX_REC];
+    for (int k = 0; k < n_rec; ++k) sym[k] = reinterpret_cast<int16_t *>(ws + p.sym[k]);
+    if (d->sym) sym[n_rec - 1] = d->sym;
+    float *bn = reinterpret_cast<float *>(ws + p.bn), *P = reinterpret_cast<float *>(ws + p.P);
+    char *scratch = ws + p.scratch;
+    {   // the coarsest record: the uniform prior, every band of every plane in one launch
+        const l3c_plan::BandedRecord &r = h.rec[0];
+        CODEC_TRY(l3c_ac_decode_bands(m.uniform_row, Lp, streams, dst_off + r.first, nbytes + r.first, B * r.C, r.H * r.W, r.L, 1, sym[0],
+                                      main_stream));
+    }
+    for (int k = 1; k < n_rec; ++k) {
+        const l3c_plan::BandedRecord &r = h.rec[k], &above = h.rec[k - 1];
+        const int s = S - k;
+        const int64_t hw = r.H * r.W;
+        CODEC_TRY(l3c_sym_to_bn(sym[k - 1], B * above.C * above.H * above.W, m.z_bin_width, m.z_x_min, bn, main_stream));
+        l3c_net_get_p_desc g;
+        memset(&g, 0, sizeof(g));
+        g.cfg_host = &c;
+        g.packed = m.packed;
+        g.packed_bytes = m.packed_bytes;
+        g.net = s;
+        g.bn_q = bn;
+        g.B = B;
+        g.h = (int)above.H;
+        g.w = (int)above.W;
+        g.fuse = k == 1 ? nullptr : reinterpret_cast<const float *>(ws + p.F[k - 1]);
+        g.P = P;
+        g.F = s > 0 ? reinterpret_cast<float *>(ws + p.F[k]) : nullptr;      // the finest scale's features feed nothing
+        g.workspace = scratch;
+        g.workspace_bytes = p.getp_ws;
+        CODEC_TRY(l3c_net_get_p(&g, main_stream));
+        // P is complete: get_p's workspace is dead and holds this scale's tables from here on
+        if (s > 0) {     // a bottleneck scale: every band (b, j) a ragged entry, the channels independent given P
+            const int64_t E = B * r.n, max_npix = r.L < hw ? r.L : hw;
+            const int64_t *ent = reinterpret_cast<const int64_t *>(plan + h.entries_off[k]);      // pixbase | hw | pix0 | npix | table_off
+            const l3c_ragged_batch batch{E, hw, ent, ent + E};
+            for (int c0 = 0; c0 < (int)r.C; c0 += 8) {
+                const int n = (int)r.C - c0 < 8 ? (int)r.C - c0 : 8;
+                l3c_table_part tp[8];
+                l3c_ragged_part rp[8];
+                l3c_ac_decode_part dp[8];
+                memset(dp, 0, sizeof(dp));
+                for (int i = 0; i < n; ++i) {
+                    const int ch = c0 + i;
+                    uint16_t *table = reinterpret_cast<uint16_t *>(scratch + ch * p.table_bytes[k]);
+                    tp[i] = l3c_table_part{ch, 0, max_npix, table, flags + k, nullptr};
+                    rp[i] = l3c_ragged_part{ent + 2 * E, ent + 3 * E, ent + 4 * E};
+                    l3c_ac_decode_part &q = dp[i];
+                    q.cdf = table;
+                    q.Lp = Lp;
+                    q.in = streams;
+                    q.in_offsets = dst_off + r.first + ch * E;
+                    q.in_nbytes = nbytes + r.first + ch * E;
+                    q.n_streams = E;
+                    q.n_sym = max_npix;
+                    q.not_monotone_flag = flags + k;
+                    q.final_chunk = 1;
+                    q.sym_out = sym[k];
+                    q.r_npix = ent + 3 * E;
+                    q.r_table_off = ent + 4 * E;
+                    q.r_pixbase = ent;
+                    q.r_hw = ent + E;
+                    q.r_pix0 = ent + 2 * E;
+                    q.r_C = (int)r.C;
+                    q.r_c = ch;
+                    q.r_table_bytes = B * hw * Lp * 2;
+                }
+                CODEC_TRY(l3c_dmll_cdf_table_ragged(P, nullptr, m.targets_z, &batch, (int)r.C, c.K, 0, Lp, tp, rp, n, main_stream));
+                CODEC_TRY(l3c_ac_decode_chunks(dp, n, main_stream));
+            }
+        } else {         // the RGB scale: the chunk pipeline over all B n bands of each channel in lock step
+            CODEC_TRY(l3c::check_hip(hipMemsetAsync(sym[k], 0, (size_t)(B * 3 * hw * 2), st), "hipMemsetAsync"));
+            l3c_rgb_banded_desc q;
+            memset(&q, 0, sizeof(q));
+            q.P = P;
+            q.targets = m.targets_rgb;
+            q.sym = sym[k];
+            q.B = B;
+            q.HW = hw;
+            q.K = c.K;
+            q.in = streams;
+            q.in_offsets = dst_off + r.first;
+            q.in_nbytes = nbytes + r.first;
+            q.band_len = h.rgb_band_len;
+            q.n_chunks = (int)h.rgb_chunks;
+            q.lag = (int)h.lag;
+            q.window_mode = 1;
+            q.workspace = scratch;
+            q.workspace_bytes = p.rgb_ws;
+            CODEC_TRY(l3c_decode_rgb_banded(&q, main_stream, h.lag == 2 ? side_stream : nullptr));
         }
     }
     return l3c_sym_to_u8(sym[n_rec - 1], B * 3 * h.H * h.W, d->pixels, main_stream);

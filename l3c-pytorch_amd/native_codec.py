@@ -2,8 +2,10 @@
 
 `NativeCodec(blueprint)` stands next to `Bitcoding` as `NativeNet` stands next to `MultiscaleNetwork`: the library runs the schedule of
 bitcoding/bitcoding.py -- the same entry points in the same order -- so the files equal `Bitcoding(bp).encode_batch(img).to_bytes(paddings)`
-byte for byte and either side decodes the other's.  L3C family, equally sized padded images, the legacy `.l3c` format; torch owns the
-memory and the streams, nothing else.  It has no knobs, and no product path (Bitcoding, l3c.py, test.py, bench.py) reads it.
+byte for byte and either side decodes the other's.  L3C family, equally sized padded images; the legacy `.l3c` format, or with
+`NativeCodec(blueprint, bands=K)` the banded one (l3c_encode_batch_banded / l3c_decode_plan_banded + l3c_decode_batch_banded: the files of
+`Bitcoding(bp, bands=K)`); `decode_batch` reads either.  torch owns the memory and the streams, nothing else.  It has no other knobs, and
+no product path (Bitcoding, l3c.py, test.py, bench.py) reads it.
 """
 import ctypes
 
@@ -12,13 +14,15 @@ import torch
 
 from . import _lib, ops
 from ._lib import CodecModel, DecodeBatchDesc, EncodeBatchDesc, ptr, stream
-from .bitcoding import upload
+from .bitcoding import container, upload
 from .bitcoding.bitcoding import Bitcoding, _staging
 from .native_net import NativeNet, _bytes, _size
 
 PLAN_MAGIC = int.from_bytes(b'L3C_PLAN', 'little')
 _PLAN_HEADER_WORDS = 26          # csrc/codec_plan.h: Header up to its records
 _PLAN_MAX_RECORDS = _lib.NET_MAX_SCALES + 1
+PLAN_BANDED_MAGIC = int.from_bytes(b'L3CBPLAN', 'little')
+_PLAN_BANDED_HEADER_WORDS = 24 + _PLAN_MAX_RECORDS     # csrc/codec_plan_banded.h: BandedHeader up to its records
 _RING = upload._H2DRing(3)
 
 
@@ -58,6 +62,55 @@ def decode_plan(cfg, files):
     return blob.tobytes(), H.value, W.value, [tuple(int(v) for v in p) for p in pads]
 
 
+def parse_plan_banded(blob):
+    """The blob l3c_decode_plan_banded writes (layout: csrc/codec_plan_banded.h) as a dict: the header's numbers, `records` = [(C, H, W, L, n,
+    first, n_streams, max_nbytes)], the arrays src_offset / dst_offset / nbytes (per band stream) and `entries` = per record None or the
+    (pixbase, hw, pix0, npix, table_off) int64 arrays of its B n bands (the bottleneck records)."""
+    raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+    w = raw[:8 * (_PLAN_BANDED_HEADER_WORDS + 8 * _PLAN_MAX_RECORDS)].view(np.int64)
+    names = ['magic', 'bytes', 'B', 'n_records', 'H', 'W', 'n_streams', 'files_bytes', 'dst_bytes', 'rgb_band_len', 'rgb_chunks', 'lag']
+    plan = {n: int(w[i]) for i, n in enumerate(names)}
+    plan['cfg'] = [int(v) for v in w[12:21]]
+    src_off, dst_off, nb_off = (int(v) for v in w[21:24])
+    ent_off = [int(v) for v in w[24:24 + _PLAN_MAX_RECORDS]]
+    h = _PLAN_BANDED_HEADER_WORDS
+    plan['records'] = [tuple(int(v) for v in w[h + 8 * k:h + 8 * k + 8]) for k in range(plan['n_records'])]
+    S = plan['n_streams']
+    plan['src_offset'] = raw[src_off:src_off + 8 * S].view(np.int64).copy()
+    plan['dst_offset'] = raw[dst_off:dst_off + 8 * S].view(np.int64).copy()
+    plan['nbytes'] = raw[nb_off:nb_off + 4 * S].view(np.uint32).copy()
+    plan['entries'] = []
+    for k, r in enumerate(plan['records']):
+        E = plan['B'] * r[4]
+        plan['entries'].append(tuple(raw[ent_off[k] + 8 * E * i:ent_off[k] + 8 * E * (i + 1)].view(np.int64).copy() for i in range(5))
+                               if ent_off[k] else None)
+    return plan
+
+
+def _plan_banded_bytes(cfg_ref, files):
+    """l3c_decode_plan_banded_bytes of host byte strings: the size function reads the framing of file 0 and the signature of every file."""
+    head = np.frombuffer(bytes(files[0]) + b''.join(bytes(f[:4]) for f in files[1:]) + b'\0' * 8, dtype=np.uint8)
+    offs = np.concatenate([[0, len(files[0])], len(files[0]) + np.cumsum([len(f[:4]) for f in files[1:]])]).astype(np.int64)
+    return _lib.load().l3c_decode_plan_banded_bytes(cfg_ref, head.ctypes.data, offs.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), len(files))
+
+
+def decode_plan_banded(cfg, files):
+    """l3c_decode_plan_banded on host byte strings -> (blob bytes, H, W, paddings).  ValueError with the library's message for an invalid
+    file, L3CError for what is outside its scope (a legacy file, a mix of both formats, more than 65535 band streams per channel)."""
+    lib = _lib.load()
+    B = len(files)
+    n_plan = _plan_banded_bytes(ctypes.byref(cfg), files)
+    _check_plan(min(n_plan, 0))
+    sizes = np.asarray([len(f) for f in files], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    data = np.frombuffer(b''.join(bytes(f) for f in files) + b'\0' * 8, dtype=np.uint8)
+    blob = np.zeros(n_plan // 8, dtype=np.int64)
+    H, W, pads = ctypes.c_int(), ctypes.c_int(), np.zeros((B, 4), dtype=np.uint16)
+    _check_plan(lib.l3c_decode_plan_banded(ctypes.byref(cfg), data.ctypes.data, offs.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), B,
+                                           blob.ctypes.data, n_plan, ctypes.byref(H), ctypes.byref(W), pads.ctypes.data))
+    return blob.tobytes(), H.value, W.value, [tuple(int(v) for v in p) for p in pads]
+
+
 def _check_plan(rc):
     if rc == 0:
         return
@@ -68,7 +121,11 @@ def _check_plan(rc):
 
 
 class NativeCodec(object):
-    def __init__(self, blueprint):
+    def __init__(self, blueprint, bands=0):
+        """bands: 0 = encode writes the legacy format; K in 1..1024 = banded files, as Bitcoding(bp, bands=K).  decode_batch reads either."""
+        if bands and not 1 <= int(bands) <= container.MAX_BANDS:
+            raise ValueError('bands must be 0 (legacy format) or in 1..{}, got {}'.format(container.MAX_BANDS, bands))
+        self.bands = int(bands)
         _lib.require_gpu()
         self.net = NativeNet(blueprint.net)
         self.cfg = self.net.cfg
@@ -87,14 +144,20 @@ class NativeCodec(object):
     # ---- sizes ---------------------------------------------------------------------------------------------------------------
 
     def file_stride(self, H, W):
+        if self.bands:
+            return _size(_lib.load().l3c_encode_banded_file_stride(self._cfg_ref, H, W, self.bands))
         return _size(_lib.load().l3c_encode_file_stride(self._cfg_ref, H, W))
 
     def encode_workspace_bytes(self, B, H, W):
+        if self.bands:
+            return _size(_lib.load().l3c_encode_batch_banded_workspace_bytes(self._cfg_ref, B, H, W, self.bands))
         return _size(_lib.load().l3c_encode_batch_workspace_bytes(self._cfg_ref, B, H, W))
 
     def decode_workspace_bytes(self, blob):
+        """Workspace of the decode of a plan blob, legacy or banded (its magic word says which)."""
         buf = np.frombuffer(bytes(blob), dtype=np.int64)
-        return _size(_lib.load().l3c_decode_batch_workspace_bytes(self._cfg_ref, buf.ctypes.data))
+        fn = 'l3c_decode_batch_banded_workspace_bytes' if int(buf[0]) == PLAN_BANDED_MAGIC else 'l3c_decode_batch_workspace_bytes'
+        return _size(getattr(_lib.load(), fn)(self._cfg_ref, buf.ctypes.data))
 
     # ---- encode --------------------------------------------------------------------------------------------------------------
 
@@ -112,7 +175,10 @@ class NativeCodec(object):
         if paddings is not None:
             pads = ops.upload_small(np.ascontiguousarray(np.asarray(paddings, dtype=np.uint16).reshape(B, 4)).view(np.int16))
         d = EncodeBatchDesc(ctypes.pointer(self.model), ptr(imgs), B, H, W, ptr(pads), ptr(files), stride, ptr(file_bytes), ptr(ws), ws.numel())
-        _lib.call('l3c_encode_batch', ctypes.byref(d), stream())
+        if self.bands:
+            _lib.call('l3c_encode_batch_banded', ctypes.byref(d), self.bands, stream())
+        else:
+            _lib.call('l3c_encode_batch', ctypes.byref(d), stream())
         return files, file_bytes
 
     def encode_batch(self, imgs, paddings=None):
@@ -135,13 +201,24 @@ class NativeCodec(object):
 
     # ---- decode --------------------------------------------------------------------------------------------------------------
 
-    def decode_batch(self, files, workspace=None):
-        """files: list of B legacy `.l3c` byte strings of equally sized (padded) images -> ((B,3,H,W) uint8 on the GPU, padding tuples).
-        The framing is parsed on the host by the library (ValueError with its message for an invalid file, L3CError for a banded one);
-        files and plan cross PCIe in one copy from page-locked memory."""
+    def decode_batch(self, files, workspace=None, sym=None):
+        """files: list of B `.l3c` byte strings of equally sized (padded) images, all legacy or all banded (their first four bytes say
+        which; a mix raises ValueError) -> ((B,3,H,W) uint8 on the GPU, padding tuples).  The framing is parsed on the host by the library
+        (ValueError with its message for an invalid file); files and plan cross PCIe in one copy from page-locked memory.
+        sym: optional int16 (B,3,H,W) device tensor that receives the same values."""
         lib = _lib.load()
         B = len(files)
-        n_plan = _size(lib.l3c_decode_plan_bytes(self._cfg_ref, B))
+        banded = [container.is_banded(f) for f in files]
+        if any(banded) and not all(banded):
+            raise ValueError('decode_batch: a batch mixes banded and legacy .l3c files')
+        banded = bool(banded and banded[0])
+        plan_fn, decode_fn, ws_fn = ((lib.l3c_decode_plan_banded, 'l3c_decode_batch_banded', lib.l3c_decode_batch_banded_workspace_bytes) if banded
+                                     else (lib.l3c_decode_plan, 'l3c_decode_batch', lib.l3c_decode_batch_workspace_bytes))
+        if banded:
+            n_plan = _plan_banded_bytes(self._cfg_ref, files)
+            _check_plan(min(n_plan, 0))
+        else:
+            n_plan = _size(lib.l3c_decode_plan_bytes(self._cfg_ref, B))
         sizes = np.asarray([len(f) for f in files], dtype=np.int64)
         offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         plan_at = (int(offs[-1]) + 4 + 15) // 16 * 16
@@ -152,21 +229,24 @@ class NativeCodec(object):
         st[offs[-1]:plan_at] = 0
         H, W, pads = ctypes.c_int(), ctypes.c_int(), np.zeros((B, 4), dtype=np.uint16)
         plan_host = stage.data_ptr() + plan_at
-        _check_plan(lib.l3c_decode_plan(self._cfg_ref, stage.data_ptr(), offs.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), B, plan_host, n_plan,
-                                        ctypes.byref(H), ctypes.byref(W), pads.ctypes.data))
+        _check_plan(plan_fn(self._cfg_ref, stage.data_ptr(), offs.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), B, plan_host, n_plan,
+                            ctypes.byref(H), ctypes.byref(W), pads.ctypes.data))
         dev = torch.empty(plan_at + n_plan, dtype=torch.uint8, device='cuda')
         dev.copy_(stage, non_blocking=True)
         _RING.sent(k)
-        ws_bytes = _size(lib.l3c_decode_batch_workspace_bytes(self._cfg_ref, plan_host))
+        ws_bytes = _size(ws_fn(self._cfg_ref, plan_host))
+        lag = int(np.frombuffer(stage.numpy()[plan_at + 88:plan_at + 96].tobytes(), dtype=np.int64)[0])      # word 11 of either header
         ws = _bytes(ws_bytes) if workspace is None else workspace
         pixels = torch.empty(B, 3, H.value, W.value, dtype=torch.uint8, device='cuda')
+        if sym is not None and (sym.dtype != torch.int16 or tuple(sym.shape) != tuple(pixels.shape) or not sym.is_contiguous()):
+            raise ValueError('sym must be a contiguous int16 tensor of shape {}'.format(tuple(pixels.shape)))
         side = None
-        if B >= 16:
+        if lag == 2:
             if self._side is None:
                 self._side = torch.cuda.Stream()
             side = self._side
-            for t in (dev, ws, pixels, self.net.packed, self.targets_rgb):
+            for t in (dev, ws, pixels, self.net.packed, self.targets_rgb) + (() if sym is None else (sym,)):
                 t.record_stream(side)
-        d = DecodeBatchDesc(ctypes.pointer(self.model), ptr(dev), plan_host, ptr(dev) + plan_at, n_plan, ptr(pixels), None, ptr(ws), ws.numel())
-        _lib.call('l3c_decode_batch', ctypes.byref(d), stream(), side.cuda_stream if side is not None else None)
+        d = DecodeBatchDesc(ctypes.pointer(self.model), ptr(dev), plan_host, ptr(dev) + plan_at, n_plan, ptr(pixels), ptr(sym), ptr(ws), ws.numel())
+        _lib.call(decode_fn, ctypes.byref(d), stream(), side.cuda_stream if side is not None else None)
         return pixels, [tuple(int(v) for v in p) for p in pads]
