@@ -3,6 +3,7 @@
  * product never loads it).  It holds the round-1/2 Winograd F(2x2,3x3) convolution kernel (csrc/conv_wino.hip), kept as an
  * independent second implementation the tests compare the product's F(4x4,3x3) kernel with (tests/test_gpu_conv.py), the exhaustive
  * check of the head's sigmoid (csrc/xcheck_dmll.hip), plus the library-level entry points of l3c_api.hip (error text).  Same conventions as include/l3c_hip.h.
+ * The library's second header, include/l3c_xcheck_small.h, declares the thin conv kernels' predecessors (csrc/xcheck_small.hip).
  */
 #ifndef L3C_XCHECK_H_
 #define L3C_XCHECK_H_

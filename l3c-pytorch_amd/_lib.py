@@ -255,6 +255,12 @@ XCHECK_PROTOTYPES = {
     'l3c_conv_wino4w_pack_weights': (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),
     'l3c_conv_wino4w': (c_int, [ctypes.POINTER(ConvDesc), c_int, c_vp]),
 }
+# include/l3c_xcheck_small.h: the thin conv kernels before their streaming rewrite (csrc/xcheck_small.hip), same library
+XCHECK_SMALL_PROTOTYPES = {
+    'l3c_xcheck_rgb_head': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    'l3c_xcheck_to_q_quantize': (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'l3c_xcheck_dec_head': (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp]),
+}
 XCHECK_LIB_PATH = os.environ.get('L3C_XCHECK_LIB') or os.path.join(_HERE, 'csrc', 'libl3c_hip_xcheck.so')   # (L3C_XCHECK_LIB: a development variant)
 
 _lib = None
@@ -288,7 +294,7 @@ def load_xcheck():
             raise L3CError('libl3c_hip_xcheck.so not found at {} -- build it with `python l3c-pytorch_amd/csrc/build.py`'.format(XCHECK_LIB_PATH))
         lib = ctypes.CDLL(XCHECK_LIB_PATH)
         lib.l3c_last_error.restype = ctypes.c_char_p
-        for name, (res, args) in XCHECK_PROTOTYPES.items():
+        for name, (res, args) in list(XCHECK_PROTOTYPES.items()) + list(XCHECK_SMALL_PROTOTYPES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _xcheck = lib

@@ -1,4 +1,4 @@
-// conv_small.hip -- the thin (3-, 5-channel) ends of the conv stack; all HBM-bound, no MFMA.
+// conv_small.hip -- the thin (3-, 5-channel) ends of the conv stack; HBM-bound (rgb_head: packed-FMA-bound), no MFMA.
 //
 //   rgb_head_kernel      sub_rgb_mean -> MeanShift(1/128) -> conv3x3 3->Cf      (multiscale_network.py:241, head.py:26-41)
 //   to_q_quantize_kernel conv1x1 Cf->C + hard quantiser                          (net.py:144-148, quantizer.py:72-87)
@@ -143,6 +143,12 @@ __global__ __launch_bounds__(256) void to_q_quantize_kernel(const float *__restr
 // for 4.2 GB); here a block's tile of 256 pixels is ONE contiguous 64 KB run, fetched with 16 coalesced 16-byte loads per thread that are
 // all in flight together, and a thread then reads its pixel's record from LDS (row stride Cf + 4 floats: 16 lanes of a ds_read_b128
 // cover the 64 banks once).  Cf % 4 == 0, Cf <= 64.
+// The weights and the levels are wave-uniform and come through the scalar cache.  C is a template parameter so that the C weight quads
+// of a feature quad are ONE group of scalar loads behind ONE wait, and the argmin walks the levels in the outer loop, a level read once
+// for all C channels: with C a run-time bound every channel of every feature quad and every (channel, level) pair was a scalar load, a
+// wait for it and a branch -- 16 * C + C * L dependent scalar-cache round trips per pixel, which at two wavefronts per SIMD was most of
+// a tile's time while its successor's loads had long landed.  Per channel nothing changes: the same fmaf chain, the levels visited in
+// ascending order, the first minimum kept.  (Tiles of 128 or 64 pixels, four or eight blocks per CU, ran within 3 % of this geometry.)
 #ifndef L3C_TQ_PIX
 #define L3C_TQ_PIX 256
 #endif
@@ -150,9 +156,10 @@ __global__ __launch_bounds__(256) void to_q_quantize_kernel(const float *__restr
 #define L3C_TQ_GRID 512       // blocks of a launch (two per CU): each walks its tiles with the next one's loads in flight [1.276 ms against 1.301 with 2048, 1.394 with a block per tile]
 #endif
 constexpr int TQ_PIX = L3C_TQ_PIX, TQ_MAX_CF = 64, TQ_LD = TQ_MAX_CF + 4;
+template <int C>
 __global__ __launch_bounds__(TQ_PIX) void to_q_quantize_tile_kernel(const float *__restrict__ feat, const float *__restrict__ w,
                                                                     const float *__restrict__ bias, const float *__restrict__ levels,
-                                                                    int64_t B, int64_t HW, int Cf, int C, int L,
+                                                                    int64_t B, int64_t HW, int Cf, int L,
                                                                     int16_t *__restrict__ sym, float *__restrict__ bn_q,
                                                                     float *__restrict__ bn) {
     __shared__ __attribute__((aligned(16))) float tile[TQ_PIX * TQ_LD];
@@ -191,74 +198,108 @@ __global__ __launch_bounds__(TQ_PIX) void to_q_quantize_tile_kernel(const float 
             const int64_t i = t0 + tid;
             const int64_t b = i / HW, n = i % HW;
             const f32x4 *px = reinterpret_cast<const f32x4 *>(&tile[tid * TQ_LD]);
-            float acc[8];
+            float acc[C];
 #pragma unroll
-            for (int c = 0; c < 8; ++c) acc[c] = 0.0f;
+            for (int c = 0; c < C; ++c) acc[c] = 0.0f;
             for (int k4 = 0; k4 < quads; ++k4) {
                 const f32x4 x4 = px[k4];
 #pragma unroll
-                for (int c = 0; c < 8; ++c)
-                    if (c < C) {
-                        const float *wc = w + c * Cf + k4 * 4;
-                        acc[c] = fmaf(x4[3], wc[3], fmaf(x4[2], wc[2], fmaf(x4[1], wc[1], fmaf(x4[0], wc[0], acc[c]))));
+                for (int c = 0; c < C; ++c) {
+                    const float *wc = w + c * Cf + k4 * 4;
+                    acc[c] = fmaf(x4[3], wc[3], fmaf(x4[2], wc[2], fmaf(x4[1], wc[1], fmaf(x4[0], wc[0], acc[c]))));
+                }
+            }
+            float x[C], dbest[C];
+            int best[C];
+            const float l0 = levels[0];
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                x[c] = acc[c] + bias[c];
+                best[c] = 0;
+                dbest[c] = (x[c] - l0) * (x[c] - l0);
+            }
+#pragma unroll 4
+            for (int l = 1; l < L; ++l) {
+                const float lv = levels[l];
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const float d = (x[c] - lv) * (x[c] - lv);
+                    if (d < dbest[c]) {   // first minimum wins (torch.min)
+                        dbest[c] = d;
+                        best[c] = l;
                     }
+                }
             }
 #pragma unroll
-            for (int c = 0; c < 8; ++c)
-                if (c < C) {
-                    const float x = acc[c] + bias[c];
-                    int best = 0;
-                    float dbest = (x - levels[0]) * (x - levels[0]);
-                    for (int l = 1; l < L; ++l) {
-                        const float d = (x - levels[l]) * (x - levels[l]);
-                        if (d < dbest) {   // first minimum wins (torch.min)
-                            dbest = d;
-                            best = l;
-                        }
-                    }
-                    const int64_t o = (b * C + c) * HW + n;
-                    sym[o] = (int16_t)best;
-                    bn_q[o] = levels[best];
-                    if (bn) bn[o] = x;
-                }
+            for (int c = 0; c < C; ++c) {
+                const int64_t o = (b * C + c) * HW + n;
+                sym[o] = (int16_t)best[c];
+                bn_q[o] = levels[best[c]];
+                if (bn) bn[o] = x[c];
+            }
         }
         __syncthreads();                                    // the tile is overwritten by the next turn
     }
 }
 
 // A thread owns one channel quad (q = tid % quads: its 4 x C weights and its bias stay in registers) and walks pixels of ONE
-// image (blockIdx.y) with 32-bit indices -- the first version divided 64-bit indices per element and re-read the weights per
-// pixel: 1.7 TB/s; the kernel only moves 5 + 64 (+ 64) floats per pixel.
-constexpr int DH_MAX_C = 8;
+// image (blockIdx.y) -- the first version divided 64-bit indices per element and re-read the weights per pixel: 1.7 TB/s; the kernel
+// only moves 5 + 64 (+ 64) floats per pixel.  Per turn a thread takes DH_P CONSECUTIVE pixels and issues every load of the turn -- the
+// C bottleneck values of its pixels, one 16-byte load per channel where the planes allow it (VEC: HW % 4 == 0 and an aligned base),
+// and the DH_P fuse quads -- before the first use: with one pixel per turn (C dword loads that the 16 lanes of a pixel repeated, one
+// fuse quad) a CU never had the bytes in flight that the memory latency asks for.  Per output as before: acc = fmaf(v_c, w_c, acc)
+// for c ascending, then + bias, then + fuse.  C is a template parameter: as a run-time bound of the unrolled loops the compiler
+// computed all eight channels and selected.
+constexpr int DH_MAX_C = 8, DH_P = 4;
+template <bool VEC, int C>
 __global__ __launch_bounds__(256) void dec_head_kernel(const float *__restrict__ bn_q, const float *__restrict__ w,
                                                        const float *__restrict__ bias, const float *__restrict__ fuse,
-                                                       int64_t B, int64_t HW, int C, int Cf, float *__restrict__ out) {
+                                                       int64_t B, int64_t HW, int Cf, float *__restrict__ out) {
     const int quads = Cf / 4;
     const int q = threadIdx.x % quads, pl = threadIdx.x / quads, ppb = 256 / quads;
     const int64_t b = blockIdx.y;
-    float wr[4][DH_MAX_C];
+    float wr[4][C];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int c = 0; c < DH_MAX_C; ++c) wr[j][c] = c < C ? w[(q * 4 + j) * C + c] : 0.0f;
+        for (int c = 0; c < C; ++c) wr[j][c] = w[(q * 4 + j) * C + c];
     const f32x4 bq = *reinterpret_cast<const f32x4 *>(&bias[q * 4]);
     const float *bn_b = bn_q + b * C * HW;
     const float *fuse_b = fuse ? fuse + b * HW * Cf + q * 4 : nullptr;
     float *out_b = out + b * HW * Cf + q * 4;
-    const int hw = (int)HW;
-    for (int64_t n = (int64_t)blockIdx.x * ppb + pl; n < hw; n += (int64_t)gridDim.x * ppb) {   // (hw may approach 2^31)
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const int64_t step = (int64_t)gridDim.x * ppb * DH_P;
+    for (int64_t n0 = ((int64_t)blockIdx.x * ppb + pl) * DH_P; n0 < HW; n0 += step) {   // (HW may approach 2^31)
+        int64_t n[DH_P];                                 // a pixel past the end reads the last one and stores nothing
 #pragma unroll
-        for (int c = 0; c < DH_MAX_C; ++c) {
-            if (c < C) {
-                const float v = bn_b[(int64_t)c * HW + n];
+        for (int p = 0; p < DH_P; ++p) n[p] = n0 + p < HW ? n0 + p : HW - 1;
+        float v[C][DH_P];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = fmaf(v, wr[j][c], acc[j]);
+        for (int c = 0; c < C; ++c) {
+            if (VEC) {                                   // HW % 4 == 0: n0 .. n0 + 3 are inside the plane and 16-byte aligned
+                const f32x4 t = *reinterpret_cast<const f32x4 *>(&bn_b[(int64_t)c * HW + n0]);
+#pragma unroll
+                for (int p = 0; p < DH_P; ++p) v[c][p] = t[p];
+            } else {
+#pragma unroll
+                for (int p = 0; p < DH_P; ++p) v[c][p] = bn_b[(int64_t)c * HW + n[p]];
             }
         }
-        f32x4 r = acc + bq;
-        if (fuse_b) r = r + *reinterpret_cast<const f32x4 *>(&fuse_b[(int64_t)n * Cf]);
-        *reinterpret_cast<f32x4 *>(&out_b[(int64_t)n * Cf]) = r;
+        f32x4 f[DH_P];
+        if (fuse_b) {
+#pragma unroll
+            for (int p = 0; p < DH_P; ++p) f[p] = *reinterpret_cast<const f32x4 *>(&fuse_b[n[p] * Cf]);
+        }
+#pragma unroll
+        for (int p = 0; p < DH_P; ++p) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] = fmaf(v[c][p], wr[j][c], acc[j]);
+            f32x4 r = acc + bq;
+            if (fuse_b) r = r + f[p];
+            if (n0 + p < HW) *reinterpret_cast<f32x4 *>(&out_b[(n0 + p) * Cf]) = r;
+        }
     }
 }
 
@@ -366,8 +407,16 @@ int l3c_to_q_quantize(const float *feat, const float *w, const float *b, const f
     if (Cf <= TQ_MAX_CF) {
         int64_t tiles = (B * HW + TQ_PIX - 1) / TQ_PIX;
         if (tiles > L3C_TQ_GRID) tiles = L3C_TQ_GRID;
-        hipLaunchKernelGGL(to_q_quantize_tile_kernel, dim3((unsigned)tiles), dim3(TQ_PIX), 0, l3c::as_stream(stream), feat, w, b,
-                           levels, B, HW, Cf, C, L, sym, bn_q, bn);
+        const dim3 grid((unsigned)tiles), block(TQ_PIX);
+        switch (C) {
+#define L3C_TQ_CASE(c)                                                                                                                \
+    case c:                                                                                                                            \
+        hipLaunchKernelGGL(to_q_quantize_tile_kernel<c>, grid, block, 0, l3c::as_stream(stream), feat, w, b, levels, B, HW, Cf, L, sym, \
+                           bn_q, bn);                                                                                                 \
+        break;
+            L3C_TQ_CASE(1) L3C_TQ_CASE(2) L3C_TQ_CASE(3) L3C_TQ_CASE(4) L3C_TQ_CASE(5) L3C_TQ_CASE(6) L3C_TQ_CASE(7) L3C_TQ_CASE(8)
+#undef L3C_TQ_CASE
+        }
         return l3c::check_launch("to_q_quantize_tile_kernel");
     }
 #endif
@@ -381,11 +430,22 @@ int l3c_dec_head(const float *bn_q, const float *w, const float *b, const float 
     L3C_REQUIRE(bn_q && w && b && out, "null pointer");
     L3C_REQUIRE(B > 0 && B < 65536 && HW > 0 && HW < (1ll << 31) && C > 0 && C <= DH_MAX_C, "bad shape (C <= 8, one image < 2^31 pixels)");
     L3C_REQUIRE(Cf % 4 == 0 && Cf >= 4 && Cf <= 1024 && 256 % (Cf / 4) == 0, "Cf must be 4 * a divisor of 256");
-    const int64_t ppb = 256 / (Cf / 4);
-    int64_t gx = (HW + ppb - 1) / ppb;
+    const int64_t span = 256 / (Cf / 4) * DH_P;         // pixels of a block's turn
+    int64_t gx = (HW + span - 1) / span;
     if (gx > 2048) gx = 2048;
-    hipLaunchKernelGGL(dec_head_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, l3c::as_stream(stream), bn_q,
-                       w, b, fuse, B, HW, C, Cf, out);
+    const dim3 grid((unsigned)gx, (unsigned)B);
+    const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(bn_q) & 15) == 0;
+    switch (C) {
+#define L3C_DH_CASE(c)                                                                                                                  \
+    case c:                                                                                                                              \
+        if (vec)                                                                                                                         \
+            hipLaunchKernelGGL((dec_head_kernel<true, c>), grid, dim3(256), 0, l3c::as_stream(stream), bn_q, w, b, fuse, B, HW, Cf, out); \
+        else                                                                                                                             \
+            hipLaunchKernelGGL((dec_head_kernel<false, c>), grid, dim3(256), 0, l3c::as_stream(stream), bn_q, w, b, fuse, B, HW, Cf, out); \
+        break;
+        L3C_DH_CASE(1) L3C_DH_CASE(2) L3C_DH_CASE(3) L3C_DH_CASE(4) L3C_DH_CASE(5) L3C_DH_CASE(6) L3C_DH_CASE(7) L3C_DH_CASE(8)
+#undef L3C_DH_CASE
+    }
     return l3c::check_launch("dec_head_kernel");
 }
 
