@@ -720,8 +720,10 @@ int l3c_net_get_p(const l3c_net_get_p_desc *desc_host, l3c_stream_t stream);
  * for the L3C family (configs/ms/cr.cf: what l3c_net_forward supports), batches of equally sized, already padded images, and the LEGACY
  * `.l3c` format (banded files: the l3c_*_banded entry points at the end of this header).  The library runs the schedule of l3c-pytorch_amd/bitcoding/bitcoding.py over the entry points above, so a file equals
  * the Python path's byte for byte and either side reads the other's.  Outside the scope -- L3C_ERR_UNSUPPORTED, with a message naming it,
- * before anything is enqueued: banded files, the RGB / RGB Shared baselines and auto_recurse; sets of differently sized images, auto-crop
- * parts and preview decode have no entry here.
+ * before anything is enqueued: banded files, the RGB / RGB Shared baselines and auto_recurse; auto-crop parts and preview decode have no
+ * entry here.  Images that are NOT planar, padded or equally sized -- interleaved RGB(X) / BGR(X), a row pitch, any size from 1 x 1, several
+ * sizes that pad to one shape in one call -- go through l3c_encode_images / l3c_decode_images at the end of this header, which pad and crop
+ * on the device (l3c_u8_gather / l3c_u8_scatter) around the same schedule; sizes that pad to DIFFERENT shapes take one call per shape.
  * Conventions as for l3c_net_forward: device pointers 16-byte aligned, every argument checked before anything is enqueued, no allocation,
  * no host synchronisation, no copy from pageable memory; workspaces are caller-owned, sized by a pure host function, and their contents
  * are garbage on entry.  Two calls on two streams with separate workspaces and outputs may share one model.
@@ -876,6 +878,104 @@ int l3c_decode_plan_banded(const l3c_net_config *cfg_host, const uint8_t *files_
                            void *plan_host, int64_t plan_bytes, int *H_out, int *W_out, uint16_t *padding_host_out);
 int64_t l3c_decode_batch_banded_workspace_bytes(const l3c_net_config *cfg_host, const void *plan_host);
 int l3c_decode_batch_banded(const l3c_decode_batch_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
+
+/* ---- pictures as they come: any size and layout, padded and cropped on the device ----------------------------------------------------- */
+
+/*
+ * One image inside ONE caller-owned byte buffer, and its place in the padded Hp x Wp frame the codec works on.  The view addresses byte
+ *     offset + y * row_stride + x * pix_stride + c * chan_stride          for y < h, x < w, c < 3 (R, G, B)
+ * of the buffer:
+ *     planar  [3][h][w]             row_stride = w (or a pitch),     pix_stride = 1, chan_stride = the plane size
+ *     RGB     [h][w][3]             row_stride = 3 w (or a pitch),   pix_stride = 3, chan_stride = 1
+ *     RGBX    [h][w][4]             row_stride = 4 w (or a pitch),   pix_stride = 4, chan_stride = 1   (the X byte is never read or written)
+ *     BGR(X)                        as RGB / RGBX with offset at the pixel's R byte (+ 2) and chan_stride = -1
+ * Images of one table may differ in size and layout as long as they share the frame.  (top, left) is free inside the frame; the files of
+ * Bitcoding use centre padding -- l3c_image_padding: (left, right, top, bottom) exactly as helpers/pad.py: padding_for, the smaller half
+ * first; top = pad_out[2], left = pad_out[0].
+ *
+ * l3c_image_table_check is the pure host validator the entries below run before they enqueue anything: for every image h, w in 1 .. 65535,
+ * pix_stride > 0, top + h <= Hp, left + w <= Wp, and -- in overflow-checked 64-bit arithmetic, over the four corners and three channels,
+ * with signed strides -- every byte the view addresses inside [0, buffer_bytes).  Anything else: L3C_ERR_INVALID_ARG, the message names
+ * the image index and the field.  Views of DIFFERENT images that overlap in a destination buffer are not diagnosed: the bytes they share
+ * are unspecified afterwards.
+ */
+typedef struct {
+    int64_t offset;       /* bytes from the base pointer to channel 0 (R) of pixel (0,0) */
+    int64_t row_stride;   /* bytes between rows (may exceed w * pix_stride) */
+    int64_t chan_stride;  /* bytes between channels: plane size for planar, 1 for RGB/RGBX, -1 for BGR(X) with offset at R */
+    int32_t pix_stride;   /* bytes between pixels of a row: 1, 3 or 4 (any positive value is legal) */
+    int32_t h, w;         /* the image's own size, 1..65535 */
+    int32_t top, left;    /* where it sits in the padded Hp x Wp frame */
+} l3c_u8_image;
+int l3c_image_padding(int h, int w, int fac, uint16_t *pad_out);
+int l3c_image_table_check(const l3c_u8_image *images_host, int64_t B, int Hp, int Wp, int64_t buffer_bytes);
+
+/*
+ * l3c_u8_gather: the B views of `src` -> uint8 planar frames dst [B][3][Hp][Wp], ONE launch whatever the mix of sizes and layouts.  Every
+ * byte of dst is written: the picture inside its frame, zero outside (padding mode 'constant').  padding_out, unless NULL, receives each
+ * image's (left, right, top, bottom) = (left, Wp - left - w, top, Hp - top - h): the device array l3c_encode_batch_desc.padding expects.
+ * l3c_u8_scatter: the inverse crop, planar frames src [B][3][Hp][Wp] -> the B views of `dst`.  Exactly the 3 h w bytes each view addresses
+ * are written; pitch gaps, the X byte of RGBX and everything between the images stay as they were.
+ *   images_host / images   the table and the caller's device copy of it (the entries_host / entries_dev precedent): the host copy is
+ *                          validated, the kernels read the device copy
+ *   src_bytes / dst_bytes  size of the strided buffer the views lie in; that buffer needs no alignment
+ * Conventions as everywhere: all arguments checked before the launch, no allocation, no host synchronisation; B < 65536; Hp, Wp below
+ * 65536, Wp a multiple of 4; the planar frames, the device table and padding_out 16-byte aligned.  The frames move as whole 4-, 8- or
+ * 16-byte accesses (the widest that divides Wp); the strided side as whole dwords where a thread's 4 to 16 pixels are one run of bytes --
+ * a dword-aligned planar row, or packed pixels (chan_stride +-1, pix_stride 3 or 4) at any alignment; RGBX only when read: its X bytes are
+ * never written -- and byte by byte otherwise.  Stores touch only validated bytes; the packed loads may read up to 3 bytes on either side of a
+ * run, always inside [0, src_bytes).
+ */
+int l3c_u8_gather(const uint8_t *src, int64_t src_bytes, const l3c_u8_image *images_host, const l3c_u8_image *images, int64_t B, int Hp, int Wp,
+                  uint8_t *dst, uint16_t *padding_out, l3c_stream_t stream);
+int l3c_u8_scatter(const uint8_t *src, int64_t B, int Hp, int Wp, uint8_t *dst, int64_t dst_bytes, const l3c_u8_image *images_host,
+                   const l3c_u8_image *images, l3c_stream_t stream);
+
+/*
+ * The codec on such a table.  l3c_encode_images: l3c_u8_gather into the workspace, then exactly the schedule of l3c_encode_batch (bands == 0:
+ * the legacy format) or l3c_encode_batch_banded (bands = 1 .. 1024) on that planar batch and padding array -- so file b equals
+ * Bitcoding(bp[, bands]).encode_batch(zero-padded batch).to_bytes(paddings)[b] byte for byte.  files / file_stride / file_bytes as for
+ * l3c_encode_batch; the file stride is l3c_encode_file_stride / l3c_encode_banded_file_stride of (Hp, Wp).
+ * l3c_decode_images: l3c_decode_batch or l3c_decode_batch_banded -- the plan blob's magic word says which; the planners are unchanged --
+ * into the workspace, then l3c_u8_scatter on main_stream.  The table is validated against the plan's B, H and W before anything is enqueued;
+ * an image's place in the frame is the caller's to set from the planner's padding_host_out (top = padding[2], left = padding[0], h = H -
+ * padding[2] - padding[3], w = W - padding[0] - padding[1]).  Stream semantics as for l3c_decode_batch.
+ * Outside the scope, as before: a padded shape the network schedule refuses and images that would need auto-crop parts (L3C_ERR_UNSUPPORTED).
+ */
+typedef struct {
+    const l3c_codec_model *model_host;
+    const uint8_t *src;             /* the buffer the views lie in (device) */
+    int64_t src_bytes;
+    const l3c_u8_image *images_host;
+    const l3c_u8_image *images;     /* device copy, 16-byte aligned */
+    int64_t B;
+    int Hp, Wp;                     /* the frame: multiples of 2^num_scales, below 65536 */
+    int bands;                      /* 0: legacy format, 1 .. 1024: banded */
+    uint8_t *files;                 /* [B][file_stride] */
+    int64_t file_stride;
+    int64_t *file_bytes;            /* int64 [B] */
+    void *workspace;
+    int64_t workspace_bytes;
+} l3c_encode_images_desc;
+int64_t l3c_encode_images_workspace_bytes(const l3c_net_config *cfg_host, int64_t B, int Hp, int Wp, int bands);
+int l3c_encode_images(const l3c_encode_images_desc *desc_host, l3c_stream_t stream);
+
+typedef struct {
+    const l3c_codec_model *model_host;
+    const uint8_t *files;
+    const void *plan_host;          /* of l3c_decode_plan or l3c_decode_plan_banded */
+    const void *plan;
+    int64_t plan_bytes;
+    uint8_t *dst;                   /* the buffer the views lie in (device) */
+    int64_t dst_bytes;
+    const l3c_u8_image *images_host;
+    const l3c_u8_image *images;     /* device copy, 16-byte aligned */
+    int16_t *sym;                   /* optional: int16 planar [B][3][H][W] */
+    void *workspace;
+    int64_t workspace_bytes;
+} l3c_decode_images_desc;
+int64_t l3c_decode_images_workspace_bytes(const l3c_net_config *cfg_host, const void *plan_host);
+int l3c_decode_images(const l3c_decode_images_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
 
 #ifdef __cplusplus
 }

@@ -145,6 +145,26 @@ class DecodeBatchDesc(ctypes.Structure):
                 ('pixels', c_vp), ('sym', c_vp), ('workspace', c_vp), ('workspace_bytes', c_i64)]
 
 
+class U8Image(ctypes.Structure):
+    """l3c_u8_image (include/l3c_hip.h): one image inside a byte buffer and its place in the padded frame."""
+    _fields_ = [('offset', c_i64), ('row_stride', c_i64), ('chan_stride', c_i64), ('pix_stride', ctypes.c_int32), ('h', ctypes.c_int32),
+                ('w', ctypes.c_int32), ('top', ctypes.c_int32), ('left', ctypes.c_int32)]
+
+
+class EncodeImagesDesc(ctypes.Structure):
+    """l3c_encode_images_desc (include/l3c_hip.h)."""
+    _fields_ = [('model_host', ctypes.POINTER(CodecModel)), ('src', c_vp), ('src_bytes', c_i64), ('images_host', c_vp), ('images', c_vp),
+                ('B', c_i64), ('Hp', c_int), ('Wp', c_int), ('bands', c_int), ('files', c_vp), ('file_stride', c_i64), ('file_bytes', c_vp),
+                ('workspace', c_vp), ('workspace_bytes', c_i64)]
+
+
+class DecodeImagesDesc(ctypes.Structure):
+    """l3c_decode_images_desc (include/l3c_hip.h)."""
+    _fields_ = [('model_host', ctypes.POINTER(CodecModel)), ('files', c_vp), ('plan_host', c_vp), ('plan', c_vp), ('plan_bytes', c_i64),
+                ('dst', c_vp), ('dst_bytes', c_i64), ('images_host', c_vp), ('images', c_vp), ('sym', c_vp), ('workspace', c_vp),
+                ('workspace_bytes', c_i64)]
+
+
 EPI_RELU, EPI_RESIDUAL, EPI_PIXEL_SHUFFLE = 1, 2, 4
 ABI_VERSION = 4      # include/l3c_hip.h: L3C_ABI_VERSION (4: grouped tables, l3c_decode_rgb, l3c_container_read; no canvas batches)
 
@@ -242,6 +262,14 @@ PROTOTYPES = {
                                        ctypes.POINTER(c_int), c_vp]),
     'l3c_decode_batch_banded_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
     'l3c_decode_batch_banded': (c_int, [ctypes.POINTER(DecodeBatchDesc), c_vp, c_vp]),
+    'l3c_image_padding': (c_int, [c_int, c_int, c_int, c_vp]),
+    'l3c_image_table_check': (c_int, [c_vp, c_i64, c_int, c_int, c_i64]),
+    'l3c_u8_gather': (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
+    'l3c_u8_scatter': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    'l3c_encode_images_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_i64, c_int, c_int, c_int]),
+    'l3c_encode_images': (c_int, [ctypes.POINTER(EncodeImagesDesc), c_vp]),
+    'l3c_decode_images_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
+    'l3c_decode_images': (c_int, [ctypes.POINTER(DecodeImagesDesc), c_vp, c_vp]),
 }
 
 # include/l3c_xcheck.h: the TEST-ONLY cross-check library (round-1/2 Winograd F(2x2,3x3) kernel); see load_xcheck()

@@ -13,6 +13,10 @@
 // with _scale_symbols_banded; framing parser: codec_plan_banded.h): per scale l3c_ac_band_intervals cuts the intervals into band groups, and
 // every band of a record decodes as a stream of its own -- l3c_ac_decode_bands, the ragged table / decoder launches, l3c_decode_rgb_banded.
 //
+// Pictures that are not planar, padded or equally sized (l3c_encode_images / l3c_decode_images): the same loops -- each encode entry is
+// split into its checks and its schedule for that -- behind l3c_u8_gather and in front of l3c_u8_scatter (csrc/images.hip), the planar
+// frames in front of the wrapped entry's workspace.
+//
 // Three small kernels of its own: the file sizes and offsets of a batch (what EncodedBatch.file_sizes sums with torch ops) for either
 // format -- a thread per legacy file, a block with a wave reduction per banded file -- and int16 symbols -> uint8 pixels.
 #include <string.h>
@@ -455,7 +459,8 @@ int64_t l3c_encode_batch_workspace_bytes(const l3c_net_config *cfg, int64_t B, i
     return p.bytes;
 }
 
-int l3c_encode_batch(const l3c_encode_batch_desc *d, l3c_stream_t stream) {
+// l3c_encode_batch in two halves, shared with l3c_encode_images: every check, then the schedule
+static int enc_check(const l3c_encode_batch_desc *d, EncPlan *plan) {
     L3C_REQUIRE(d, "null descriptor");
     CODEC_TRY(check_model(d->model_host));
     const l3c_codec_model &m = *d->model_host;
@@ -473,8 +478,13 @@ int l3c_encode_batch(const l3c_encode_batch_desc *d, l3c_stream_t stream) {
                           (long long)d->file_stride, (long long)stride);
     if (d->workspace_bytes < p.bytes)
         return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
+    *plan = p;
+    return L3C_OK;
+}
 
-    // ---- everything checked: enqueue
+static int enc_run(const l3c_encode_batch_desc *d, const EncPlan &p, l3c_stream_t stream) {
+    const l3c_codec_model &m = *d->model_host;
+    const l3c_net_config &c = *m.cfg_host;
     const int64_t B = d->B;
     const int S = p.S;
     char *ws = base256(d->workspace);
@@ -537,6 +547,12 @@ int l3c_encode_batch(const l3c_encode_batch_desc *d, l3c_stream_t stream) {
     la.file_bytes = d->file_bytes;
     CODEC_TRY(launch_layout(la, stream));
     return l3c_container_write(scales, S + 1, B, padding, file_offset, d->files, stream);
+}
+
+int l3c_encode_batch(const l3c_encode_batch_desc *d, l3c_stream_t stream) {
+    EncPlan p;
+    CODEC_TRY(enc_check(d, &p));
+    return enc_run(d, p, stream);     // everything checked: enqueue
 }
 
 int64_t l3c_decode_plan_bytes(const l3c_net_config *cfg, int64_t B) {
@@ -743,7 +759,8 @@ int64_t l3c_encode_batch_banded_workspace_bytes(const l3c_net_config *cfg, int64
     return p.bytes;
 }
 
-int l3c_encode_batch_banded(const l3c_encode_batch_desc *d, int bands, l3c_stream_t stream) {
+// l3c_encode_batch_banded in the same two halves
+static int enc_banded_check(const l3c_encode_batch_desc *d, int bands, EncBandPlan *plan) {
     L3C_REQUIRE(d, "null descriptor");
     CODEC_TRY(check_model(d->model_host));
     const l3c_codec_model &m = *d->model_host;
@@ -762,8 +779,13 @@ int l3c_encode_batch_banded(const l3c_encode_batch_desc *d, int bands, l3c_strea
                           (long long)d->file_stride, (long long)stride);
     if (d->workspace_bytes < p.bytes)
         return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
+    *plan = p;
+    return L3C_OK;
+}
 
-    // ---- everything checked: enqueue
+static int enc_banded_run(const l3c_encode_batch_desc *d, const EncBandPlan &p, l3c_stream_t stream) {
+    const l3c_codec_model &m = *d->model_host;
+    const l3c_net_config &c = *m.cfg_host;
     const int64_t B = d->B;
     const int S = p.S;
     char *ws = base256(d->workspace);
@@ -838,6 +860,12 @@ int l3c_encode_batch_banded(const l3c_encode_batch_desc *d, int bands, l3c_strea
     la.file_bytes = d->file_bytes;
     CODEC_TRY(launch_layout_banded(la, stream));
     return l3c_container_write_banded(scales, S + 1, B, padding, file_offset, d->files, cs + p.pos, B * p.streams_per_image * 8, stream);
+}
+
+int l3c_encode_batch_banded(const l3c_encode_batch_desc *d, int bands, l3c_stream_t stream) {
+    EncBandPlan p;
+    CODEC_TRY(enc_banded_check(d, bands, &p));
+    return enc_banded_run(d, p, stream);     // everything checked: enqueue
 }
 
 int64_t l3c_decode_plan_banded_bytes(const l3c_net_config *cfg, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B) {
@@ -1000,5 +1028,122 @@ int l3c_decode_batch_banded(const l3c_decode_batch_desc *d, l3c_stream_t main_st
         }
     }
     return l3c_sym_to_u8(sym[n_rec - 1], B * 3 * h.H * h.W, d->pixels, main_stream);
+}
+
+// ---- pictures as they come: a table of views, padded and cropped on the device (csrc/images.hip) -----------------------------------
+//
+// Both calls put the planar frames in front of the workspace of the entry they wrap:  frames [B][3][Hp][Wp] | padding uint16 [B][4]
+// (encode) | the wrapped entry's workspace.  + ALIGN: the caller's pointer is 16-byte aligned, the frames start at the next multiple of 256.
+
+int64_t l3c_encode_images_workspace_bytes(const l3c_net_config *cfg, int64_t B, int Hp, int Wp, int bands) {
+    const int64_t inner = bands ? l3c_encode_batch_banded_workspace_bytes(cfg, B, Hp, Wp, bands) : l3c_encode_batch_workspace_bytes(cfg, B, Hp, Wp);
+    if (inner < 0) return inner;
+    return up(B * 3 * (int64_t)Hp * Wp) + up(B * 8) + inner + ALIGN;
+}
+
+int l3c_encode_images(const l3c_encode_images_desc *d, l3c_stream_t stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    CODEC_TRY(check_model(d->model_host));
+    const l3c_net_config &c = *d->model_host->cfg_host;
+    L3C_REQUIRE(d->src && d->images_host && d->images && d->files && d->file_bytes && d->workspace, "null pointer");
+    L3C_REQUIRE(aligned16(d->images) && aligned16(d->files) && aligned16(d->file_bytes) && aligned16(d->workspace),
+                "every pointer but src must be 16-byte aligned");
+    L3C_REQUIRE(d->B > 0 && d->B < 65536, "bad batch size (1 .. 65535)");
+    CODEC_TRY(check_sides(c, d->Hp, d->Wp));
+    if (d->bands) CODEC_TRY(check_bands(d->bands));
+    const int64_t need = l3c_encode_images_workspace_bytes(&c, d->B, d->Hp, d->Wp, d->bands);
+    if (need < 0) return (int)need;
+    if (d->workspace_bytes < need)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)need);
+    char *ws = base256(d->workspace);
+    const int64_t frames = up(d->B * 3 * (int64_t)d->Hp * d->Wp), head = frames + up(d->B * 8);
+    uint8_t *img = reinterpret_cast<uint8_t *>(ws);
+    uint16_t *padding = reinterpret_cast<uint16_t *>(ws + frames);
+    l3c_encode_batch_desc e;
+    memset(&e, 0, sizeof(e));
+    e.model_host = d->model_host;
+    e.img = img;
+    e.B = d->B;
+    e.H = d->Hp;
+    e.W = d->Wp;
+    e.padding = padding;
+    e.files = d->files;
+    e.file_stride = d->file_stride;
+    e.file_bytes = d->file_bytes;
+    e.workspace = ws + head;
+    e.workspace_bytes = d->workspace_bytes - head - (ws - static_cast<char *>(d->workspace));
+    EncPlan p;
+    EncBandPlan pb;
+    if (d->bands)
+        CODEC_TRY(enc_banded_check(&e, d->bands, &pb));
+    else
+        CODEC_TRY(enc_check(&e, &p));
+    CODEC_TRY(l3c::images_check(d->images_host, d->images, d->B, d->Hp, d->Wp, d->src_bytes));
+
+    // ---- everything checked: enqueue
+    CODEC_TRY(l3c_u8_gather(d->src, d->src_bytes, d->images_host, d->images, d->B, d->Hp, d->Wp, img, padding, stream));
+    return d->bands ? enc_banded_run(&e, pb, stream) : enc_run(&e, p, stream);
+}
+
+// the plan blob's first word: which of the two decoders reads it
+static int plan_is_banded(const void *plan_host, bool *banded) {
+    L3C_REQUIRE(plan_host, "null pointer: plan_host");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(plan_host) & 7) == 0, "plan_host must be 8-byte aligned");
+    int64_t magic;
+    memcpy(&magic, plan_host, sizeof(magic));
+    *banded = magic == l3c_plan::BANDED_MAGIC;
+    return L3C_OK;
+}
+
+int64_t l3c_decode_images_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) {
+    CODEC_TRY(codec_config(cfg));
+    bool banded;
+    CODEC_TRY(plan_is_banded(plan_host, &banded));
+    const int64_t inner = banded ? l3c_decode_batch_banded_workspace_bytes(cfg, plan_host) : l3c_decode_batch_workspace_bytes(cfg, plan_host);
+    if (inner < 0) return inner;
+    const int64_t *w = static_cast<const int64_t *>(plan_host);      // words 2, 4, 5 of either header: B, H, W (checked by the call above)
+    return up(w[2] * 3 * w[4] * w[5]) + inner + ALIGN;
+}
+
+int l3c_decode_images(const l3c_decode_images_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    CODEC_TRY(check_model(d->model_host));
+    const l3c_net_config &c = *d->model_host->cfg_host;
+    L3C_REQUIRE(d->files && d->plan_host && d->plan && d->dst && d->images_host && d->images && d->workspace, "null pointer");
+    L3C_REQUIRE(aligned16(d->files) && aligned16(d->plan) && aligned16(d->images) && aligned16(d->sym) && aligned16(d->workspace),
+                "every pointer but dst must be 16-byte aligned");
+    bool banded;
+    CODEC_TRY(plan_is_banded(d->plan_host, &banded));
+    int64_t B, H, W;
+    if (banded) {
+        l3c_plan::BandedHeader h;
+        CODEC_TRY(l3c_plan::check_blob_banded(c, d->plan_host, d->plan_bytes, &h, l3c::error_buffer(), 512));
+        B = h.B, H = h.H, W = h.W;
+    } else {
+        l3c_plan::Header h;
+        CODEC_TRY(l3c_plan::check_blob(c, d->plan_host, d->plan_bytes, &h, l3c::error_buffer(), 512));
+        B = h.B, H = h.H, W = h.W;
+    }
+    const int64_t need = l3c_decode_images_workspace_bytes(&c, d->plan_host);
+    if (need < 0) return (int)need;
+    if (d->workspace_bytes < need)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)need);
+    CODEC_TRY(l3c::images_check(d->images_host, d->images, B, (int)H, (int)W, d->dst_bytes));
+    char *ws = base256(d->workspace);
+    const int64_t head = up(B * 3 * H * W);
+    l3c_decode_batch_desc q;
+    memset(&q, 0, sizeof(q));
+    q.model_host = d->model_host;
+    q.files = d->files;
+    q.plan_host = d->plan_host;
+    q.plan = d->plan;
+    q.plan_bytes = d->plan_bytes;
+    q.pixels = reinterpret_cast<uint8_t *>(ws);
+    q.sym = d->sym;
+    q.workspace = ws + head;
+    q.workspace_bytes = d->workspace_bytes - head - (ws - static_cast<char *>(d->workspace));
+    // the wrapped entry checks its own arguments (the side stream among them) before it enqueues anything, the scatter's are checked above
+    CODEC_TRY(banded ? l3c_decode_batch_banded(&q, main_stream, side_stream) : l3c_decode_batch(&q, main_stream, side_stream));
+    return l3c_u8_scatter(q.pixels, B, (int)H, (int)W, d->dst, d->dst_bytes, d->images_host, d->images, main_stream);
 }
 }

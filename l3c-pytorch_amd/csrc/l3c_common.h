@@ -33,6 +33,10 @@ inline hipStream_t as_stream(l3c_stream_t s) { return reinterpret_cast<hipStream
 int ac_decode_chunks_entries(const l3c_ac_decode_part *parts, int n_parts, const int32_t *final_chunk_dev, const int *chunk_host,
                              l3c_stream_t stream);
 
+// what l3c_u8_gather / l3c_u8_scatter check of their table and frame before a launch (csrc/images.hip), for the codec entries that wrap
+// them: B, Hp, Wp in range, Wp a multiple of 4, the device table 16-byte aligned, every view inside [0, buffer_bytes) (csrc/image_table.h)
+int images_check(const l3c_u8_image *images_host, const l3c_u8_image *images, int64_t B, int Hp, int Wp, int64_t buffer_bytes);
+
 }  // namespace l3c
 
 #define L3C_REQUIRE(cond, msg)                                                         \

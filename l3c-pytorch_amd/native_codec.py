@@ -6,6 +6,10 @@ byte for byte and either side decodes the other's.  L3C family, equally sized pa
 `NativeCodec(blueprint, bands=K)` the banded one (l3c_encode_batch_banded / l3c_decode_plan_banded + l3c_decode_batch_banded: the files of
 `Bitcoding(bp, bands=K)`); `decode_batch` reads either.  torch owns the memory and the streams, nothing else.  It has no other knobs, and
 no product path (Bitcoding, l3c.py, test.py, bench.py) reads it.
+
+`encode_images` / `decode_images` take pictures as they come -- a list of host images, each of its own size, planar or interleaved RGB /
+RGBX / BGR(X) -- and leave padding and cropping to the library (l3c_encode_images / l3c_decode_images: l3c_u8_gather / l3c_u8_scatter driven
+by a table of l3c_u8_image entries, one call per group of images that pad to one shape).
 """
 import ctypes
 
@@ -13,9 +17,10 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import CodecModel, DecodeBatchDesc, EncodeBatchDesc, ptr, stream
+from ._lib import CodecModel, DecodeBatchDesc, DecodeImagesDesc, EncodeBatchDesc, EncodeImagesDesc, ptr, stream
 from .bitcoding import container, upload
 from .bitcoding.bitcoding import Bitcoding, _staging
+from .helpers import dataset_codec
 from .native_net import NativeNet, _bytes, _size
 
 PLAN_MAGIC = int.from_bytes(b'L3C_PLAN', 'little')
@@ -24,6 +29,40 @@ _PLAN_MAX_RECORDS = _lib.NET_MAX_SCALES + 1
 PLAN_BANDED_MAGIC = int.from_bytes(b'L3CBPLAN', 'little')
 _PLAN_BANDED_HEADER_WORDS = 24 + _PLAN_MAX_RECORDS     # csrc/codec_plan_banded.h: BandedHeader up to its records
 _RING = upload._H2DRing(3)
+
+
+# l3c_u8_image (include/l3c_hip.h) as a numpy record: a table is an array of these
+IMAGE_DTYPE = np.dtype({'names': ['offset', 'row_stride', 'chan_stride', 'pix_stride', 'h', 'w', 'top', 'left'],
+                        'formats': ['<i8', '<i8', '<i8', '<i4', '<i4', '<i4', '<i4', '<i4'], 'offsets': [0, 8, 16, 24, 28, 32, 36, 40], 'itemsize': 48})
+LAYOUTS = ('chw', 'hwc', 'hwcx', 'bgr')
+
+
+def image_shape(layout, h, w, channels=3):
+    """Array shape of a contiguous h x w image: 'chw' (3,h,w); 'hwc' (h,w,3); 'hwcx' (h,w,4); 'bgr' (h,w,channels), channels 3 or 4 (BGRX)."""
+    if layout not in LAYOUTS:
+        raise ValueError('layout must be one of {}, got {!r}'.format(LAYOUTS, layout))
+    return (3, h, w) if layout == 'chw' else (h, w, {'hwc': 3, 'hwcx': 4, 'bgr': channels}[layout])
+
+
+def image_entry(layout, shape, offset, top=0, left=0):
+    """The l3c_u8_image fields of a CONTIGUOUS image of array shape `shape` lying `offset` bytes into its buffer -> (offset, row_stride,
+    chan_stride, pix_stride, h, w, top, left); a row pitch or a bottom-up image is the caller's to put into row_stride."""
+    if layout == 'chw':
+        if len(shape) != 3 or shape[0] != 3:
+            raise ValueError("layout 'chw' expects (3, h, w), got {}".format(tuple(shape)))
+        _, h, w = shape
+        return (offset, w, h * w, 1, h, w, top, left)
+    if len(shape) != 3 or tuple(shape) != image_shape(layout, shape[0], shape[1], shape[2] if layout == 'bgr' and shape[2] in (3, 4) else 3):
+        raise ValueError('layout {!r} expects {}, got {}'.format(layout, image_shape(layout, 'h', 'w'), tuple(shape)))
+    h, w, px = shape
+    return (offset + 2, px * w, -1, px, h, w, top, left) if layout == 'bgr' else (offset, px * w, 1, px, h, w, top, left)
+
+
+def _host_u8(i, img):
+    a = img.numpy() if isinstance(img, torch.Tensor) and not img.is_cuda else img
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+        raise ValueError('encode_images: image {} must be a host uint8 tensor or numpy array'.format(i))
+    return np.ascontiguousarray(a)
 
 
 def parse_plan(blob):
@@ -250,3 +289,147 @@ class NativeCodec(object):
         d = DecodeBatchDesc(ctypes.pointer(self.model), ptr(dev), plan_host, ptr(dev) + plan_at, n_plan, ptr(pixels), ptr(sym), ptr(ws), ws.numel())
         _lib.call(decode_fn, ctypes.byref(d), stream(), side.cuda_stream if side is not None else None)
         return pixels, [tuple(int(v) for v in p) for p in pads]
+
+    # ---- pictures as they come -----------------------------------------------------------------------------------------------
+
+    @property
+    def fac(self):
+        return 1 << self.cfg.num_scales
+
+    def encode_images_workspace_bytes(self, B, Hp, Wp):
+        return _size(_lib.load().l3c_encode_images_workspace_bytes(self._cfg_ref, B, Hp, Wp, self.bands))
+
+    def encode_images_device(self, src, table, Hp, Wp, table_dev=None, src_bytes=None, workspace=None):
+        """For pixels that are already on the GPU.  src: device uint8 buffer the views of `table` (numpy array of IMAGE_DTYPE, one entry per
+        image, `top` / `left` set: centre padding is l3c_image_padding / pad.padding_for) lie in; table_dev: its device copy (a device
+        pointer or uint8 tensor; None: uploaded here).  Enqueues l3c_encode_images on the current stream -> (files uint8 (B, file_stride),
+        file_bytes int64 (B,)) on the device, as encode_device."""
+        table = np.ascontiguousarray(table, dtype=IMAGE_DTYPE)
+        B = len(table)
+        if table_dev is None:
+            table_dev = ops.upload_small(table.view(np.uint8))
+        stride = self.file_stride(Hp, Wp)
+        ws = _bytes(self.encode_images_workspace_bytes(B, Hp, Wp)) if workspace is None else workspace
+        files = torch.empty(B, stride, dtype=torch.uint8, device='cuda')
+        file_bytes = torch.empty(B, dtype=torch.int64, device='cuda')
+        d = EncodeImagesDesc(ctypes.pointer(self.model), ptr(src), src.numel() if src_bytes is None else src_bytes, table.ctypes.data,
+                             table_dev if isinstance(table_dev, int) else ptr(table_dev), B, Hp, Wp, self.bands, ptr(files), stride,
+                             ptr(file_bytes), ptr(ws), ws.numel())
+        _lib.call('l3c_encode_images', ctypes.byref(d), stream())
+        return files, file_bytes
+
+    def encode_images(self, images, layout='chw', max_batch=16):
+        """images: list of host uint8 tensors or numpy arrays, each of its own size, all in `layout` ('chw' (3,h,w); 'hwc' (h,w,3); 'hwcx'
+        (h,w,4), the fourth byte ignored; 'bgr' (h,w,3) or (h,w,4) in B, G, R[, X] order) -> list of `.l3c` byte strings in input order: the
+        files of Bitcoding on the zero-padded images (dataset_codec.encode_set's).  Images that pad to one shape share a call of at most
+        max_batch; each group is staged back to back in page-locked memory with its table and crosses PCIe in ONE copy."""
+        arrs = [_host_u8(i, im) for i, im in enumerate(images)]
+        entries = [image_entry(layout, a.shape, 0) for a in arrs]
+        shapes = {i: (e[4], e[5]) for i, e in enumerate(entries)}
+        chunks, padded, pads, _ = dataset_codec.plan_set(shapes, range(len(arrs)), max_batch, self.fac)
+        pending = []
+        for chunk, (Hp, Wp) in zip(chunks, padded):
+            sizes = [arrs[i].size for i in chunk]
+            table_at = (sum(sizes) + 15) // 16 * 16
+            k, stage = _RING.take(table_at + IMAGE_DTYPE.itemsize * len(chunk))
+            st = stage.numpy()
+            table = st[table_at:].view(IMAGE_DTYPE)
+            off = 0
+            for b, (i, n) in enumerate(zip(chunk, sizes)):
+                st[off:off + n] = arrs[i].reshape(-1)
+                left, _, top, _ = pads[i]
+                table[b] = image_entry(layout, arrs[i].shape, off, top, left)
+                off += n
+            dev = torch.empty(stage.numel(), dtype=torch.uint8, device='cuda')
+            dev.copy_(stage, non_blocking=True)
+            _RING.sent(k)
+            pending.append((chunk, self.encode_images_device(dev, table, Hp, Wp, table_dev=dev.data_ptr() + table_at, src_bytes=table_at)))
+        out = [None] * len(arrs)
+        for chunk, (files, file_bytes) in pending:
+            for i, f in zip(chunk, self.to_bytes(files, file_bytes)):
+                out[i] = f
+        return out
+
+    def decode_images_workspace_bytes(self, blob):
+        buf = np.frombuffer(bytes(blob), dtype=np.int64)
+        return _size(_lib.load().l3c_decode_images_workspace_bytes(self._cfg_ref, buf.ctypes.data))
+
+    def _side_stream(self, lag, tensors):
+        if lag != 2:
+            return None
+        if self._side is None:
+            self._side = torch.cuda.Stream()
+        for t in tensors:
+            if t is not None:
+                t.record_stream(self._side)
+        return self._side.cuda_stream
+
+    def decode_images_device(self, files_dev, plan_blob, plan_dev, dst, table, table_dev=None, workspace=None, sym=None):
+        """For callers whose buffers are already on the GPU.  files_dev: the files' bytes at the offsets the plan was made with; plan_blob:
+        the planner's blob (decode_plan / decode_plan_banded) on the host, plan_dev its device copy (pointer or uint8 tensor); dst: the
+        device uint8 buffer the views of `table` (numpy IMAGE_DTYPE array; top / left / h / w from the planner's paddings) lie in.
+        Enqueues l3c_decode_images on the current stream; exactly the bytes the views address are written."""
+        table = np.ascontiguousarray(table, dtype=IMAGE_DTYPE)
+        if table_dev is None:
+            table_dev = ops.upload_small(table.view(np.uint8))
+        blob = np.frombuffer(bytes(plan_blob), dtype=np.int64)
+        self._decode_images_call(files_dev, blob.ctypes.data, plan_dev if isinstance(plan_dev, int) else ptr(plan_dev), blob.nbytes, int(blob[11]), dst,
+                                 table.ctypes.data, table_dev if isinstance(table_dev, int) else ptr(table_dev), workspace, sym, (plan_dev, table_dev))
+
+    def _decode_images_call(self, files_dev, plan_host, plan_dev, n_plan, lag, dst, table_host, table_dev, workspace, sym, keep=()):
+        ws = _bytes(_size(_lib.load().l3c_decode_images_workspace_bytes(self._cfg_ref, plan_host))) if workspace is None else workspace
+        side = self._side_stream(lag, [files_dev, ws, dst, sym, self.net.packed, self.targets_rgb] + [t for t in keep if isinstance(t, torch.Tensor)])
+        d = DecodeImagesDesc(ctypes.pointer(self.model), ptr(files_dev), plan_host, plan_dev, n_plan, ptr(dst), dst.numel(), table_host, table_dev,
+                             ptr(sym), ptr(ws), ws.numel())
+        _lib.call('l3c_decode_images', ctypes.byref(d), stream(), side)
+
+    def decode_images(self, files, layout='chw', max_batch=16):
+        """files: list of `.l3c` byte strings, legacy and banded alike, of any sizes -> list of device uint8 tensors in input order, each the
+        ORIGINAL size (the padding undone) in `layout` ('hwcx': the fourth byte is 0; 'bgr': (h,w,3)).  Files of one format and padded shape
+        share a call of at most max_batch (dataset_codec.plan_decode_set); each group decodes into one packed buffer, the tensors are views
+        of it.  Files, plan and table cross PCIe in one copy from page-locked memory."""
+        lib = _lib.load()
+        image_shape(layout, 1, 1)
+        chunks, _ = dataset_codec.plan_decode_set(files, range(len(files)), max_batch)
+        out = [None] * len(files)
+        for chunk in chunks:
+            fs = [files[i] for i in chunk]
+            B = len(fs)
+            if container.is_banded(fs[0]):
+                plan_fn = lib.l3c_decode_plan_banded
+                n_plan = _plan_banded_bytes(self._cfg_ref, fs)
+                _check_plan(min(n_plan, 0))
+            else:
+                plan_fn, n_plan = lib.l3c_decode_plan, _size(lib.l3c_decode_plan_bytes(self._cfg_ref, B))
+            offs = np.concatenate([[0], np.cumsum([len(f) for f in fs])]).astype(np.int64)
+            plan_at = (int(offs[-1]) + 4 + 15) // 16 * 16
+            table_at = plan_at + (n_plan + 15) // 16 * 16
+            k, stage = _RING.take(table_at + IMAGE_DTYPE.itemsize * B)
+            st = stage.numpy()
+            for b, f in enumerate(fs):
+                st[offs[b]:offs[b + 1]] = np.frombuffer(f, dtype=np.uint8)
+            st[offs[-1]:plan_at] = 0
+            H, W, pads = ctypes.c_int(), ctypes.c_int(), np.zeros((B, 4), dtype=np.uint16)
+            plan_host = stage.data_ptr() + plan_at
+            _check_plan(plan_fn(self._cfg_ref, stage.data_ptr(), offs.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), B, plan_host, n_plan,
+                                ctypes.byref(H), ctypes.byref(W), pads.ctypes.data))
+            table = st[table_at:].view(IMAGE_DTYPE)
+            views, off = [], 0
+            for b, (left, right, top, bottom) in enumerate(pads.astype(np.int64).tolist()):
+                h, w = H.value - top - bottom, W.value - left - right
+                if h < 1 or w < 1:
+                    raise ValueError('invalid file: the padding {} leaves nothing of the {} x {} image'.format((left, right, top, bottom), H.value, W.value))
+                shape = image_shape(layout, h, w)
+                table[b] = image_entry(layout, shape, off, top, left)
+                views.append((off, shape))
+                off += int(np.prod(shape))
+            dev = torch.empty(stage.numel(), dtype=torch.uint8, device='cuda')
+            dev.copy_(stage, non_blocking=True)
+            _RING.sent(k)
+            lag = int(st[plan_at + 88:plan_at + 96].view(np.int64)[0])      # word 11 of either header
+            dst = (torch.zeros if layout == 'hwcx' else torch.empty)(off, dtype=torch.uint8, device='cuda')
+            self._decode_images_call(dev, plan_host, dev.data_ptr() + plan_at, n_plan, lag, dst, stage.data_ptr() + table_at,
+                                     dev.data_ptr() + table_at, None, None)
+            for i, (o, shape) in zip(chunk, views):
+                out[i] = dst[o:o + int(np.prod(shape))].view(shape)
+        return out
