@@ -288,6 +288,8 @@ XCHECK_SMALL_PROTOTYPES = {
     'l3c_xcheck_rgb_head': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     'l3c_xcheck_to_q_quantize': (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'l3c_xcheck_dec_head': (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp]),
+    # the encoder's interval head before its vector fill and compile-time shapes (csrc/xcheck_iv.hip)
+    'l3c_xcheck_dmll_encode_intervals': (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp]),
 }
 XCHECK_LIB_PATH = os.environ.get('L3C_XCHECK_LIB') or os.path.join(_HERE, 'csrc', 'libl3c_hip_xcheck.so')   # (L3C_XCHECK_LIB: a development variant)
 

@@ -34,53 +34,139 @@ using l3c::cdf_quantise;
 
 // ---- P tile -> LDS ------------------------------------------------------------------------------------------------------
 // npix pixel rows of Kp floats (contiguous in memory) into tile[pixel][ld = Kp + 1] (the odd stride keeps the per-pixel column reads of
-// the compute phases conflict-free).  Kp % 4 == 0 (the RGB scale: 120) and a 16-byte aligned source: one 16-byte load per four values and
-// one division per load -- by multiplication with a host-made reciprocal (exact for the < 2^16 indices of a tile) -- instead of a
-// 4-byte load and an integer division per value (round 5: the divisions were a quarter of the interval kernel's VALU work).
+// the compute phases conflict-free).  The fill only moves data; it has four forms, chosen per tile from Kp and the alignment of the tile's
+// first byte (uniform over the block):
+//   Kp % 4 == 0 (the RGB scale: 120), 16-byte aligned:  one 16-byte load per four values of a row;
+//   Kp % 4 == 2 (the bottleneck scales: 150), 16-byte aligned:  16-byte loads as well, each placed as two float2 HALVES -- a half never
+//               crosses a row because Kp is even, the two halves of a piece may lie in consecutive rows.  A tile of 64 rows is a multiple of
+//               16 bytes long; the last tile of an image with an odd number of rows ends in a single half, loaded as 8 bytes;
+//   Kp % 4 == 2, only 8-byte aligned (rows are 8 mod 16 bytes long, so the tiles of every other image of an odd HW, and the table kernel's
+//               ranges that start at an odd pixel):  8-byte loads, one half each;
+//   everything else (odd Kp, a base that is not even 8-byte aligned, Kp % 4 == 0 off 16-byte alignment):  4-byte loads.
+// The row of a piece comes from one division per load -- by multiplication with a host-made reciprocal (exact for the < 2^16 indices of a
+// tile, checked exhaustively by the host) -- instead of an integer division per value (round 5: the divisions were a quarter of the
+// interval kernel's VALU work; the 4-byte form still pays them: about twenty integer instructions per value).
 struct TileDiv {
-    unsigned q4, magic;   // q4 = Kp / 4 (0: scalar fill); i / q4 == (i * magic) >> 20 for i < 65536 / ... (checked by the host)
+    unsigned vec, q, magic;   // vec = 4 / 2: q = Kp / vec pieces per row, i / q == (i * magic) >> 20 for every piece index of a tile; 0: 4-byte fill
 };
-static TileDiv tile_div(int Kp, int max_pix) {
-    TileDiv d{0u, 0u};
+static TileDiv tile_div_checked(int Kp, int max_pix) {
+    TileDiv d{0u, 0u, 0u};
 #ifdef L3C_IV_SCALAR_FILL
     return d;       // (A/B builds: the scalar fill of rounds 1-4)
 #endif
-    if (Kp % 4 != 0) return d;
-    const unsigned q = (unsigned)(Kp / 4);
+    if (Kp % 2 != 0) return d;
+    const unsigned vec = Kp % 4 == 0 ? 4u : 2u;
+    const unsigned q = (unsigned)Kp / vec;
     const unsigned magic = ((1u << 20) + q - 1u) / q;
     for (unsigned i = 0; i < (unsigned)max_pix * q; ++i)
-        if (i / q != (unsigned)(((unsigned long long)i * magic) >> 20)) return d;   // (never for the shapes of this path; falls back to scalar)
-    d.q4 = q;
+        if ((unsigned long long)i * magic > 0xffffffffull || i / q != (unsigned)(((unsigned long long)i * magic) >> 20))
+            return d;   // (never for the shapes of this path; falls back to the 4-byte fill)
+    d.vec = vec;
+    d.q = q;
     d.magic = magic;
     return d;
 }
+// (the check walks every index of a tile -- a few microseconds -- and a decode launches a table kernel per chunk: each thread remembers
+// the last few shapes it was asked for)
+static TileDiv tile_div(int Kp, int max_pix) {
+    struct Slot {
+        int Kp, max_pix;
+        TileDiv d;
+    };
+    static thread_local Slot slots[4] = {};
+    static thread_local unsigned next = 0;
+    for (const Slot &s : slots)
+        if (s.Kp == Kp && s.max_pix == max_pix) return s.d;
+    Slot &s = slots[next++ & 3u];
+    s.Kp = Kp;
+    s.max_pix = max_pix;
+    s.d = tile_div_checked(Kp, max_pix);
+    return s.d;
+}
 // NT threads (a compile-time constant) fill; the loads of a batch of U turns are all issued before the first value is stored, so that the
 // batch pays one memory round trip (with a run-time stride the compiler keeps one load in flight per turn: the 150-channel tiles of
-// the bottleneck scales then took 30 round trips, twice the time of the whole kernel before).
+// the bottleneck scales then took 30 round trips, twice the time of the whole kernel before).  A turn past the end of the tile REPEATS the
+// batch's first one, load and store (the same thread puts the same values in the same place again), so that neither is predicated: the
+// compiler sinks a load whose only use is a predicated store into that block and waits for it alone (one load in four was, in the ISA).
 template <int NT>
 __device__ __forceinline__ void fill_tile(float *__restrict__ tile, const float *__restrict__ src, int npix, int Kp, int ld, TileDiv dv, int tid) {
-    if (dv.q4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+    const unsigned align = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15);
+    if (dv.vec == 4 && align == 0) {
         constexpr int U = 4;
         const float4 *src4 = reinterpret_cast<const float4 *>(src);
-        const int n4 = npix * (int)dv.q4;
+        const int n4 = npix * (int)dv.q;
         for (int i0 = tid; i0 < n4; i0 += NT * U) {
             float4 v[U];
+            int idx[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int i = i0 + u * NT;
-                v[u] = src4[i < n4 ? i : i0];
+                idx[u] = i0 + u * NT < n4 ? i0 + u * NT : i0;
+                v[u] = src4[idx[u]];
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int i = i0 + u * NT;
-                if (i < n4) {
-                    const int p = (int)(((unsigned)i * dv.magic) >> 20);
-                    float *dst = tile + p * ld + (i - p * (int)dv.q4) * 4;
-                    dst[0] = v[u].x;
-                    dst[1] = v[u].y;
-                    dst[2] = v[u].z;
-                    dst[3] = v[u].w;
-                }
+                const int i = idx[u];
+                const int p = (int)(((unsigned)i * dv.magic) >> 20);
+                float *dst = tile + p * ld + (i - p * (int)dv.q) * 4;
+                dst[0] = v[u].x;
+                dst[1] = v[u].y;
+                dst[2] = v[u].z;
+                dst[3] = v[u].w;
+            }
+        }
+    } else if (dv.vec == 2 && align == 0) {
+        constexpr int U = 4;
+        const float4 *src4 = reinterpret_cast<const float4 *>(src);
+        const int q = (int)dv.q;
+        const int nh = npix * q;      // halves in the tile; piece i = halves 2 i, 2 i + 1
+        const int n4 = nh >> 1;
+        for (int i0 = tid; i0 < n4; i0 += NT * U) {
+            float4 v[U];
+            int idx[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                idx[u] = i0 + u * NT < n4 ? i0 + u * NT : i0;
+                v[u] = src4[idx[u]];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int h = 2 * idx[u];
+                const int p = (int)(((unsigned)h * dv.magic) >> 20);
+                const int col = h - p * q;
+                float *d0 = tile + p * ld + col * 2;
+                float *d1 = col + 1 == q ? tile + (p + 1) * ld : d0 + 2;   // the second half: next in the row, or first of the next row
+                d0[0] = v[u].x;
+                d0[1] = v[u].y;
+                d1[0] = v[u].z;
+                d1[1] = v[u].w;
+            }
+        }
+        if ((nh & 1) && tid == 0) {   // odd npix: the last row's last half
+            const float2 v = reinterpret_cast<const float2 *>(src)[nh - 1];
+            float *d0 = tile + (npix - 1) * ld + (q - 1) * 2;
+            d0[0] = v.x;
+            d0[1] = v.y;
+        }
+    } else if (dv.vec == 2 && (align & 7) == 0) {
+        constexpr int U = 8;
+        const float2 *src2 = reinterpret_cast<const float2 *>(src);
+        const int q = (int)dv.q;
+        const int nh = npix * q;
+        for (int i0 = tid; i0 < nh; i0 += NT * U) {
+            float2 v[U];
+            int idx[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                idx[u] = i0 + u * NT < nh ? i0 + u * NT : i0;
+                v[u] = src2[idx[u]];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = idx[u];
+                const int p = (int)(((unsigned)i * dv.magic) >> 20);
+                float *dst = tile + p * ld + (i - p * q) * 2;
+                dst[0] = v[u].x;
+                dst[1] = v[u].y;
             }
         }
     } else {
@@ -88,16 +174,14 @@ __device__ __forceinline__ void fill_tile(float *__restrict__ tile, const float 
         const int n = npix * Kp;
         for (int i0 = tid; i0 < n; i0 += NT * U) {
             float v[U];
+            int idx[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int i = i0 + u * NT;
-                v[u] = src[i < n ? i : i0];
+                idx[u] = i0 + u * NT < n ? i0 + u * NT : i0;
+                v[u] = src[idx[u]];
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int i = i0 + u * NT;
-                if (i < n) tile[(i / Kp) * ld + (i % Kp)] = v[u];
-            }
+            for (int u = 0; u < U; ++u) tile[(idx[u] / Kp) * ld + (idx[u] % Kp)] = v[u];
         }
     }
 }
@@ -379,10 +463,12 @@ constexpr int kHeadPix = 64;  // == interval block length, so one block writes w
 
 // (Tried: kHeadPix * C threads per block -- one (pixel, channel) item per thread, no idle lanes in the compute phase: 4.4 ->
 // 6.8 ms per launch at batch 128 [PMC]: fewer wavefronts per CU for the LDS-bound tile fill outweigh the busier lanes.)
+// The kernel for ANY shape: C, K and rgb are run-time values (the k loops keep their `break`, the lambda tests are branches inside them).
+// The two shapes of the L3C configurations go through encode_intervals_kernel below instead.
 template <int NT>
-__global__ __launch_bounds__(NT) void encode_intervals_kernel(const float *__restrict__ P, const int16_t *__restrict__ sym,
-                                                               const float *__restrict__ targets, int64_t HW, int C, int K,
-                                                               int rgb, int Lp, uint32_t *__restrict__ iv, TileDiv dv) {
+__global__ __launch_bounds__(NT) void encode_intervals_rt_kernel(const float *__restrict__ P, const int16_t *__restrict__ sym,
+                                                                  const float *__restrict__ targets, int64_t HW, int C, int K,
+                                                                  int rgb, int Lp, uint32_t *__restrict__ iv, TileDiv dv) {
     extern __shared__ __attribute__((aligned(16))) float tile[];   // [kHeadPix][Kp + 1]
     const int Kp = (rgb ? 4 : 3) * C * K;
     const int ld = Kp + 1;
@@ -443,13 +529,118 @@ __global__ __launch_bounds__(NT) void encode_intervals_kernel(const float *__res
     }
 }
 
+// Compile-time shapes: (C, K, RGB) = (3, 10, true) and (5, 10, false).  The SAME calls into csrc/dmll_core.h on the same operands, the
+// sums over k in the same sequential order -- hence the same bits as the run-time kernel (tests/test_gpu_interval_head_bits.py) -- as
+// straight-line code: the k loops are unrolled without a `break`, a thread's tile columns are compile-time offsets read into registers
+// ahead of the arithmetic, and which lambdas a channel couples to is known per instantiation (CH; the RGB scale's wavefronts branch once,
+// uniformly, on their channel).  A scale without coupling needs no CH: its item reads the tile from column c * K on as channel 0.
+template <int C, int K, bool RGB, int CH>
+__device__ __forceinline__ void interval_item(const float *__restrict__ px, float x0, float x1, float t_lo, float t_hi, float &acc_lo,
+                                              float &acc_hi) {
+    constexpr int CK = C * K;
+    constexpr int NLAM = !RGB ? 0 : CH == 1 ? K : CH == 2 ? 2 * K : 0;
+    constexpr int LAM0 = 3 * CK + (CH == 2 ? K : 0);      // first lambda column this channel reads
+    float r_l[K], r_mu[K], r_ls[K], r_lam[NLAM > 0 ? NLAM : 1];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        r_l[k] = px[CH * K + k];
+        r_mu[k] = px[CK + CH * K + k];
+        r_ls[k] = px[2 * CK + CH * K + k];
+    }
+#pragma unroll
+    for (int j = 0; j < NLAM; ++j) r_lam[j] = px[LAM0 + j];
+    auto get = [&](int ch) {      // (ch is a constant wherever this is called: the selection folds away)
+        return ch < CK ? r_l[ch - CH * K] : ch < 2 * CK ? r_mu[ch - CK - CH * K] : ch < 3 * CK ? r_ls[ch - 2 * CK - CH * K] : r_lam[ch - LAM0];
+    };
+    MixStats st;
+    st.max_logit = get(CH * K);
+#pragma unroll
+    for (int k = 1; k < K; ++k) st.max_logit = fmaxf(st.max_logit, get(CH * K + k));
+    float e[K];
+    st.denom = 0.0f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        e[k] = expf(get(CH * K + k) - st.max_logit);
+        st.denom = st.denom + e[k];
+    }
+    acc_lo = 0.0f;
+    acc_hi = 0.0f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const MixComponent m = mix_component_e(get, st, e[k], C, K, RGB ? 1 : 0, CH, k, x0, x1);
+        const float inv = expf(-m.log_sigma);
+        acc_lo = acc_lo + cdf_term(m.pi, m.mu, inv, t_lo);
+        acc_hi = acc_hi + cdf_term(m.pi, m.mu, inv, t_hi);
+    }
+}
+
+template <int C, int K, bool RGB, int NT>
+__global__ __launch_bounds__(NT) void encode_intervals_kernel(const float *__restrict__ P, const int16_t *__restrict__ sym,
+                                                               const float *__restrict__ targets, int64_t HW, int Lp,
+                                                               uint32_t *__restrict__ iv, TileDiv dv) {
+    static_assert(kHeadPix * C <= NT && kHeadPix == 64, "one (pixel, channel) item per thread, a channel per wavefront");
+    static_assert(!RGB || C == 3, "lambda coupling is only defined for C == 3");
+    extern __shared__ __attribute__((aligned(16))) float tile[];   // [kHeadPix][Kp + 1]
+    constexpr int Kp = (RGB ? 4 : 3) * C * K;
+    constexpr int ld = Kp + 1;
+    const int64_t b = blockIdx.y;
+    const int64_t chunk = blockIdx.x;
+    const int64_t pix0 = chunk * kHeadPix;
+    const int npix = (int)((HW - pix0) < kHeadPix ? (HW - pix0) : kHeadPix);
+    const int tid = threadIdx.x;
+    const int p = tid & (kHeadPix - 1), c = tid / kHeadPix;     // c: uniform over the wavefront
+    const bool item = c < C && p < npix;
+    // the item's symbols: asked for before the tile, so that they arrive under its fill; the targets they select: under the barrier
+    int x = 0;
+    float x0 = 0.f, x1 = 0.f, t_lo = 0.f, t_hi = 0.f;
+    if (item) {
+        const int64_t n = pix0 + p;
+        x = sym[(b * C + c) * HW + n];
+        if (RGB && c > 0) {
+            x0 = (float)sym[(b * C + 0) * HW + n];
+            if (c > 1) x1 = (float)sym[(b * C + 1) * HW + n];
+        }
+    }
+    fill_tile<NT>(tile, P + (b * HW + pix0) * Kp, npix, Kp, ld, dv, tid);
+    if (item) {
+        t_lo = targets[x];
+        t_hi = targets[x + 1];
+    }
+    __syncthreads();
+    if (c >= C) return;       // (the RGB scale's fourth wavefront: it helped fill the tile)
+    uint32_t word0 = 0, word1 = 0;   // the stream's lane pair reads one word per role (csrc/ac_core.h: role_word)
+    if (item) {
+        const float *px = tile + p * ld;
+        float acc_lo, acc_hi;
+        if constexpr (RGB) {
+            if (c == 0)
+                interval_item<C, K, true, 0>(px, x0, x1, t_lo, t_hi, acc_lo, acc_hi);
+            else if (c == 1)
+                interval_item<C, K, true, 1>(px, x0, x1, t_lo, t_hi, acc_lo, acc_hi);
+            else
+                interval_item<C, K, true, 2>(px, x0, x1, t_lo, t_hi, acc_lo, acc_hi);
+        } else {
+            interval_item<C, K, false, 0>(px + c * K, x0, x1, t_lo, t_hi, acc_lo, acc_hi);
+        }
+        const float scale = (float)(65536 - (Lp - 1));
+        const uint32_t c_lo = cdf_quantise(acc_lo, scale, x);
+        const uint32_t c_hi = (x == Lp - 2) ? 0x10000u : cdf_quantise(acc_hi, scale, x + 1);
+        word0 = l3c::role_word(c_lo, c_hi, 0);
+        word1 = l3c::role_word(c_lo, c_hi, 1);
+    }
+    const int64_t n_streams = (int64_t)gridDim.y * C;
+    uint32_t *dst = iv + (chunk * n_streams + b * C + c) * (2 * kHeadPix) + p;
+    dst[0] = word0;
+    dst[kHeadPix] = word1;
+}
+
 // ---- negative log-likelihood map ---------------------------------------------------------------------------------------
 
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.0f ? x : log1pf(expf(x)); }  // F.softplus defaults
 
 __global__ __launch_bounds__(256) void nll_kernel(const float *__restrict__ P, const float *__restrict__ xs, int64_t HW,
                                                   int C, int K, int rgb, float x_lower, float x_upper, float half_bin,
-                                                  float *__restrict__ nll) {
+                                                  float *__restrict__ nll, TileDiv dv) {
     extern __shared__ __attribute__((aligned(16))) float tile[];
     const int Kp = (rgb ? 4 : 3) * C * K;
     const int CK = C * K;
@@ -459,7 +650,7 @@ __global__ __launch_bounds__(256) void nll_kernel(const float *__restrict__ P, c
     const int npix = (int)((HW - pix0) < kHeadPix ? (HW - pix0) : kHeadPix);
     const int tid = threadIdx.x;
     const float *src = P + (b * HW + pix0) * Kp;
-    for (int i = tid; i < npix * Kp; i += 256) tile[(i / Kp) * ld + (i % Kp)] = src[i];
+    fill_tile<256>(tile, src, npix, Kp, ld, dv, tid);
     __syncthreads();
     for (int w = tid; w < kHeadPix * C; w += 256) {
         const int p = w % kHeadPix, c = w / kHeadPix;
@@ -514,7 +705,7 @@ __global__ __launch_bounds__(256) void nll_kernel(const float *__restrict__ P, c
 // the kernel is a pure function (and comparable with the oracle).
 __global__ __launch_bounds__(256) void sample_kernel(const float *__restrict__ P, const float *__restrict__ u_mix,
                                                      const float *__restrict__ u_log, int64_t HW, int C, int K, int rgb,
-                                                     float *__restrict__ x_out) {
+                                                     float *__restrict__ x_out, TileDiv dv) {
     extern __shared__ __attribute__((aligned(16))) float tile[];
     const int Kp = (rgb ? 4 : 3) * C * K;
     const int CK = C * K;
@@ -524,7 +715,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float *__restrict__ P
     const int npix = (int)((HW - pix0) < kHeadPix ? (HW - pix0) : kHeadPix);
     const int tid = threadIdx.x;
     const float *src = P + (b * HW + pix0) * Kp;
-    for (int i = tid; i < npix * Kp; i += 256) tile[(i / Kp) * ld + (i % Kp)] = src[i];
+    fill_tile<256>(tile, src, npix, Kp, ld, dv, tid);
     __syncthreads();
     for (int p = tid; p < npix; p += 256) {
         const float *px = tile + p * ld;
@@ -744,13 +935,23 @@ int l3c_dmll_encode_intervals(const float *P, const int16_t *sym, const float *t
 #else
     const int nthreads = kHeadPix * C == 320 ? 320 : 256;
 #endif
+    const TileDiv dv = tile_div(Kp, kHeadPix);
+    const hipStream_t s = l3c::as_stream(stream);
+#ifndef L3C_IV_RUNTIME_SHAPES   // (A/B builds: every shape through the run-time kernel)
+    if (C == 3 && K == 10 && rgb) {
+        hipLaunchKernelGGL((encode_intervals_kernel<3, 10, true, 256>), grid, dim3(256), lds, s, P, sym, targets, HW, Lp, intervals, dv);
+        return l3c::check_launch("encode_intervals_kernel");
+    }
+    if (C == 5 && K == 10 && !rgb) {
+        hipLaunchKernelGGL((encode_intervals_kernel<5, 10, false, 320>), grid, dim3(320), lds, s, P, sym, targets, HW, Lp, intervals, dv);
+        return l3c::check_launch("encode_intervals_kernel");
+    }
+#endif
     if (nthreads == 320)
-        hipLaunchKernelGGL(encode_intervals_kernel<320>, grid, dim3(320), lds, l3c::as_stream(stream), P, sym, targets, HW, C, K, rgb, Lp,
-                           intervals, tile_div(Kp, kHeadPix));
+        hipLaunchKernelGGL(encode_intervals_rt_kernel<320>, grid, dim3(320), lds, s, P, sym, targets, HW, C, K, rgb, Lp, intervals, dv);
     else
-        hipLaunchKernelGGL(encode_intervals_kernel<256>, grid, dim3(256), lds, l3c::as_stream(stream), P, sym, targets, HW, C, K, rgb, Lp,
-                           intervals, tile_div(Kp, kHeadPix));
-    return l3c::check_launch("encode_intervals_kernel");
+        hipLaunchKernelGGL(encode_intervals_rt_kernel<256>, grid, dim3(256), lds, s, P, sym, targets, HW, C, K, rgb, Lp, intervals, dv);
+    return l3c::check_launch("encode_intervals_rt_kernel");
 }
 
 int l3c_dmll_nll(const float *P, const float *x, int64_t B, int64_t HW, int C, int K, int rgb, float x_min, float x_max,
@@ -768,7 +969,7 @@ int l3c_dmll_nll(const float *P, const float *x, int64_t B, int64_t HW, int C, i
     const float x_lower = (float)((double)x_min + 0.001), x_upper = (float)((double)x_max - 0.001);
     const dim3 grid((unsigned)((HW + kHeadPix - 1) / kHeadPix), (unsigned)B);
     hipLaunchKernelGGL(nll_kernel, grid, dim3(256), lds, l3c::as_stream(stream), P, x, HW, C, K, rgb, x_lower, x_upper,
-                       (float)(bin / 2.0), nll);
+                       (float)(bin / 2.0), nll, tile_div(Kp, kHeadPix));
     return l3c::check_launch("nll_kernel");
 }
 
@@ -782,7 +983,8 @@ int l3c_dmll_sample(const float *P, const float *u_mix, const float *u_logistic,
     const size_t lds = (size_t)kHeadPix * (Kp + 1) * sizeof(float);
     L3C_REQUIRE(lds <= 64 * 1024, "Kp too large for the LDS tile");
     const dim3 grid((unsigned)((HW + kHeadPix - 1) / kHeadPix), (unsigned)B);
-    hipLaunchKernelGGL(sample_kernel, grid, dim3(256), lds, l3c::as_stream(stream), P, u_mix, u_logistic, HW, C, K, rgb, x);
+    hipLaunchKernelGGL(sample_kernel, grid, dim3(256), lds, l3c::as_stream(stream), P, u_mix, u_logistic, HW, C, K, rgb, x,
+                       tile_div(Kp, kHeadPix));
     return l3c::check_launch("sample_kernel");
 }
 

@@ -4,7 +4,7 @@
 `conv_wino4_kernel` holds 144 accumulators per lane and runs two blocks per CU: every variant the network launches must fit 256
 VGPRs WITHOUT scratch spills (a spill inside the chunk loop is a scratch round trip per MFMA group; the round-3 residual variant spilled 7
 registers until its residual ring was deepened -- the allocator's choice, not visible in the source).  The decoder ring kernel keeps its
-table row in named registers: no spills either.  Compiles with csrc/build.py's flags and reads the code-object
+table row in named registers: no spills either.  The encoder's interval head must keep five wavefronts per SIMD.  Compiles with csrc/build.py's flags and reads the code-object
 metadata hipcc prints into the ISA listing.
 
     python tools/check_registers.py
@@ -27,6 +27,10 @@ BUDGET = {
     'conv_pw.hip': [('conv_pw_kernelILi4ELb0', 168, 0),                # three blocks of four waves per CU
                     ('conv_pw_kernelILi4ELb1', 256, 0)],               # the split-fifth-group form (128 < Cout <= 160): two blocks per CU
     'ac_kernels.hip': [('ac_decode_ring_kernel', 256, 0), ('ac_decode_lean_kernel', 256, 0)],
+    # the interval head: its LDS tile admits 20 wavefronts per CU (five blocks of four, four of five): five per SIMD need <= 96 VGPRs;
+    # the straight-line bodies of the compile-time shapes keep their tile columns in registers and must not spill them
+    'dmll_kernels.hip': [('encode_intervals_kernelILi3ELi10ELb1E', 96, 0), ('encode_intervals_kernelILi5ELi10ELb0E', 96, 0),
+                         ('encode_intervals_rt_kernel', 96, 0)],
 }
 
 

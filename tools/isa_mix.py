@@ -81,10 +81,11 @@ def main():
     print('{:14s}'.format('whole kernel') + ''.join('{:8d}'.format(tot_all.get(k, 0)) for k in keys) + '  {:6d}'.format(n))
     # the steady-state loop = the block with the most MFMAs
     loop = max(blocks, key=lambda b: b['n'].get('mfma', 0))
-    m = loop['n']['mfma']
+    m = loop['n'].get('mfma', 0)
     others = sum(loop['n'].values()) - m
-    print('steady-state block {}: {} MFMAs of {} cycles, {} other instructions = {:.2f} per MFMA = {:.2f} per 32 matrix-pipe cycles'.format(
-        loop['label'], m, mfma_cycles, others, others / m, others / m * 32 / mfma_cycles))
+    if m:       # (a kernel without MFMAs, e.g. the interval head: the whole-kernel line above is its mix)
+        print('steady-state block {}: {} MFMAs of {} cycles, {} other instructions = {:.2f} per MFMA = {:.2f} per 32 matrix-pipe cycles'.format(
+            loop['label'], m, mfma_cycles, others, others / m, others / m * 32 / mfma_cycles))
     for l in lines[end:end + 400]:
         if re.search(r'\.(vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size|agpr_count)', l):
             pass
