@@ -977,6 +977,75 @@ typedef struct {
 int64_t l3c_decode_images_workspace_bytes(const l3c_net_config *cfg_host, const void *plan_host);
 int l3c_decode_images(const l3c_decode_images_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
 
+/* ---- sealed files: what the decoded frame must hash to, checked on decode (opt-in; INTEGRATION.md "Sealed files") ---------------------- */
+
+/*
+ * A `.l3c` file decodes correctly only with the bitstream generation and the checkpoint that wrote it; anything else, or a damaged payload
+ * byte, comes out of the range decoder as a picture of the right size with the wrong pixels.  A SEAL is 24 bytes behind the file's last
+ * separator, the same for legacy and banded files, little-endian:
+ *     0 'L3CS' | 4 u8 version = 1 | 5 u8 flags = 0 | 6 u16 generation | 8 u32 frame CRC | 12 u64 model id | 20 u32 check
+ *   generation   l3c_bitstream_generation() of the writer
+ *   frame CRC    CRC-32 (the zlib polynomial: zlib.crc32) of the 3 H W bytes of the PADDED planar frame [3][H][W] the codec codes: the
+ *                encoder's l3c_encode_batch_desc.img, the decoder's l3c_decode_batch_desc.pixels -- independent of layout and padding
+ *   model id     the first 8 bytes, little-endian, of SHA-256 over every tensor of the checkpoint in l3c_net_param order as contiguous
+ *                little-endian fp32; a result of 0 is stored as 1, and 0 means "not stated"
+ *   check        CRC-32 of the file's 8 padding bytes (file bytes 0..7; bytes 6..13 of a banded file) followed by seal bytes 0..19: a damaged
+ *                padding field would crop the wrong window out of a correct frame
+ * A file is sealed exactly when it has at least 28 bytes, file[-24:-20] is 'L3CS' and file[-28:-24] is the scale separator 46 E2 84 92 that
+ * every unsealed file of either format ends with.  The planners and parsers are unchanged and go on rejecting trailing bytes: a reader
+ * strips the seal (l3c_seal_find) and hands them the body.  A reader checks, in this order: the generation; the model id when both its own
+ * and the file's are non-zero -- both before anything is enqueued --; after the decode, l3c_u8_crc32 of `pixels` against the frame CRC.
+ *
+ * l3c_seal_find / l3c_seal_write are pure host code (csrc/seal.h: no HIP, compiles stand-alone).  l3c_seal_find returns 1: sealed
+ * (*body_bytes_out = file_bytes - 24, *seal_out filled), 0: unsealed (*body_bytes_out = file_bytes), L3C_ERR_INVALID_ARG, "invalid file:
+ * seal ...": a recognised seal with an unknown version, non-zero flags or a wrong check word -- never treated as absent.  l3c_seal_write
+ * stores the 24 bytes for a file whose 8 padding bytes are padding8_host.
+ */
+#define L3C_SEAL_BYTES 24
+typedef struct {
+    uint16_t generation;
+    uint32_t frame_crc;
+    uint64_t model_id;
+} l3c_seal;
+int l3c_seal_find(const uint8_t *file_host, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out);
+int l3c_seal_write(const l3c_seal *seal_host, const uint8_t *padding8_host, uint8_t *dst_host);
+
+/*
+ * l3c_u8_crc32: crc_out[i] = zlib CRC-32 of the item_bytes bytes at data + i * item_stride, for n_items items in two launches.  Integer
+ * only; the result does not depend on the launch geometry; no atomics.  A block folds a TILE of block_bytes bytes: each thread keeps four
+ * remainders, one per dword of its 16-byte loads (thread t reads bytes 16 t .. 16 t + 15 of every 4096-byte row of the tile: whole cache
+ * lines per wave), advances them by one row -- a multiplication with x^(8 * 4096) mod P -- through 4-bit tables in LDS that every lane reads
+ * in a bank of its own, then shifts them to the end of the tile (thread_bytes = 16 * rows per tile: what one thread folds) and the block
+ * XORs them together; the tile's remainder goes to the workspace.  The second launch, a wavefront per item, combines an item's tiles with
+ * multiplications by x^(8 * block_bytes), undoes the zero bytes its last tile was filled up with, and applies zlib's initial and final XOR
+ * as one word that depends on the length alone.  The constants of the fixed run lengths are computed at build time, those of the item length
+ * on the host per call.
+ *   data          4-byte aligned (16-byte aligned data and stride: the full load rate)      item_stride   % 4 == 0 and >= item_bytes
+ *   item_bytes    >= 0 (0: CRC 0), n_items >= 1, any int64 sizes with n_items * ceil(item_bytes / block_bytes) < 2^40
+ *   workspace     l3c_u8_crc32_workspace_bytes(n_items, item_bytes) bytes, 16-byte aligned; garbage on entry
+ * Bytes between items are never read into a result; nothing past the last item's last byte is read.  No allocation, no host sync.
+ * l3c_u8_crc32_tile: thread_bytes and block_bytes, the lengths the tests place their cases around.
+ */
+int64_t l3c_u8_crc32_workspace_bytes(int64_t n_items, int64_t item_bytes);
+int l3c_u8_crc32(const uint8_t *data, int64_t n_items, int64_t item_bytes, int64_t item_stride, uint32_t *crc_out, void *workspace,
+                 int64_t workspace_bytes, l3c_stream_t stream);
+int l3c_u8_crc32_tile(int *thread_bytes_out, int *block_bytes_out);
+
+/*
+ * l3c_seal_append: this build's seal behind every file of an encode, on the device: 24 bytes at files + b * file_stride + file_bytes[b],
+ * file_bytes[b] += 24.  One thread per file, byte stores.  A sealed encode is three calls on one stream with no host round trip:
+ * l3c_encode_batch (or _banded), l3c_u8_crc32 on desc.img (n_items = B, item_bytes = item_stride = 3 H W), l3c_seal_append; the body of the
+ * sealed file is the unsealed file.  It needs file_stride >= l3c_encode_file_stride(...) + 32 (l3c_encode_banded_file_stride(...) + 32).
+ * With pictures as they come: l3c_u8_gather into a frame buffer of the caller's, then the three calls on those frames and on its
+ * padding_out -- the files of l3c_encode_images byte for byte, sealed.
+ *   frame_crc   uint32 [B], l3c_u8_crc32's crc_out           padding   the uint16 [B][4] array of the encode, NULL = zeros
+ *   model_id    0 = not stated                               file_bytes[b] == -1 stays -1; a slot without room for 24 more bytes becomes -1
+ *                                                            and nothing is stored outside a slot
+ * B < 65536; file_stride > 0.
+ */
+int l3c_seal_append(uint8_t *files, int64_t file_stride, int64_t *file_bytes, const uint32_t *frame_crc, const uint16_t *padding,
+                    uint64_t model_id, int64_t B, l3c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

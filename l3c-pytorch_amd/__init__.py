@@ -13,7 +13,7 @@ Layout
   native_net.py  NativeNet: MultiscaleNetwork.forward / get_P as ONE C-ABI call each (l3c_net_forward / l3c_net_get_p)
   native_codec.py NativeCodec: Bitcoding.encode_batch(...).to_bytes() / decode_batch as ONE C-ABI call each (l3c_encode_batch / l3c_decode_batch)
   criterion/     DiscretizedMixLogisticLoss, CDFOut
-  bitcoding/     Bitcoding (.l3c container), coders, part-suffix helper
+  bitcoding/     Bitcoding (.l3c container), coders, part-suffix helper; container.py: the framing of legacy, banded and SEALED files
   blueprints/    MultiscaleBlueprint
   helpers/       .cf config parser, pad, synthetic checkpoints, paths / log-dir parsing
   auto_crop.py   recursive 2x2 tiling of large images

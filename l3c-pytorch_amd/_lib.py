@@ -165,6 +165,12 @@ class DecodeImagesDesc(ctypes.Structure):
                 ('workspace_bytes', c_i64)]
 
 
+class Seal(ctypes.Structure):
+    """l3c_seal (include/l3c_hip.h)."""
+    _fields_ = [('generation', ctypes.c_uint16), ('frame_crc', ctypes.c_uint32), ('model_id', ctypes.c_uint64)]
+
+
+SEAL_BYTES = 24      # include/l3c_hip.h: L3C_SEAL_BYTES
 EPI_RELU, EPI_RESIDUAL, EPI_PIXEL_SHUFFLE = 1, 2, 4
 ABI_VERSION = 4      # include/l3c_hip.h: L3C_ABI_VERSION (4: grouped tables, l3c_decode_rgb, l3c_container_read; no canvas batches)
 
@@ -270,6 +276,12 @@ PROTOTYPES = {
     'l3c_encode_images': (c_int, [ctypes.POINTER(EncodeImagesDesc), c_vp]),
     'l3c_decode_images_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
     'l3c_decode_images': (c_int, [ctypes.POINTER(DecodeImagesDesc), c_vp, c_vp]),
+    'l3c_seal_find': (c_int, [c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(Seal)]),
+    'l3c_seal_write': (c_int, [ctypes.POINTER(Seal), c_vp, c_vp]),
+    'l3c_u8_crc32_workspace_bytes': (c_i64, [c_i64, c_i64]),
+    'l3c_u8_crc32': (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    'l3c_u8_crc32_tile': (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'l3c_seal_append': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.c_uint64, c_i64, c_vp]),
 }
 
 # include/l3c_xcheck.h: the TEST-ONLY cross-check library (round-1/2 Winograd F(2x2,3x3) kernel); see load_xcheck()

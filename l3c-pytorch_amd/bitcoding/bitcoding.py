@@ -22,6 +22,7 @@ import torch
 
 from .. import auto_crop, ops
 from ..helpers import pad
+from ..modules import schema
 from . import container, part_suffix_helper, upload
 from .container import (_MAGIC_VALUE_SEP, BANDED_SIGNATURE, MAX_BANDS, band_len, count_scale_records, is_banded, n_bands,  # noqa: F401
                         parse_banded, parse_containers)
@@ -98,6 +99,8 @@ class EncodedBatch(object):
         self.pending = []                    # (C, H, W, intervals) of prepare_batch, consumed by Bitcoding.code
         self.done = []                       # events on the coder streams; wait() orders the current stream after them
         self.coder_stream = None             # the side stream of the last `code` call (the natural place for the D2H of the files)
+        self.frame_crc = None                # Bitcoding(seal=True): int32 (B,) device tensor, CRC-32 of every padded frame (ops.u8_crc32)
+        self.seal = None                     # ... and (bitstream generation, model id) of the encoder: every whole file is then sealed
 
     def _coder_outputs(self):
         """(C, H, W, out, nbytes) of every coder group, nbytes reshaped to (B, streams per image of that group)."""
@@ -115,6 +118,8 @@ class EncodedBatch(object):
         for _, _, _, out, nbytes in self._coder_outputs():     # allocated under the coder's side stream, consumed on this one
             out.record_stream(cur)
             nbytes.record_stream(cur)
+        if self.frame_crc is not None:
+            self.frame_crc.record_stream(cur)
         return self
 
     def total_payload_bytes(self):
@@ -186,6 +191,14 @@ class EncodedBatch(object):
         reused staging buffer: consume it before the next call."""
         return EncodedBatch.many_to_host_buffer([self], [padding_tuples])
 
+    @staticmethod
+    def _seals(encs, bodies):
+        """The seal of every file of `encs` (b'' for a batch encoded without): ONE D2H of the frame CRCs, the check words on the host."""
+        sealed = [e for e in encs if e.seal is not None]
+        crcs = iter(torch.cat([e.wait().frame_crc for e in sealed]).cpu().numpy().view(np.uint32).tolist()) if sealed else None
+        return [[container.make_seal(body, e.seal[0], next(crcs), e.seal[1]) if e.seal is not None else b'' for body in files]
+                for e, files in zip(encs, bodies)]
+
     def _write_container(self, dst, offsets, padding_tuples):
         """Enqueue the assembly of this batch's files into `dst` at the (device, int64) byte `offsets`."""
         from .. import _lib
@@ -214,6 +227,13 @@ class EncodedBatch(object):
     def many_to_host_buffer(encs, padding_lists=None):
         """The files of several EncodedBatches in ONE device buffer, ONE host synchronisation (their sizes) and ONE D2H copy.
         -> (uint8 numpy array, file offsets, file sizes); files in the order of `encs`, batch order inside."""
+        if any(e.seal is not None for e in encs):
+            raise ValueError('the packed host buffer holds unsealed files back to back and cannot carry a seal: to_bytes / many_to_bytes '
+                             'return the sealed files of Bitcoding(seal=True)')
+        return EncodedBatch._many_to_host_buffer(encs, padding_lists)
+
+    @staticmethod
+    def _many_to_host_buffer(encs, padding_lists=None):
         for e in encs:
             e.wait()
         sizes = torch.cat([e.file_sizes() for e in encs])
@@ -235,24 +255,27 @@ class EncodedBatch(object):
     @staticmethod
     def many_to_bytes(encs, padding_lists=None):
         """-> per EncodedBatch the list of its `.l3c` byte strings."""
-        host, offs, sizes = EncodedBatch.many_to_host_buffer(encs, padding_lists)
+        host, offs, sizes = EncodedBatch._many_to_host_buffer(encs, padding_lists)
         res, k = [], 0
         for e in encs:
             res.append([host[offs[k + b]:offs[k + b] + sizes[k + b]].tobytes() for b in range(e.B)])
             k += e.B
+        if any(e.seal is not None for e in encs):
+            res = [[f + s for f, s in zip(files, seals)] for files, seals in zip(res, EncodedBatch._seals(encs, res))]
         return res
 
     def to_bytes_host_assembled(self, padding_tuples=None):
         """Reference implementation of `to_bytes` on the host (per-scale copies + Python joins); kept for the tests."""
         pl = self.payloads()
         scales = [s[:4] for s in self.banded_scales] if self.bands else [s[:3] for s in self.scales]
-        return [container.write_file(padding_tuples[b] if padding_tuples else (0, 0, 0, 0), scales, [p[b] for p in pl], bool(self.bands))
-                for b in range(self.B)]
+        files = [container.write_file(padding_tuples[b] if padding_tuples else (0, 0, 0, 0), scales, [p[b] for p in pl], bool(self.bands))
+                 for b in range(self.B)]
+        return [f + s for f, s in zip(files, EncodedBatch._seals([self], [files])[0])]
 
 
 class Bitcoding(object):
     def __init__(self, blueprint, times=None, compare_with_theory=False, coder_cus=0, auto_recurse=0, file_writer=None,
-                 coder_streams=4, forward_streams=3, decode_overlap=None, rgb_window='auto', bands=0):
+                 coder_streams=4, forward_streams=3, decode_overlap=None, rgb_window='auto', bands=0, seal=False):
         """coder_streams: side streams the range-coder launches rotate over; forward_streams: streams `encode_many` spreads the forward
         passes of a heterogeneous set over (used when the HIP runtime runs with >= 8 hardware queues -- helpers/runtime.py; the package
         does NOT ask for them on import: applications that code image sets call l3c_pytorch_amd.configure_hip_queues() before their
@@ -270,10 +293,16 @@ class Bitcoding(object):
         itself, `decode` waits for a pending write of the path it is asked to read.
         bands: 0 = the legacy format (byte for byte); K in 1..1024 = BANDED files: every channel of every scale cut into at most K
         independently coded bands (band_len), so that one image's serial coder chains are K times shorter.  The decoder reads either
-        format whatever this says."""
+        format whatever this says.
+        seal: True = every whole file this object returns or writes (to_bytes, many_to_bytes, encode and its .partN files) ends with a
+        24-byte SEAL (container.make_seal): the bitstream generation, the checkpoint's id and the CRC-32 of the padded frame, computed on the
+        device (ops.u8_crc32) while the encode is enqueued; the body of a sealed file is the unsealed file.  The decoder verifies every
+        sealed file whatever this says (decode_batch)."""
         if bands and not 1 <= int(bands) <= MAX_BANDS:
             raise ValueError('bands must be 0 (legacy format) or in 1..{}, got {}'.format(MAX_BANDS, bands))
         self.bands = int(bands)
+        self.seal = bool(seal)
+        self._model_id = None
         self.blueprint = blueprint
         self.auto_recurse = int(auto_recurse)
         if self.auto_recurse and not blueprint.net.config_ms.rgb_bicubic_baseline:
@@ -337,6 +366,18 @@ class Bitcoding(object):
             self._const[key] = uniform_cdf_row(L).cuda()
         return self._const[key]
 
+    def model_id(self):
+        """The checkpoint's id in a seal (modules/schema.model_id), computed on first use."""
+        if self._model_id is None:
+            net = self.blueprint.net
+            self._model_id = schema.model_id(net.state_dict(), net.config_ms)
+        return self._model_id
+
+    @staticmethod
+    def generation():
+        from .. import _lib
+        return _lib.load().l3c_bitstream_generation()
+
     def n_predicted_scales(self):
         """Scales coded with the network's prediction (the coarsest one on top of them is coded with the uniform prior)."""
         return self.blueprint.net.scales + self.auto_recurse
@@ -367,6 +408,9 @@ class Bitcoding(object):
         raw = out.raw
         K = net.config_ms.prob.K
         enc = EncodedBatch(B, (H, W), self.bands)
+        if self.seal:
+            enc.frame_crc = ops.u8_crc32(imgs.to('cuda').to(torch.uint8).contiguous().view(-1), B, 3 * H * W)
+            enc.seal = (self.generation(), self.model_id())
         for scale, dmll, uniform in self.iter_scale_dmll():
             sym = raw.sym[scale]
             _, C, Hs, Ws = sym.shape
@@ -504,7 +548,7 @@ class Bitcoding(object):
         with torch.cuda.stream(first.coder_stream):
             on_group([(k, result[k]) for k in indices])
 
-    def decode_batch(self, files, out_dtype=torch.int64):
+    def decode_batch(self, files, out_dtype=torch.int64, verify=True):
         """files: list of B `.l3c` byte strings of equally sized (padded) images -> ((B,3,H,W) int64 on the GPU (the reference's
         dtype, bitcoding.py:125-161; out_dtype: torch.uint8 / int16 for callers that want the pixels without the 8-byte form),
         list of padding tuples).
@@ -516,8 +560,22 @@ class Bitcoding(object):
         own, so that one part's latency-bound decoder launches would leave room for another part's convolutions and tables:
         0.70 s became 0.87 - 2.98 s with the runtime's four hardware queues (the parts' main and side streams alias and serialise
         each other's long decoder launches) and 0.76 / 1.00 s with 8 or 16 queues -- a decoder wavefront that shares its SIMD
-        with MFMA wavefronts runs 2.3x slower, which costs more than the overlap saves; profiles/r02_decode_parts_tried.log.)"""
-        return self._decode_batch(files, out_dtype, None)
+        with MFMA wavefronts runs 2.3x slower, which costs more than the overlap saves; profiles/r02_decode_parts_tried.log.)
+        SEALED files (container.split_seal; a batch may mix sealed and unsealed ones): the seals are split off, then -- verify=True --
+        every seal's generation and, where both sides state one, its model id are checked BEFORE anything is enqueued
+        (container.SealError, reason 'generation' / 'model'); after the decode ops.u8_crc32 hashes the decoded frames on the device and ONE
+        D2H of B words is compared with the seals (SealError, reason 'pixels').  verify=False strips the seals and checks nothing."""
+        split = [container.split_seal(f, view=True) for f in files]
+        files, seals = [b for b, _ in split], [s for _, s in split]
+        check = verify and any(s is not None for s in seals)
+        if check:
+            container.check_seals(seals, self.generation(), self.model_id)
+        out, padding = self._decode_batch(files, torch.uint8 if check else out_dtype, None)
+        if check:
+            B = out.shape[0]
+            container.check_frame_crcs(seals, ops.u8_crc32(out.view(-1), B, out.numel() // B).cpu().numpy())
+            out = out.to(out_dtype)
+        return out, padding
 
     # ---- the walk over a file's scale records, coarse -> fine: what decode_batch (legacy and banded files) and the set decoder share -----
     # The headers are untrusted input: a wrong C / H / W would make the table and decoder kernels index P and the symbol buffers out of
@@ -618,6 +676,7 @@ class Bitcoding(object):
         complete record present but the finest; more than the data holds raises ValueError.  Only the bytes of the records decoded cross
         PCIe; nothing synchronises with the host."""
         total = self.n_predicted_scales() + 1
+        files = [f[:-container.SEAL_BYTES] if container.is_sealed(f) else f for f in files]     # a preview is not lossless: nothing to verify
         recs, framing, banded, n = container.parse_prefix(files, total + 1)
         if n > total:
             raise ValueError('invalid file: more than {} scale records, the model codes {}'.format(total, total))
@@ -885,30 +944,31 @@ class Bitcoding(object):
         with open(path, 'rb') as fin:
             return fin.read()
 
-    def _decode_parts(self, paths):
+    def _decode_parts(self, paths, verify=True):
         """Part files of one image: parts of equal (padded) shape are decoded as one batch."""
         datas = [self._read_file(p) for p in paths]
         groups = {}
         for i, d in enumerate(datas):
-            groups.setdefault((is_banded(d), container.padded_shape(d)), []).append(i)
+            groups.setdefault((is_banded(d), container.padded_shape(container.split_seal(d)[0])), []).append(i)
         parts = [None] * len(datas)
         for idxs in groups.values():
-            out, padding = self.decode_batch([datas[i] for i in idxs])
+            out, padding = self.decode_batch([datas[i] for i in idxs], verify=verify)
             for k, i in enumerate(idxs):
                 o = out[k:k + 1]
                 parts[i] = pad.undo_pad(o, *padding[k]) if any(padding[k]) else o
         return parts
 
-    def decode(self, pin, _recurse_part=True):
-        """-> decoded image, 1CHW long (on the GPU)."""
+    def decode(self, pin, _recurse_part=True, verify=True):
+        """-> decoded image, 1CHW long (on the GPU).  A sealed file (and every sealed part file) is verified as decode_batch verifies it;
+        verify=False strips the seal and checks nothing."""
         if self.file_writer is not None:
             self.file_writer.wait(pin)                 # (a part suffix is resolved below: every part is waited for when read)
         if _recurse_part and part_suffix_helper.contains_part_suffix(pin):
-            parts = self._decode_parts(list(part_suffix_helper.iter_part_suffixes(pin)))
+            parts = self._decode_parts(list(part_suffix_helper.iter_part_suffixes(pin)), verify)
             print('Stitching {} parts...'.format(len(parts)))
             return auto_crop.stitch(parts)
         data = self._read_file(pin)
-        out, padding = self.decode_batch([data])
+        out, padding = self.decode_batch([data], verify=verify)
         if any(padding[0]):
             out = pad.undo_pad(out, *padding[0])
         return out

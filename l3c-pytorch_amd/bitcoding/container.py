@@ -325,3 +325,98 @@ def image_entry_table(hws, pixbase0=0):
     """Whole images of hws pixels, one after the other from pixel pixbase0: an entry per image, pix0 = 0 and length = hw."""
     hw = np.asarray(hws, dtype=np.int64)
     return pixbase0 + np.cumsum(hw) - hw, hw, np.zeros(hw.shape[0], dtype=np.int64), hw
+
+
+# ---- SEALED files (opt-in, Bitcoding(seal=True); INTEGRATION.md "Sealed files"; the C side is csrc/seal.h) -----------------------------------
+#
+# 24 bytes behind the last separator of a file of either format, little-endian:
+#     'L3CS' | u8 version = 1 | u8 flags = 0 | u16 bitstream generation | u32 frame CRC | u64 model id | u32 check
+# frame CRC: zlib.crc32 of the padded planar frame [3][H][W]; model id: 0 = not stated; check: zlib.crc32 of the file's 8 padding bytes
+# followed by seal bytes 0..19.  The parsers above never see a seal: callers split it off first.
+
+SEAL_SIGNATURE = b'L3CS'
+SEAL_VERSION = 1
+SEAL_BYTES = 24
+
+
+class Seal(object):
+    def __init__(self, generation, frame_crc, model_id):
+        self.generation, self.frame_crc, self.model_id = int(generation), int(frame_crc), int(model_id)
+
+    def __eq__(self, other):
+        return isinstance(other, Seal) and (self.generation, self.frame_crc, self.model_id) == (other.generation, other.frame_crc, other.model_id)
+
+    def __repr__(self):
+        return 'Seal(generation={}, frame_crc=0x{:08x}, model_id=0x{:016x})'.format(self.generation, self.frame_crc, self.model_id)
+
+
+class SealError(ValueError):
+    """A sealed file that this decoder must not, or did not, decode to the pixels that were encoded.  reason: 'generation' (written by
+    another bitstream generation), 'model' (by another checkpoint) -- both raised before anything is decoded --, 'pixels' (the decoded
+    frame does not hash to the seal's CRC: a damaged payload, or a checkpoint the seal does not state).  index: the file's place in the call."""
+
+    def __init__(self, reason, index, message):
+        ValueError.__init__(self, message)
+        self.reason, self.index = reason, index
+
+
+def _padding_bytes(body):
+    at = 6 if is_banded(body) else 0
+    if len(body) < at + 8:
+        raise ValueError('invalid file: seal on a file too short for its padding fields')
+    return bytes(body[at:at + 8])
+
+
+def is_sealed(data):
+    """Whether the file ends with a seal: at least 28 bytes, 'L3CS' 24 bytes before the end and the scale separator in front of it (every
+    unsealed file of either format ends with that separator).  A damaged seal still counts: split_seal raises for it."""
+    return len(data) >= SEAL_BYTES + 4 and bytes(data[-24:-20]) == SEAL_SIGNATURE and bytes(data[-28:-24]) == _MAGIC_VALUE_SEP
+
+
+def make_seal(body, generation, frame_crc, model_id=0):
+    """The 24 seal bytes for the unsealed file `body` (its padding fields go into the check word)."""
+    import zlib
+    head = SEAL_SIGNATURE + struct.pack('<BBHIQ', SEAL_VERSION, 0, generation, frame_crc & 0xffffffff, model_id)
+    return head + struct.pack('<I', zlib.crc32(_padding_bytes(body) + head) & 0xffffffff)
+
+
+def split_seal(data, view=False):
+    """-> (body, Seal or None): the file without its seal, as the parsers above expect it.  ValueError('invalid file: seal ...') for a
+    recognised seal with an unknown version, non-zero flags or a wrong check word: never silently treated as absent.
+    view=True: the body of a sealed file is a memoryview of `data`, not a copy (the decoders: a copy of every file is a millisecond per
+    10 MB on the host, more than the hash costs on the device); everything above reads either."""
+    import zlib
+    if not is_sealed(data):
+        return data, None
+    body, s = (memoryview(data) if view else data)[:-SEAL_BYTES], bytes(data[-SEAL_BYTES:])
+    version, flags, generation, frame_crc, model_id, check = struct.unpack('<BBHIQI', s[4:])
+    if version != SEAL_VERSION:
+        raise ValueError('invalid file: seal of an unknown version')
+    if flags:
+        raise ValueError('invalid file: seal with non-zero flags')
+    if check != zlib.crc32(_padding_bytes(body) + s[:20]) & 0xffffffff:
+        raise ValueError('invalid file: seal check word does not match (damaged seal or padding fields)')
+    return body, Seal(generation, frame_crc, model_id)
+
+
+def check_seals(seals, generation, model_id):
+    """What a decoder checks BEFORE it decodes: every seal's generation, then its model id where both sides state one.  seals: per file a
+    Seal or None; model_id: a callable (the id is only computed when a seal asks for it) or an int."""
+    for i, s in enumerate(seals):
+        if s is not None and s.generation != generation:
+            raise SealError('generation', i, 'file {} was written by bitstream generation {}, this decoder is generation {}: it would decode '
+                            'to wrong pixels'.format(i, s.generation, generation))
+    for i, s in enumerate(seals):
+        if s is not None and s.model_id:
+            mine = model_id() if callable(model_id) else model_id
+            if mine and mine != s.model_id:
+                raise SealError('model', i, 'file {} was written with checkpoint {:016x}, this decoder holds {:016x}: it would decode to wrong '
+                                'pixels'.format(i, s.model_id, mine))
+
+
+def check_frame_crcs(seals, crcs):
+    """After the decode: crcs[i] (the CRC-32 of decoded frame i) against seal i."""
+    for i, s in enumerate(seals):
+        if s is not None and (int(crcs[i]) & 0xffffffff) != s.frame_crc:
+            raise SealError('pixels', i, 'file {} decoded to pixels whose CRC-32 {:08x} is not the sealed {:08x}: damaged payload, or not the '
+                            'checkpoint that wrote it'.format(i, int(crcs[i]) & 0xffffffff, s.frame_crc))

@@ -61,6 +61,9 @@ class SetDecoder(object):
 
     def decode_many(self, batches, on_batch, lanes, chain_cus, out_dtype, ragged, banded):
         """Bitcoding.decode_many (the arguments and the result are described there)."""
+        if any(container.is_sealed(f) for files in batches for f in files):
+            raise ValueError('decode_many does not read sealed .l3c files: container.split_seal gives the body and the seal to check, '
+                             'or decode_batch / decode verify them')
         fmt = [any(container.is_banded(f) for f in files) for files in batches]
         if any(fmt) and not banded:
             raise ValueError('decode_many reads legacy .l3c files only: a banded file (L3CB format) goes through decode_batch / decode')

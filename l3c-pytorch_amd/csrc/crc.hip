@@ -1,0 +1,321 @@
+// crc.hip -- sealed files (include/l3c_hip.h: l3c_u8_crc32, l3c_seal_append, l3c_seal_find / l3c_seal_write; the format is csrc/seal.h).
+//
+// l3c_u8_crc32: zlib's CRC-32 of n_items byte runs, integer only, the same words whatever the launch geometry, no atomics.
+//
+// Arithmetic.  A CRC register is a polynomial over GF(2) modulo P, reflected as zlib keeps it: bit 31 is x^0, `x` is 0x40000000, "times x" is
+// a right shift with a conditional XOR of 0xEDB88320.  With R(A) the remainder of a message from a zero register and without the final
+// XOR, R is linear, leading zero bytes do not change it, and
+//     R(A | B) = R(A) x^(8 |B|) + R(B)              zlib.crc32(A) = R(A) + Z(|A|),  Z(n) = 0xFFFFFFFF x^(8 n) + 0xFFFFFFFF
+// so a little-endian dword D that starts m bytes before the end of the message contributes D x^(8 m), wherever it is folded.
+//
+// First launch: a block per TILE of ROWS rows of 4096 bytes.  Thread t loads bytes 16 t .. 16 t + 15 of every row -- a wave reads whole
+// cache lines -- and keeps one remainder per dword j of that load: acc_j = acc_j K + D_j per row, K = x^(8 * 4096).  "Times K" is linear in
+// the 32 register bits, so it is the XOR of 8 table entries, one per nibble (MULK); the table lies in LDS 32 times, entry e of lane l at
+// dword 32 e + (l & 31), so every lane of a 32-lane half reads a bank of its own: 8 conflict-free ds_read_b32 per dword, where a 256-entry
+// byte table would be 4 reads that serialise about 3.4-fold on random indices.  The lookups of a row are cheap next to the latency of its
+// load, so a whole tile is straight-line code with DEPTH rows of loads in flight per thread (fold_rows).  After the last row the four remainders are folded like the
+// dwords of slice-by-4 (MUL32: "times x^32", the second table), the thread shifts its value over the 16 (255 - t) bytes that follow its
+// column in a row (a bitwise multiplication with the constant SHIFT[t]), and the block XORs the 256 values: the remainder of the tile's rows,
+// a last tile filled up with zero bytes to whole rows.  It goes to partial[item][tile].
+// Second launch: a wavefront per item.  Lane l runs Horner over its share of the full tiles with x^(8 * TILE), weighs it with the tiles behind
+// it, the wave XORs; lane 0 adds the last tile, multiplies by x^(-8 fill) to undo the zero fill, and XORs Z(item_bytes).
+// The constants that depend on item_bytes come from the host as kernel arguments; all others are compile-time tables.
+#include "l3c_common.h"
+#include "seal.h"
+
+namespace {
+
+constexpr uint32_t POLY = 0xEDB88320u;
+constexpr uint32_t ONE = 0x80000000u, X1 = 0x40000000u, X_INV = 0xDB710641u;
+constexpr int THREADS = 256, ROW_BYTES = THREADS * 16, ROWS = 32, TILE_BYTES = ROWS * ROW_BYTES, THREAD_BYTES = ROWS * 16;
+constexpr int MAX_GRID = 4096, DEPTH = 8;
+
+// a b mod P (zlib's multmodp)
+__host__ __device__ constexpr uint32_t mulmod(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int i = 31; i >= 0; --i) {
+        p ^= b & (0u - ((a >> i) & 1u));
+        b = (b >> 1) ^ (POLY & (0u - (b & 1u)));
+    }
+    return p;
+}
+
+// base^e mod P
+__host__ __device__ constexpr uint32_t powmod(uint32_t base, uint64_t e) {
+    uint32_t r = ONE;
+    while (e) {
+        if (e & 1) r = mulmod(r, base);
+        base = mulmod(base, base);
+        e >>= 1;
+    }
+    return r;
+}
+
+constexpr uint32_t X8 = powmod(X1, 8), X8_INV = powmod(X_INV, 8);
+constexpr uint32_t K_ROW = powmod(X8, ROW_BYTES), K_TILE = powmod(X8, TILE_BYTES);
+static_assert(mulmod(X1, X_INV) == ONE && mulmod(X8, X8_INV) == ONE, "x^-1 mod P");
+static_assert(powmod(X1, 32) == POLY, "x^32 mod P is the polynomial's low part");
+
+// [0]: MULK, [1]: MUL32 -- entry 16 k + n is (n << 4 k) times the constant
+struct NibbleTables {
+    uint32_t v[2][128];
+};
+constexpr NibbleTables make_tables() {
+    NibbleTables t{};
+    for (int k = 0; k < 8; ++k)
+        for (uint32_t n = 0; n < 16; ++n) {
+            t.v[0][16 * k + n] = mulmod(n << (4 * k), K_ROW);
+            t.v[1][16 * k + n] = mulmod(n << (4 * k), POLY);
+        }
+    return t;
+}
+// SHIFT[t] = x^(8 * 16 (255 - t)): the bytes of a row behind thread t's 16
+struct ShiftTable {
+    uint32_t v[THREADS];
+};
+constexpr ShiftTable make_shifts() {
+    ShiftTable s{};
+    const uint32_t step = powmod(X8, 16);
+    uint32_t c = ONE;
+    for (int t = THREADS - 1; t >= 0; --t) {
+        s.v[t] = c;
+        c = mulmod(c, step);
+    }
+    return s;
+}
+__device__ const NibbleTables g_tables = make_tables();
+__device__ const ShiftTable g_shifts = make_shifts();
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+struct __attribute__((aligned(4))) Quad {      // a 16-byte load that needs no more than the data's 4-byte alignment
+    uint32_t d[4];
+};
+
+// the 16 bytes at item + off as four little-endian dwords, zero from byte `len` on; nothing at or behind item + len is read
+__device__ __forceinline__ u32x4 load16(const uint8_t *item, int64_t off, int64_t len) {
+    u32x4 r = {0u, 0u, 0u, 0u};
+    if (off + 16 <= len) {
+        const Quad q = *reinterpret_cast<const Quad *>(item + off);
+        r = u32x4{q.d[0], q.d[1], q.d[2], q.d[3]};
+    } else if (off < len) {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        const int n = (int)(len - off);
+#pragma unroll
+        for (int i = 0; i < 15; ++i)
+            if (i < n) w[i >> 2] |= (uint32_t)item[off + i] << (8 * (i & 3));
+        r = u32x4{w[0], w[1], w[2], w[3]};
+    }
+    return r;
+}
+
+// v times the table's constant; tab: the lane's column of one table in LDS
+__device__ __forceinline__ uint32_t times(const uint32_t *tab, uint32_t v) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r ^= tab[(16 * k + ((v >> (4 * k)) & 15u)) * 32];
+    return r;
+}
+
+// one row: a_j = a_j K + d_j for the four remainders.  All 32 lookups are issued before the first is used: the four chains are independent,
+// and one LDS round trip per row instead of four is what the loop's time is made of
+__device__ __forceinline__ void row_step(const uint32_t *tab, uint32_t (&a)[4], u32x4 d) {
+    uint32_t r[4][8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[j][k] = tab[(16 * k + ((a[j] >> (4 * k)) & 15u)) * 32];
+    const uint32_t in[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] = ((r[j][0] ^ r[j][1] ^ r[j][2]) ^ (r[j][3] ^ r[j][4] ^ r[j][5])) ^ (r[j][6] ^ r[j][7] ^ in[j]);
+}
+
+__device__ __forceinline__ u32x4 load_quad(const uint8_t *p) {
+    const Quad q = *reinterpret_cast<const Quad *>(p);
+    return u32x4{q.d[0], q.d[1], q.d[2], q.d[3]};
+}
+
+// N whole rows from p on, straight-line code: up to DEPTH rows of loads in flight per thread -- 16 waves x DEPTH KiB per CU, what it takes to
+// hide the memory latency behind a row's arithmetic -- and, with no branch in between, a wait for exactly the load a row needs
+template <int N>
+__device__ __forceinline__ void fold_rows(const uint32_t *tab, uint32_t (&a)[4], const uint8_t *p) {
+    constexpr int D = N < DEPTH ? N : DEPTH;
+    u32x4 q[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) q[i] = load_quad(p + i * ROW_BYTES);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const u32x4 cur = q[i % D];
+        if (i + D < N) q[i % D] = load_quad(p + (i + D) * ROW_BYTES);
+        row_step(tab, a, cur);
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void u8_crc32_tiles_kernel(const uint8_t *__restrict__ data, int64_t item_bytes, int64_t item_stride,
+                                                                int64_t tiles_per_item, int64_t units, uint32_t *__restrict__ partial) {
+    __shared__ uint32_t lds[2 * 128 * 32];
+    __shared__ uint32_t wave_xor[THREADS / 64];
+    const int t = threadIdx.x;
+    for (int i = 0; i < 32; ++i) {
+        const int idx = i * THREADS + t;
+        lds[idx] = (&g_tables.v[0][0])[idx >> 5];
+    }
+    const uint32_t shift = g_shifts.v[t];
+    const uint32_t *mulk = lds + (t & 31), *mul32 = lds + 128 * 32 + (t & 31);
+    __syncthreads();
+    for (int64_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
+        const int64_t item = unit / tiles_per_item, tile = unit - item * tiles_per_item;
+        const uint8_t *base = data + item * item_stride;
+        const int64_t tile_at = tile * TILE_BYTES;
+        const int64_t left = item_bytes - tile_at;                                          // > 0
+        const int whole = left >= TILE_BYTES ? ROWS : (int)(left / ROW_BYTES);              // rows that lie inside the item: plain loads
+        uint32_t a[4] = {0u, 0u, 0u, 0u};
+        const uint8_t *p = base + tile_at + 16 * t;
+        if (whole == ROWS) {
+            fold_rows<ROWS>(mulk, a, p);
+        } else {                                                                             // an item's last tile
+            int g = 0;
+            for (; g + DEPTH <= whole; g += DEPTH) fold_rows<DEPTH>(mulk, a, p + (int64_t)g * ROW_BYTES);
+            for (; g < whole; ++g) fold_rows<1>(mulk, a, p + (int64_t)g * ROW_BYTES);
+        }
+        if (whole < ROWS && left > (int64_t)whole * ROW_BYTES)                               // the item ends inside this row
+            row_step(mulk, a, load16(base, tile_at + (int64_t)whole * ROW_BYTES + 16 * t, item_bytes));
+        uint32_t v = times(mul32, a[0]);
+        v = times(mul32, v ^ a[1]);
+        v = times(mul32, v ^ a[2]);
+        v = times(mul32, v ^ a[3]);
+        v = mulmod(v, shift);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d, 64);
+        if ((t & 63) == 0) wave_xor[t >> 6] = v;
+        __syncthreads();
+        if (t == 0) partial[unit] = wave_xor[0] ^ wave_xor[1] ^ wave_xor[2] ^ wave_xor[3];
+        __syncthreads();
+    }
+}
+
+// k_last = x^(8 * bytes of the last tile's rows), unfill = x^(-8 * zero bytes it was filled up with), z = Z(item_bytes)
+__global__ __launch_bounds__(64) void u8_crc32_combine_kernel(const uint32_t *__restrict__ partial, int64_t n_items, int64_t tiles_per_item,
+                                                              uint32_t k_last, uint32_t unfill, uint32_t z, uint32_t *__restrict__ crc_out) {
+    const int lane = threadIdx.x;
+    for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        if (tiles_per_item == 0) {
+            if (lane == 0) crc_out[item] = z;
+            continue;
+        }
+        const uint32_t *p = partial + item * tiles_per_item;
+        const int64_t full = tiles_per_item - 1, share = (full + 63) / 64;
+        const int64_t lo = lane * share < full ? lane * share : full, hi = lo + share < full ? lo + share : full;
+        uint32_t a = 0;
+        for (int64_t b = lo; b < hi; ++b) a = mulmod(a, K_TILE) ^ p[b];
+        if (hi > lo && hi < full) a = mulmod(a, powmod(K_TILE, (uint64_t)(full - hi)));
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) a ^= __shfl_xor(a, d, 64);
+        if (lane == 0) crc_out[item] = mulmod(mulmod(a, k_last) ^ p[full], unfill) ^ z;
+    }
+}
+
+// one thread per file: the 24 seal bytes as six words in registers, the check word bitwise over padding | words 0..4
+__global__ __launch_bounds__(64) void seal_append_kernel(uint8_t *__restrict__ files, int64_t file_stride, int64_t *__restrict__ file_bytes,
+                                                         const uint32_t *__restrict__ frame_crc, const uint16_t *__restrict__ padding,
+                                                         uint64_t model_id, uint32_t generation, int64_t B) {
+    const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const int64_t n = file_bytes[b];
+    if (n < 0) return;
+    if (n > file_stride - L3C_SEAL_BYTES) {
+        file_bytes[b] = -1;
+        return;
+    }
+    uint32_t w[8];
+    w[0] = padding ? (uint32_t)padding[4 * b] | (uint32_t)padding[4 * b + 1] << 16 : 0u;
+    w[1] = padding ? (uint32_t)padding[4 * b + 2] | (uint32_t)padding[4 * b + 3] << 16 : 0u;
+    w[2] = 0x5343334Cu;                                                // 'L3CS'
+    w[3] = (uint32_t)l3c_sealing::VERSION | generation << 16;             // version, flags = 0, generation
+    w[4] = frame_crc[b];
+    w[5] = (uint32_t)model_id;
+    w[6] = (uint32_t)(model_id >> 32);
+    uint32_t crc = 0xFFFFFFFFu;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        crc ^= w[i];
+        for (int k = 0; k < 32; ++k) crc = (crc >> 1) ^ (POLY & (0u - (crc & 1u)));
+    }
+    w[7] = ~crc;
+    uint8_t *dst = files + b * file_stride + n;
+#pragma unroll
+    for (int i = 0; i < L3C_SEAL_BYTES; ++i) dst[i] = (uint8_t)(w[2 + (i >> 2)] >> (8 * (i & 3)));
+    file_bytes[b] = n + L3C_SEAL_BYTES;
+}
+
+inline int64_t tiles_of(int64_t item_bytes) { return item_bytes / TILE_BYTES + (item_bytes % TILE_BYTES != 0); }
+
+}  // namespace
+
+extern "C" {
+
+int l3c_seal_find(const uint8_t *file_host, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out) {
+    L3C_REQUIRE(file_host && file_bytes >= 0, "null pointer or negative size");
+    return l3c_sealing::find(file_host, file_bytes, body_bytes_out, seal_out, l3c::error_buffer(), 512);
+}
+
+int l3c_seal_write(const l3c_seal *seal_host, const uint8_t *padding8_host, uint8_t *dst_host) {
+    L3C_REQUIRE(seal_host && padding8_host && dst_host, "null pointer");
+    l3c_sealing::write(*seal_host, padding8_host, dst_host);
+    return L3C_OK;
+}
+
+int l3c_u8_crc32_tile(int *thread_bytes_out, int *block_bytes_out) {
+    L3C_REQUIRE(thread_bytes_out && block_bytes_out, "null pointer");
+    *thread_bytes_out = THREAD_BYTES;
+    *block_bytes_out = TILE_BYTES;
+    return L3C_OK;
+}
+
+int64_t l3c_u8_crc32_workspace_bytes(int64_t n_items, int64_t item_bytes) {
+    if (n_items < 1 || item_bytes < 0 || tiles_of(item_bytes) >= ((int64_t)1 << 40) / n_items)
+        return l3c::fail(L3C_ERR_INVALID_ARG, "%s", "bad sizes: n_items >= 1, item_bytes >= 0, n_items * tiles below 2^40");
+    return (4 * n_items * tiles_of(item_bytes) + 15) / 16 * 16 + 16;
+}
+
+int l3c_u8_crc32(const uint8_t *data, int64_t n_items, int64_t item_bytes, int64_t item_stride, uint32_t *crc_out, void *workspace,
+                 int64_t workspace_bytes, l3c_stream_t stream) {
+    L3C_REQUIRE(data && crc_out && workspace, "null pointer");
+    const int64_t need = l3c_u8_crc32_workspace_bytes(n_items, item_bytes);
+    if (need < 0) return (int)need;
+    L3C_REQUIRE(item_stride % 4 == 0 && item_stride >= item_bytes, "item_stride must be a multiple of 4 and at least item_bytes");
+    L3C_REQUIRE(n_items == 1 || item_stride <= INT64_MAX / n_items, "n_items * item_stride overflows");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(data) & 3) == 0 && (reinterpret_cast<uintptr_t>(crc_out) & 3) == 0, "data and crc_out must be 4-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "the workspace must be 16-byte aligned");
+    L3C_REQUIRE(workspace_bytes >= need, "workspace_bytes too small");
+    const hipStream_t st = l3c::as_stream(stream);
+    const int64_t tiles = tiles_of(item_bytes), units = n_items * tiles;
+    uint32_t *partial = static_cast<uint32_t *>(workspace);
+    uint32_t k_last = 0, unfill = 0, z = 0;
+    if (tiles) {
+        const int64_t last_rows_bytes = (item_bytes - (tiles - 1) * TILE_BYTES + ROW_BYTES - 1) / ROW_BYTES * ROW_BYTES;
+        k_last = powmod(X8, (uint64_t)last_rows_bytes);
+        unfill = powmod(X8_INV, (uint64_t)((tiles - 1) * TILE_BYTES + last_rows_bytes - item_bytes));
+        z = mulmod(powmod(X8, (uint64_t)item_bytes), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
+        hipLaunchKernelGGL(u8_crc32_tiles_kernel, dim3((unsigned)(units < MAX_GRID ? units : MAX_GRID)), dim3(THREADS), 0, st, data, item_bytes,
+                           item_stride, tiles, units, partial);
+        const int rc = l3c::check_launch("u8_crc32_tiles_kernel");
+        if (rc != L3C_OK) return rc;
+    }
+    hipLaunchKernelGGL(u8_crc32_combine_kernel, dim3((unsigned)(n_items < MAX_GRID ? n_items : MAX_GRID)), dim3(64), 0, st, partial, n_items, tiles,
+                       k_last, unfill, z, crc_out);
+    return l3c::check_launch("u8_crc32_combine_kernel");
+}
+
+int l3c_seal_append(uint8_t *files, int64_t file_stride, int64_t *file_bytes, const uint32_t *frame_crc, const uint16_t *padding,
+                    uint64_t model_id, int64_t B, l3c_stream_t stream) {
+    L3C_REQUIRE(files && file_bytes && frame_crc, "null pointer");
+    L3C_REQUIRE(B > 0 && B < 65536, "bad batch size (1 .. 65535)");
+    L3C_REQUIRE(file_stride > 0 && file_stride <= INT64_MAX / B, "bad file_stride");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(file_bytes) & 7) == 0 && (reinterpret_cast<uintptr_t>(frame_crc) & 3) == 0 &&
+                    (reinterpret_cast<uintptr_t>(padding) & 1) == 0,
+                "file_bytes, frame_crc and padding must be aligned to their element size");
+    hipLaunchKernelGGL(seal_append_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, l3c::as_stream(stream), files, file_stride, file_bytes,
+                       frame_crc, padding, model_id, (uint32_t)L3C_BITSTREAM_GENERATION, B);
+    return l3c::check_launch("seal_append_kernel");
+}
+}

@@ -221,6 +221,10 @@ def decode_set(bc, files, order, max_batch=16, marks=None, lanes=None, chain_cus
         if marks is not None:
             marks[name] = time.perf_counter()
 
+    from ..bitcoding import container
+    if any(container.is_sealed(files[i]) for i in order):
+        raise ValueError('decode_set does not read sealed .l3c files: container.split_seal gives the body and the seal to check, or '
+                         'Bitcoding.decode_batch / decode verify them')
     n_lanes = bc.set_decoder.N_DECODE_LANES if lanes is None else int(lanes)
     if n_pinned is None:
         n_pinned = max(n_lanes, min(bc.set_decoder.RAGGED_GROUP, len(order))) + 2     # a finished batch must never wait for a free D2H buffer (a ragged group finishes all its batches at once)

@@ -69,3 +69,15 @@ def check_state_dict(state_dict, config_ms):
                            '  Missing key(s): {}\n  Unexpected key(s): {}\n  Size mismatch: {}'.format(
                                missing, unexpected, wrong))
     return schema
+
+
+def model_id(state_dict, config_ms):
+    """The checkpoint's id in a sealed file (include/l3c_hip.h "sealed files"): the first 8 bytes, little-endian, of SHA-256 over every
+    tensor in param_schema order (= l3c_net_param order) as contiguous little-endian fp32; a result of 0 becomes 1 (0 = "not stated")."""
+    import hashlib
+
+    import numpy as np
+    h = hashlib.sha256()
+    for key in param_schema(config_ms):
+        h.update(np.ascontiguousarray(state_dict[key].detach().cpu().float().numpy()).astype('<f4', copy=False).tobytes())
+    return int.from_bytes(h.digest()[:8], 'little') or 1

@@ -10,6 +10,10 @@ no product path (Bitcoding, l3c.py, test.py, bench.py) reads it.
 `encode_images` / `decode_images` take pictures as they come -- a list of host images, each of its own size, planar or interleaved RGB /
 RGBX / BGR(X) -- and leave padding and cropping to the library (l3c_encode_images / l3c_decode_images: l3c_u8_gather / l3c_u8_scatter driven
 by a table of l3c_u8_image entries, one call per group of images that pad to one shape).
+
+`NativeCodec(blueprint, seal=True)` writes SEALED files (include/l3c_hip.h "sealed files"; the files of `Bitcoding(bp, seal=True)` byte for
+byte): l3c_encode_batch(_banded), l3c_u8_crc32 on the input frames, l3c_seal_append -- one stream of work, no host round trip.  The decoders
+verify every sealed file they are given: generation and model id before anything is enqueued, l3c_u8_crc32 of the decoded frames after.
 """
 import ctypes
 
@@ -21,6 +25,7 @@ from ._lib import CodecModel, DecodeBatchDesc, DecodeImagesDesc, EncodeBatchDesc
 from .bitcoding import container, upload
 from .bitcoding.bitcoding import Bitcoding, _staging
 from .helpers import dataset_codec
+from .modules import schema
 from .native_net import NativeNet, _bytes, _size
 
 PLAN_MAGIC = int.from_bytes(b'L3C_PLAN', 'little')
@@ -160,11 +165,15 @@ def _check_plan(rc):
 
 
 class NativeCodec(object):
-    def __init__(self, blueprint, bands=0):
-        """bands: 0 = encode writes the legacy format; K in 1..1024 = banded files, as Bitcoding(bp, bands=K).  decode_batch reads either."""
+    def __init__(self, blueprint, bands=0, seal=False):
+        """bands: 0 = encode writes the legacy format; K in 1..1024 = banded files, as Bitcoding(bp, bands=K).  decode_batch reads either.
+        seal: True = every file the encoders return ends with a seal, as Bitcoding(bp, seal=True); the decoders verify sealed files whatever
+        this says."""
         if bands and not 1 <= int(bands) <= container.MAX_BANDS:
             raise ValueError('bands must be 0 (legacy format) or in 1..{}, got {}'.format(container.MAX_BANDS, bands))
         self.bands = int(bands)
+        self.seal = bool(seal)
+        self._network, self._model_id = blueprint.net, None
         _lib.require_gpu()
         self.net = NativeNet(blueprint.net)
         self.cfg = self.net.cfg
@@ -183,9 +192,20 @@ class NativeCodec(object):
     # ---- sizes ---------------------------------------------------------------------------------------------------------------
 
     def file_stride(self, H, W):
+        """The slot of one file: the library's stride, and with seal=True the 32 bytes more that l3c_seal_append asks for."""
         if self.bands:
-            return _size(_lib.load().l3c_encode_banded_file_stride(self._cfg_ref, H, W, self.bands))
-        return _size(_lib.load().l3c_encode_file_stride(self._cfg_ref, H, W))
+            return _size(_lib.load().l3c_encode_banded_file_stride(self._cfg_ref, H, W, self.bands)) + 32 * self.seal
+        return _size(_lib.load().l3c_encode_file_stride(self._cfg_ref, H, W)) + 32 * self.seal
+
+    def model_id(self):
+        """The checkpoint's id in a seal (modules/schema.model_id), computed on first use."""
+        if self._model_id is None:
+            self._model_id = schema.model_id(self._network.state_dict(), self._network.config_ms)
+        return self._model_id
+
+    @staticmethod
+    def generation():
+        return _lib.load().l3c_bitstream_generation()
 
     def encode_workspace_bytes(self, B, H, W):
         if self.bands:
@@ -205,19 +225,27 @@ class NativeCodec(object):
         if imgs.dim() != 4 or imgs.shape[1] != 3 or imgs.dtype != torch.uint8:
             raise ValueError('Expected a uint8 B3HW image batch, got {} {}'.format(imgs.dtype, tuple(imgs.shape)))
         imgs = imgs.to('cuda').contiguous()
+        B = imgs.shape[0]
+        pads = None
+        if paddings is not None:
+            pads = ops.upload_small(np.ascontiguousarray(np.asarray(paddings, dtype=np.uint16).reshape(B, 4)).view(np.int16))
+        return self._encode_frames(imgs, pads, workspace)
+
+    def _encode_frames(self, imgs, pads, workspace):
+        """The batch entry on device frames (B,3,H,W) and a device padding array (int16 (B,4) or None); sealed: the frames' CRCs
+        (l3c_u8_crc32) and l3c_seal_append behind it on the same stream."""
         B, _, H, W = imgs.shape
         stride = self.file_stride(H, W)
         ws = _bytes(self.encode_workspace_bytes(B, H, W)) if workspace is None else workspace
         files = torch.empty(B, stride, dtype=torch.uint8, device='cuda')
         file_bytes = torch.empty(B, dtype=torch.int64, device='cuda')
-        pads = None
-        if paddings is not None:
-            pads = ops.upload_small(np.ascontiguousarray(np.asarray(paddings, dtype=np.uint16).reshape(B, 4)).view(np.int16))
         d = EncodeBatchDesc(ctypes.pointer(self.model), ptr(imgs), B, H, W, ptr(pads), ptr(files), stride, ptr(file_bytes), ptr(ws), ws.numel())
         if self.bands:
             _lib.call('l3c_encode_batch_banded', ctypes.byref(d), self.bands, stream())
         else:
             _lib.call('l3c_encode_batch', ctypes.byref(d), stream())
+        if self.seal:
+            ops.seal_append(files, file_bytes, ops.u8_crc32(imgs.view(-1), B, 3 * H * W), pads, self.model_id())
         return files, file_bytes
 
     def encode_batch(self, imgs, paddings=None):
@@ -240,13 +268,17 @@ class NativeCodec(object):
 
     # ---- decode --------------------------------------------------------------------------------------------------------------
 
-    def decode_batch(self, files, workspace=None, sym=None):
+    def decode_batch(self, files, workspace=None, sym=None, verify=True):
         """files: list of B `.l3c` byte strings of equally sized (padded) images, all legacy or all banded (their first four bytes say
         which; a mix raises ValueError) -> ((B,3,H,W) uint8 on the GPU, padding tuples).  The framing is parsed on the host by the library
         (ValueError with its message for an invalid file); files and plan cross PCIe in one copy from page-locked memory.
-        sym: optional int16 (B,3,H,W) device tensor that receives the same values."""
+        sym: optional int16 (B,3,H,W) device tensor that receives the same values.
+        Sealed files (a batch may mix sealed and unsealed ones): as Bitcoding.decode_batch -- container.SealError('generation' / 'model')
+        before anything is enqueued, l3c_u8_crc32 on `pixels` and one D2H of B words after, SealError('pixels'); verify=False strips the
+        seals and checks nothing."""
         lib = _lib.load()
         B = len(files)
+        files, seals = self._split(files, verify)
         banded = [container.is_banded(f) for f in files]
         if any(banded) and not all(banded):
             raise ValueError('decode_batch: a batch mixes banded and legacy .l3c files')
@@ -288,7 +320,18 @@ class NativeCodec(object):
                 t.record_stream(side)
         d = DecodeBatchDesc(ctypes.pointer(self.model), ptr(dev), plan_host, ptr(dev) + plan_at, n_plan, ptr(pixels), ptr(sym), ptr(ws), ws.numel())
         _lib.call(decode_fn, ctypes.byref(d), stream(), side.cuda_stream if side is not None else None)
+        if seals is not None:
+            container.check_frame_crcs(seals, ops.u8_crc32(pixels.view(-1), B, 3 * H.value * W.value).cpu().numpy())
         return pixels, [tuple(int(v) for v in p) for p in pads]
+
+    def _split(self, files, verify):
+        """-> (the files without their seals, the seals to verify after the decode or None); generation and model id are checked here."""
+        split = [container.split_seal(f, view=True) for f in files]
+        seals = [s for _, s in split]
+        if not verify or all(s is None for s in seals):
+            return [b for b, _ in split], None
+        container.check_seals(seals, self.generation(), self.model_id)
+        return [b for b, _ in split], seals
 
     # ---- pictures as they come -----------------------------------------------------------------------------------------------
 
@@ -308,6 +351,12 @@ class NativeCodec(object):
         B = len(table)
         if table_dev is None:
             table_dev = ops.upload_small(table.view(np.uint8))
+        if self.seal:      # the seal hashes the padded frames: gather them into a buffer of our own, then the batch entry on them (the same files)
+            frames = torch.empty(B, 3, Hp, Wp, dtype=torch.uint8, device='cuda')
+            pads = torch.empty(B, 4, dtype=torch.int16, device='cuda')
+            _lib.call('l3c_u8_gather', ptr(src), src.numel() if src_bytes is None else src_bytes, table.ctypes.data,
+                      table_dev if isinstance(table_dev, int) else ptr(table_dev), B, Hp, Wp, ptr(frames), ptr(pads), stream())
+            return self._encode_frames(frames, pads, None)
         stride = self.file_stride(Hp, Wp)
         ws = _bytes(self.encode_images_workspace_bytes(B, Hp, Wp)) if workspace is None else workspace
         files = torch.empty(B, stride, dtype=torch.uint8, device='cuda')
@@ -383,13 +432,18 @@ class NativeCodec(object):
                              ptr(sym), ptr(ws), ws.numel())
         _lib.call('l3c_decode_images', ctypes.byref(d), stream(), side)
 
-    def decode_images(self, files, layout='chw', max_batch=16):
+    def decode_images(self, files, layout='chw', max_batch=16, verify=True):
         """files: list of `.l3c` byte strings, legacy and banded alike, of any sizes -> list of device uint8 tensors in input order, each the
         ORIGINAL size (the padding undone) in `layout` ('hwcx': the fourth byte is 0; 'bgr': (h,w,3)).  Files of one format and padded shape
         share a call of at most max_batch (dataset_codec.plan_decode_set); each group decodes into one packed buffer, the tensors are views
-        of it.  Files, plan and table cross PCIe in one copy from page-locked memory."""
+        of it.  Files, plan and table cross PCIe in one copy from page-locked memory.
+        Sealed files are verified as in decode_batch: a group that holds one decodes through l3c_decode_batch(_banded) into a frame buffer,
+        l3c_u8_crc32 on it, then l3c_u8_scatter -- what l3c_decode_images does, with the hash in between; the CRC words of all groups come
+        back in ONE D2H at the end.  SealError.index is the file's place in `files`."""
         lib = _lib.load()
         image_shape(layout, 1, 1)
+        files, seals = self._split(files, verify)
+        crcs = []
         chunks, _ = dataset_codec.plan_decode_set(files, range(len(files)), max_batch)
         out = [None] * len(files)
         for chunk in chunks:
@@ -428,8 +482,23 @@ class NativeCodec(object):
             _RING.sent(k)
             lag = int(st[plan_at + 88:plan_at + 96].view(np.int64)[0])      # word 11 of either header
             dst = (torch.zeros if layout == 'hwcx' else torch.empty)(off, dtype=torch.uint8, device='cuda')
-            self._decode_images_call(dev, plan_host, dev.data_ptr() + plan_at, n_plan, lag, dst, stage.data_ptr() + table_at,
-                                     dev.data_ptr() + table_at, None, None)
+            if seals is not None and any(seals[i] is not None for i in chunk):
+                banded = container.is_banded(fs[0])
+                ws = _bytes(_size((lib.l3c_decode_batch_banded_workspace_bytes if banded else lib.l3c_decode_batch_workspace_bytes)(self._cfg_ref, plan_host)))
+                pixels = torch.empty(B, 3, H.value, W.value, dtype=torch.uint8, device='cuda')
+                side = self._side_stream(lag, [dev, ws, pixels, self.net.packed, self.targets_rgb])
+                d = DecodeBatchDesc(ctypes.pointer(self.model), ptr(dev), plan_host, dev.data_ptr() + plan_at, n_plan, ptr(pixels), None, ptr(ws), ws.numel())
+                _lib.call('l3c_decode_batch_banded' if banded else 'l3c_decode_batch', ctypes.byref(d), stream(), side)
+                crcs.append((chunk, ops.u8_crc32(pixels.view(-1), B, 3 * H.value * W.value)))
+                _lib.call('l3c_u8_scatter', ptr(pixels), B, H.value, W.value, ptr(dst), dst.numel(), stage.data_ptr() + table_at,
+                          dev.data_ptr() + table_at, stream())
+            else:
+                self._decode_images_call(dev, plan_host, dev.data_ptr() + plan_at, n_plan, lag, dst, stage.data_ptr() + table_at,
+                                         dev.data_ptr() + table_at, None, None)
             for i, (o, shape) in zip(chunk, views):
                 out[i] = dst[o:o + int(np.prod(shape))].view(shape)
+        if crcs:
+            words = torch.cat([c for _, c in crcs]).cpu().numpy()
+            got = dict(zip([i for chunk, _ in crcs for i in chunk], words))
+            container.check_frame_crcs([s if i in got else None for i, s in enumerate(seals)], [got.get(i, 0) for i in range(len(seals))])
         return out

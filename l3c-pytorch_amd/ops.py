@@ -789,3 +789,34 @@ def table_is_monotone(cdf):
     flag = torch.zeros(1, dtype=torch.int32, device=cdf.device)
     call('l3c_cdf_check_monotone', ptr(cdf), cdf.numel() // Lp, Lp, ptr(flag), stream())
     return int(flag.item()) == 0
+
+
+def u8_crc32_tile():
+    """(bytes one thread folds, bytes one block folds) of l3c_u8_crc32."""
+    t, s = ctypes.c_int(), ctypes.c_int()
+    call('l3c_u8_crc32_tile', ctypes.byref(t), ctypes.byref(s))
+    return t.value, s.value
+
+
+def u8_crc32(data, n_items, item_bytes, item_stride=None, out=None, workspace=None):
+    """l3c_u8_crc32: zlib.crc32 of the n_items runs of item_bytes bytes that start item_stride bytes apart (default: back to back) in the
+    contiguous uint8 device tensor `data` -> int32 (n_items,) device tensor holding the CRC words (view it as uint32 on the host); no
+    host synchronisation."""
+    item_stride = item_bytes if item_stride is None else item_stride
+    if data.dtype != torch.uint8 or n_items < 1 or item_bytes < 0 or data.numel() < (n_items - 1) * item_stride + item_bytes:
+        raise ValueError('u8_crc32: {} items of {} bytes, {} apart, do not fit a {} tensor of {} elements'.format(
+            n_items, item_bytes, item_stride, data.dtype, data.numel()))
+    n_ws = _lib.load().l3c_u8_crc32_workspace_bytes(n_items, item_bytes)
+    _lib.check(min(n_ws, 0))
+    ws = torch.empty(n_ws, dtype=torch.uint8, device=data.device) if workspace is None else workspace
+    out = torch.empty(n_items, dtype=torch.int32, device=data.device) if out is None else out
+    call('l3c_u8_crc32', ptr(data, torch.uint8), n_items, item_bytes, item_stride, ptr(out, torch.int32), ptr(ws, torch.uint8), ws.numel(), stream())
+    return out
+
+
+def seal_append(files, file_bytes, frame_crc, padding=None, model_id=0):
+    """l3c_seal_append: this build's seal behind every file of an encode, in place.  files uint8 (B, file_stride), file_bytes int64 (B,),
+    frame_crc int32 (B,) (u8_crc32 of the padded frames), padding int16 (B, 4) device tensor or None -- all on the device."""
+    B, stride = files.shape
+    call('l3c_seal_append', ptr(files, torch.uint8), stride, ptr(file_bytes, torch.int64), ptr(frame_crc, torch.int32), ptr(padding, torch.int16),
+         int(model_id), B, stream())

@@ -194,7 +194,8 @@ class MultiscaleTester(object):
         self.file_writer = AsyncFileWriter() if getattr(flags, 'write_to_files', None) else None
         self.bc = Bitcoding(self.blueprint, times=self.times if getattr(flags, 'write_to_files', None) else None,
                             compare_with_theory=bool(getattr(flags, 'compare_theory', False)), auto_recurse=self.recursive,
-                            file_writer=self.file_writer, bands=int(getattr(flags, 'bands', 0) or 0))
+                            file_writer=self.file_writer, bands=int(getattr(flags, 'bands', 0) or 0),
+                            seal=bool(getattr(flags, 'seal', False)))
         self.max_batch = int(getattr(flags, 'batch', None) or 8)
         self.io_threads = int(getattr(flags, 'io_threads', None) or 4)
         exp_name = os.path.basename(experiment_dir)
@@ -509,7 +510,8 @@ class MultiscaleTester(object):
         bpsp = self.bc.encode(img, pout=pout)
         from .. import _lib
         # the container has no version field (reference bitcoding.py:326-375): say which decoder generation reads this file
-        print('---\nSaved: {}  (bitstream generation {}, include/l3c_hip.h)'.format(pout, _lib.load().l3c_bitstream_generation()))
+        print('---\nSaved: {}  (bitstream generation {}, include/l3c_hip.h{})'.format(pout, _lib.load().l3c_bitstream_generation(),
+                                                                                 '; sealed' if self.bc.seal else ''))
         return bpsp
 
     def decode(self, pin, png_out_p):
@@ -518,8 +520,17 @@ class MultiscaleTester(object):
             raise DecodeError('png_out_p directory ({}) does not exists!'.format(pout_dir))
         if not png_out_p.endswith('.png'):
             raise DecodeError('png_out_p must end in .png, got {}'.format(png_out_p))
-        decoded = self.bc.decode(pin)
+        from ..bitcoding import container
+        verify = not getattr(self.flags, 'no_verify', False)
+        try:
+            with open(pin, 'rb') as fin:
+                _, seal = container.split_seal(fin.read())
+            decoded = self.bc.decode(pin, verify=verify)
+        except container.SealError as e:
+            raise DecodeError('seal: {}'.format(e))
         self._write_img(decoded, png_out_p)
+        if seal is not None:
+            print('seal: ok (generation {})'.format(seal.generation) if verify else 'seal: not verified (--no-verify)')
         print('---\nDecoded: {}'.format(png_out_p))
 
     def preview(self, pin, png_out_p, records=None, max_bytes=None):

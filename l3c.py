@@ -54,8 +54,12 @@ def main(argv=None):
     enc.add_argument('--bands', type=int, nargs='?', const=DEFAULT_BANDS, default=0, metavar='K',
                      help='write a BANDED file: every channel cut into at most K independently coded bands, for fast one-image '
                           'encode / decode (1..1024; the flag alone: {}).  Without the flag: the legacy format.'.format(DEFAULT_BANDS))
+    enc.add_argument('--seal', action='store_true',
+                     help='write a SEALED file: 24 bytes behind the last record that state the bitstream generation, the checkpoint and the '
+                          'CRC-32 of the image, so that dec refuses to return wrong pixels')
     dec.add_argument('img_p')
     dec.add_argument('out_p_png')
+    dec.add_argument('--no-verify', dest='no_verify', action='store_true', help='do not check the seal of a sealed file')
     pre = mode.add_parser('preview', help='Picture from the coarse scale records of a file: preview IMG_P OUT_P_PNG [--records R] [--bytes N]')
     pre.add_argument('img_p')
     pre.add_argument('out_p_png')
