@@ -23,7 +23,7 @@ import torch
 from .. import auto_crop, ops
 from ..helpers import pad
 from ..modules import schema
-from . import container, part_suffix_helper, upload
+from . import container, part_suffix_helper, region, upload
 from .container import (_MAGIC_VALUE_SEP, BANDED_SIGNATURE, MAX_BANDS, band_len, count_scale_records, is_banded, n_bands,  # noqa: F401
                         parse_banded, parse_containers)
 from .set_decode import SetDecoder
@@ -639,11 +639,13 @@ class Bitcoding(object):
         streams = upload._upload_streams(files, framing)
         return self._walk_records(records, framing, banded, streams, n_pred, len(records), side).to(out_dtype), framing.padding
 
-    def _walk_records(self, records, framing, banded, streams, n_pred, n_decoded, side):
+    def _walk_records(self, records, framing, banded, streams, n_pred, n_decoded, side, finest=None):
         """The walk over the n_pred + 1 scale records of B files, coarse -> fine, on the current stream -> the finest scale's symbols
         (B, 3, H, W) int16.  records / framing / banded: what container.parse_batch or parse_prefix gave, streams: the files on the device
         (upload._upload_streams).  The first n_decoded records are decoded by the range decoder; every record past them takes the MEAN of
-        the mixture the network predicts for it (ops.dmll_mean) in the shape the network predicts.  side: see _rgb_schedule."""
+        the mixture the network predicts for it (ops.dmll_mean) in the shape the network predicts.  side: see _rgb_schedule.
+        finest (decode_region): the walk ends BEFORE the finest record and returns finest(k, dmll, record, hw, bn, F) -- the record's index,
+        loss and header, the (H, W) of the record before it, and the decoder's inputs for it."""
         B = len(framing.padding)
         symbols = self._scale_symbols_of(banded)
         K = self.blueprint.net.config_ms.prob.K
@@ -652,6 +654,8 @@ class Bitcoding(object):
             Cs = 3 if dmll.rgb_scale else self.blueprint.net.config_ms.q.C
             record = records[k] if k < n_decoded else (Cs, 2 * hw[0], 2 * hw[1])
             H, W = record[1:3]
+            if finest is not None and scale == 0:
+                return finest(k, dmll, record, hw, bn, F)
             if not uniform:
                 Kp = self._check_header(scale, dmll, record, hw)
                 P, F = self._get_P(scale, n_pred, bn, F, (B, H, W, Kp))
@@ -693,6 +697,82 @@ class Bitcoding(object):
         framing = container.ParsedFraming(framing.padding, framing.scales[:records], framing.offset[:records], framing.nbytes[:records])
         streams = upload._upload_streams([f[:int(e)] for f, e in zip(files, ends)], framing)
         return self._walk_records(recs, framing, banded, streams, total - 1, records, None).to(out_dtype), framing.padding
+
+    def decode_region(self, files, box, out_dtype=torch.uint8, verify=True):
+        """The pixels of a BOX of B files of equally padded images, banded or legacy, without decoding the rest of their finest record
+        -> ((B, 3, y1 - y0, x1 - x0) out_dtype on the GPU, region.RegionInfo).
+        box: (y0, y1) or (y0, y1, x0, x1) in the coordinates of the UNPADDED image (frame row = top padding + y); the files must share one
+        padding tuple; ValueError for an empty box or one that leaves the image.
+        The coarser records (5 % of the bytes, a quarter of the convolution work) are decoded whole, as _walk_records decodes them.  Of the
+        finest record only the bands that hold a pixel of the box rows are range-decoded (region.region_plan; the last of them stops at the
+        box's last row), as ONE ops.decode_rgb_entries call over the B (j1 - j0) band entries, and the scale's convolutions run on the rows
+        those symbols need plus the halo -- its decoder stage, at half resolution, on an apron of 192 rows more beyond every cut edge, which
+        keeps the last bits of P (MultiscaleNetwork.get_P_rows, region.apron_rows): a full-frame P is never built, and in a frame of a few
+        hundred rows the decoder stage is the whole frame.  Columns are cropped at the end.  A
+        LEGACY file is one band: its one entry per image is pixels [0, y1 W) -- the rows below the box are saved, the rows above are not.
+        Every file still crosses PCIe whole (the banded framing interleaves length fields and payloads).
+        SEALED files: generation and model are checked as decode_batch checks them (verify=True), before anything is enqueued; the frame CRC
+        covers the whole frame and is NOT checked -- the info says so.  L3C only: the RGB baselines raise NotImplementedError."""
+        net = self.blueprint.net
+        if net.config_ms.rgb_bicubic_baseline:
+            raise NotImplementedError('decode_region: the RGB baselines are not windowed (every scale of theirs is an RGB scale)')
+        if not files:
+            raise ValueError('decode_region: no files')
+        split = [container.split_seal(f, view=True) for f in files]
+        files, seals = [b for b, _ in split], [s for _, s in split]
+        sealed = sum(s is not None for s in seals)
+        check = bool(verify and sealed)
+        if check:
+            container.check_seals(seals, self.generation(), self.model_id)
+        records, framing, banded = container.parse_batch(files)
+        n_pred = self._n_predicted(len(records))
+        self._check_coarsest(records[0], banded, int(framing.nbytes[0].max()))
+        Hf, Wf = records[-1][1:3]
+        rows, cols = region.parse_box(box, region.shared_padding(framing.padding), (Hf, Wf))
+        B = len(files)
+        streams = upload._upload_streams(files, framing)
+        K = net.config_ms.prob.K
+        found = {}
+
+        def finest(k, dmll, record, hw, bn, F):
+            Kp = self._check_header(0, dmll, record, hw)
+            C, H, W = record[:3]
+            L = record[3] if banded else H * W
+            n = n_bands(H * W, L)
+            plan = region.region_plan(H, W, L, rows, region.halo_rows(net.config_ms))
+            c0, c1 = plan.conv_rows
+            P = net.get_P_rows(0, bn, F, plan.conv_rows)
+            if tuple(P.shape) != (B, c1 - c0, W, Kp):
+                raise ValueError('invalid file: the network predicts {} on rows {}, the file says {}'.format(
+                    tuple(P.shape), plan.conv_rows, (B, c1 - c0, W, Kp)))
+            j0, j1 = plan.bands
+            buf, _, _ = streams.scale(k)                                       # (the finest record's streams are staged and uploaded HERE)
+            o_h, l_h = streams.scale_host_channel_image_band(k, C, B)         # (C, B n): an image's bands adjacent
+            pick = (np.arange(B)[:, None] * n + np.arange(j0, j1)[None, :]).reshape(-1)
+            o_h, l_h = o_h[:, pick], l_h[:, pick]
+            pixbase, hw_e, pix0, length = region.entry_table(plan, B)
+            # chunks per entry: a banded file's rule (RGB_BAND_CHUNKS, 64 symbols per chunk at least); the one long entry of a legacy file is
+            # chunked as its whole-image decode chunks a channel
+            chunks = (max(1, min(self.RGB_BAND_CHUNKS, int(length.min()) // 64)) if banded else
+                      max(1, min(self.RGB_CHUNKS_FEW, int(length.min()) // 4096)))
+            sym = torch.zeros(B, C, c1 - c0, W, dtype=torch.int16, device='cuda')
+            ops.decode_rgb_entries(P.view(-1, Kp), self._targets(dmll), sym.view(-1), buf, o_h, l_h, pixbase, hw_e, pix0, length, chunks, K,
+                                   *self._rgb_schedule(B * (j1 - j0), None))             # (everything is enqueued when it returns)
+            found.update(plan=plan, n=n, streams_used=int(l_h.size), bytes_used=int(l_h.sum()))
+            return sym
+
+        sym = self._walk_records(records, framing, banded, streams, n_pred, len(records), None, finest)
+        plan = found['plan']
+        c0 = plan.conv_rows[0]
+        out = sym[:, :, rows[0] - c0:rows[1] - c0, cols[0]:cols[1]].to(out_dtype)
+        left, _, top, _ = framing.padding[0]
+        info = region.RegionInfo(box=(rows[0] - top, rows[1] - top, cols[0] - left, cols[1] - left), bands=plan.bands, n_bands=found['n'],
+                                 sym_rows=plan.sym_rows, conv_rows=plan.conv_rows, valid_rows=plan.valid_rows,
+                                 decoder_rows=region.decoder_rows(Hf, plan.conv_rows, region.apron_rows(net.config_ms)), frame_rows=Hf,
+                                 streams_used=found['streams_used'], streams_total=int(framing.nbytes[-1].size),
+                                 bytes_used=found['bytes_used'], bytes_total=int(framing.nbytes[-1].sum()), sealed=sealed,
+                                 verified=('generation', 'model') if check else (), pixel_crc_checked=False)
+        return out, info
 
     def _scale_symbols_of(self, banded):
         """The decoder of one scale record of a batch, by the files' format (the walk and the set decoder's coarsest scale)."""
@@ -958,9 +1038,16 @@ class Bitcoding(object):
                 parts[i] = pad.undo_pad(o, *padding[k]) if any(padding[k]) else o
         return parts
 
-    def decode(self, pin, _recurse_part=True, verify=True):
+    def decode(self, pin, _recurse_part=True, verify=True, region=None):
         """-> decoded image, 1CHW long (on the GPU).  A sealed file (and every sealed part file) is verified as decode_batch verifies it;
-        verify=False strips the seal and checks nothing."""
+        verify=False strips the seal and checks nothing.
+        region: a box (y0, y1) or (y0, y1, x0, x1) of the image -> (its pixels, 1CHW long, region.RegionInfo): decode_region on the one
+        file; an auto-cropped image (.partN files) raises NotImplementedError."""
+        if region is not None:
+            if part_suffix_helper.contains_part_suffix(pin):
+                raise NotImplementedError('region decode of an auto-cropped image: its .partN files are images of their own, a box would have '
+                                          'to be mapped onto every part ({})'.format(pin))
+            return self.decode_region([self._read_file(pin)], region, out_dtype=torch.int64, verify=verify)
         if self.file_writer is not None:
             self.file_writer.wait(pin)                 # (a part suffix is resolved below: every part is waited for when read)
         if _recurse_part and part_suffix_helper.contains_part_suffix(pin):

@@ -316,6 +316,52 @@ class MultiscaleNetwork(nn.Module):
         P = self._prob(F, net, pk)
         return P.permute(0, 3, 1, 2), F.permute(0, 3, 1, 2)
 
+    def _check_rows_dispatch(self, H, W, pk):
+        """The windowed step is only bit-identical to get_P where every layer of scale 0 runs, on the FULL H x W frame, the kernel it runs
+        on a row window: ops.conv also picks by tensor size (an image of 2 GB or more leaves the Winograd kernel for the implicit GEMM,
+        which sums in another order), and a window is smaller.  NotImplementedError where any layer would fall outside the Winograd /
+        pointwise kernels at full size."""
+        d, pr, Cf = pk['dec'][0], pk['prob'][0], self.config_ms.Cf
+        half = [c for blk in d['blocks'] for c in blk] + [d['tail'], d['up']]
+        for layers, h, w in ((half, H // 2, W // 2), (pr['atrous'], H, W)):
+            for layer in layers:
+                if layer.packed_wino4 is None or layer.Cout % 4 != 0 or h * w * Cf * 4 >= 0x7ffffff0:
+                    raise NotImplementedError('region decode: a 3x3 layer of scale 0 leaves the Winograd kernel on the full {}x{} frame; '
+                                              'a row window would not reproduce its bits'.format(H, W))
+        if d['up'].Cout != 256 or pr['lin'].packed_pw is None:
+            raise NotImplementedError('region decode: the pixel-shuffle tail or the 1x1 classifier of scale 0 has no Winograd / pointwise form')
+
+    def get_P_rows(self, scale, bn_q, dec_F_prev, conv_rows):
+        """get_P of scale 0 on a ROW WINDOW: P of full-resolution rows [c0, c1) = conv_rows of the frame, pixel-major (B, c1 - c0, W, Kp),
+        from bn_q (B, C, H/2, W/2) and dec_F_prev (logical NCHW, as get_P hands it out), with get_P's own steps (_decoder, _prob) on row
+        slices; for one image every slice is a view.  Two stages, because P must be the frame's BIT FOR BIT where a file is decoded with it:
+          decoder     on half-resolution rows of conv_rows plus the APRON (bitcoding.region.apron_rows / decoder_rows) beyond every cut
+                      edge: a Winograd tile's rounding depends on all six of its input rows, so a cut edge changes last bits four rows
+                      deeper per layer -- after the decoder's 18 layers its features are the frame's on rows [c0, c1) exactly;
+          classifier  on those rows [c0, c1) of the features.
+        P is then the frame's, bit for bit, `region.halo_rows` rows inside every cut edge of conv_rows (none at an image border), provided
+        c0 is a multiple of region.GRANULE and c1 another one or the frame's end (region_plan): every kept output keeps its tile and its
+        place in it.  L3C only."""
+        from ..bitcoding import region
+        if self._rgb:
+            raise NotImplementedError('get_P_rows: the RGB baselines are not windowed')
+        if scale != 0:
+            raise NotImplementedError('get_P_rows: only scale 0 is windowed, got scale {}'.format(scale))
+        _lib.require_gpu()
+        pk = self._prepare()
+        B, _, H2, W2 = bn_q.shape
+        c0, c1 = (int(v) for v in conv_rows)
+        if not (0 <= c0 < c1 <= 2 * H2 and c0 % 2 == 0 and c1 % 2 == 0):
+            raise ValueError('conv_rows {} must be even rows inside the {} frame rows'.format((c0, c1), 2 * H2))
+        if dec_F_prev is None or tuple(dec_F_prev.shape[2:]) != (H2, W2):
+            raise ValueError('get_P_rows: dec_F_prev must be the coarser decoder\'s {}x{} features'.format(H2, W2))
+        self._check_rows_dispatch(2 * H2, 2 * W2, pk)
+        a0, a1 = region.decoder_rows(2 * H2, (c0, c1), region.apron_rows(self.config_ms))
+        bn = bn_q.to('cuda', torch.float32)[:, :, a0 // 2:a1 // 2].contiguous()
+        fuse = dec_F_prev.permute(0, 2, 3, 1)[:, a0 // 2:a1 // 2].contiguous()      # (pixel-major storage: contiguous as it is for B == 1)
+        F = self._decoder(bn, fuse, 0, pk)[:, c0 - a0:c1 - a0].contiguous()         # (likewise)
+        return self._prob(F, 0, pk)
+
     @staticmethod
     def _as_device_image(x):
         if x.dim() != 4 or x.shape[1] != 3:

@@ -514,7 +514,8 @@ class MultiscaleTester(object):
                                                                                  '; sealed' if self.bc.seal else ''))
         return bpsp
 
-    def decode(self, pin, png_out_p):
+    def decode(self, pin, png_out_p, region=None):
+        """region: a box (y0, y1) or (y0, y1, x0, x1) of the image -- only that box is decoded (Bitcoding.decode_region) and written."""
         pout_dir = os.path.dirname(os.path.abspath(png_out_p))
         if not os.path.isdir(pout_dir):
             raise DecodeError('png_out_p directory ({}) does not exists!'.format(pout_dir))
@@ -522,6 +523,17 @@ class MultiscaleTester(object):
             raise DecodeError('png_out_p must end in .png, got {}'.format(png_out_p))
         from ..bitcoding import container
         verify = not getattr(self.flags, 'no_verify', False)
+        if region is not None:
+            try:
+                decoded, info = self.bc.decode(pin, verify=verify, region=region)
+            except container.SealError as e:
+                raise DecodeError('seal: {}'.format(e))
+            except (ValueError, NotImplementedError) as e:
+                raise DecodeError(str(e))
+            self._write_img(decoded, png_out_p)
+            print(info.line())
+            print('---\nDecoded region: {}'.format(png_out_p))
+            return
         try:
             with open(pin, 'rb') as fin:
                 _, seal = container.split_seal(fin.read())

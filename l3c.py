@@ -2,7 +2,7 @@
 """Encoder / decoder CLI -- same arguments as the reference's src/l3c.py:74-125:
 
     python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] enc IMG_P OUT_P [--overwrite]
-    python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] dec IMG_P OUT_P_PNG
+    python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] dec [--region Y0:Y1[,X0:X1]] IMG_P OUT_P_PNG
     python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] preview IMG_P OUT_P_PNG [--records R] [--bytes N]
 
 Everything runs on the MI355X path; `--device cpu` is refused (there is no CPU back end in this build).
@@ -37,6 +37,17 @@ def parse_device_flag(flag):
     print('*** Using the HIP back end on', torch.cuda.get_device_name(0))
 
 
+def parse_region(text):
+    """'Y0:Y1' or 'Y0:Y1,X0:X1' -> (y0, y1) or (y0, y1, x0, x1): rows [Y0, Y1) and columns [X0, X1) of the image."""
+    try:
+        parts = [tuple(int(v) for v in part.split(':')) for part in text.split(',')]
+    except ValueError:
+        parts = []
+    if len(parts) not in (1, 2) or any(len(part) != 2 for part in parts):
+        raise argparse.ArgumentTypeError('expected Y0:Y1 or Y0:Y1,X0:X1, got {!r}'.format(text))
+    return tuple(v for part in parts for v in part)
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description='Encoder/Decoder for L3C')
     p.add_argument('log_dir', help='Directory of experiments.')
@@ -60,6 +71,9 @@ def main(argv=None):
     dec.add_argument('img_p')
     dec.add_argument('out_p_png')
     dec.add_argument('--no-verify', dest='no_verify', action='store_true', help='do not check the seal of a sealed file')
+    dec.add_argument('--region', type=parse_region, default=None, metavar='Y0:Y1[,X0:X1]',
+                     help='decode only rows [Y0, Y1) (and columns [X0, X1)) of the image: of a banded file only the bands and rows that '
+                          'box needs are decoded; OUT_P_PNG receives the box')
     pre = mode.add_parser('preview', help='Picture from the coarse scale records of a file: preview IMG_P OUT_P_PNG [--records R] [--bytes N]')
     pre.add_argument('img_p')
     pre.add_argument('out_p_png')
@@ -86,7 +100,7 @@ def main(argv=None):
             return 1
     else:
         try:
-            tester.decode(flags.img_p, flags.out_p_png)
+            tester.decode(flags.img_p, flags.out_p_png, flags.region)
         except DecodeError as e:
             print('*** DecodeError:', e)
             return 1
