@@ -1032,6 +1032,33 @@ int l3c_u8_crc32(const uint8_t *data, int64_t n_items, int64_t item_bytes, int64
 int l3c_u8_crc32_tile(int *thread_bytes_out, int *block_bytes_out);
 
 /*
+ * l3c_u8_crc32_spans: crc_out[i] = zlib CRC-32 of bytes [spans[i].offset, spans[i].offset + spans[i].bytes) of `data`, for n_spans spans
+ * of DIFFERENT lengths in at most three launches, however many spans: the frames of a ragged group of differently sized images, which lie
+ * in one buffer.  Integer only; the result does not depend on the launch geometry; no atomics; no allocation, no host sync.
+ * A tile of a span is folded by the tile code of l3c_u8_crc32 (the same rows, tables and loads), so a full tile costs what it costs there.
+ * What differs per span is found on the device: the first launch turns `spans` into a prefix of tile counts (one block) and, a thread per
+ * span and constant, into the three words that depend on a span's length -- x^(8 * bytes of its last tile's rows), x^(-8 * zero fill) and
+ * Z(bytes), which l3c_u8_crc32 gets as kernel arguments -- in the workspace; a block of the second launch finds its tile's span by
+ * bisecting that prefix; the third, a wavefront per span, combines a span's tiles as l3c_u8_crc32's second launch does.  A call whose spans
+ * are all empty skips the second.
+ *   spans_host    the table on the host, validated before anything is launched (an error names the span)
+ *   spans         the caller's device copy of the same table, 8-byte aligned
+ *   span          offset % 4 == 0 and >= 0, bytes >= 0 (0: CRC 0), offset + bytes <= data_bytes; spans may come in any order, overlap and
+ *                 leave gaps; the tiles of all spans together (ceil(bytes / block_bytes) each) stay below 2^40
+ *   data          4-byte aligned (16-byte aligned data and offsets: the full load rate)
+ *   crc_out       uint32 [n_spans], 4-byte aligned
+ *   workspace     l3c_u8_crc32_spans_workspace_bytes(spans_host, n_spans) bytes, 16-byte aligned; garbage on entry
+ * Nothing at or behind offset + bytes of a span is read into a result or read at all: a span may end with the buffer.
+ */
+typedef struct l3c_u8_span {
+    int64_t offset;
+    int64_t bytes;
+} l3c_u8_span;     /* bytes [offset, offset + bytes) of `data` */
+int64_t l3c_u8_crc32_spans_workspace_bytes(const l3c_u8_span *spans_host, int64_t n_spans);
+int l3c_u8_crc32_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, int64_t n_spans,
+                       uint32_t *crc_out, void *workspace, int64_t workspace_bytes, l3c_stream_t stream);
+
+/*
  * l3c_seal_append: this build's seal behind every file of an encode, on the device: 24 bytes at files + b * file_stride + file_bytes[b],
  * file_bytes[b] += 24.  One thread per file, byte stores.  A sealed encode is three calls on one stream with no host round trip:
  * l3c_encode_batch (or _banded), l3c_u8_crc32 on desc.img (n_items = B, item_bytes = item_stride = 3 H W), l3c_seal_append; the body of the

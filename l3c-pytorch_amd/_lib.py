@@ -151,6 +151,11 @@ class U8Image(ctypes.Structure):
                 ('w', ctypes.c_int32), ('top', ctypes.c_int32), ('left', ctypes.c_int32)]
 
 
+class U8Span(ctypes.Structure):
+    """l3c_u8_span (include/l3c_hip.h): bytes [offset, offset + bytes) of a buffer."""
+    _fields_ = [('offset', c_i64), ('bytes', c_i64)]
+
+
 class EncodeImagesDesc(ctypes.Structure):
     """l3c_encode_images_desc (include/l3c_hip.h)."""
     _fields_ = [('model_host', ctypes.POINTER(CodecModel)), ('src', c_vp), ('src_bytes', c_i64), ('images_host', c_vp), ('images', c_vp),
@@ -281,6 +286,8 @@ PROTOTYPES = {
     'l3c_u8_crc32_workspace_bytes': (c_i64, [c_i64, c_i64]),
     'l3c_u8_crc32': (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]),
     'l3c_u8_crc32_tile': (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'l3c_u8_crc32_spans_workspace_bytes': (c_i64, [c_vp, c_i64]),
+    'l3c_u8_crc32_spans': (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     'l3c_seal_append': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.c_uint64, c_i64, c_vp]),
 }
 

@@ -839,7 +839,7 @@ class Bitcoding(object):
             self._set_decoder = SetDecoder(self)
         return self._set_decoder
 
-    def decode_many(self, batches, on_batch=None, lanes=None, chain_cus=0, out_dtype=torch.int64, ragged=None, banded=False):
+    def decode_many(self, batches, on_batch=None, lanes=None, chain_cus=0, out_dtype=torch.int64, ragged=None, banded=False, sealed=False):
         """batches: list of lists of `.l3c` byte strings; the files of ONE entry are equally sized (padded) images (a forward pass of
         `encode_many`), entries may differ in shape.  -> list, in the order given, of ((B_i,3,H_i,W_i) int64 on the GPU, padding tuples),
         or None per entry when `on_batch(index, pixels, padding)` consumes the results as they are enqueued (called under the stream
@@ -857,8 +857,18 @@ class Bitcoding(object):
         lane; with the chains on 64 CUs of their own 125-147 -- the round-5 verdict's bar for keeping that overlap was 180.
         banded=True: BANDED files (Bitcoding(bands=K)) are accepted too -- an entry is then all banded (one band length per scale: what one
         `encode_many` pass writes) or all legacy.  Ragged groups are format-pure; in a banded group every BAND of every image is a ragged
-        entry of its own (l3c_decode_rgb_entries, ops.decode_z_entries), so the group's chains are a band long, not an image."""
-        return self.set_decoder.decode_many(batches, on_batch, lanes, chain_cus, out_dtype, ragged, banded)
+        entry of its own (l3c_decode_rgb_entries, ops.decode_z_entries), so the group's chains are a band long, not an image.
+        sealed=True: SEALED files (Bitcoding(seal=True)) are accepted too, alone or mixed with unsealed ones, which are decoded and not
+        verified; without it a sealed file is refused.  Before anything is enqueued every seal's generation and model id are checked
+        (container.SealError, reason 'generation' / 'model', .index = (entry, file)).  The frames are hashed on the device -- a ragged
+        group's in ONE call over the group's pixel buffer (ops.u8_crc32_spans, a span per image), a lane's batch with ops.u8_crc32 on its
+        lane -- and the words stay there: no group or lane waits for the host.  At the end of the call, when the caller's stream has waited
+        for every lane and group, ONE D2H brings all words back and they are compared with the seals: SealError('pixels') with .index the
+        first failing (entry, file) in call order and .failed all of them; nothing is returned.  (One lane, or batches of 64 images and
+        more: decode_batch verifies each batch as it is decoded, and the error is raised there.)  set_decoder.frame_crcs then holds the
+        words.  With `on_batch`, the pixels of a batch are handed over BEFORE the call has verified them -- the call still raises at its
+        end: a consumer that must not act on unverified pixels waits for the call to return."""
+        return self.set_decoder.decode_many(batches, on_batch, lanes, chain_cus, out_dtype, ragged, banded, sealed)
 
     @classmethod
     def ragged_rgb_chunk_plan(cls, hws, rgb_window):

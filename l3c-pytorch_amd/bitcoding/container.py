@@ -353,11 +353,14 @@ class Seal(object):
 class SealError(ValueError):
     """A sealed file that this decoder must not, or did not, decode to the pixels that were encoded.  reason: 'generation' (written by
     another bitstream generation), 'model' (by another checkpoint) -- both raised before anything is decoded --, 'pixels' (the decoded
-    frame does not hash to the seal's CRC: a damaged payload, or a checkpoint the seal does not state).  index: the file's place in the call."""
+    frame does not hash to the seal's CRC: a damaged payload, or a checkpoint the seal does not state).  index: the file's place in the call
+    (the set readers: (entry, file), or the caller's key); failed: the places of ALL files known to have failed for that reason when the
+    error was raised, in call order -- `index` is the first of them."""
 
-    def __init__(self, reason, index, message):
+    def __init__(self, reason, index, message, failed=None):
         ValueError.__init__(self, message)
         self.reason, self.index = reason, index
+        self.failed = [index] if failed is None else list(failed)
 
 
 def _padding_bytes(body):
@@ -415,8 +418,9 @@ def check_seals(seals, generation, model_id):
 
 
 def check_frame_crcs(seals, crcs):
-    """After the decode: crcs[i] (the CRC-32 of decoded frame i) against seal i."""
-    for i, s in enumerate(seals):
-        if s is not None and (int(crcs[i]) & 0xffffffff) != s.frame_crc:
-            raise SealError('pixels', i, 'file {} decoded to pixels whose CRC-32 {:08x} is not the sealed {:08x}: damaged payload, or not the '
-                            'checkpoint that wrote it'.format(i, int(crcs[i]) & 0xffffffff, s.frame_crc))
+    """After the decode: crcs[i] (the CRC-32 of decoded frame i) against seal i.  The error names the first failing file and lists all."""
+    failed = [i for i, s in enumerate(seals) if s is not None and (int(crcs[i]) & 0xffffffff) != s.frame_crc]
+    if failed:
+        i = failed[0]
+        raise SealError('pixels', i, 'file {} decoded to pixels whose CRC-32 {:08x} is not the sealed {:08x}: damaged payload, or not the '
+                        'checkpoint that wrote it'.format(i, int(crcs[i]) & 0xffffffff, seals[i].frame_crc), failed)

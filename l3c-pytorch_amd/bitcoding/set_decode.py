@@ -37,6 +37,8 @@ class SetDecoder(object):
         self._lane_streams, self._lane_key = None, None
         self._rgb_streams = None
         self._alloc_stream = None
+        # sealed=True: {(entry, file): CRC-32 the device computed of that file's decoded frame} of the last call (lane and ragged forms)
+        self.frame_crcs = {}
 
     def _own_streams(self, n, chain_cus, ragged):
         """Creates what is missing of: `n` lane pairs (main stream, side stream); for the ragged form the stream pair of the ragged phases and
@@ -59,11 +61,15 @@ class SetDecoder(object):
             self._rgb_streams = (torch.cuda.Stream(), torch.cuda.Stream())
             self._alloc_stream = torch.cuda.Stream()
 
-    def decode_many(self, batches, on_batch, lanes, chain_cus, out_dtype, ragged, banded):
+    def decode_many(self, batches, on_batch, lanes, chain_cus, out_dtype, ragged, banded, sealed=False):
         """Bitcoding.decode_many (the arguments and the result are described there)."""
-        if any(container.is_sealed(f) for files in batches for f in files):
-            raise ValueError('decode_many does not read sealed .l3c files: container.split_seal gives the body and the seal to check, '
-                             'or decode_batch / decode verify them')
+        seals, self.frame_crcs = None, {}
+        if sealed:
+            sealed_files = batches
+            batches, seals = self._split_seals(sealed_files)
+        elif any(container.is_sealed(f) for files in batches for f in files):
+            raise ValueError('decode_many does not read sealed .l3c files unless it is told to (sealed=True verifies them): '
+                             'container.split_seal gives the body and the seal to check, or decode_batch / decode verify them')
         fmt = [any(container.is_banded(f) for f in files) for files in batches]
         if any(fmt) and not banded:
             raise ValueError('decode_many reads legacy .l3c files only: a banded file (L3CB format) goes through decode_batch / decode')
@@ -72,8 +78,11 @@ class SetDecoder(object):
             n = 1
         result = [None] * len(batches)
         if n <= 1 or len(batches) <= 1:
-            for i, files in enumerate(batches):
-                pixels, padding = self.bc.decode_batch(files, out_dtype)
+            for i, files in enumerate(sealed_files if sealed else batches):
+                try:
+                    pixels, padding = self.bc.decode_batch(files, out_dtype)        # verifies the sealed files of the batch itself
+                except container.SealError as e:
+                    raise container.SealError(e.reason, (i, e.index), 'entry {}: {}'.format(i, e), [(i, k) for k in e.failed])
                 if on_batch is not None:
                     on_batch(i, pixels, padding)
                 else:
@@ -88,6 +97,7 @@ class SetDecoder(object):
         for main, _ in self._lane_streams:
             main.wait_event(start)
         done = []
+        words = []                                     # sealed: (CRC words on the device, [(entry, file)] they belong to) per batch or group
 
         def finish(i, pixels, padding, stream):
             if on_batch is not None:
@@ -99,19 +109,53 @@ class SetDecoder(object):
         if not use_ragged:
             for i, files in enumerate(batches):
                 main, side = self._lane_streams[i % n]
+                check = seals is not None and any(s is not None for s in seals[i])
                 with torch.cuda.stream(main):
-                    pixels, padding = self.bc._decode_batch(files, out_dtype, side)
+                    pixels, padding = self.bc._decode_batch(files, torch.uint8 if check else out_dtype, side)
+                    if check:
+                        B = pixels.shape[0]
+                        words.append((ops.u8_crc32(pixels.view(-1), B, pixels.numel() // B), [(i, k) for k in range(B)]))
+                        pixels = pixels.to(out_dtype)
                     finish(i, pixels, padding, main)
                     done.append(main.record_event())
         else:
             rgb_main = self._rgb_streams[0]
             rgb_main.wait_event(start)
             for group, b in self._plan_groups(batches, fmt):
-                self.decode_group(group, out_dtype, finish, banded=b)
+                check = seals is not None and any(s is not None for i, _ in group for s in seals[i])
+                self.decode_group(group, out_dtype, finish, banded=b, words=words if check else None)
             done.append(rgb_main.record_event())
         for ev in done:
             outer.wait_event(ev)
+        if words:
+            self._check_words(words, seals, outer)
         return result
+
+    def _split_seals(self, batches):
+        """sealed=True, before anything is enqueued: every file split into body and seal (container.split_seal: a view, not a copy), every
+        seal's generation and model id checked (container.check_seals over all files of the call; SealError with index (entry, file)).
+        -> (the bodies, the seals) in the shape of `batches`."""
+        split = [[container.split_seal(f, view=True) for f in files] for files in batches]
+        where = [(i, k) for i, files in enumerate(batches) for k in range(len(files))]
+        try:
+            container.check_seals([s for fs in split for _, s in fs], self.bc.generation(), self.bc.model_id)
+        except container.SealError as e:
+            raise container.SealError(e.reason, where[e.index], 'entry {} file {}: {}'.format(*where[e.index], e))
+        return [[b for b, _ in fs] for fs in split], [[s for _, s in fs] for fs in split]
+
+    def _check_words(self, words, seals, outer):
+        """sealed=True, at the end of the call: ONE D2H of every CRC word the lanes and groups left on the device (`outer` has waited for all
+        of them), compared with the seals; SealError('pixels') naming the first failing file in call order, .failed listing all."""
+        for t, _ in words:
+            t.record_stream(outer)
+        host = torch.cat([t for t, _ in words]).cpu().numpy().view(np.uint32).tolist()
+        self.frame_crcs = dict(zip([key for _, keys in words for key in keys], host))
+        failed = sorted(key for key, w in self.frame_crcs.items() if seals[key[0]][key[1]] is not None and seals[key[0]][key[1]].frame_crc != w)
+        if failed:
+            i, k = failed[0]
+            raise container.SealError('pixels', (i, k), 'entry {} file {} decoded to pixels whose CRC-32 {:08x} is not the sealed {:08x}: damaged '
+                                      'payload, or not the checkpoint that wrote it ({} of the call\'s files failed)'.format(
+                                          i, k, self.frame_crcs[i, k], seals[i][k].frame_crc, len(failed)), failed)
 
     def _plan_groups(self, batches, fmt):
         """The ragged groups of a set, in decoding order -> (group: [(index, files)], banded) each; fmt[i]: entry i holds banded files.
@@ -139,7 +183,7 @@ class SetDecoder(object):
 
     # ---- one ragged group ---------------------------------------------------------------------------------------------------------
 
-    def decode_group(self, group, out_dtype, finish, banded=False):
+    def decode_group(self, group, out_dtype, finish, banded=False, words=None):
         """One group of decode_many's ragged form, in PHASES over all its entries (batches of different shapes):
             lanes:   upload, the coarsest scale (uniform prior), P of the next scale (get_P per shape)      -- small launches, a lane per entry
             ragged:  that scale's symbols of ALL images in lock step (bottleneck scale: one table launch + one decoder launch for every
@@ -149,7 +193,11 @@ class SetDecoder(object):
         per image; what is left per image are the decoder-side convolutions of its shape.
         banded: the group's files are BANDED (an entry's files share the band length of every scale).  The phases are the same; a ragged
         phase then runs over every band of every image as an entry of its own -- pixels [j L, j L + len_j) of its image -- and the chains
-        paid per group are a band long.  A legacy group is the same with one entry per image."""
+        paid per group are a band long.  A legacy group is the same with one entry per image.
+        words (decode_many's sealed=True, a group with sealed files): behind the last scale the group's symbols become pixels in ONE launch
+        (ops.sym_to_u8 over the whole ragged buffer) and ONE ops.u8_crc32_spans hashes every image's frame -- image b of entry g is bytes
+        [3 pixbase[g] + b 3 H W, + 3 H W) -- on the stream of the ragged phases; (the words on the device, their (entry, file)) is appended
+        to `words`, nothing waits for them here.  uint8 results are then views of that pixel buffer."""
         st, n_pred = self._parse_group(group, banded)
         plan = list(self.bc.iter_scale_dmll(n_pred))          # record k -> (scale, dmll, uniform), coarse -> fine
         self._decode_coarsest(st, plan[0], banded)
@@ -164,8 +212,22 @@ class SetDecoder(object):
             del P_rag          # (its block goes back to the allocator as soon as the streams that touched it have passed this point: a group's three P buffers never pile up)
         rgb_main = self._rgb_streams[0]
         with torch.cuda.stream(rgb_main):
-            for e in st:
-                finish(e.index, e.sym.to(out_dtype), e.parsed.padding, rgb_main)
+            if words is not None:
+                pix = ops.sym_to_u8(sym_rag)
+                offs, lens, keys = [], [], []
+                for g, e in enumerate(st):
+                    n = 3 * e.hw[0] * e.hw[1]
+                    offs += [3 * pixbase[g] + b * n for b in range(e.B)]
+                    lens += [n] * e.B
+                    keys += [(e.index, b) for b in range(e.B)]
+                words.append((ops.u8_crc32_spans(pix, offs, lens), keys))
+            for g, e in enumerate(st):
+                if words is not None and out_dtype == torch.uint8:
+                    H, W = e.hw
+                    out = pix[3 * pixbase[g]:3 * (pixbase[g] + e.B * H * W)].view(e.B, 3, H, W)
+                else:
+                    out = e.sym.to(out_dtype)
+                finish(e.index, out, e.parsed.padding, rgb_main)
         del keep
 
     def _parse_group(self, group, banded):

@@ -20,41 +20,19 @@
 // Second launch: a wavefront per item.  Lane l runs Horner over its share of the full tiles with x^(8 * TILE), weighs it with the tiles behind
 // it, the wave XORs; lane 0 adds the last tile, multiplies by x^(-8 fill) to undo the zero fill, and XORs Z(item_bytes).
 // The constants that depend on item_bytes come from the host as kernel arguments; all others are compile-time tables.
+//
+// l3c_u8_crc32_spans: the same for runs of DIFFERENT lengths anywhere in one buffer (a ragged group's frames), in three launches however many
+// runs.  The tile code is shared (fold_tile); what the uniform form knows from its arguments -- which run a tile belongs to, the three
+// length-dependent constants -- a first launch computes on the device from the span table (crc_spans.h holds the arithmetic and the
+// table's validator, HIP-free), and the tile launch bisects a prefix of tile counts.
 #include "l3c_common.h"
+#include "crc_spans.h"
 #include "seal.h"
 
 namespace {
 
-constexpr uint32_t POLY = 0xEDB88320u;
-constexpr uint32_t ONE = 0x80000000u, X1 = 0x40000000u, X_INV = 0xDB710641u;
-constexpr int THREADS = 256, ROW_BYTES = THREADS * 16, ROWS = 32, TILE_BYTES = ROWS * ROW_BYTES, THREAD_BYTES = ROWS * 16;
+using namespace l3c_crc;      // crc_spans.h: mulmod, powmod, the tile geometry, the constants of a run's length
 constexpr int MAX_GRID = 4096, DEPTH = 8;
-
-// a b mod P (zlib's multmodp)
-__host__ __device__ constexpr uint32_t mulmod(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 31; i >= 0; --i) {
-        p ^= b & (0u - ((a >> i) & 1u));
-        b = (b >> 1) ^ (POLY & (0u - (b & 1u)));
-    }
-    return p;
-}
-
-// base^e mod P
-__host__ __device__ constexpr uint32_t powmod(uint32_t base, uint64_t e) {
-    uint32_t r = ONE;
-    while (e) {
-        if (e & 1) r = mulmod(r, base);
-        base = mulmod(base, base);
-        e >>= 1;
-    }
-    return r;
-}
-
-constexpr uint32_t X8 = powmod(X1, 8), X8_INV = powmod(X_INV, 8);
-constexpr uint32_t K_ROW = powmod(X8, ROW_BYTES), K_TILE = powmod(X8, TILE_BYTES);
-static_assert(mulmod(X1, X_INV) == ONE && mulmod(X8, X8_INV) == ONE, "x^-1 mod P");
-static_assert(powmod(X1, 32) == POLY, "x^32 mod P is the polynomial's low part");
 
 // [0]: MULK, [1]: MUL32 -- entry 16 k + n is (n << 4 k) times the constant
 struct NibbleTables {
@@ -150,46 +128,113 @@ __device__ __forceinline__ void fold_rows(const uint32_t *tab, uint32_t (&a)[4],
     }
 }
 
+// What the tile launches of l3c_u8_crc32 and l3c_u8_crc32_spans share.  Tables: the two nibble tables into LDS (a barrier follows).
+__device__ __forceinline__ void stage_tables(uint32_t *lds, int t) {
+    for (int i = 0; i < 32; ++i) {
+        const int idx = i * THREADS + t;
+        lds[idx] = (&g_tables.v[0][0])[idx >> 5];
+    }
+}
+
+// Tile `tile` of the run of item_bytes bytes at `base`, filled up with zero bytes to whole rows: the block's 256 threads fold it and thread 0
+// stores its remainder to *out.  Ends with a barrier: wave_xor is free again.
+__device__ __forceinline__ void fold_tile(const uint32_t *mulk, const uint32_t *mul32, uint32_t shift, uint32_t *wave_xor, int t,
+                                          const uint8_t *base, int64_t item_bytes, int64_t tile, uint32_t *out) {
+    const int64_t tile_at = tile * TILE_BYTES;
+    const int64_t left = item_bytes - tile_at;                                          // > 0
+    const int whole = left >= TILE_BYTES ? ROWS : (int)(left / ROW_BYTES);              // rows that lie inside the item: plain loads
+    uint32_t a[4] = {0u, 0u, 0u, 0u};
+    const uint8_t *p = base + tile_at + 16 * t;
+    if (whole == ROWS) {
+        fold_rows<ROWS>(mulk, a, p);
+    } else {                                                                             // an item's last tile
+        int g = 0;
+        for (; g + DEPTH <= whole; g += DEPTH) fold_rows<DEPTH>(mulk, a, p + (int64_t)g * ROW_BYTES);
+        for (; g < whole; ++g) fold_rows<1>(mulk, a, p + (int64_t)g * ROW_BYTES);
+    }
+    if (whole < ROWS && left > (int64_t)whole * ROW_BYTES)                               // the item ends inside this row
+        row_step(mulk, a, load16(base, tile_at + (int64_t)whole * ROW_BYTES + 16 * t, item_bytes));
+    uint32_t v = times(mul32, a[0]);
+    v = times(mul32, v ^ a[1]);
+    v = times(mul32, v ^ a[2]);
+    v = times(mul32, v ^ a[3]);
+    v = mulmod(v, shift);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d, 64);
+    if ((t & 63) == 0) wave_xor[t >> 6] = v;
+    __syncthreads();
+    if (t == 0) *out = wave_xor[0] ^ wave_xor[1] ^ wave_xor[2] ^ wave_xor[3];
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(THREADS) void u8_crc32_tiles_kernel(const uint8_t *__restrict__ data, int64_t item_bytes, int64_t item_stride,
                                                                 int64_t tiles_per_item, int64_t units, uint32_t *__restrict__ partial) {
     __shared__ uint32_t lds[2 * 128 * 32];
     __shared__ uint32_t wave_xor[THREADS / 64];
     const int t = threadIdx.x;
-    for (int i = 0; i < 32; ++i) {
-        const int idx = i * THREADS + t;
-        lds[idx] = (&g_tables.v[0][0])[idx >> 5];
-    }
+    stage_tables(lds, t);
     const uint32_t shift = g_shifts.v[t];
     const uint32_t *mulk = lds + (t & 31), *mul32 = lds + 128 * 32 + (t & 31);
     __syncthreads();
     for (int64_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
         const int64_t item = unit / tiles_per_item, tile = unit - item * tiles_per_item;
-        const uint8_t *base = data + item * item_stride;
-        const int64_t tile_at = tile * TILE_BYTES;
-        const int64_t left = item_bytes - tile_at;                                          // > 0
-        const int whole = left >= TILE_BYTES ? ROWS : (int)(left / ROW_BYTES);              // rows that lie inside the item: plain loads
-        uint32_t a[4] = {0u, 0u, 0u, 0u};
-        const uint8_t *p = base + tile_at + 16 * t;
-        if (whole == ROWS) {
-            fold_rows<ROWS>(mulk, a, p);
-        } else {                                                                             // an item's last tile
-            int g = 0;
-            for (; g + DEPTH <= whole; g += DEPTH) fold_rows<DEPTH>(mulk, a, p + (int64_t)g * ROW_BYTES);
-            for (; g < whole; ++g) fold_rows<1>(mulk, a, p + (int64_t)g * ROW_BYTES);
+        fold_tile(mulk, mul32, shift, wave_xor, t, data + item * item_stride, item_bytes, tile, partial + unit);
+    }
+}
+
+// l3c_u8_crc32_spans, first launch.  Block 0: first[k] = tiles of the spans in front of span k, first[n] = all tiles -- every thread sums a
+// contiguous share of the spans, the block scans the 256 sums.  The other blocks: a thread per span and constant, the three words that
+// depend on a span's length (crc_spans.h: span_k_last, span_unfill, span_z), which l3c_u8_crc32 computes on the host.
+constexpr int PREP_THREADS = 256;
+__global__ __launch_bounds__(PREP_THREADS) void u8_crc32_spans_prepare_kernel(const l3c_u8_span *__restrict__ spans, int64_t n,
+                                                                              int64_t *__restrict__ first, uint32_t *__restrict__ consts) {
+    const int t = threadIdx.x;
+    if (blockIdx.x == 0) {
+        __shared__ int64_t sum[PREP_THREADS];
+        const int64_t share = (n + PREP_THREADS - 1) / PREP_THREADS;
+        const int64_t lo = t * share < n ? t * share : n, hi = lo + share < n ? lo + share : n;
+        int64_t mine = 0;
+        for (int64_t k = lo; k < hi; ++k) mine += tiles_of(spans[k].bytes);
+        sum[t] = mine;
+        __syncthreads();
+        for (int d = 1; d < PREP_THREADS; d <<= 1) {
+            const int64_t v = t >= d ? sum[t - d] : 0;
+            __syncthreads();
+            sum[t] += v;
+            __syncthreads();
         }
-        if (whole < ROWS && left > (int64_t)whole * ROW_BYTES)                               // the item ends inside this row
-            row_step(mulk, a, load16(base, tile_at + (int64_t)whole * ROW_BYTES + 16 * t, item_bytes));
-        uint32_t v = times(mul32, a[0]);
-        v = times(mul32, v ^ a[1]);
-        v = times(mul32, v ^ a[2]);
-        v = times(mul32, v ^ a[3]);
-        v = mulmod(v, shift);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d, 64);
-        if ((t & 63) == 0) wave_xor[t >> 6] = v;
-        __syncthreads();
-        if (t == 0) partial[unit] = wave_xor[0] ^ wave_xor[1] ^ wave_xor[2] ^ wave_xor[3];
-        __syncthreads();
+        int64_t at = sum[t] - mine;
+        for (int64_t k = lo; k < hi; ++k) {
+            first[k] = at;
+            at += tiles_of(spans[k].bytes);
+        }
+        if (t == PREP_THREADS - 1) first[n] = sum[t];
+        return;
+    }
+    const int64_t step = (int64_t)(gridDim.x - 1) * PREP_THREADS;
+    for (int64_t i = (int64_t)(blockIdx.x - 1) * PREP_THREADS + t; i < 3 * n; i += step) {      // constant-major: a wavefront runs ONE of the three loops
+        const int c = (int)(i / n);
+        const int64_t k = i - c * n, bytes = spans[k].bytes;
+        consts[4 * k + c] = c == 0 ? span_k_last(bytes) : c == 1 ? span_unfill(bytes) : span_z(bytes);
+    }
+}
+
+// Second launch: u8_crc32_tiles_kernel with the run looked up per tile.  Unit u is tile u - first[k] of the span k with
+// first[k] <= u < first[k + 1] (a span of no tiles is never found); the bisection is uniform over the block.
+__global__ __launch_bounds__(THREADS) void u8_crc32_span_tiles_kernel(const uint8_t *__restrict__ data, const l3c_u8_span *__restrict__ spans,
+                                                                     const int64_t *__restrict__ first, int64_t n_spans, int64_t units,
+                                                                     uint32_t *__restrict__ partial) {
+    __shared__ uint32_t lds[2 * 128 * 32];
+    __shared__ uint32_t wave_xor[THREADS / 64];
+    const int t = threadIdx.x;
+    stage_tables(lds, t);
+    const uint32_t shift = g_shifts.v[t];
+    const uint32_t *mulk = lds + (t & 31), *mul32 = lds + 128 * 32 + (t & 31);
+    __syncthreads();
+    for (int64_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
+        const int64_t k = span_of_unit(first, n_spans, unit);
+        const l3c_u8_span s = spans[k];
+        fold_tile(mulk, mul32, shift, wave_xor, t, data + s.offset, s.bytes, unit - first[k], partial + unit);
     }
 }
 
@@ -211,6 +256,27 @@ __global__ __launch_bounds__(64) void u8_crc32_combine_kernel(const uint32_t *__
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) a ^= __shfl_xor(a, d, 64);
         if (lane == 0) crc_out[item] = mulmod(mulmod(a, k_last) ^ p[full], unfill) ^ z;
+    }
+}
+
+// Third launch: u8_crc32_combine_kernel with a span's tiles and constants read from the workspace.
+__global__ __launch_bounds__(64) void u8_crc32_spans_combine_kernel(const uint32_t *__restrict__ partial, const int64_t *__restrict__ first,
+                                                                    const SpanConsts *__restrict__ consts, int64_t n_spans,
+                                                                    uint32_t *__restrict__ crc_out) {
+    const int lane = threadIdx.x;
+    for (int64_t span = blockIdx.x; span < n_spans; span += gridDim.x) {
+        const int64_t at = first[span], tiles = first[span + 1] - at;
+        const SpanConsts c = consts[span];
+        if (tiles == 0) {
+            if (lane == 0) crc_out[span] = c.z;
+            continue;
+        }
+        const uint32_t *p = partial + at;
+        const int64_t full = tiles - 1;
+        uint32_t a = lane_share(p, full, lane);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) a ^= __shfl_xor(a, d, 64);
+        if (lane == 0) crc_out[span] = finish(a, p[full], c.k_last, c.unfill, c.z);
     }
 }
 
@@ -246,8 +312,6 @@ __global__ __launch_bounds__(64) void seal_append_kernel(uint8_t *__restrict__ f
     for (int i = 0; i < L3C_SEAL_BYTES; ++i) dst[i] = (uint8_t)(w[2 + (i >> 2)] >> (8 * (i & 3)));
     file_bytes[b] = n + L3C_SEAL_BYTES;
 }
-
-inline int64_t tiles_of(int64_t item_bytes) { return item_bytes / TILE_BYTES + (item_bytes % TILE_BYTES != 0); }
 
 }  // namespace
 
@@ -304,6 +368,42 @@ int l3c_u8_crc32(const uint8_t *data, int64_t n_items, int64_t item_bytes, int64
     hipLaunchKernelGGL(u8_crc32_combine_kernel, dim3((unsigned)(n_items < MAX_GRID ? n_items : MAX_GRID)), dim3(64), 0, st, partial, n_items, tiles,
                        k_last, unfill, z, crc_out);
     return l3c::check_launch("u8_crc32_combine_kernel");
+}
+
+int64_t l3c_u8_crc32_spans_workspace_bytes(const l3c_u8_span *spans_host, int64_t n_spans) {
+    const int64_t tiles = count_tiles(spans_host, n_spans, l3c::error_buffer(), 512);
+    return tiles < 0 ? tiles : span_workspace(n_spans, tiles).bytes;
+}
+
+int l3c_u8_crc32_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, int64_t n_spans,
+                       uint32_t *crc_out, void *workspace, int64_t workspace_bytes, l3c_stream_t stream) {
+    L3C_REQUIRE(data && spans_host && spans && crc_out && workspace, "null pointer");
+    const int64_t units = check_spans(spans_host, n_spans, data_bytes, l3c::error_buffer(), 512);
+    if (units < 0) return (int)units;
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(data) & 3) == 0 && (reinterpret_cast<uintptr_t>(crc_out) & 3) == 0, "data and crc_out must be 4-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(spans) & 7) == 0, "spans (the device table) must be 8-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "the workspace must be 16-byte aligned");
+    const SpanWorkspace w = span_workspace(n_spans, units);
+    L3C_REQUIRE(workspace_bytes >= w.bytes, "workspace_bytes too small");
+    const hipStream_t st = l3c::as_stream(stream);
+    char *ws = static_cast<char *>(workspace);
+    int64_t *first = reinterpret_cast<int64_t *>(ws + w.first_at);
+    SpanConsts *consts = reinterpret_cast<SpanConsts *>(ws + w.consts_at);
+    uint32_t *partial = reinterpret_cast<uint32_t *>(ws + w.partial_at);
+    const int64_t prep = (3 * n_spans + PREP_THREADS - 1) / PREP_THREADS;
+    hipLaunchKernelGGL(u8_crc32_spans_prepare_kernel, dim3(1 + (unsigned)(prep < MAX_GRID ? prep : MAX_GRID)), dim3(PREP_THREADS), 0, st, spans, n_spans,
+                       first, reinterpret_cast<uint32_t *>(consts));
+    int rc = l3c::check_launch("u8_crc32_spans_prepare_kernel");
+    if (rc != L3C_OK) return rc;
+    if (units) {
+        hipLaunchKernelGGL(u8_crc32_span_tiles_kernel, dim3((unsigned)(units < MAX_GRID ? units : MAX_GRID)), dim3(THREADS), 0, st, data, spans, first,
+                           n_spans, units, partial);
+        rc = l3c::check_launch("u8_crc32_span_tiles_kernel");
+        if (rc != L3C_OK) return rc;
+    }
+    hipLaunchKernelGGL(u8_crc32_spans_combine_kernel, dim3((unsigned)(n_spans < MAX_GRID ? n_spans : MAX_GRID)), dim3(64), 0, st, partial, first, consts,
+                       n_spans, crc_out);
+    return l3c::check_launch("u8_crc32_spans_combine_kernel");
 }
 
 int l3c_seal_append(uint8_t *files, int64_t file_stride, int64_t *file_bytes, const uint32_t *frame_crc, const uint16_t *padding,

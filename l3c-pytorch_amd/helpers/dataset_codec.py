@@ -194,11 +194,13 @@ def file_padded_shape(data):
 def plan_decode_set(files, order, max_batch):
     """Host-side plan of a set decode: files of equal padded shape share a batch of at most max_batch (the mirror of plan_set, from
     the files' own headers) -- and of equal format: banded files only with banded files of the same band length at every scale, which is
-    what one batch decodes.  -> (chunks: list of index lists, padded shape per chunk)."""
+    what one batch decodes.  A sealed file is planned by its BODY (container.split_seal).
+    -> (chunks: list of index lists, padded shape per chunk)."""
     from ..bitcoding import container
     groups = collections.defaultdict(list)
     for i in order:
-        groups[(file_padded_shape(files[i]), container.band_lengths(files[i]))].append(i)
+        body = container.split_seal(files[i], view=True)[0]
+        groups[(file_padded_shape(body), container.band_lengths(body))].append(i)
     chunks, padded = [], []
     for (shape, _), idxs in groups.items():
         for k in range(0, len(idxs), max_batch):
@@ -207,13 +209,18 @@ def plan_decode_set(files, order, max_batch):
     return chunks, padded
 
 
-def decode_set(bc, files, order, max_batch=16, marks=None, lanes=None, chain_cus=0, n_pinned=None, ragged=None, banded=False):
+def decode_set(bc, files, order, max_batch=16, marks=None, lanes=None, chain_cus=0, n_pinned=None, ragged=None, banded=False, sealed=False,
+               _pixels=True):
     """files: {index: `.l3c` bytes} (as `encode_set` returns them); order: the indices to decode.  -> {index: uint8 (3,H,W) HOST tensor},
     the padding undone.  The mirror of `encode_set` for the reference's folder evaluation, which decodes EVERY file it wrote and
     compares it with the input (multiscale_tester.py:353-381, assert_equal at :373): files of equal padded shape share a batch,
     largest batches first, the batches stream through `Bitcoding.decode_many` (batch i + 1's convolutions beside batch i's RGB chains);
     the decoded pixels leave the device as uint8 through `n_pinned` page-locked buffers while later batches decode.
-    banded=True: the set may hold BANDED files (Bitcoding(bands=K), alone or beside legacy ones); without it such a file is refused."""
+    banded=True: the set may hold BANDED files (Bitcoding(bands=K), alone or beside legacy ones); without it such a file is refused.
+    sealed=True: the set may hold SEALED files (Bitcoding(seal=True), alone or beside unsealed ones, which are decoded and not verified);
+    without it such a file is refused.  Every sealed file is verified as Bitcoding.decode_many(sealed=True) verifies it: generation and
+    model id before anything is enqueued, the CRC-32 of every decoded frame -- computed on the device, one D2H of all words at the end --
+    against its seal.  container.SealError: .index and .failed hold the caller's keys from `order`; nothing is returned then."""
     import time
     from . import pad as _pad
 
@@ -222,9 +229,9 @@ def decode_set(bc, files, order, max_batch=16, marks=None, lanes=None, chain_cus
             marks[name] = time.perf_counter()
 
     from ..bitcoding import container
-    if any(container.is_sealed(files[i]) for i in order):
-        raise ValueError('decode_set does not read sealed .l3c files: container.split_seal gives the body and the seal to check, or '
-                         'Bitcoding.decode_batch / decode verify them')
+    if not sealed and any(container.is_sealed(files[i]) for i in order):
+        raise ValueError('decode_set does not read sealed .l3c files unless it is told to (sealed=True verifies them): '
+                         'container.split_seal gives the body and the seal to check, or Bitcoding.decode_batch / decode verify them')
     n_lanes = bc.set_decoder.N_DECODE_LANES if lanes is None else int(lanes)
     if n_pinned is None:
         n_pinned = max(n_lanes, min(bc.set_decoder.RAGGED_GROUP, len(order))) + 2     # a finished batch must never wait for a free D2H buffer (a ragged group finishes all its batches at once)
@@ -248,6 +255,8 @@ def decode_set(bc, files, order, max_batch=16, marks=None, lanes=None, chain_cus
                 out[i] = img.clone()
 
     def on_batch(n, pixels, paddings):
+        if not _pixels:                                   # verify_set: the frames are hashed where they are, no pixel leaves the device
+            return
         ci = by_size[n]
         u8 = pixels                                       # uint8: 0..255 by construction (symbols of a 256-symbol alphabet)
         collect(True, keep=n_pinned - 1)                  # the buffer about to be reused must have been read out
@@ -261,8 +270,56 @@ def decode_set(bc, files, order, max_batch=16, marks=None, lanes=None, chain_cus
         pending.append((ci, host, ev, paddings))
         collect(False)
 
-    bc.decode_many([[files[i] for i in chunks[ci]] for ci in by_size], on_batch=on_batch, lanes=lanes, chain_cus=chain_cus,
-                   out_dtype=torch.uint8, ragged=ragged, banded=banded)
+    def key(where):
+        return chunks[by_size[where[0]]][where[1]]
+
+    try:
+        bc.decode_many([[files[i] for i in chunks[ci]] for ci in by_size], on_batch=on_batch, lanes=lanes, chain_cus=chain_cus,
+                       out_dtype=torch.uint8, ragged=ragged, banded=banded, sealed=sealed)
+    except container.SealError as e:
+        collect(True)                                     # the copies in flight read the page-locked ring: let them end before it is reused
+        err = container.SealError(e.reason, key(e.index), 'file {!r}: {}'.format(key(e.index), e), [key(w) for w in e.failed])
+        err.frame_crcs = {key(w): crc for w, crc in bc.set_decoder.frame_crcs.items()}      # what verify_set reports
+        raise err
     collect(True)
     mark('parse + H2D + decode + D2H (pipelined)')
+    if not _pixels:
+        return {key(w): crc for w, crc in bc.set_decoder.frame_crcs.items()}
     return out
+
+
+def verify_set(bc, files, order, max_batch=16, banded=False, info=None):
+    """An archive scrub: files: {index: `.l3c` bytes}; order: the indices to check.  -> {index: status}, a status being
+        'unsealed'     the file has no seal: it is decoded with the others, and nothing can be said about its pixels
+        'generation'   written by another bitstream generation                } reported from the seal alone:
+        'model'        written with another checkpoint than bc's              } such a file is not decoded
+        'pixels'       the decoded frame does not hash to the seal's CRC-32: a damaged payload, or a checkpoint the seal does not state
+        'ok'           it does.
+    The files that pass the first two checks go through the set decode of decode_set(sealed=True) -- the same batches, lanes and ragged
+    groups -- but no pixel leaves the device: the frames are hashed there and only the CRC words cross PCIe.  A bad file never raises; a
+    MALFORMED seal (unknown version, wrong check word) is still ValueError, as in container.split_seal, and so is a file that cannot be
+    parsed.  banded: as decode_set.  info (dict): receives 'frame_crc': {index: the CRC-32 the device computed} for the files hashed on the
+    device (every file of a batch or ragged group that holds a sealed one; none where a single batch is left, which decode_batch verifies)."""
+    from ..bitcoding import container
+    status, todo = {}, []
+    for i in order:
+        seal = container.split_seal(files[i], view=True)[1]
+        if seal is not None:
+            try:
+                container.check_seals([seal], bc.generation(), bc.model_id)
+            except container.SealError as e:
+                status[i] = e.reason
+                continue
+        status[i] = 'unsealed' if seal is None else 'ok'
+        todo.append(i)
+    crcs = {}
+    if todo:
+        try:
+            crcs = decode_set(bc, files, todo, max_batch=min(max_batch, 63), banded=banded, sealed=True, _pixels=False)
+        except container.SealError as e:                 # 'pixels': the other reasons were sorted out above
+            for i in e.failed:
+                status[i] = 'pixels'
+            crcs = e.frame_crcs
+    if info is not None:
+        info['frame_crc'] = crcs
+    return status

@@ -259,6 +259,14 @@ def sym_to_bn(sym, bin_width, x_min):
     return bn
 
 
+def sym_to_u8(sym):
+    """l3c_sym_to_u8: int16 symbols -> uint8 tensor of the same shape (the low byte: the decoded RGB symbols as pixels)."""
+    out = torch.empty(sym.shape, dtype=torch.uint8, device=sym.device)
+    if sym.numel():
+        call('l3c_sym_to_u8', ptr(sym, torch.int16), sym.numel(), ptr(out, torch.uint8), stream())
+    return out
+
+
 # ---- RGB baselines: bicubic pyramid encoder ------------------------------------------------------------------------------
 
 _RGB_MEAN = None
@@ -811,6 +819,34 @@ def u8_crc32(data, n_items, item_bytes, item_stride=None, out=None, workspace=No
     ws = torch.empty(n_ws, dtype=torch.uint8, device=data.device) if workspace is None else workspace
     out = torch.empty(n_items, dtype=torch.int32, device=data.device) if out is None else out
     call('l3c_u8_crc32', ptr(data, torch.uint8), n_items, item_bytes, item_stride, ptr(out, torch.int32), ptr(ws, torch.uint8), ws.numel(), stream())
+    return out
+
+
+SPAN_DTYPE = np.dtype([('offset', '<i8'), ('bytes', '<i8')])      # l3c_u8_span (include/l3c_hip.h)
+
+
+def u8_crc32_spans(data, offsets, lengths, out=None, workspace=None):
+    """l3c_u8_crc32_spans: zlib.crc32 of data[offsets[i]:offsets[i] + lengths[i]] for every i, in one call of at most three launches -- the
+    frames of a ragged group.  data: contiguous uint8 device tensor; offsets (multiples of 4), lengths: host sequences or int64 arrays of
+    one length n >= 1; the spans may come in any order, overlap and leave gaps.  The table is checked on the host and goes up through
+    upload_small.  -> int32 (n,) device tensor holding the CRC words (view it as uint32 on the host); no host synchronisation."""
+    offsets, lengths = np.asarray(offsets), np.asarray(lengths)
+    if data.dtype != torch.uint8 or not data.is_contiguous() or offsets.ndim != 1 or offsets.shape != lengths.shape or offsets.shape[0] < 1 \
+            or offsets.dtype.kind not in 'iu' or lengths.dtype.kind not in 'iu':
+        raise ValueError('u8_crc32_spans: a contiguous uint8 tensor and two integer sequences of one length >= 1, got {} and {} / {}'.format(
+            data.dtype, offsets.shape, lengths.shape))
+    table = np.empty(offsets.shape[0], dtype=SPAN_DTYPE)
+    table['offset'], table['bytes'] = offsets, lengths
+    n = table.shape[0]
+    n_ws = _lib.load().l3c_u8_crc32_spans_workspace_bytes(table.ctypes.data, n)
+    _lib.check(min(n_ws, 0))
+    ws = torch.empty(n_ws, dtype=torch.uint8, device=data.device) if workspace is None else workspace
+    out = torch.empty(n, dtype=torch.int32, device=data.device) if out is None else out
+    if out.dtype != torch.int32 or out.numel() != n or not out.is_contiguous():
+        raise ValueError('u8_crc32_spans: out must be a contiguous int32 tensor of {} elements'.format(n))
+    table_d = upload_small(table.view(np.int64))
+    call('l3c_u8_crc32_spans', ptr(data, torch.uint8), data.numel(), table.ctypes.data, ptr(table_d, torch.int64), n, ptr(out, torch.int32),
+         ptr(ws, torch.uint8), ws.numel(), stream())
     return out
 
 

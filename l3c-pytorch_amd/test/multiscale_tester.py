@@ -461,7 +461,7 @@ class MultiscaleTester(object):
         with self.times.run('=== file read ({} files)'.format(len(order))):
             datas = {i: self.bc._read_file(paths_[i]) for i in order}
         with self.times.run('=== bc.decode, {} files as a set (parse, H2D, decode, D2H)'.format(len(order))):
-            back = dataset_codec.decode_set(self.bc, datas, order, max_batch=self.max_batch, banded=bool(self.bc.bands))
+            back = dataset_codec.decode_set(self.bc, datas, order, max_batch=self.max_batch, banded=bool(self.bc.bands), sealed=self.bc.seal)
         with self.times.run('=== compare with the inputs'):
             for i in order:
                 if not torch.equal(back[i], imgs[i]):

@@ -3,7 +3,7 @@
 
     python test.py LOG_DIR LOG_DATES IMAGES [--match_filenames F ..] [-m MAX] [--crop N] [--names N,..] [--overwrite_cache]
                    [--reset_entire_cache] [-i ITR,..] [--write_to_files DIR [--compare_theory] [--time_report PATH]]
-                   [--sort_output testset|exp|itr|res] [--batch B] [--bands K]
+                   [--sort_output testset|exp|itr|res] [--batch B] [--bands K] [--seal]
 
 Prints the mean bpsp of every (test set, experiment, iteration); results are cached in LOG_DIR_test/<experiment>/cache.pkl.
 `--write_to_files` encodes every image to DIR/<name>.l3c with the HIP coder, decodes it again and asserts equality.
@@ -55,6 +55,9 @@ def main(argv=None):
     p.add_argument('--bands', type=int, default=0, metavar='K',
                    help='--write_to_files: write BANDED .l3c files (every channel cut into at most K independently coded bands) and decode '
                         'them as a set, every band a stream of its own (0: the legacy format)')
+    p.add_argument('--seal', action='store_true',
+                   help='--write_to_files: write SEALED .l3c files (bitstream generation, checkpoint id and the CRC-32 of the frame behind every '
+                        'file) and verify every seal while the folder is decoded as a set and compared')
     flags = p.parse_args(argv)
 
     if flags.compare_theory and not flags.write_to_files:
