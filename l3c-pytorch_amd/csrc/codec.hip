@@ -3,15 +3,18 @@
 // Two host loops over entry points the library already has, in the order the Python schedule calls them:
 //     encode   Bitcoding.prepare_batch + code + EncodedBatch._write_container (bitcoding/bitcoding.py): image -> l3c_net_forward -> per scale
 //              the interval head -> ONE grouped coder launch -> file sizes -> l3c_container_write
-//     decode   Bitcoding._walk_records for legacy files: l3c_container_read -> the coarsest record on the uniform row -> per finer record
-//              l3c_sym_to_bn, l3c_net_get_p, tables + range decoders (the RGB scale: l3c_decode_rgb) -> pixels
+//     decode   Bitcoding._walk_records: l3c_container_read -> the coarsest record on the uniform row -> per finer record
+//              l3c_sym_to_bn, l3c_net_get_p, tables + range decoders (the RGB scale: the chunk pipeline) -> pixels
 // so the files equal the Python path's byte for byte and either side decodes the other's.  Every buffer lives in ONE caller-owned workspace
 // whose contents are garbage on entry; nothing is allocated, nothing synchronises with the host.  The framing of an untrusted file is
-// parsed by the HIP-free codec_plan.h.
+// parsed by the HIP-free codec_plan.h (legacy files) and codec_plan_banded.h (BANDED files).
 //
-// The same two loops for BANDED files (l3c_encode_batch_banded / l3c_decode_batch_banded: Bitcoding.code with enc.bands and _walk_records
-// with _scale_symbols_banded; framing parser: codec_plan_banded.h): per scale l3c_ac_band_intervals cuts the intervals into band groups, and
-// every band of a record decodes as a stream of its own -- l3c_ac_decode_bands, the ragged table / decoder launches, l3c_decode_rgb_banded.
+// BANDED files (l3c_encode_batch_banded / l3c_decode_batch_banded: Bitcoding.code with enc.bands) go through the same two loops:
+//     encode   one plan (a legacy channel is one band), one descriptor check, one front half (enc_forward) and one interval head per scale
+//              (enc_intervals); enc_run and enc_banded_run keep what differs: how a scale's intervals become coder groups -- l3c_ac_band_intervals
+//              cuts them into band groups -- which layout kernel sizes the files and which writer writes them
+//     decode   dec_check and the walk dec_run are templates over the plan header; the three steps that differ are overloaded on it: in a banded
+//              file every band of a record decodes as a stream of its own -- l3c_ac_decode_bands, the ragged launches, l3c_decode_rgb_banded
 //
 // Pictures that are not planar, padded or equally sized (l3c_encode_images / l3c_decode_images): the same loops -- each encode entry is
 // split into its checks and its schedule for that -- behind l3c_u8_gather and in front of l3c_u8_scatter (csrc/images.hip), the planar
@@ -156,6 +159,27 @@ int launch_layout_banded(const BandedLayoutArgs &a, l3c_stream_t stream) {
     return l3c::check_launch("container_layout_banded_kernel");
 }
 
+// what l3c_container_layout and l3c_container_layout_banded ask of their arguments alike
+int check_layout_args(const void *scales, int n_scales, int64_t B, int64_t file_stride, const int64_t *file_offset, const int64_t *file_bytes) {
+    L3C_REQUIRE(scales && file_offset && file_bytes, "null pointer");
+    L3C_REQUIRE(n_scales > 0 && n_scales <= LayoutArgs::MAX_SCALES, "1..8 scales");
+    L3C_REQUIRE(B > 0 && B < 65536, "bad batch size (1 .. 65535)");
+    const bool stride_ok = file_stride > 0 && file_stride % 16 == 0;
+    L3C_REQUIRE(stride_ok, "file_stride must be a positive multiple of 16");
+    L3C_REQUIRE(aligned16(file_offset) && aligned16(file_bytes), "every pointer must be 16-byte aligned");
+    return L3C_OK;
+}
+
+// the batch of either kernel's arguments
+template <class Args>
+void layout_batch(Args &a, int n_scales, int64_t B, int64_t file_stride, int64_t *file_offset, int64_t *file_bytes) {
+    a.n_scales = n_scales;
+    a.B = B;
+    a.file_stride = file_stride;
+    a.file_offset = file_offset;
+    a.file_bytes = file_bytes;
+}
+
 // ---- the model ---------------------------------------------------------------------------------------------------------------
 
 int kp_of(const l3c_net_config &c, int s) {
@@ -192,137 +216,14 @@ int check_sides(const l3c_net_config &c, int H, int W) {
     return L3C_OK;
 }
 
-// ---- encode ------------------------------------------------------------------------------------------------------------------
+// ---- encode plans --------------------------------------------------------------------------------------------------------------
 
+inline int64_t take(int64_t &at, int64_t n) { const int64_t o = at; at += up(n); return o; }
+
+// The workspace of either encode.  bands == 0 is the legacy format: every channel of a scale is ONE band, the last (L = hw, n = 1), and
+// the scale's intervals go to the coder from a buffer of their own (iv_l).  A banded scale's intervals go through the one buffer iv,
+// from which l3c_ac_band_intervals re-lays them into the full bands' group (absent when n == 1) and the last bands' group.
 struct EncPlan {
-    int S;
-    int Cs[MAX_REC];
-    int64_t hw[MAX_REC];
-    int64_t img, sym[MAX_REC], bn_q[MAX_REC], P[MAX_REC], nb[MAX_REC], clean[MAX_REC], file_offset, zero_pad;
-    int64_t scratch;                               // the forward's workspace, then the coder's buffers
-    int64_t net_ws, iv[MAX_REC], out[MAX_REC], out_stride[MAX_REC], ac_ws;
-    int64_t bytes;
-};
-
-int64_t file_stride_of(const l3c_net_config &c, int H, int W) {
-    int64_t n = 8;
-    for (int s = 0; s <= c.num_scales; ++s) {
-        const int Cs = s == 0 ? 3 : c.C;
-        n += 5 + 4 * Cs + 4 + Cs * l3c_ac_max_bytes((int64_t)(H >> s) * (W >> s));
-    }
-    return (n + 15) / 16 * 16;
-}
-
-int enc_plan(const l3c_net_config &c, int64_t B, int H, int W, EncPlan *out) {
-    EncPlan p{};
-    p.S = c.num_scales;
-    p.net_ws = l3c_net_forward_workspace_bytes(&c, B, H, W);     // (checks the image against the schedule's limits)
-    if (p.net_ws < 0) return (int)p.net_ws;
-    int64_t at = 0, total_streams = 0;
-    auto take = [&at](int64_t n) { const int64_t o = at; at += up(n); return o; };
-    p.img = take(B * 3 * (int64_t)H * W * 4);
-    for (int s = 0; s <= p.S; ++s) {
-        p.Cs[s] = s == 0 ? 3 : c.C;
-        p.hw[s] = (int64_t)(H >> s) * (W >> s);
-        const int64_t n = B * p.Cs[s] * p.hw[s];
-        p.sym[s] = take(n * 2);
-        if (s) p.bn_q[s] = take(n * 4);
-        if (s < p.S) p.P[s] = take(B * p.hw[s] * kp_of(c, s) * 4);
-        p.nb[s] = take(B * p.Cs[s] * 4);
-        p.clean[s] = take(B * p.Cs[s] * 4);
-        total_streams += B * p.Cs[s];
-    }
-    p.file_offset = take(B * 8);
-    p.zero_pad = take(B * 8);
-    p.scratch = at;
-    int64_t coder = 0;
-    auto take_c = [&coder](int64_t n) { const int64_t o = coder; coder += up(n); return o; };
-    for (int s = 0; s <= p.S; ++s) {
-        p.iv[s] = take_c(l3c_interval_words(B * p.Cs[s], p.hw[s]) * 4);
-        p.out_stride[s] = l3c_ac_max_bytes(p.hw[s]);
-        p.out[s] = take_c(B * p.Cs[s] * p.out_stride[s]);
-    }
-    p.ac_ws = take_c(l3c_ac_encode_groups_workspace_bytes(p.S + 1, total_streams));
-    p.bytes = p.scratch + (coder > up(p.net_ws) ? coder : up(p.net_ws)) + ALIGN;   // + ALIGN: the caller's pointer is 16-byte aligned
-    *out = p;
-    return L3C_OK;
-}
-
-// ---- decode ------------------------------------------------------------------------------------------------------------------
-
-struct DecPlan {
-    int64_t streams, sym[MAX_REC], bn, F[MAX_REC], P, flags, scratch, table_bytes[MAX_REC], getp_ws, rgb_ws;
-    int64_t bytes;
-};
-
-// the records of either plan as the workspace layout reads them
-struct RecShape {
-    int64_t C, H, W;
-};
-
-// rgb_ws: the workspace of the RGB record's pipeline (l3c_decode_rgb or l3c_decode_rgb_banded), negative: a bad plan
-int dec_plan_of(const l3c_net_config &c, int64_t B, int n_rec, const RecShape *rec, int64_t H, int64_t W, int64_t dst_bytes, int64_t rgb_ws,
-                DecPlan *out) {
-    DecPlan p{};
-    const int S = c.num_scales;
-    int64_t at = 0, scratch = 0;
-    auto take = [&at](int64_t n) { const int64_t o = at; at += up(n); return o; };
-    p.streams = take(dst_bytes);
-    int64_t bn = 0, P = 0;
-    for (int k = 0; k < n_rec; ++k) {
-        const RecShape &r = rec[k];
-        const int64_t hw = r.H * r.W;
-        if (r.H < 1 || r.W < 1 || r.C < 1 || r.C > 8 || (k && (r.H != 2 * rec[k - 1].H || r.W != 2 * rec[k - 1].W)))
-            return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent record %d", k);
-        p.sym[k] = take(B * r.C * hw * 2);             // (the finest record's: unused when the caller takes the symbols)
-        if (k + 1 < n_rec) bn = B * r.C * hw * 4 > bn ? B * r.C * hw * 4 : bn;
-        if (k) {
-            const int s = S - k;                       // the network that predicts this record
-            const int64_t ws = l3c_net_get_p_workspace_bytes(&c, B, (int)rec[k - 1].H, (int)rec[k - 1].W);
-            if (ws < 0) return (int)ws;
-            p.getp_ws = ws > p.getp_ws ? ws : p.getp_ws;
-            const int64_t Pk = B * hw * kp_of(c, s) * 4;
-            P = Pk > P ? Pk : P;
-            if (s > 0) {
-                p.F[k] = take(B * hw * c.Cf * 4);
-                p.table_bytes[k] = up(B * hw * (c.L + 1) * 2);
-                scratch = r.C * p.table_bytes[k] > scratch ? r.C * p.table_bytes[k] : scratch;
-            }
-        }
-    }
-    if (rec[n_rec - 1].H != H || rec[n_rec - 1].W != W) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent image size");
-    p.bn = take(bn);
-    p.P = take(P);
-    p.flags = take(MAX_REC * 4);
-    p.rgb_ws = rgb_ws;
-    if (p.rgb_ws < 0) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: bad chunk list");
-    scratch = p.getp_ws > scratch ? p.getp_ws : scratch;
-    scratch = p.rgb_ws > scratch ? p.rgb_ws : scratch;
-    p.scratch = at;                                    // get_p's workspace, then the scale's tables / the RGB pipeline's workspace
-    p.bytes = at + up(scratch) + ALIGN;
-    *out = p;
-    return L3C_OK;
-}
-
-int dec_plan(const l3c_net_config &c, const l3c_plan::Header &h, DecPlan *out) {
-    RecShape rec[MAX_REC];
-    const int n_rec = (int)h.n_records;
-    for (int k = 0; k < n_rec; ++k) rec[k] = RecShape{h.rec[k].C, h.rec[k].H, h.rec[k].W};
-    return dec_plan_of(c, h.B, n_rec, rec, h.H, h.W, h.dst_bytes, l3c_decode_rgb_workspace_bytes(h.B, h.max_chunk_npix, (int)h.n_chunks, (int)h.lag),
-                       out);
-}
-
-int dec_plan_banded(const l3c_net_config &c, const l3c_plan::BandedHeader &h, DecPlan *out) {
-    RecShape rec[MAX_REC];
-    const int n_rec = (int)h.n_records;
-    for (int k = 0; k < n_rec; ++k) rec[k] = RecShape{h.rec[k].C, h.rec[k].H, h.rec[k].W};
-    return dec_plan_of(c, h.B, n_rec, rec, h.H, h.W, h.dst_bytes,
-                       l3c_decode_rgb_banded_workspace_bytes(h.B, h.H * h.W, h.rgb_band_len, (int)h.rgb_chunks, (int)h.lag), out);
-}
-
-// ---- banded encode -----------------------------------------------------------------------------------------------------------
-
-struct EncBandPlan {
     int S;
     int Cs[MAX_REC];
     int64_t hw[MAX_REC], L[MAX_REC], n[MAX_REC], last[MAX_REC];         // per scale: band length, bands per channel, symbols of the last band
@@ -330,35 +231,35 @@ struct EncBandPlan {
     int64_t nb_f[MAX_REC], nb_l[MAX_REC], clean_f[MAX_REC], clean_l[MAX_REC];
     int64_t scratch;                                                     // the forward's workspace, then the coder's buffers
     int64_t net_ws, iv, iv_f[MAX_REC], iv_l[MAX_REC], out_f[MAX_REC], out_l[MAX_REC], stride_f[MAX_REC], stride_l[MAX_REC], ac_ws, pos;
-    int64_t streams_per_image, framing;
+    int64_t streams_per_image, framing;                                  // (banded files)
     int64_t bytes;
 };
 
-inline int64_t band_len_of(int64_t hw, int bands) { return 64 * ((hw + 64 * (int64_t)bands - 1) / (64 * (int64_t)bands)); }
+inline int64_t band_len_of(int64_t hw, int bands) { return bands ? 64 * ((hw + 64 * (int64_t)bands - 1) / (64 * (int64_t)bands)) : hw; }
 
 int check_bands(int bands) {
     if (bands < 1 || bands > l3c_plan::MAX_BANDS) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "bands = %d: must be 1 .. 1024", bands);
     return L3C_OK;
 }
 
-int64_t banded_file_stride_of(const l3c_net_config &c, int H, int W, int bands) {
-    int64_t total = 14;
+// framing (legacy: 8 + 5 + 4 C + 4 per scale, banded: 14 + 9 + 4 C n + 4 per scale) and the longest payloads, up to a multiple of 16
+int64_t file_stride_of(const l3c_net_config &c, int H, int W, int bands) {
+    int64_t total = bands ? 14 : 8;
     for (int s = 0; s <= c.num_scales; ++s) {
         const int64_t Cs = s == 0 ? 3 : c.C, hw = (int64_t)(H >> s) * (W >> s), L = band_len_of(hw, bands), n = (hw + L - 1) / L;
-        total += 9 + 4 * Cs * n + 4 + Cs * ((n - 1) * l3c_ac_max_bytes(L) + l3c_ac_max_bytes(hw - (n - 1) * L));
+        total += (bands ? 9 : 5) + 4 * Cs * n + 4 + Cs * ((n - 1) * l3c_ac_max_bytes(L) + l3c_ac_max_bytes(hw - (n - 1) * L));
     }
     return (total + 15) / 16 * 16;
 }
 
-int enc_band_plan(const l3c_net_config &c, int64_t B, int H, int W, int bands, EncBandPlan *out) {
-    EncBandPlan p{};
+int enc_plan(const l3c_net_config &c, int64_t B, int H, int W, int bands, EncPlan *out) {
+    EncPlan p{};
     p.S = c.num_scales;
     p.net_ws = l3c_net_forward_workspace_bytes(&c, B, H, W);     // (checks the image against the schedule's limits)
     if (p.net_ws < 0) return (int)p.net_ws;
-    int64_t at = 0, total_streams = 0, iv_words = 0;
+    int64_t at = 0, coder = 0, total_streams = 0, iv_words = 0;
     int n_groups = 0;
-    auto take = [&at](int64_t n) { const int64_t o = at; at += up(n); return o; };
-    p.img = take(B * 3 * (int64_t)H * W * 4);
+    p.img = take(at, B * 3 * (int64_t)H * W * 4);
     p.framing = 14;
     for (int s = 0; s <= p.S; ++s) {
         p.Cs[s] = s == 0 ? 3 : c.C;
@@ -367,16 +268,16 @@ int enc_band_plan(const l3c_net_config &c, int64_t B, int H, int W, int bands, E
         p.n[s] = (p.hw[s] + p.L[s] - 1) / p.L[s];
         p.last[s] = p.hw[s] - (p.n[s] - 1) * p.L[s];
         const int64_t streams = B * p.Cs[s], n = streams * p.hw[s];
-        if (B * p.n[s] > l3c_plan::MAX_BAND_STREAMS)
+        if (bands && B * p.n[s] > l3c_plan::MAX_BAND_STREAMS)
             return CODEC_FAIL(L3C_ERR_UNSUPPORTED, "unsupported batch: %lld images x %lld bands at scale %d, more than 65535 band streams per channel "
                               "in one call: slice the batch", (long long)B, (long long)p.n[s], s);
-        p.sym[s] = take(n * 2);
-        if (s) p.bn_q[s] = take(n * 4);
-        if (s < p.S) p.P[s] = take(B * p.hw[s] * kp_of(c, s) * 4);
-        p.nb_f[s] = take(streams * (p.n[s] - 1) * 4);
-        p.clean_f[s] = take(streams * (p.n[s] - 1) * 4);
-        p.nb_l[s] = take(streams * 4);
-        p.clean_l[s] = take(streams * 4);
+        p.sym[s] = take(at, n * 2);
+        if (s) p.bn_q[s] = take(at, n * 4);
+        if (s < p.S) p.P[s] = take(at, B * p.hw[s] * kp_of(c, s) * 4);
+        p.nb_f[s] = take(at, streams * (p.n[s] - 1) * 4);
+        p.clean_f[s] = take(at, streams * (p.n[s] - 1) * 4);
+        p.nb_l[s] = take(at, streams * 4);
+        p.clean_l[s] = take(at, streams * 4);
         total_streams += streams * p.n[s];
         n_groups += p.n[s] > 1 ? 2 : 1;
         p.streams_per_image += p.Cs[s] * p.n[s];
@@ -384,83 +285,32 @@ int enc_band_plan(const l3c_net_config &c, int64_t B, int H, int W, int bands, E
         const int64_t w = l3c_interval_words(streams, p.hw[s]);
         iv_words = w > iv_words ? w : iv_words;
     }
-    p.file_offset = take(B * 8);
-    p.zero_pad = take(B * 8);
+    p.file_offset = take(at, B * 8);
+    p.zero_pad = take(at, B * 8);
     p.scratch = at;
-    int64_t coder = 0;
-    auto take_c = [&coder](int64_t n) { const int64_t o = coder; coder += up(n); return o; };
-    p.iv = take_c(iv_words * 4);                                  // one scale's intervals at a time: l3c_ac_band_intervals copies them out
+    if (bands) p.iv = take(coder, iv_words * 4);                  // one scale's intervals at a time: l3c_ac_band_intervals copies them out
     for (int s = 0; s <= p.S; ++s) {
         const int64_t streams = B * p.Cs[s];
         if (p.n[s] > 1) {
-            p.iv_f[s] = take_c(l3c_interval_words(streams * (p.n[s] - 1), p.L[s]) * 4);
+            p.iv_f[s] = take(coder, l3c_interval_words(streams * (p.n[s] - 1), p.L[s]) * 4);
             p.stride_f[s] = l3c_ac_max_bytes(p.L[s]);
-            p.out_f[s] = take_c(streams * (p.n[s] - 1) * p.stride_f[s]);
+            p.out_f[s] = take(coder, streams * (p.n[s] - 1) * p.stride_f[s]);
         }
-        p.iv_l[s] = take_c(l3c_interval_words(streams, p.last[s]) * 4);
+        p.iv_l[s] = take(coder, l3c_interval_words(streams, p.last[s]) * 4);
         p.stride_l[s] = l3c_ac_max_bytes(p.last[s]);
-        p.out_l[s] = take_c(streams * p.stride_l[s]);
+        p.out_l[s] = take(coder, streams * p.stride_l[s]);
     }
-    p.ac_ws = take_c(l3c_ac_encode_groups_workspace_bytes(n_groups, total_streams));
-    p.pos = take_c(B * p.streams_per_image * 8);
+    p.ac_ws = take(coder, l3c_ac_encode_groups_workspace_bytes(n_groups, total_streams));
+    if (bands) p.pos = take(coder, B * p.streams_per_image * 8);
     p.bytes = p.scratch + (coder > up(p.net_ws) ? coder : up(p.net_ws)) + ALIGN;   // + ALIGN: the caller's pointer is 16-byte aligned
     *out = p;
     return L3C_OK;
 }
 
-}  // namespace
+// ---- encode: every check, then the schedule (two halves, shared with l3c_encode_images) ------------------------------------------
 
-extern "C" {
-
-int l3c_container_layout(const l3c_container_scale *scales, int n_scales, int64_t B, int64_t file_stride, int64_t *file_offset,
-                         int64_t *file_bytes, l3c_stream_t stream) {
-    L3C_REQUIRE(scales && file_offset && file_bytes, "null pointer");
-    L3C_REQUIRE(n_scales > 0 && n_scales <= LayoutArgs::MAX_SCALES, "1..8 scales");
-    L3C_REQUIRE(B > 0 && B < 65536, "bad batch size (1 .. 65535)");
-    const bool stride_ok = file_stride > 0 && file_stride % 16 == 0;
-    L3C_REQUIRE(stride_ok, "file_stride must be a positive multiple of 16");
-    L3C_REQUIRE(aligned16(file_offset) && aligned16(file_bytes), "every pointer must be 16-byte aligned");
-    LayoutArgs a{};
-    a.n_scales = n_scales;
-    a.B = B;
-    a.file_stride = file_stride;
-    a.file_offset = file_offset;
-    a.file_bytes = file_bytes;
-    for (int k = 0; k < n_scales; ++k) {
-        L3C_REQUIRE(scales[k].nbytes && scales[k].C > 0 && scales[k].C < 256, "bad scale descriptor");
-        L3C_REQUIRE((reinterpret_cast<uintptr_t>(scales[k].nbytes) & 3) == 0, "nbytes arrays must be 4-byte aligned");
-        a.nbytes[k] = scales[k].nbytes;
-        a.C[k] = scales[k].C;
-    }
-    return launch_layout(a, stream);
-}
-
-int l3c_sym_to_u8(const int16_t *sym, int64_t n, uint8_t *out, l3c_stream_t stream) {
-    L3C_REQUIRE(sym && out, "null pointer");
-    L3C_REQUIRE(n > 0, "empty input");
-    L3C_REQUIRE(aligned16(sym) && aligned16(out), "every pointer must be 16-byte aligned");
-    const int64_t blocks = ((n >> 4) + 255) / 256;
-    hipLaunchKernelGGL(sym_to_u8_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks))), dim3(256), 0,
-                       l3c::as_stream(stream), sym, n, out);
-    return l3c::check_launch("sym_to_u8_kernel");
-}
-
-int64_t l3c_encode_file_stride(const l3c_net_config *cfg, int H, int W) {
-    CODEC_TRY(codec_config(cfg));
-    CODEC_TRY(check_sides(*cfg, H, W));
-    return file_stride_of(*cfg, H, W);
-}
-
-int64_t l3c_encode_batch_workspace_bytes(const l3c_net_config *cfg, int64_t B, int H, int W) {
-    CODEC_TRY(codec_config(cfg));
-    CODEC_TRY(check_sides(*cfg, H, W));
-    EncPlan p;
-    CODEC_TRY(enc_plan(*cfg, B, H, W, &p));
-    return p.bytes;
-}
-
-// l3c_encode_batch in two halves, shared with l3c_encode_images: every check, then the schedule
-static int enc_check(const l3c_encode_batch_desc *d, EncPlan *plan) {
+// the descriptor of either entry; bands is 0 for the legacy format
+int enc_check_desc(const l3c_encode_batch_desc *d, bool banded, int bands, EncPlan *plan) {
     L3C_REQUIRE(d, "null descriptor");
     CODEC_TRY(check_model(d->model_host));
     const l3c_codec_model &m = *d->model_host;
@@ -470,50 +320,58 @@ static int enc_check(const l3c_encode_batch_desc *d, EncPlan *plan) {
                 "every pointer must be 16-byte aligned");
     L3C_REQUIRE(d->B > 0 && d->B < 65536, "bad batch size (1 .. 65535)");
     CODEC_TRY(check_sides(c, d->H, d->W));
-    EncPlan p;
-    CODEC_TRY(enc_plan(c, d->B, d->H, d->W, &p));
-    const int64_t stride = file_stride_of(c, d->H, d->W);
+    if (banded) CODEC_TRY(check_bands(bands));
+    CODEC_TRY(enc_plan(c, d->B, d->H, d->W, bands, plan));
+    const int64_t stride = file_stride_of(c, d->H, d->W, bands);
     if (d->file_stride < stride || d->file_stride % 16)
-        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "file_stride %lld: must be a multiple of 16 and at least l3c_encode_file_stride = %lld",
-                          (long long)d->file_stride, (long long)stride);
-    if (d->workspace_bytes < p.bytes)
-        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
-    *plan = p;
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "file_stride %lld: must be a multiple of 16 and at least %s = %lld", (long long)d->file_stride,
+                          banded ? "l3c_encode_banded_file_stride" : "l3c_encode_file_stride", (long long)stride);
+    if (d->workspace_bytes < plan->bytes)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)plan->bytes);
     return L3C_OK;
 }
 
-static int enc_run(const l3c_encode_batch_desc *d, const EncPlan &p, l3c_stream_t stream) {
+// the front half of either schedule: a padding of zeros when the caller has none, the image's symbols and floats, the whole network
+int enc_forward(const l3c_encode_batch_desc *d, const EncPlan &p, char *ws, l3c_stream_t stream, l3c_net_forward_desc *out) {
     const l3c_codec_model &m = *d->model_host;
-    const l3c_net_config &c = *m.cfg_host;
-    const int64_t B = d->B;
-    const int S = p.S;
-    char *ws = base256(d->workspace);
-    const hipStream_t st = l3c::as_stream(stream);
-    const uint16_t *padding = d->padding;
-    if (!padding) {
-        CODEC_TRY(l3c::check_hip(hipMemsetAsync(ws + p.zero_pad, 0, (size_t)B * 8, st), "hipMemsetAsync"));
-        padding = reinterpret_cast<const uint16_t *>(ws + p.zero_pad);
-    }
+    if (!d->padding)
+        CODEC_TRY(l3c::check_hip(hipMemsetAsync(ws + p.zero_pad, 0, (size_t)d->B * 8, l3c::as_stream(stream)), "hipMemsetAsync"));
     const float zero_mean[3] = {0.f, 0.f, 0.f};
     float *img = reinterpret_cast<float *>(ws + p.img);
-    CODEC_TRY(l3c_u8_to_sym_bn(d->img, zero_mean, B, p.hw[0], reinterpret_cast<int16_t *>(ws + p.sym[0]), img, stream));
-    l3c_net_forward_desc f;
+    CODEC_TRY(l3c_u8_to_sym_bn(d->img, zero_mean, d->B, p.hw[0], reinterpret_cast<int16_t *>(ws + p.sym[0]), img, stream));
+    l3c_net_forward_desc &f = *out;
     memset(&f, 0, sizeof(f));
-    f.cfg_host = &c;
+    f.cfg_host = m.cfg_host;
     f.packed = m.packed;
     f.packed_bytes = m.packed_bytes;
     f.img = img;
-    f.B = B;
+    f.B = d->B;
     f.H = d->H;
     f.W = d->W;
-    for (int s = 0; s <= S; ++s) {
+    for (int s = 0; s <= p.S; ++s) {
         f.sym[s] = reinterpret_cast<int16_t *>(ws + p.sym[s]);
         if (s) f.bn_q[s] = reinterpret_cast<float *>(ws + p.bn_q[s]);
-        if (s < S) f.P[s] = reinterpret_cast<float *>(ws + p.P[s]);
+        if (s < p.S) f.P[s] = reinterpret_cast<float *>(ws + p.P[s]);
     }
     f.workspace = ws + p.scratch;
     f.workspace_bytes = p.net_ws;
-    CODEC_TRY(l3c_net_forward(&f, stream));
+    return l3c_net_forward(&f, stream);
+}
+
+// the intervals of scale s: the coarsest on the uniform row, every other through the mixture head
+int enc_intervals(const l3c_codec_model &m, const l3c_net_forward_desc &f, const EncPlan &p, int s, uint32_t *iv, l3c_stream_t stream) {
+    const l3c_net_config &c = *m.cfg_host;
+    if (s == p.S) return l3c_ac_intervals_from_table(m.uniform_row, 0, c.L + 1, f.sym[s], f.B * p.Cs[s], p.hw[s], iv, stream);
+    return l3c_dmll_encode_intervals(f.P[s], f.sym[s], s == 0 ? m.targets_rgb : m.targets_z, f.B, p.hw[s], p.Cs[s], c.K, s == 0,
+                                     s == 0 ? 257 : c.L + 1, iv, stream);
+}
+
+int enc_run(const l3c_encode_batch_desc *d, const EncPlan &p, l3c_stream_t stream) {
+    const int64_t B = d->B;
+    const int S = p.S;
+    char *ws = base256(d->workspace);
+    l3c_net_forward_desc f;
+    CODEC_TRY(enc_forward(d, p, ws, stream, &f));
 
     // the forward's workspace is dead: the coder's intervals and output rows take its place.  Scales coarsest first: file order.
     char *cs = ws + p.scratch;
@@ -522,16 +380,12 @@ static int enc_run(const l3c_encode_batch_desc *d, const EncPlan &p, l3c_stream_
     LayoutArgs la{};
     for (int k = 0; k <= S; ++k) {
         const int s = S - k;
-        uint32_t *iv = reinterpret_cast<uint32_t *>(cs + p.iv[s]);
-        if (s == S)
-            CODEC_TRY(l3c_ac_intervals_from_table(m.uniform_row, 0, c.L + 1, f.sym[s], B * p.Cs[s], p.hw[s], iv, stream));
-        else
-            CODEC_TRY(l3c_dmll_encode_intervals(f.P[s], f.sym[s], s == 0 ? m.targets_rgb : m.targets_z, B, p.hw[s], p.Cs[s], c.K, s == 0,
-                                                s == 0 ? 257 : c.L + 1, iv, stream));
-        uint8_t *out = reinterpret_cast<uint8_t *>(cs + p.out[s]);
-        uint32_t *nb = reinterpret_cast<uint32_t *>(ws + p.nb[s]), *clean = reinterpret_cast<uint32_t *>(ws + p.clean[s]);
-        groups[k] = l3c_ac_group{iv, out, nb, B * p.Cs[s], p.hw[s], p.out_stride[s]};
-        scales[k] = l3c_container_scale{out, clean, p.out_stride[s], p.Cs[s], d->H >> s, d->W >> s};
+        uint32_t *iv = reinterpret_cast<uint32_t *>(cs + p.iv_l[s]);
+        CODEC_TRY(enc_intervals(*d->model_host, f, p, s, iv, stream));
+        uint8_t *out = reinterpret_cast<uint8_t *>(cs + p.out_l[s]);
+        uint32_t *nb = reinterpret_cast<uint32_t *>(ws + p.nb_l[s]), *clean = reinterpret_cast<uint32_t *>(ws + p.clean_l[s]);
+        groups[k] = l3c_ac_group{iv, out, nb, B * p.Cs[s], p.hw[s], p.stride_l[s]};
+        scales[k] = l3c_container_scale{out, clean, p.stride_l[s], p.Cs[s], d->H >> s, d->W >> s};
         la.nbytes[k] = nb;
         la.clean[k] = clean;
         la.C[k] = p.Cs[s];
@@ -539,282 +393,18 @@ static int enc_run(const l3c_encode_batch_desc *d, const EncPlan &p, l3c_stream_
     CODEC_TRY(l3c_ac_encode_groups(groups, S + 1, cs + p.ac_ws, stream));
     // file sizes and offsets; a stream that overran (L3C_AC_OVERRUN) marks its file -1 and is written as an empty payload, so that
     // the writer below stays inside the file's slot whatever the coder reported
-    int64_t *file_offset = reinterpret_cast<int64_t *>(ws + p.file_offset);
-    la.n_scales = S + 1;
-    la.B = B;
-    la.file_stride = d->file_stride;
-    la.file_offset = file_offset;
-    la.file_bytes = d->file_bytes;
+    layout_batch(la, S + 1, B, d->file_stride, reinterpret_cast<int64_t *>(ws + p.file_offset), d->file_bytes);
     CODEC_TRY(launch_layout(la, stream));
-    return l3c_container_write(scales, S + 1, B, padding, file_offset, d->files, stream);
+    const uint16_t *padding = d->padding ? d->padding : reinterpret_cast<const uint16_t *>(ws + p.zero_pad);
+    return l3c_container_write(scales, S + 1, B, padding, la.file_offset, d->files, stream);
 }
 
-int l3c_encode_batch(const l3c_encode_batch_desc *d, l3c_stream_t stream) {
-    EncPlan p;
-    CODEC_TRY(enc_check(d, &p));
-    return enc_run(d, p, stream);     // everything checked: enqueue
-}
-
-int64_t l3c_decode_plan_bytes(const l3c_net_config *cfg, int64_t B) {
-    CODEC_TRY(codec_config(cfg));
-    if (B < 1 || B >= 65536) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "bad batch size: B = %lld, must be 1 .. 65535", (long long)B);
-    return l3c_plan::plan_bytes(*cfg, B);
-}
-
-int l3c_decode_plan(const l3c_net_config *cfg, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B, void *plan_host,
-                    int64_t plan_bytes, int *H_out, int *W_out, uint16_t *padding_host_out) {
-    CODEC_TRY(codec_config(cfg));
-    CODEC_TRY(l3c_plan::make_plan(cfg, files_host, file_offset_host, B, plan_host, plan_bytes, H_out, W_out, padding_host_out,
-                                  l3c::error_buffer(), 512));
-    // the header's sizes against the network schedule itself (codec_plan.h restates its limits; this is the schedule's own answer)
-    l3c_plan::Header h;
-    memcpy(&h, plan_host, sizeof(h));
-    DecPlan p;
-    const int rc = dec_plan(*cfg, h, &p);
-    if (rc != L3C_OK) {
-        char why[400];
-        snprintf(why, sizeof(why), "%s", l3c::error_buffer());
-        memset(plan_host, 0, sizeof(int64_t));     // no plan
-        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "invalid file: %lld x %lld pixels: %s", (long long)h.H, (long long)h.W, why);
-    }
-    return L3C_OK;
-}
-
-int64_t l3c_decode_batch_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) {
-    CODEC_TRY(codec_config(cfg));
-    l3c_plan::Header h;
-    CODEC_TRY(l3c_plan::check_blob(*cfg, plan_host, -1, &h, l3c::error_buffer(), 512));
-    DecPlan p;
-    CODEC_TRY(dec_plan(*cfg, h, &p));
-    return p.bytes;
-}
-
-int l3c_decode_batch(const l3c_decode_batch_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
-    L3C_REQUIRE(d, "null descriptor");
-    CODEC_TRY(check_model(d->model_host));
-    const l3c_codec_model &m = *d->model_host;
-    const l3c_net_config &c = *m.cfg_host;
-    L3C_REQUIRE(d->files && d->plan_host && d->plan && d->pixels && d->workspace, "null pointer");
-    L3C_REQUIRE(aligned16(d->files) && aligned16(d->plan) && aligned16(d->pixels) && aligned16(d->sym) && aligned16(d->workspace),
-                "every pointer must be 16-byte aligned");
-    L3C_REQUIRE((reinterpret_cast<uintptr_t>(d->plan_host) & 7) == 0, "plan_host must be 8-byte aligned");
-    l3c_plan::Header h;
-    CODEC_TRY(l3c_plan::check_blob(c, d->plan_host, d->plan_bytes, &h, l3c::error_buffer(), 512));
-    L3C_REQUIRE(h.lag == 1 || (side_stream && side_stream != main_stream),
-                "a batch of 16 images or more decodes on two streams (lag 2): side_stream must be a stream of its own");
-    DecPlan p;
-    CODEC_TRY(dec_plan(c, h, &p));
-    if (d->workspace_bytes < p.bytes)
-        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
-
-    // ---- everything checked: enqueue
-    const int64_t B = h.B;
-    const int n_rec = (int)h.n_records, S = c.num_scales;
-    char *ws = base256(d->workspace);
-    const hipStream_t st = l3c::as_stream(main_stream);
-    const char *plan = static_cast<const char *>(d->plan);
-    const int64_t *src_off = reinterpret_cast<const int64_t *>(plan + h.src_off), *dst_off = reinterpret_cast<const int64_t *>(plan + h.dst_off);
-    const uint32_t *nbytes = reinterpret_cast<const uint32_t *>(plan + h.nbytes_off);
-    const char *plan_h = static_cast<const char *>(d->plan_host);
-    uint8_t *streams = reinterpret_cast<uint8_t *>(ws + p.streams);
-    int32_t *flags = reinterpret_cast<int32_t *>(ws + p.flags);
-    CODEC_TRY(l3c::check_hip(hipMemsetAsync(flags, 0, MAX_REC * 4, st), "hipMemsetAsync"));
-    for (int k = 0; k < n_rec; ++k)
-        for (int64_t a = h.rec[k].first, e = a + h.rec[k].n_streams; a < e; a += 65535) {
-            const int64_t n = e - a < 65535 ? e - a : 65535;
-            CODEC_TRY(l3c_container_read(d->files, src_off + a, dst_off + a, nbytes + a, n, (uint32_t)h.rec[k].max_nbytes, streams, main_stream));
-        }
-    int16_t *sym[MAX_REC];
-    for (int k = 0; k < n_rec; ++k) sym[k] = reinterpret_cast<int16_t *>(ws + p.sym[k]);
-    if (d->sym) sym[n_rec - 1] = d->sym;
-    float *bn = reinterpret_cast<float *>(ws + p.bn), *P = reinterpret_cast<float *>(ws + p.P);
-    char *scratch = ws + p.scratch;
-    {   // the coarsest record: the uniform prior
-        const l3c_plan::Record &r = h.rec[0];
-        CODEC_TRY(l3c_ac_decode(m.uniform_row, 0, c.L + 1, streams, dst_off + r.first, nbytes + r.first, B * r.C, r.H * r.W, 1, sym[0], main_stream));
-    }
-    for (int k = 1; k < n_rec; ++k) {
-        const l3c_plan::Record &r = h.rec[k], &above = h.rec[k - 1];
-        const int s = S - k;
-        const int64_t hw = r.H * r.W;
-        CODEC_TRY(l3c_sym_to_bn(sym[k - 1], B * above.C * above.H * above.W, m.z_bin_width, m.z_x_min, bn, main_stream));
-        l3c_net_get_p_desc g;
-        memset(&g, 0, sizeof(g));
-        g.cfg_host = &c;
-        g.packed = m.packed;
-        g.packed_bytes = m.packed_bytes;
-        g.net = s;
-        g.bn_q = bn;
-        g.B = B;
-        g.h = (int)above.H;
-        g.w = (int)above.W;
-        g.fuse = k == 1 ? nullptr : reinterpret_cast<const float *>(ws + p.F[k - 1]);
-        g.P = P;
-        g.F = s > 0 ? reinterpret_cast<float *>(ws + p.F[k]) : nullptr;      // the finest scale's features feed nothing
-        g.workspace = scratch;
-        g.workspace_bytes = p.getp_ws;
-        CODEC_TRY(l3c_net_get_p(&g, main_stream));
-        // P is complete: get_p's workspace is dead and holds this scale's tables from here on
-        if (s > 0) {     // a bottleneck scale: its channels are independent given P
-            for (int c0 = 0; c0 < (int)r.C; c0 += 8) {
-                const int n = (int)r.C - c0 < 8 ? (int)r.C - c0 : 8;
-                l3c_table_part tp[8];
-                l3c_ac_decode_part dp[8];
-                memset(dp, 0, sizeof(dp));
-                for (int i = 0; i < n; ++i) {
-                    const int ch = c0 + i;
-                    uint16_t *table = reinterpret_cast<uint16_t *>(scratch + ch * p.table_bytes[k]);
-                    tp[i] = l3c_table_part{ch, 0, hw, table, flags + k, nullptr};
-                    l3c_ac_decode_part &q = dp[i];
-                    q.cdf = table;
-                    q.Lp = c.L + 1;
-                    q.in = streams;
-                    q.in_offsets = dst_off + r.first + ch * B;
-                    q.in_nbytes = nbytes + r.first + ch * B;
-                    q.n_streams = B;
-                    q.n_sym = hw;
-                    q.not_monotone_flag = flags + k;
-                    q.final_chunk = 1;
-                    q.sym_out = sym[k];
-                    q.sym_stride = r.C * hw;
-                    q.sym_offset = ch * hw;
-                }
-                CODEC_TRY(l3c_dmll_cdf_table_parts(P, nullptr, m.targets_z, B, hw, (int)r.C, c.K, 0, c.L + 1, tp, n, main_stream));
-                CODEC_TRY(l3c_ac_decode_chunks(dp, n, main_stream));
-            }
-        } else {         // the RGB scale: the chunk pipeline
-            CODEC_TRY(l3c::check_hip(hipMemsetAsync(sym[k], 0, (size_t)(B * 3 * hw * 2), st), "hipMemsetAsync"));
-            l3c_rgb_decode_desc q;
-            memset(&q, 0, sizeof(q));
-            q.P = P;
-            q.targets = m.targets_rgb;
-            q.sym = sym[k];
-            q.B = B;
-            q.HW = hw;
-            q.K = c.K;
-            q.in = streams;
-            q.in_offsets = dst_off + r.first;
-            q.in_nbytes = nbytes + r.first;
-            q.n_chunks = (int)h.n_chunks;
-            q.chunk_pix0_host = reinterpret_cast<const int64_t *>(plan_h + h.chunk_pix0_off);
-            q.chunk_npix_host = reinterpret_cast<const int64_t *>(plan_h + h.chunk_npix_off);
-            q.lag = (int)h.lag;
-            q.window_mode = 1;
-            q.workspace = scratch;
-            q.workspace_bytes = p.rgb_ws;
-            CODEC_TRY(l3c_decode_rgb(&q, main_stream, h.lag == 2 ? side_stream : nullptr));
-        }
-    }
-    return l3c_sym_to_u8(sym[n_rec - 1], B * 3 * h.H * h.W, d->pixels, main_stream);
-}
-
-// ---- banded files ------------------------------------------------------------------------------------------------------------
-
-int l3c_container_layout_banded(const l3c_banded_scale *scales, int n_scales, int64_t B, int64_t file_stride, int64_t *file_offset,
-                                int64_t *file_bytes, l3c_stream_t stream) {
-    L3C_REQUIRE(scales && file_offset && file_bytes, "null pointer");
-    L3C_REQUIRE(n_scales > 0 && n_scales <= BandedLayoutArgs::MAX_SCALES, "1..8 scales");
-    L3C_REQUIRE(B > 0 && B < 65536, "bad batch size (1 .. 65535)");
-    const bool stride_ok = file_stride > 0 && file_stride % 16 == 0;
-    L3C_REQUIRE(stride_ok, "file_stride must be a positive multiple of 16");
-    L3C_REQUIRE(aligned16(file_offset) && aligned16(file_bytes), "every pointer must be 16-byte aligned");
-    BandedLayoutArgs a{};
-    a.n_scales = n_scales;
-    a.B = B;
-    a.file_stride = file_stride;
-    a.file_offset = file_offset;
-    a.file_bytes = file_bytes;
-    a.framing = 14;
-    for (int k = 0; k < n_scales; ++k) {
-        const l3c_banded_scale &q = scales[k];
-        L3C_REQUIRE(q.C > 0 && q.C < 256 && q.H > 0 && q.H < 65536 && q.W > 0 && q.W < 65536, "bad scale descriptor (C < 256, H and W fit u16)");
-        L3C_REQUIRE(q.band_len >= 64 && q.band_len % 64 == 0, "band_len must be a positive multiple of 64");
-        const int64_t n = ((int64_t)q.H * q.W + q.band_len - 1) / q.band_len;
-        L3C_REQUIRE(n <= l3c_plan::MAX_BANDS, "more than 1024 bands per channel");
-        L3C_REQUIRE(q.nbytes_last && (n == 1 || q.nbytes_full), "bad scale descriptor (null nbytes array)");
-        L3C_REQUIRE(((reinterpret_cast<uintptr_t>(q.nbytes_last) | (n == 1 ? 0 : reinterpret_cast<uintptr_t>(q.nbytes_full))) & 3) == 0,
-                    "nbytes arrays must be 4-byte aligned");
-        a.nb_full[k] = n == 1 ? nullptr : q.nbytes_full;
-        a.nb_last[k] = q.nbytes_last;
-        a.C[k] = q.C;
-        a.n[k] = n;
-        a.framing += 9 + 4 * q.C * n + 4;
-    }
-    return launch_layout_banded(a, stream);
-}
-
-int64_t l3c_encode_banded_file_stride(const l3c_net_config *cfg, int H, int W, int bands) {
-    CODEC_TRY(codec_config(cfg));
-    CODEC_TRY(check_sides(*cfg, H, W));
-    CODEC_TRY(check_bands(bands));
-    return banded_file_stride_of(*cfg, H, W, bands);
-}
-
-int64_t l3c_encode_batch_banded_workspace_bytes(const l3c_net_config *cfg, int64_t B, int H, int W, int bands) {
-    CODEC_TRY(codec_config(cfg));
-    CODEC_TRY(check_sides(*cfg, H, W));
-    CODEC_TRY(check_bands(bands));
-    EncBandPlan p;
-    CODEC_TRY(enc_band_plan(*cfg, B, H, W, bands, &p));
-    return p.bytes;
-}
-
-// l3c_encode_batch_banded in the same two halves
-static int enc_banded_check(const l3c_encode_batch_desc *d, int bands, EncBandPlan *plan) {
-    L3C_REQUIRE(d, "null descriptor");
-    CODEC_TRY(check_model(d->model_host));
-    const l3c_codec_model &m = *d->model_host;
-    const l3c_net_config &c = *m.cfg_host;
-    L3C_REQUIRE(d->img && d->files && d->file_bytes && d->workspace, "null pointer");
-    L3C_REQUIRE(aligned16(d->img) && aligned16(d->padding) && aligned16(d->files) && aligned16(d->file_bytes) && aligned16(d->workspace),
-                "every pointer must be 16-byte aligned");
-    L3C_REQUIRE(d->B > 0 && d->B < 65536, "bad batch size (1 .. 65535)");
-    CODEC_TRY(check_sides(c, d->H, d->W));
-    CODEC_TRY(check_bands(bands));
-    EncBandPlan p;
-    CODEC_TRY(enc_band_plan(c, d->B, d->H, d->W, bands, &p));
-    const int64_t stride = banded_file_stride_of(c, d->H, d->W, bands);
-    if (d->file_stride < stride || d->file_stride % 16)
-        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "file_stride %lld: must be a multiple of 16 and at least l3c_encode_banded_file_stride = %lld",
-                          (long long)d->file_stride, (long long)stride);
-    if (d->workspace_bytes < p.bytes)
-        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
-    *plan = p;
-    return L3C_OK;
-}
-
-static int enc_banded_run(const l3c_encode_batch_desc *d, const EncBandPlan &p, l3c_stream_t stream) {
-    const l3c_codec_model &m = *d->model_host;
-    const l3c_net_config &c = *m.cfg_host;
+int enc_banded_run(const l3c_encode_batch_desc *d, const EncPlan &p, l3c_stream_t stream) {
     const int64_t B = d->B;
     const int S = p.S;
     char *ws = base256(d->workspace);
-    const hipStream_t st = l3c::as_stream(stream);
-    const uint16_t *padding = d->padding;
-    if (!padding) {
-        CODEC_TRY(l3c::check_hip(hipMemsetAsync(ws + p.zero_pad, 0, (size_t)B * 8, st), "hipMemsetAsync"));
-        padding = reinterpret_cast<const uint16_t *>(ws + p.zero_pad);
-    }
-    const float zero_mean[3] = {0.f, 0.f, 0.f};
-    float *img = reinterpret_cast<float *>(ws + p.img);
-    CODEC_TRY(l3c_u8_to_sym_bn(d->img, zero_mean, B, p.hw[0], reinterpret_cast<int16_t *>(ws + p.sym[0]), img, stream));
     l3c_net_forward_desc f;
-    memset(&f, 0, sizeof(f));
-    f.cfg_host = &c;
-    f.packed = m.packed;
-    f.packed_bytes = m.packed_bytes;
-    f.img = img;
-    f.B = B;
-    f.H = d->H;
-    f.W = d->W;
-    for (int s = 0; s <= S; ++s) {
-        f.sym[s] = reinterpret_cast<int16_t *>(ws + p.sym[s]);
-        if (s) f.bn_q[s] = reinterpret_cast<float *>(ws + p.bn_q[s]);
-        if (s < S) f.P[s] = reinterpret_cast<float *>(ws + p.P[s]);
-    }
-    f.workspace = ws + p.scratch;
-    f.workspace_bytes = p.net_ws;
-    CODEC_TRY(l3c_net_forward(&f, stream));
+    CODEC_TRY(enc_forward(d, p, ws, stream, &f));
 
     // the forward's workspace is dead.  Scales coarsest first (file order): the interval head into the one interval buffer, then its bands
     // re-laid into the scale's two coder groups -- the full bands (absent when n == 1) and the last bands
@@ -827,11 +417,7 @@ static int enc_banded_run(const l3c_encode_batch_desc *d, const EncBandPlan &p, 
     for (int k = 0; k <= S; ++k) {
         const int s = S - k;
         const int64_t streams = B * p.Cs[s];
-        if (s == S)
-            CODEC_TRY(l3c_ac_intervals_from_table(m.uniform_row, 0, c.L + 1, f.sym[s], streams, p.hw[s], iv, stream));
-        else
-            CODEC_TRY(l3c_dmll_encode_intervals(f.P[s], f.sym[s], s == 0 ? m.targets_rgb : m.targets_z, B, p.hw[s], p.Cs[s], c.K, s == 0,
-                                                s == 0 ? 257 : c.L + 1, iv, stream));
+        CODEC_TRY(enc_intervals(*d->model_host, f, p, s, iv, stream));
         const bool full = p.n[s] > 1;
         uint32_t *iv_f = full ? reinterpret_cast<uint32_t *>(cs + p.iv_f[s]) : nullptr, *iv_l = reinterpret_cast<uint32_t *>(cs + p.iv_l[s]);
         CODEC_TRY(l3c_ac_band_intervals(iv, streams, p.hw[s], p.L[s], iv_f, iv_l, stream));
@@ -851,20 +437,447 @@ static int enc_banded_run(const l3c_encode_batch_desc *d, const EncBandPlan &p, 
     CODEC_TRY(l3c_ac_encode_groups(groups, n_groups, cs + p.ac_ws, stream));
     // file sizes and offsets; a band that overran (L3C_AC_OVERRUN) marks its file -1 and is written as an empty payload, so that the
     // writer below stays inside the file's slot whatever the coder reported
-    int64_t *file_offset = reinterpret_cast<int64_t *>(ws + p.file_offset);
-    la.n_scales = S + 1;
+    layout_batch(la, S + 1, B, d->file_stride, reinterpret_cast<int64_t *>(ws + p.file_offset), d->file_bytes);
     la.framing = p.framing;
-    la.B = B;
-    la.file_stride = d->file_stride;
-    la.file_offset = file_offset;
-    la.file_bytes = d->file_bytes;
     CODEC_TRY(launch_layout_banded(la, stream));
-    return l3c_container_write_banded(scales, S + 1, B, padding, file_offset, d->files, cs + p.pos, B * p.streams_per_image * 8, stream);
+    const uint16_t *padding = d->padding ? d->padding : reinterpret_cast<const uint16_t *>(ws + p.zero_pad);
+    return l3c_container_write_banded(scales, S + 1, B, padding, la.file_offset, d->files, cs + p.pos, B * p.streams_per_image * 8, stream);
+}
+
+// ---- decode: one plan, one check and one walk over either plan header --------------------------------------------------------------
+
+using l3c_plan::BandedHeader, l3c_plan::Header;
+
+struct DecPlan {
+    int64_t streams, sym[MAX_REC], bn, F[MAX_REC], P, flags, scratch, table_bytes[MAX_REC], getp_ws, rgb_ws;
+    int64_t bytes;
+};
+
+// what differs between the two headers before the walk: the parser of the blob, the RGB record's workspace, the rule of the side stream
+inline int check_blob_of(const l3c_net_config &c, const void *plan_host, int64_t cap, Header *h) {
+    return l3c_plan::check_blob(c, plan_host, cap, h, l3c::error_buffer(), 512);
+}
+inline int check_blob_of(const l3c_net_config &c, const void *plan_host, int64_t cap, BandedHeader *h) {
+    return l3c_plan::check_blob_banded(c, plan_host, cap, h, l3c::error_buffer(), 512);
+}
+inline int64_t rgb_ws_of(const Header &h) { return l3c_decode_rgb_workspace_bytes(h.B, h.max_chunk_npix, (int)h.n_chunks, (int)h.lag); }
+inline int64_t rgb_ws_of(const BandedHeader &h) {
+    return l3c_decode_rgb_banded_workspace_bytes(h.B, h.H * h.W, h.rgb_band_len, (int)h.rgb_chunks, (int)h.lag);
+}
+inline const char *lag_rule_of(const Header &) {
+    return "a batch of 16 images or more decodes on two streams (lag 2): side_stream must be a stream of its own";
+}
+inline const char *lag_rule_of(const BandedHeader &) {
+    return "16 bands per channel or more decode on two streams (lag 2): side_stream must be a stream of its own";
+}
+
+template <class Hdr>
+int dec_plan(const l3c_net_config &c, const Hdr &h, DecPlan *out) {
+    DecPlan p{};
+    const int S = c.num_scales, n_rec = (int)h.n_records;
+    const int64_t B = h.B, rgb_ws = rgb_ws_of(h);          // negative: a bad plan
+    int64_t at = 0, scratch = 0;
+    p.streams = take(at, h.dst_bytes);
+    int64_t bn = 0, P = 0;
+    for (int k = 0; k < n_rec; ++k) {
+        const auto &r = h.rec[k];
+        const int64_t hw = r.H * r.W;
+        if (r.H < 1 || r.W < 1 || r.C < 1 || r.C > 8 || (k && (r.H != 2 * h.rec[k - 1].H || r.W != 2 * h.rec[k - 1].W)))
+            return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent record %d", k);
+        p.sym[k] = take(at, B * r.C * hw * 2);         // (the finest record's: unused when the caller takes the symbols)
+        if (k + 1 < n_rec) bn = B * r.C * hw * 4 > bn ? B * r.C * hw * 4 : bn;
+        if (k) {
+            const int s = S - k;                       // the network that predicts this record
+            const int64_t ws = l3c_net_get_p_workspace_bytes(&c, B, (int)h.rec[k - 1].H, (int)h.rec[k - 1].W);
+            if (ws < 0) return (int)ws;
+            p.getp_ws = ws > p.getp_ws ? ws : p.getp_ws;
+            const int64_t Pk = B * hw * kp_of(c, s) * 4;
+            P = Pk > P ? Pk : P;
+            if (s > 0) {
+                p.F[k] = take(at, B * hw * c.Cf * 4);
+                p.table_bytes[k] = up(B * hw * (c.L + 1) * 2);
+                scratch = r.C * p.table_bytes[k] > scratch ? r.C * p.table_bytes[k] : scratch;
+            }
+        }
+    }
+    if (h.rec[n_rec - 1].H != h.H || h.rec[n_rec - 1].W != h.W) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent image size");
+    p.bn = take(at, bn);
+    p.P = take(at, P);
+    p.flags = take(at, MAX_REC * 4);
+    p.rgb_ws = rgb_ws;
+    if (p.rgb_ws < 0) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: bad chunk list");
+    scratch = p.getp_ws > scratch ? p.getp_ws : scratch;
+    scratch = p.rgb_ws > scratch ? p.rgb_ws : scratch;
+    p.scratch = at;                                    // get_p's workspace, then the scale's tables / the RGB pipeline's workspace
+    p.bytes = at + up(scratch) + ALIGN;
+    *out = p;
+    return L3C_OK;
+}
+
+// the tail of l3c_decode_plan / l3c_decode_plan_banded: the header's sizes against the network schedule itself (the planners restate
+// its limits; this is the schedule's own answer)
+template <class Hdr>
+int plan_recheck(const l3c_net_config &c, void *plan_host) {
+    Hdr h;
+    memcpy(&h, plan_host, sizeof(h));
+    DecPlan p;
+    if (dec_plan(c, h, &p) == L3C_OK) return L3C_OK;
+    char why[400];
+    snprintf(why, sizeof(why), "%s", l3c::error_buffer());
+    memset(plan_host, 0, sizeof(int64_t));     // no plan
+    return CODEC_FAIL(L3C_ERR_INVALID_ARG, "invalid file: %lld x %lld pixels: %s", (long long)h.H, (long long)h.W, why);
+}
+
+template <class Hdr>
+int64_t dec_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) {
+    CODEC_TRY(codec_config(cfg));
+    Hdr h;
+    CODEC_TRY(check_blob_of(*cfg, plan_host, -1, &h));
+    DecPlan p;
+    CODEC_TRY(dec_plan(*cfg, h, &p));
+    return p.bytes;
+}
+
+template <class Hdr>
+int dec_check(const l3c_decode_batch_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream, Hdr *hdr, DecPlan *plan) {
+    L3C_REQUIRE(d, "null descriptor");
+    CODEC_TRY(check_model(d->model_host));
+    const l3c_net_config &c = *d->model_host->cfg_host;
+    L3C_REQUIRE(d->files && d->plan_host && d->plan && d->pixels && d->workspace, "null pointer");
+    L3C_REQUIRE(aligned16(d->files) && aligned16(d->plan) && aligned16(d->pixels) && aligned16(d->sym) && aligned16(d->workspace),
+                "every pointer must be 16-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(d->plan_host) & 7) == 0, "plan_host must be 8-byte aligned");
+    Hdr &h = *hdr;
+    CODEC_TRY(check_blob_of(c, d->plan_host, d->plan_bytes, &h));
+    L3C_REQUIRE(h.lag == 1 || (side_stream && side_stream != main_stream), lag_rule_of(h));
+    CODEC_TRY(dec_plan(c, h, plan));
+    if (d->workspace_bytes < plan->bytes)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)plan->bytes);
+    return L3C_OK;
+}
+
+// what the steps of the walk read
+struct DecWalk {
+    const l3c_codec_model &m;
+    const l3c_net_config &c;
+    const DecPlan &p;
+    const char *plan, *plan_h;                 // the blob on the device and on the host
+    const int64_t *dst_off;                    // of the blob: where the streams lie in `streams`, and how long they are
+    const uint32_t *nbytes;
+    uint8_t *streams;                          // of the workspace
+    int32_t *flags;
+    float *P;
+    char *scratch;
+    l3c_stream_t main_stream, side_stream;
+    int16_t *sym[MAX_REC];
+};
+
+// the coarsest record: the uniform prior
+int dec_coarsest(const DecWalk &x, const Header &h) {
+    const l3c_plan::Record &r = h.rec[0];
+    return l3c_ac_decode(x.m.uniform_row, 0, x.c.L + 1, x.streams, x.dst_off + r.first, x.nbytes + r.first, h.B * r.C, r.H * r.W, 1, x.sym[0], x.main_stream);
+}
+
+// ... every band of every plane in one launch
+int dec_coarsest(const DecWalk &x, const BandedHeader &h) {
+    const l3c_plan::BandedRecord &r = h.rec[0];
+    return l3c_ac_decode_bands(x.m.uniform_row, x.c.L + 1, x.streams, x.dst_off + r.first, x.nbytes + r.first, h.B * r.C, r.H * r.W, r.L, 1, x.sym[0],
+                               x.main_stream);
+}
+
+// channel ch of bottleneck record k: its table in the scratch, and the decoder part of its n_streams streams from `first` on
+inline uint16_t *table_of(const DecWalk &x, int k, int ch) { return reinterpret_cast<uint16_t *>(x.scratch + ch * x.p.table_bytes[k]); }
+
+l3c_ac_decode_part decode_part_of(const DecWalk &x, int k, int ch, int64_t first, int64_t n_streams, int64_t n_sym) {
+    l3c_ac_decode_part q;
+    memset(&q, 0, sizeof(q));
+    q.cdf = table_of(x, k, ch);
+    q.Lp = x.c.L + 1;
+    q.in = x.streams;
+    q.in_offsets = x.dst_off + first;
+    q.in_nbytes = x.nbytes + first;
+    q.n_streams = n_streams;
+    q.n_sym = n_sym;
+    q.not_monotone_flag = x.flags + k;
+    q.final_chunk = 1;
+    q.sym_out = x.sym[k];
+    return q;
+}
+
+// a bottleneck record: its channels are independent given P.  get_p's workspace is dead and holds the record's tables
+int dec_bottleneck(const DecWalk &x, const Header &h, int k) {
+    const l3c_plan::Record &r = h.rec[k];
+    const l3c_net_config &c = x.c;
+    const int64_t B = h.B, hw = r.H * r.W;
+    for (int c0 = 0; c0 < (int)r.C; c0 += 8) {
+        const int n = (int)r.C - c0 < 8 ? (int)r.C - c0 : 8;
+        l3c_table_part tp[8];
+        l3c_ac_decode_part dp[8];
+        for (int i = 0; i < n; ++i) {
+            const int ch = c0 + i;
+            tp[i] = l3c_table_part{ch, 0, hw, table_of(x, k, ch), x.flags + k, nullptr};
+            l3c_ac_decode_part &q = dp[i] = decode_part_of(x, k, ch, r.first + ch * B, B, hw);
+            q.sym_stride = r.C * hw;
+            q.sym_offset = ch * hw;
+        }
+        CODEC_TRY(l3c_dmll_cdf_table_parts(x.P, nullptr, x.m.targets_z, B, hw, (int)r.C, c.K, 0, c.L + 1, tp, n, x.main_stream));
+        CODEC_TRY(l3c_ac_decode_chunks(dp, n, x.main_stream));
+    }
+    return L3C_OK;
+}
+
+// ... every band (b, j) a ragged entry
+int dec_bottleneck(const DecWalk &x, const BandedHeader &h, int k) {
+    const l3c_plan::BandedRecord &r = h.rec[k];
+    const l3c_net_config &c = x.c;
+    const int Lp = c.L + 1;
+    const int64_t B = h.B, hw = r.H * r.W;
+    const int64_t E = B * r.n, max_npix = r.L < hw ? r.L : hw;
+    const int64_t *ent = reinterpret_cast<const int64_t *>(x.plan + h.entries_off[k]);      // pixbase | hw | pix0 | npix | table_off
+    const l3c_ragged_batch batch{E, hw, ent, ent + E};
+    for (int c0 = 0; c0 < (int)r.C; c0 += 8) {
+        const int n = (int)r.C - c0 < 8 ? (int)r.C - c0 : 8;
+        l3c_table_part tp[8];
+        l3c_ragged_part rp[8];
+        l3c_ac_decode_part dp[8];
+        for (int i = 0; i < n; ++i) {
+            const int ch = c0 + i;
+            tp[i] = l3c_table_part{ch, 0, max_npix, table_of(x, k, ch), x.flags + k, nullptr};
+            rp[i] = l3c_ragged_part{ent + 2 * E, ent + 3 * E, ent + 4 * E};
+            l3c_ac_decode_part &q = dp[i] = decode_part_of(x, k, ch, r.first + ch * E, E, max_npix);
+            q.r_npix = ent + 3 * E;
+            q.r_table_off = ent + 4 * E;
+            q.r_pixbase = ent;
+            q.r_hw = ent + E;
+            q.r_pix0 = ent + 2 * E;
+            q.r_C = (int)r.C;
+            q.r_c = ch;
+            q.r_table_bytes = B * hw * Lp * 2;
+        }
+        CODEC_TRY(l3c_dmll_cdf_table_ragged(x.P, nullptr, x.m.targets_z, &batch, (int)r.C, c.K, 0, Lp, tp, rp, n, x.main_stream));
+        CODEC_TRY(l3c_ac_decode_chunks(dp, n, x.main_stream));
+    }
+    return L3C_OK;
+}
+
+// the RGB record: what either pipeline's descriptor says of it
+template <class Desc, class Hdr>
+void rgb_desc_of(const DecWalk &x, const Hdr &h, int k, Desc *out) {
+    const auto &r = h.rec[k];
+    Desc &q = *out;
+    memset(&q, 0, sizeof(q));
+    q.P = x.P;
+    q.targets = x.m.targets_rgb;
+    q.sym = x.sym[k];
+    q.B = h.B;
+    q.HW = r.H * r.W;
+    q.K = x.c.K;
+    q.in = x.streams;
+    q.in_offsets = x.dst_off + r.first;
+    q.in_nbytes = x.nbytes + r.first;
+    q.lag = (int)h.lag;
+    q.window_mode = 1;
+    q.workspace = x.scratch;
+    q.workspace_bytes = x.p.rgb_ws;
+}
+
+// the chunk pipeline
+int dec_rgb(const DecWalk &x, const Header &h, int k) {
+    l3c_rgb_decode_desc q;
+    rgb_desc_of(x, h, k, &q);
+    q.n_chunks = (int)h.n_chunks;
+    q.chunk_pix0_host = reinterpret_cast<const int64_t *>(x.plan_h + h.chunk_pix0_off);
+    q.chunk_npix_host = reinterpret_cast<const int64_t *>(x.plan_h + h.chunk_npix_off);
+    return l3c_decode_rgb(&q, x.main_stream, h.lag == 2 ? x.side_stream : nullptr);
+}
+
+// ... over all B n bands of each channel in lock step
+int dec_rgb(const DecWalk &x, const BandedHeader &h, int k) {
+    l3c_rgb_banded_desc q;
+    rgb_desc_of(x, h, k, &q);
+    q.band_len = h.rgb_band_len;
+    q.n_chunks = (int)h.rgb_chunks;
+    return l3c_decode_rgb_banded(&q, x.main_stream, h.lag == 2 ? x.side_stream : nullptr);
+}
+
+// the walk over the records of a checked plan: nothing below fails on an argument
+template <class Hdr>
+int dec_run(const l3c_decode_batch_desc *d, const Hdr &h, const DecPlan &p, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    const l3c_codec_model &m = *d->model_host;
+    const l3c_net_config &c = *m.cfg_host;
+    const int64_t B = h.B;
+    const int n_rec = (int)h.n_records, S = c.num_scales;
+    char *ws = base256(d->workspace);
+    const hipStream_t st = l3c::as_stream(main_stream);
+    const char *plan = static_cast<const char *>(d->plan);
+    const int64_t *src_off = reinterpret_cast<const int64_t *>(plan + h.src_off);
+    DecWalk x{m, c, p, plan, static_cast<const char *>(d->plan_host), reinterpret_cast<const int64_t *>(plan + h.dst_off),
+              reinterpret_cast<const uint32_t *>(plan + h.nbytes_off), reinterpret_cast<uint8_t *>(ws + p.streams),
+              reinterpret_cast<int32_t *>(ws + p.flags), reinterpret_cast<float *>(ws + p.P), ws + p.scratch, main_stream, side_stream, {}};
+    CODEC_TRY(l3c::check_hip(hipMemsetAsync(x.flags, 0, MAX_REC * 4, st), "hipMemsetAsync"));
+    for (int k = 0; k < n_rec; ++k)
+        for (int64_t a = h.rec[k].first, e = a + h.rec[k].n_streams; a < e; a += 65535) {
+            const int64_t n = e - a < 65535 ? e - a : 65535;
+            CODEC_TRY(l3c_container_read(d->files, src_off + a, x.dst_off + a, x.nbytes + a, n, (uint32_t)h.rec[k].max_nbytes, x.streams, main_stream));
+        }
+    for (int k = 0; k < n_rec; ++k) x.sym[k] = reinterpret_cast<int16_t *>(ws + p.sym[k]);
+    if (d->sym) x.sym[n_rec - 1] = d->sym;
+    float *bn = reinterpret_cast<float *>(ws + p.bn);
+    CODEC_TRY(dec_coarsest(x, h));
+    for (int k = 1; k < n_rec; ++k) {
+        const auto &r = h.rec[k], &above = h.rec[k - 1];
+        const int s = S - k;
+        CODEC_TRY(l3c_sym_to_bn(x.sym[k - 1], B * above.C * above.H * above.W, m.z_bin_width, m.z_x_min, bn, main_stream));
+        l3c_net_get_p_desc g;
+        memset(&g, 0, sizeof(g));
+        g.cfg_host = &c;
+        g.packed = m.packed;
+        g.packed_bytes = m.packed_bytes;
+        g.net = s;
+        g.bn_q = bn;
+        g.B = B;
+        g.h = (int)above.H;
+        g.w = (int)above.W;
+        g.fuse = k == 1 ? nullptr : reinterpret_cast<const float *>(ws + p.F[k - 1]);
+        g.P = x.P;
+        g.F = s > 0 ? reinterpret_cast<float *>(ws + p.F[k]) : nullptr;      // the finest scale's features feed nothing
+        g.workspace = x.scratch;
+        g.workspace_bytes = p.getp_ws;
+        CODEC_TRY(l3c_net_get_p(&g, main_stream));
+        // P is complete: get_p's workspace is dead and holds this record's tables / the RGB pipeline's workspace from here on
+        if (s == 0) CODEC_TRY(l3c::check_hip(hipMemsetAsync(x.sym[k], 0, (size_t)(B * 3 * r.H * r.W * 2), st), "hipMemsetAsync"));
+        CODEC_TRY(s > 0 ? dec_bottleneck(x, h, k) : dec_rgb(x, h, k));
+    }
+    return l3c_sym_to_u8(x.sym[n_rec - 1], B * 3 * h.H * h.W, d->pixels, main_stream);
+}
+
+template <class Hdr>
+int dec_batch(const l3c_decode_batch_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    Hdr h;
+    DecPlan p;
+    CODEC_TRY(dec_check(d, main_stream, side_stream, &h, &p));
+    return dec_run(d, h, p, main_stream, side_stream);     // everything checked: enqueue
+}
+
+// which of the two decoders reads a plan blob (its first word), and the batch and padded image size it was made for: the checked header's
+int plan_dims(const l3c_net_config &c, const void *plan_host, int64_t plan_bytes, bool *banded, int64_t *B, int64_t *H, int64_t *W) {
+    L3C_REQUIRE(plan_host, "null pointer: plan_host");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(plan_host) & 7) == 0, "plan_host must be 8-byte aligned");
+    int64_t magic;
+    memcpy(&magic, plan_host, sizeof(magic));
+    *banded = magic == l3c_plan::BANDED_MAGIC;
+    auto dims = [&](auto h) {
+        CODEC_TRY(check_blob_of(c, plan_host, plan_bytes, &h));
+        *B = h.B, *H = h.H, *W = h.W;
+        return (int)L3C_OK;
+    };
+    return *banded ? dims(BandedHeader{}) : dims(Header{});
+}
+
+// the size functions of an encode (bands 0: legacy): the file stride, or the workspace of a batch
+int64_t enc_size(const l3c_net_config *cfg, int64_t B, int H, int W, bool banded, int bands, bool workspace) {
+    CODEC_TRY(codec_config(cfg));
+    CODEC_TRY(check_sides(*cfg, H, W));
+    if (banded) CODEC_TRY(check_bands(bands));
+    if (!workspace) return file_stride_of(*cfg, H, W, bands);
+    EncPlan p;
+    CODEC_TRY(enc_plan(*cfg, B, H, W, bands, &p));
+    return p.bytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+int l3c_container_layout(const l3c_container_scale *scales, int n_scales, int64_t B, int64_t file_stride, int64_t *file_offset,
+                         int64_t *file_bytes, l3c_stream_t stream) {
+    CODEC_TRY(check_layout_args(scales, n_scales, B, file_stride, file_offset, file_bytes));
+    LayoutArgs a{};
+    layout_batch(a, n_scales, B, file_stride, file_offset, file_bytes);
+    for (int k = 0; k < n_scales; ++k) {
+        L3C_REQUIRE(scales[k].nbytes && scales[k].C > 0 && scales[k].C < 256, "bad scale descriptor");
+        L3C_REQUIRE((reinterpret_cast<uintptr_t>(scales[k].nbytes) & 3) == 0, "nbytes arrays must be 4-byte aligned");
+        a.nbytes[k] = scales[k].nbytes;
+        a.C[k] = scales[k].C;
+    }
+    return launch_layout(a, stream);
+}
+
+int l3c_container_layout_banded(const l3c_banded_scale *scales, int n_scales, int64_t B, int64_t file_stride, int64_t *file_offset,
+                                int64_t *file_bytes, l3c_stream_t stream) {
+    CODEC_TRY(check_layout_args(scales, n_scales, B, file_stride, file_offset, file_bytes));
+    BandedLayoutArgs a{};
+    layout_batch(a, n_scales, B, file_stride, file_offset, file_bytes);
+    a.framing = 14;
+    for (int k = 0; k < n_scales; ++k) {
+        const l3c_banded_scale &q = scales[k];
+        L3C_REQUIRE(q.C > 0 && q.C < 256 && q.H > 0 && q.H < 65536 && q.W > 0 && q.W < 65536, "bad scale descriptor (C < 256, H and W fit u16)");
+        L3C_REQUIRE(q.band_len >= 64 && q.band_len % 64 == 0, "band_len must be a positive multiple of 64");
+        const int64_t n = ((int64_t)q.H * q.W + q.band_len - 1) / q.band_len;
+        L3C_REQUIRE(n <= l3c_plan::MAX_BANDS, "more than 1024 bands per channel");
+        L3C_REQUIRE(q.nbytes_last && (n == 1 || q.nbytes_full), "bad scale descriptor (null nbytes array)");
+        L3C_REQUIRE(((reinterpret_cast<uintptr_t>(q.nbytes_last) | (n == 1 ? 0 : reinterpret_cast<uintptr_t>(q.nbytes_full))) & 3) == 0,
+                    "nbytes arrays must be 4-byte aligned");
+        a.nb_full[k] = n == 1 ? nullptr : q.nbytes_full;
+        a.nb_last[k] = q.nbytes_last;
+        a.C[k] = q.C;
+        a.n[k] = n;
+        a.framing += 9 + 4 * q.C * n + 4;
+    }
+    return launch_layout_banded(a, stream);
+}
+
+int l3c_sym_to_u8(const int16_t *sym, int64_t n, uint8_t *out, l3c_stream_t stream) {
+    L3C_REQUIRE(sym && out, "null pointer");
+    L3C_REQUIRE(n > 0, "empty input");
+    L3C_REQUIRE(aligned16(sym) && aligned16(out), "every pointer must be 16-byte aligned");
+    const int64_t blocks = ((n >> 4) + 255) / 256;
+    hipLaunchKernelGGL(sym_to_u8_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks))), dim3(256), 0,
+                       l3c::as_stream(stream), sym, n, out);
+    return l3c::check_launch("sym_to_u8_kernel");
+}
+
+int64_t l3c_encode_file_stride(const l3c_net_config *cfg, int H, int W) { return enc_size(cfg, 0, H, W, false, 0, false); }
+
+int64_t l3c_encode_batch_workspace_bytes(const l3c_net_config *cfg, int64_t B, int H, int W) { return enc_size(cfg, B, H, W, false, 0, true); }
+
+int l3c_encode_batch(const l3c_encode_batch_desc *d, l3c_stream_t stream) {
+    EncPlan p;
+    CODEC_TRY(enc_check_desc(d, false, 0, &p));
+    return enc_run(d, p, stream);     // everything checked: enqueue
+}
+
+int64_t l3c_decode_plan_bytes(const l3c_net_config *cfg, int64_t B) {
+    CODEC_TRY(codec_config(cfg));
+    if (B < 1 || B >= 65536) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "bad batch size: B = %lld, must be 1 .. 65535", (long long)B);
+    return l3c_plan::plan_bytes(*cfg, B);
+}
+
+int l3c_decode_plan(const l3c_net_config *cfg, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B, void *plan_host,
+                    int64_t plan_bytes, int *H_out, int *W_out, uint16_t *padding_host_out) {
+    CODEC_TRY(codec_config(cfg));
+    CODEC_TRY(l3c_plan::make_plan(cfg, files_host, file_offset_host, B, plan_host, plan_bytes, H_out, W_out, padding_host_out,
+                                  l3c::error_buffer(), 512));
+    return plan_recheck<Header>(*cfg, plan_host);
+}
+
+int64_t l3c_decode_batch_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) { return dec_workspace_bytes<Header>(cfg, plan_host); }
+
+int l3c_decode_batch(const l3c_decode_batch_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    return dec_batch<Header>(d, main_stream, side_stream);
+}
+
+// ---- banded files ------------------------------------------------------------------------------------------------------------
+
+int64_t l3c_encode_banded_file_stride(const l3c_net_config *cfg, int H, int W, int bands) { return enc_size(cfg, 0, H, W, true, bands, false); }
+
+int64_t l3c_encode_batch_banded_workspace_bytes(const l3c_net_config *cfg, int64_t B, int H, int W, int bands) {
+    return enc_size(cfg, B, H, W, true, bands, true);
 }
 
 int l3c_encode_batch_banded(const l3c_encode_batch_desc *d, int bands, l3c_stream_t stream) {
-    EncBandPlan p;
-    CODEC_TRY(enc_banded_check(d, bands, &p));
+    EncPlan p;
+    CODEC_TRY(enc_check_desc(d, true, bands, &p));
     return enc_banded_run(d, p, stream);     // everything checked: enqueue
 }
 
@@ -878,156 +891,15 @@ int l3c_decode_plan_banded(const l3c_net_config *cfg, const uint8_t *files_host,
     CODEC_TRY(codec_config(cfg));
     CODEC_TRY(l3c_plan::make_plan_banded(cfg, files_host, file_offset_host, B, plan_host, plan_bytes, H_out, W_out, padding_host_out,
                                          l3c::error_buffer(), 512));
-    // the header's sizes against the network schedule itself, as l3c_decode_plan does
-    l3c_plan::BandedHeader h;
-    memcpy(&h, plan_host, sizeof(h));
-    DecPlan p;
-    const int rc = dec_plan_banded(*cfg, h, &p);
-    if (rc != L3C_OK) {
-        char why[400];
-        snprintf(why, sizeof(why), "%s", l3c::error_buffer());
-        memset(plan_host, 0, sizeof(int64_t));     // no plan
-        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "invalid file: %lld x %lld pixels: %s", (long long)h.H, (long long)h.W, why);
-    }
-    return L3C_OK;
+    return plan_recheck<BandedHeader>(*cfg, plan_host);
 }
 
 int64_t l3c_decode_batch_banded_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) {
-    CODEC_TRY(codec_config(cfg));
-    l3c_plan::BandedHeader h;
-    CODEC_TRY(l3c_plan::check_blob_banded(*cfg, plan_host, -1, &h, l3c::error_buffer(), 512));
-    DecPlan p;
-    CODEC_TRY(dec_plan_banded(*cfg, h, &p));
-    return p.bytes;
+    return dec_workspace_bytes<BandedHeader>(cfg, plan_host);
 }
 
 int l3c_decode_batch_banded(const l3c_decode_batch_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
-    L3C_REQUIRE(d, "null descriptor");
-    CODEC_TRY(check_model(d->model_host));
-    const l3c_codec_model &m = *d->model_host;
-    const l3c_net_config &c = *m.cfg_host;
-    L3C_REQUIRE(d->files && d->plan_host && d->plan && d->pixels && d->workspace, "null pointer");
-    L3C_REQUIRE(aligned16(d->files) && aligned16(d->plan) && aligned16(d->pixels) && aligned16(d->sym) && aligned16(d->workspace),
-                "every pointer must be 16-byte aligned");
-    L3C_REQUIRE((reinterpret_cast<uintptr_t>(d->plan_host) & 7) == 0, "plan_host must be 8-byte aligned");
-    l3c_plan::BandedHeader h;
-    CODEC_TRY(l3c_plan::check_blob_banded(c, d->plan_host, d->plan_bytes, &h, l3c::error_buffer(), 512));
-    L3C_REQUIRE(h.lag == 1 || (side_stream && side_stream != main_stream),
-                "16 bands per channel or more decode on two streams (lag 2): side_stream must be a stream of its own");
-    DecPlan p;
-    CODEC_TRY(dec_plan_banded(c, h, &p));
-    if (d->workspace_bytes < p.bytes)
-        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
-
-    // ---- everything checked: enqueue
-    const int64_t B = h.B;
-    const int n_rec = (int)h.n_records, S = c.num_scales, Lp = c.L + 1;
-    char *ws = base256(d->workspace);
-    const hipStream_t st = l3c::as_stream(main_stream);
-    const char *plan = static_cast<const char *>(d->plan);
-    const int64_t *src_off = reinterpret_cast<const int64_t *>(plan + h.src_off), *dst_off = reinterpret_cast<const int64_t *>(plan + h.dst_off);
-    const uint32_t *nbytes = reinterpret_cast<const uint32_t *>(plan + h.nbytes_off);
-    uint8_t *streams = reinterpret_cast<uint8_t *>(ws + p.streams);
-    int32_t *flags = reinterpret_cast<int32_t *>(ws + p.flags);
-    CODEC_TRY(l3c::check_hip(hipMemsetAsync(flags, 0, MAX_REC * 4, st), "hipMemsetAsync"));
-    for (int k = 0; k < n_rec; ++k)
-        for (int64_t a = h.rec[k].first, e = a + h.rec[k].n_streams; a < e; a += 65535) {
-            const int64_t n = e - a < 65535 ? e - a : 65535;
-            CODEC_TRY(l3c_container_read(d->files, src_off + a, dst_off + a, nbytes + a, n, (uint32_t)h.rec[k].max_nbytes, streams, main_stream));
-        }
-    int16_t *sym[MAX_REC];
-    for (int k = 0; k < n_rec; ++k) sym[k] = reinterpret_cast<int16_t *>(ws + p.sym[k]);
-    if (d->sym) sym[n_rec - 1] = d->sym;
-    float *bn = reinterpret_cast<float *>(ws + p.bn), *P = reinterpret_cast<float *>(ws + p.P);
-    char *scratch = ws + p.scratch;
-    {   // the coarsest record: the uniform prior, every band of every plane in one launch
-        const l3c_plan::BandedRecord &r = h.rec[0];
-        CODEC_TRY(l3c_ac_decode_bands(m.uniform_row, Lp, streams, dst_off + r.first, nbytes + r.first, B * r.C, r.H * r.W, r.L, 1, sym[0],
-                                      main_stream));
-    }
-    for (int k = 1; k < n_rec; ++k) {
-        const l3c_plan::BandedRecord &r = h.rec[k], &above = h.rec[k - 1];
-        const int s = S - k;
-        const int64_t hw = r.H * r.W;
-        CODEC_TRY(l3c_sym_to_bn(sym[k - 1], B * above.C * above.H * above.W, m.z_bin_width, m.z_x_min, bn, main_stream));
-        l3c_net_get_p_desc g;
-        memset(&g, 0, sizeof(g));
-        g.cfg_host = &c;
-        g.packed = m.packed;
-        g.packed_bytes = m.packed_bytes;
-        g.net = s;
-        g.bn_q = bn;
-        g.B = B;
-        g.h = (int)above.H;
-        g.w = (int)above.W;
-        g.fuse = k == 1 ? nullptr : reinterpret_cast<const float *>(ws + p.F[k - 1]);
-        g.P = P;
-        g.F = s > 0 ? reinterpret_cast<float *>(ws + p.F[k]) : nullptr;      // the finest scale's features feed nothing
-        g.workspace = scratch;
-        g.workspace_bytes = p.getp_ws;
-        CODEC_TRY(l3c_net_get_p(&g, main_stream));
-        // P is complete: get_p's workspace is dead and holds this scale's tables from here on
-        if (s > 0) {     // a bottleneck scale: every band (b, j) a ragged entry, the channels independent given P
-            const int64_t E = B * r.n, max_npix = r.L < hw ? r.L : hw;
-            const int64_t *ent = reinterpret_cast<const int64_t *>(plan + h.entries_off[k]);      // pixbase | hw | pix0 | npix | table_off
-            const l3c_ragged_batch batch{E, hw, ent, ent + E};
-            for (int c0 = 0; c0 < (int)r.C; c0 += 8) {
-                const int n = (int)r.C - c0 < 8 ? (int)r.C - c0 : 8;
-                l3c_table_part tp[8];
-                l3c_ragged_part rp[8];
-                l3c_ac_decode_part dp[8];
-                memset(dp, 0, sizeof(dp));
-                for (int i = 0; i < n; ++i) {
-                    const int ch = c0 + i;
-                    uint16_t *table = reinterpret_cast<uint16_t *>(scratch + ch * p.table_bytes[k]);
-                    tp[i] = l3c_table_part{ch, 0, max_npix, table, flags + k, nullptr};
-                    rp[i] = l3c_ragged_part{ent + 2 * E, ent + 3 * E, ent + 4 * E};
-                    l3c_ac_decode_part &q = dp[i];
-                    q.cdf = table;
-                    q.Lp = Lp;
-                    q.in = streams;
-                    q.in_offsets = dst_off + r.first + ch * E;
-                    q.in_nbytes = nbytes + r.first + ch * E;
-                    q.n_streams = E;
-                    q.n_sym = max_npix;
-                    q.not_monotone_flag = flags + k;
-                    q.final_chunk = 1;
-                    q.sym_out = sym[k];
-                    q.r_npix = ent + 3 * E;
-                    q.r_table_off = ent + 4 * E;
-                    q.r_pixbase = ent;
-                    q.r_hw = ent + E;
-                    q.r_pix0 = ent + 2 * E;
-                    q.r_C = (int)r.C;
-                    q.r_c = ch;
-                    q.r_table_bytes = B * hw * Lp * 2;
-                }
-                CODEC_TRY(l3c_dmll_cdf_table_ragged(P, nullptr, m.targets_z, &batch, (int)r.C, c.K, 0, Lp, tp, rp, n, main_stream));
-                CODEC_TRY(l3c_ac_decode_chunks(dp, n, main_stream));
-            }
-        } else {         // the RGB scale: the chunk pipeline over all B n bands of each channel in lock step
-            CODEC_TRY(l3c::check_hip(hipMemsetAsync(sym[k], 0, (size_t)(B * 3 * hw * 2), st), "hipMemsetAsync"));
-            l3c_rgb_banded_desc q;
-            memset(&q, 0, sizeof(q));
-            q.P = P;
-            q.targets = m.targets_rgb;
-            q.sym = sym[k];
-            q.B = B;
-            q.HW = hw;
-            q.K = c.K;
-            q.in = streams;
-            q.in_offsets = dst_off + r.first;
-            q.in_nbytes = nbytes + r.first;
-            q.band_len = h.rgb_band_len;
-            q.n_chunks = (int)h.rgb_chunks;
-            q.lag = (int)h.lag;
-            q.window_mode = 1;
-            q.workspace = scratch;
-            q.workspace_bytes = p.rgb_ws;
-            CODEC_TRY(l3c_decode_rgb_banded(&q, main_stream, h.lag == 2 ? side_stream : nullptr));
-        }
-    }
-    return l3c_sym_to_u8(sym[n_rec - 1], B * 3 * h.H * h.W, d->pixels, main_stream);
+    return dec_batch<BandedHeader>(d, main_stream, side_stream);
 }
 
 // ---- pictures as they come: a table of views, padded and cropped on the device (csrc/images.hip) -----------------------------------
@@ -1073,36 +945,22 @@ int l3c_encode_images(const l3c_encode_images_desc *d, l3c_stream_t stream) {
     e.workspace = ws + head;
     e.workspace_bytes = d->workspace_bytes - head - (ws - static_cast<char *>(d->workspace));
     EncPlan p;
-    EncBandPlan pb;
-    if (d->bands)
-        CODEC_TRY(enc_banded_check(&e, d->bands, &pb));
-    else
-        CODEC_TRY(enc_check(&e, &p));
+    CODEC_TRY(enc_check_desc(&e, d->bands != 0, d->bands, &p));
     CODEC_TRY(l3c::images_check(d->images_host, d->images, d->B, d->Hp, d->Wp, d->src_bytes));
 
     // ---- everything checked: enqueue
     CODEC_TRY(l3c_u8_gather(d->src, d->src_bytes, d->images_host, d->images, d->B, d->Hp, d->Wp, img, padding, stream));
-    return d->bands ? enc_banded_run(&e, pb, stream) : enc_run(&e, p, stream);
-}
-
-// the plan blob's first word: which of the two decoders reads it
-static int plan_is_banded(const void *plan_host, bool *banded) {
-    L3C_REQUIRE(plan_host, "null pointer: plan_host");
-    L3C_REQUIRE((reinterpret_cast<uintptr_t>(plan_host) & 7) == 0, "plan_host must be 8-byte aligned");
-    int64_t magic;
-    memcpy(&magic, plan_host, sizeof(magic));
-    *banded = magic == l3c_plan::BANDED_MAGIC;
-    return L3C_OK;
+    return d->bands ? enc_banded_run(&e, p, stream) : enc_run(&e, p, stream);
 }
 
 int64_t l3c_decode_images_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) {
     CODEC_TRY(codec_config(cfg));
     bool banded;
-    CODEC_TRY(plan_is_banded(plan_host, &banded));
+    int64_t B, H, W;
+    CODEC_TRY(plan_dims(*cfg, plan_host, -1, &banded, &B, &H, &W));
     const int64_t inner = banded ? l3c_decode_batch_banded_workspace_bytes(cfg, plan_host) : l3c_decode_batch_workspace_bytes(cfg, plan_host);
     if (inner < 0) return inner;
-    const int64_t *w = static_cast<const int64_t *>(plan_host);      // words 2, 4, 5 of either header: B, H, W (checked by the call above)
-    return up(w[2] * 3 * w[4] * w[5]) + inner + ALIGN;
+    return up(B * 3 * H * W) + inner + ALIGN;
 }
 
 int l3c_decode_images(const l3c_decode_images_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
@@ -1113,17 +971,8 @@ int l3c_decode_images(const l3c_decode_images_desc *d, l3c_stream_t main_stream,
     L3C_REQUIRE(aligned16(d->files) && aligned16(d->plan) && aligned16(d->images) && aligned16(d->sym) && aligned16(d->workspace),
                 "every pointer but dst must be 16-byte aligned");
     bool banded;
-    CODEC_TRY(plan_is_banded(d->plan_host, &banded));
     int64_t B, H, W;
-    if (banded) {
-        l3c_plan::BandedHeader h;
-        CODEC_TRY(l3c_plan::check_blob_banded(c, d->plan_host, d->plan_bytes, &h, l3c::error_buffer(), 512));
-        B = h.B, H = h.H, W = h.W;
-    } else {
-        l3c_plan::Header h;
-        CODEC_TRY(l3c_plan::check_blob(c, d->plan_host, d->plan_bytes, &h, l3c::error_buffer(), 512));
-        B = h.B, H = h.H, W = h.W;
-    }
+    CODEC_TRY(plan_dims(c, d->plan_host, d->plan_bytes, &banded, &B, &H, &W));
     const int64_t need = l3c_decode_images_workspace_bytes(&c, d->plan_host);
     if (need < 0) return (int)need;
     if (d->workspace_bytes < need)
