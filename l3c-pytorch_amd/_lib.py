@@ -127,6 +127,13 @@ class NetGetPDesc(ctypes.Structure):
                 ('workspace_bytes', c_i64)]
 
 
+class NetGetPRowsDesc(ctypes.Structure):
+    """l3c_net_get_p_rows_desc (include/l3c_hip.h)."""
+    _fields_ = [('cfg_host', ctypes.POINTER(NetConfig)), ('packed', c_vp), ('packed_bytes', c_i64), ('net', c_int), ('bn_q', c_vp),
+                ('B', c_i64), ('h', c_int), ('w', c_int), ('fuse', c_vp), ('c0', c_int), ('c1', c_int), ('P', c_vp), ('workspace', c_vp),
+                ('workspace_bytes', c_i64)]
+
+
 class CodecModel(ctypes.Structure):
     """l3c_codec_model (include/l3c_hip.h)."""
     _fields_ = [('cfg_host', ctypes.POINTER(NetConfig)), ('packed', c_vp), ('packed_bytes', c_i64), ('targets_rgb', c_vp),
@@ -167,6 +174,26 @@ class DecodeImagesDesc(ctypes.Structure):
     """l3c_decode_images_desc (include/l3c_hip.h)."""
     _fields_ = [('model_host', ctypes.POINTER(CodecModel)), ('files', c_vp), ('plan_host', c_vp), ('plan', c_vp), ('plan_bytes', c_i64),
                 ('dst', c_vp), ('dst_bytes', c_i64), ('images_host', c_vp), ('images', c_vp), ('sym', c_vp), ('workspace', c_vp),
+                ('workspace_bytes', c_i64)]
+
+
+class RegionBox(ctypes.Structure):
+    """l3c_region_box (include/l3c_hip.h)."""
+    _fields_ = [('y0', ctypes.c_int32), ('y1', ctypes.c_int32), ('x0', ctypes.c_int32), ('x1', ctypes.c_int32)]
+
+
+class RegionInfo(ctypes.Structure):
+    """l3c_region_info (include/l3c_hip.h)."""
+    _fields_ = [('bands', ctypes.c_int32 * 2), ('n_bands', ctypes.c_int32), ('sym_rows', ctypes.c_int32 * 2), ('conv_rows', ctypes.c_int32 * 2),
+                ('valid_rows', ctypes.c_int32 * 2), ('decoder_rows', ctypes.c_int32 * 2), ('frame_rows', ctypes.c_int32),
+                ('n_chunks', ctypes.c_int32), ('lag', ctypes.c_int32), ('out_rows', ctypes.c_int32), ('out_cols', ctypes.c_int32),
+                ('streams_used', c_i64), ('streams_total', c_i64), ('bytes_used', c_i64), ('bytes_total', c_i64)]
+
+
+class DecodeRegionDesc(ctypes.Structure):
+    """l3c_decode_region_desc (include/l3c_hip.h)."""
+    _fields_ = [('model_host', ctypes.POINTER(CodecModel)), ('files', c_vp), ('plan_host', c_vp), ('plan', c_vp), ('plan_bytes', c_i64),
+                ('region_host', c_vp), ('region', c_vp), ('region_bytes', c_i64), ('pixels', c_vp), ('workspace', c_vp),
                 ('workspace_bytes', c_i64)]
 
 
@@ -281,6 +308,15 @@ PROTOTYPES = {
     'l3c_encode_images': (c_int, [ctypes.POINTER(EncodeImagesDesc), c_vp]),
     'l3c_decode_images_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
     'l3c_decode_images': (c_int, [ctypes.POINTER(DecodeImagesDesc), c_vp, c_vp]),
+    'l3c_net_halo_rows': (c_int, [c_int]),
+    'l3c_net_apron_rows': (c_int, [c_int]),
+    'l3c_net_get_p_rows_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_i64, c_int, c_int, c_int, c_int]),
+    'l3c_net_get_p_rows': (c_int, [ctypes.POINTER(NetGetPRowsDesc), c_vp]),
+    'l3c_decode_region_plan_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
+    'l3c_decode_region_plan': (c_int, [ctypes.POINTER(NetConfig), c_vp, c_i64, c_vp, ctypes.POINTER(RegionBox), c_vp, c_i64,
+                                       ctypes.POINTER(RegionInfo)]),
+    'l3c_decode_region_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp, c_vp]),
+    'l3c_decode_region': (c_int, [ctypes.POINTER(DecodeRegionDesc), c_vp, c_vp]),
     'l3c_seal_find': (c_int, [c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(Seal)]),
     'l3c_seal_write': (c_int, [ctypes.POINTER(Seal), c_vp, c_vp]),
     'l3c_u8_crc32_workspace_bytes': (c_i64, [c_i64, c_i64]),

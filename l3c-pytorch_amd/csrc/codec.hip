@@ -20,12 +20,17 @@
 // split into its checks and its schedule for that -- behind l3c_u8_gather and in front of l3c_u8_scatter (csrc/images.hip), the planar
 // frames in front of the wrapped entry's workspace.
 //
+// A BOX of the pictures (l3c_decode_region_plan / l3c_decode_region: Bitcoding.decode_region): the walk of dec_run ended one record early --
+// the same steps, shared -- then the finest step on a row window: the picked band streams (codec_plan_region.h), l3c_net_get_p_rows, one
+// l3c_decode_rgb_entries call, l3c_u8_scatter with the blob's crop table.
+//
 // Three small kernels of its own: the file sizes and offsets of a batch (what EncodedBatch.file_sizes sums with torch ops) for either
 // format -- a thread per legacy file, a block with a wave reduction per banded file -- and int16 symbols -> uint8 pixels.
 #include <string.h>
 
 #include "codec_plan.h"
 #include "codec_plan_banded.h"
+#include "codec_plan_region.h"
 #include "l3c_common.h"
 
 #define CODEC_FAIL(code, ...) (snprintf(l3c::error_buffer(), 512, __VA_ARGS__), (code))
@@ -700,6 +705,36 @@ int dec_rgb(const DecWalk &x, const BandedHeader &h, int k) {
     return l3c_decode_rgb_banded(&q, x.main_stream, h.lag == 2 ? x.side_stream : nullptr);
 }
 
+// the input of the network that predicts record k: the symbols of the record above it as bottleneck values
+template <class Hdr>
+int dec_bn(const DecWalk &x, const Hdr &h, int k, float *bn) {
+    const auto &above = h.rec[k - 1];
+    return l3c_sym_to_bn(x.sym[k - 1], h.B * above.C * above.H * above.W, x.m.z_bin_width, x.m.z_x_min, bn, x.main_stream);
+}
+
+// P of record k (and, for a bottleneck record, the features the next record's decoder fuses); ws: the workspace the plan's offsets count from
+template <class Hdr>
+int dec_get_p(const DecWalk &x, const Hdr &h, int k, const float *bn, char *ws) {
+    const auto &above = h.rec[k - 1];
+    const int s = x.c.num_scales - k;
+    l3c_net_get_p_desc g;
+    memset(&g, 0, sizeof(g));
+    g.cfg_host = &x.c;
+    g.packed = x.m.packed;
+    g.packed_bytes = x.m.packed_bytes;
+    g.net = s;
+    g.bn_q = bn;
+    g.B = h.B;
+    g.h = (int)above.H;
+    g.w = (int)above.W;
+    g.fuse = k == 1 ? nullptr : reinterpret_cast<const float *>(ws + x.p.F[k - 1]);
+    g.P = x.P;
+    g.F = s > 0 ? reinterpret_cast<float *>(ws + x.p.F[k]) : nullptr;      // the finest scale's features feed nothing
+    g.workspace = x.scratch;
+    g.workspace_bytes = x.p.getp_ws;
+    return l3c_net_get_p(&g, x.main_stream);
+}
+
 // the walk over the records of a checked plan: nothing below fails on an argument
 template <class Hdr>
 int dec_run(const l3c_decode_batch_desc *d, const Hdr &h, const DecPlan &p, l3c_stream_t main_stream, l3c_stream_t side_stream) {
@@ -725,25 +760,10 @@ int dec_run(const l3c_decode_batch_desc *d, const Hdr &h, const DecPlan &p, l3c_
     float *bn = reinterpret_cast<float *>(ws + p.bn);
     CODEC_TRY(dec_coarsest(x, h));
     for (int k = 1; k < n_rec; ++k) {
-        const auto &r = h.rec[k], &above = h.rec[k - 1];
+        const auto &r = h.rec[k];
         const int s = S - k;
-        CODEC_TRY(l3c_sym_to_bn(x.sym[k - 1], B * above.C * above.H * above.W, m.z_bin_width, m.z_x_min, bn, main_stream));
-        l3c_net_get_p_desc g;
-        memset(&g, 0, sizeof(g));
-        g.cfg_host = &c;
-        g.packed = m.packed;
-        g.packed_bytes = m.packed_bytes;
-        g.net = s;
-        g.bn_q = bn;
-        g.B = B;
-        g.h = (int)above.H;
-        g.w = (int)above.W;
-        g.fuse = k == 1 ? nullptr : reinterpret_cast<const float *>(ws + p.F[k - 1]);
-        g.P = x.P;
-        g.F = s > 0 ? reinterpret_cast<float *>(ws + p.F[k]) : nullptr;      // the finest scale's features feed nothing
-        g.workspace = x.scratch;
-        g.workspace_bytes = p.getp_ws;
-        CODEC_TRY(l3c_net_get_p(&g, main_stream));
+        CODEC_TRY(dec_bn(x, h, k, bn));
+        CODEC_TRY(dec_get_p(x, h, k, bn, ws));
         // P is complete: get_p's workspace is dead and holds this record's tables / the RGB pipeline's workspace from here on
         if (s == 0) CODEC_TRY(l3c::check_hip(hipMemsetAsync(x.sym[k], 0, (size_t)(B * 3 * r.H * r.W * 2), st), "hipMemsetAsync"));
         CODEC_TRY(s > 0 ? dec_bottleneck(x, h, k) : dec_rgb(x, h, k));
@@ -772,6 +792,202 @@ int plan_dims(const l3c_net_config &c, const void *plan_host, int64_t plan_bytes
         return (int)L3C_OK;
     };
     return *banded ? dims(BandedHeader{}) : dims(Header{});
+}
+
+// ---- region decode: the walk ended one record early, then the finest step on a row window (codec_plan_region.h) ---------------------------
+
+using l3c_plan::RegionHeader;
+
+struct RegPlan {
+    DecPlan p;          // what the shared steps of the walk read: the coarser records' streams, symbols, features and tables, bn, P, flags, scratch
+    int64_t coarse_bytes, picked, sym_win, u8_win, rows_ws, entries_ws;
+};
+
+template <class Hdr>
+int reg_plan(const l3c_net_config &c, const Hdr &h, const RegionHeader &g, const void *plan_host, const void *region_host, RegPlan *out) {
+    RegPlan q{};
+    DecPlan &p = q.p;
+    const int S = c.num_scales, n_rec = (int)h.n_records;
+    const int64_t B = h.B;
+    // the stream buffer of the walk ends where the finest record's streams would begin
+    q.coarse_bytes = reinterpret_cast<const int64_t *>(static_cast<const char *>(plan_host) + h.dst_off)[h.rec[n_rec - 1].first];
+    if (q.coarse_bytes < 0 || q.coarse_bytes > h.dst_bytes) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent stream offsets");
+    int64_t at = 0, scratch = 0, bn = 0, P = 0;
+    p.streams = take(at, q.coarse_bytes);
+    q.picked = take(at, g.dst_bytes);
+    for (int k = 0; k < n_rec - 1; ++k) {
+        const auto &r = h.rec[k];
+        const int64_t hw = r.H * r.W;
+        if (r.H < 1 || r.W < 1 || r.H >= 65536 || r.W >= 65536 || r.C < 1 || r.C > 8 || (k && (r.H != 2 * h.rec[k - 1].H || r.W != 2 * h.rec[k - 1].W)))
+            return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent record %d", k);
+        p.sym[k] = take(at, B * r.C * hw * 2);
+        bn = B * r.C * hw * 4 > bn ? B * r.C * hw * 4 : bn;
+        if (k) {
+            const int64_t ws = l3c_net_get_p_workspace_bytes(&c, B, (int)h.rec[k - 1].H, (int)h.rec[k - 1].W);
+            if (ws < 0) return (int)ws;
+            p.getp_ws = ws > p.getp_ws ? ws : p.getp_ws;
+            const int64_t Pk = B * hw * kp_of(c, S - k) * 4;
+            P = Pk > P ? Pk : P;
+            p.F[k] = take(at, B * hw * c.Cf * 4);
+            p.table_bytes[k] = up(B * hw * (c.L + 1) * 2);
+            scratch = r.C * p.table_bytes[k] > scratch ? r.C * p.table_bytes[k] : scratch;
+        }
+    }
+    const auto &above = h.rec[n_rec - 2];
+    if (g.H != 2 * above.H || g.W != 2 * above.W) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "plan blob: inconsistent image size");
+    const int64_t rows = g.rows.c1 - g.rows.c0;
+    q.rows_ws = l3c_net_get_p_rows_workspace_bytes(&c, B, (int)above.H, (int)above.W, (int)g.rows.c0, (int)g.rows.c1);
+    if (q.rows_ws < 0) return (int)q.rows_ws;
+    const int64_t Pw = B * rows * g.W * kp_of(c, 0) * 4;
+    P = Pw > P ? Pw : P;
+    q.entries_ws = l3c_decode_rgb_entries_workspace_bytes(g.S, reinterpret_cast<const int64_t *>(static_cast<const char *>(region_host) + g.entries_off) + 3 * g.S,
+                                                          (int)g.n_chunks, (int)g.lag);
+    if (q.entries_ws < 0) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "region blob: bad entry table");
+    p.bn = take(at, bn);
+    p.P = take(at, P);
+    q.sym_win = take(at, B * 3 * rows * g.W * 2);
+    q.u8_win = take(at, B * 3 * rows * g.W);
+    p.flags = take(at, MAX_REC * 4);
+    scratch = p.getp_ws > scratch ? p.getp_ws : scratch;
+    scratch = q.rows_ws > scratch ? q.rows_ws : scratch;
+    scratch = q.entries_ws > scratch ? q.entries_ws : scratch;
+    p.scratch = at;
+    p.bytes = at + up(scratch) + ALIGN;
+    *out = q;
+    return L3C_OK;
+}
+
+// both blobs, each against its own rules and the region blob against the plan blob; then the plan of the workspace
+template <class Hdr>
+int reg_blobs(const l3c_net_config &c, const void *plan_host, int64_t plan_bytes, const void *region_host, int64_t region_bytes, Hdr *h,
+              RegionHeader *g, RegPlan *q) {
+    CODEC_TRY(l3c_plan::region_config(&c, l3c::error_buffer(), 512));
+    L3C_REQUIRE(plan_host && region_host, "null pointer: plan_host / region_host");
+    L3C_REQUIRE(((reinterpret_cast<uintptr_t>(plan_host) | reinterpret_cast<uintptr_t>(region_host)) & 7) == 0, "plan_host and region_host must be 8-byte aligned");
+    CODEC_TRY(check_blob_of(c, plan_host, plan_bytes, h));
+    CODEC_TRY(l3c_plan::region_check(c, plan_host, plan_bytes, region_host, region_bytes, g, l3c::error_buffer(), 512));
+    return reg_plan(c, *h, *g, plan_host, region_host, q);
+}
+
+template <class Hdr>
+int reg_run(const l3c_decode_region_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    CODEC_TRY(check_model(d->model_host));
+    const l3c_codec_model &m = *d->model_host;
+    const l3c_net_config &c = *m.cfg_host;
+    L3C_REQUIRE(d->files && d->plan_host && d->plan && d->region_host && d->region && d->pixels && d->workspace, "null pointer");
+    L3C_REQUIRE(aligned16(d->files) && aligned16(d->plan) && aligned16(d->region) && aligned16(d->pixels) && aligned16(d->workspace),
+                "every pointer must be 16-byte aligned");
+    Hdr h;
+    RegionHeader g;
+    RegPlan q;
+    CODEC_TRY(reg_blobs(c, d->plan_host, d->plan_bytes, d->region_host, d->region_bytes, &h, &g, &q));
+    L3C_REQUIRE(g.lag == 1 || (side_stream && side_stream != main_stream),
+                "16 entries or more decode on two streams (lag 2): side_stream must be a stream of its own");
+    const DecPlan &p = q.p;
+    if (d->workspace_bytes < p.bytes)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
+    const int64_t B = h.B, W = g.W, rows = g.rows.c1 - g.rows.c0, S = g.S;
+    const int64_t box_bytes = B * 3 * (g.box[1] - g.box[0]) * (g.box[3] - g.box[2]);
+    const char *region = static_cast<const char *>(d->region), *region_h = static_cast<const char *>(d->region_host);
+    const l3c_u8_image *crop = reinterpret_cast<const l3c_u8_image *>(region + g.crop_off);
+    const l3c_u8_image *crop_h = reinterpret_cast<const l3c_u8_image *>(region_h + g.crop_off);
+    CODEC_TRY(l3c::images_check(crop_h, crop, B, (int)rows, (int)W, box_bytes));
+
+    // ---- everything checked: enqueue.  The walk of dec_run over every record but the finest ...
+    const int n_rec = (int)h.n_records;
+    char *ws = base256(d->workspace);
+    const hipStream_t st = l3c::as_stream(main_stream);
+    const char *plan = static_cast<const char *>(d->plan);
+    const int64_t *src_off = reinterpret_cast<const int64_t *>(plan + h.src_off);
+    DecWalk x{m, c, p, plan, static_cast<const char *>(d->plan_host), reinterpret_cast<const int64_t *>(plan + h.dst_off),
+              reinterpret_cast<const uint32_t *>(plan + h.nbytes_off), reinterpret_cast<uint8_t *>(ws + p.streams),
+              reinterpret_cast<int32_t *>(ws + p.flags), reinterpret_cast<float *>(ws + p.P), ws + p.scratch, main_stream, side_stream, {}};
+    CODEC_TRY(l3c::check_hip(hipMemsetAsync(x.flags, 0, MAX_REC * 4, st), "hipMemsetAsync"));
+    for (int k = 0; k < n_rec - 1; ++k)
+        for (int64_t a = h.rec[k].first, e = a + h.rec[k].n_streams; a < e; a += 65535) {
+            const int64_t n = e - a < 65535 ? e - a : 65535;
+            CODEC_TRY(l3c_container_read(d->files, src_off + a, x.dst_off + a, x.nbytes + a, n, (uint32_t)h.rec[k].max_nbytes, x.streams, main_stream));
+        }
+    for (int k = 0; k < n_rec - 1; ++k) x.sym[k] = reinterpret_cast<int16_t *>(ws + p.sym[k]);
+    float *bn = reinterpret_cast<float *>(ws + p.bn);
+    CODEC_TRY(dec_coarsest(x, h));
+    for (int k = 1; k < n_rec - 1; ++k) {
+        CODEC_TRY(dec_bn(x, h, k, bn));
+        CODEC_TRY(dec_get_p(x, h, k, bn, ws));
+        CODEC_TRY(dec_bottleneck(x, h, k));
+    }
+
+    // ... and the finest step on the window: the picked streams, P of the conv rows, ONE entries call, the box out of the window frames
+    const int64_t *pk_src = reinterpret_cast<const int64_t *>(region + g.src_off), *pk_dst = reinterpret_cast<const int64_t *>(region + g.dst_off);
+    const uint32_t *pk_nbytes = reinterpret_cast<const uint32_t *>(region + g.nbytes_off);
+    uint8_t *picked = reinterpret_cast<uint8_t *>(ws + q.picked);
+    for (int64_t a = 0; a < 3 * S; a += 65535) {
+        const int64_t n = 3 * S - a < 65535 ? 3 * S - a : 65535;
+        CODEC_TRY(l3c_container_read(d->files, pk_src + a, pk_dst + a, pk_nbytes + a, n, (uint32_t)g.max_nbytes, picked, main_stream));
+    }
+    const auto &above = h.rec[n_rec - 2];
+    CODEC_TRY(dec_bn(x, h, n_rec - 1, bn));
+    l3c_net_get_p_rows_desc w;
+    memset(&w, 0, sizeof(w));
+    w.cfg_host = &c;
+    w.packed = m.packed;
+    w.packed_bytes = m.packed_bytes;
+    w.net = 0;
+    w.bn_q = bn;
+    w.B = B;
+    w.h = (int)above.H;
+    w.w = (int)above.W;
+    w.fuse = reinterpret_cast<const float *>(ws + p.F[n_rec - 2]);
+    w.c0 = (int)g.rows.c0;
+    w.c1 = (int)g.rows.c1;
+    w.P = x.P;
+    w.workspace = x.scratch;
+    w.workspace_bytes = q.rows_ws;
+    CODEC_TRY(l3c_net_get_p_rows(&w, main_stream));
+    int16_t *sym = reinterpret_cast<int16_t *>(ws + q.sym_win);
+    CODEC_TRY(l3c::check_hip(hipMemsetAsync(sym, 0, (size_t)(B * 3 * rows * W * 2), st), "hipMemsetAsync"));
+    l3c_rgb_entries_desc e;
+    memset(&e, 0, sizeof(e));
+    e.P = x.P;
+    e.targets = m.targets_rgb;
+    e.sym = sym;
+    e.S = S;
+    e.total_pix = B * rows * W;
+    e.entries_dev = reinterpret_cast<const int64_t *>(region + g.entries_off);
+    e.entries_host = reinterpret_cast<const int64_t *>(region_h + g.entries_off);
+    e.K = c.K;
+    e.in = picked;
+    e.in_offsets = pk_dst;
+    e.in_nbytes = pk_nbytes;
+    e.n_chunks = (int)g.n_chunks;
+    e.lag = (int)g.lag;
+    e.window_mode = 1;
+    e.workspace = x.scratch;          // P is complete: get_p_rows' workspace is dead
+    e.workspace_bytes = q.entries_ws;
+    CODEC_TRY(l3c_decode_rgb_entries(&e, main_stream, g.lag == 2 ? side_stream : nullptr));
+    uint8_t *u8 = reinterpret_cast<uint8_t *>(ws + q.u8_win);
+    CODEC_TRY(l3c_sym_to_u8(sym, B * 3 * rows * W, u8, main_stream));
+    return l3c_u8_scatter(u8, B, (int)rows, (int)W, d->pixels, box_bytes, crop_h, crop, main_stream);
+}
+
+// which walk reads a plan blob
+int plan_is_banded(const void *plan_host, bool *banded) {
+    L3C_REQUIRE(plan_host, "null pointer: plan_host");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(plan_host) & 7) == 0, "plan_host must be 8-byte aligned");
+    int64_t magic;
+    memcpy(&magic, plan_host, sizeof(magic));
+    *banded = magic == l3c_plan::BANDED_MAGIC;
+    return L3C_OK;
+}
+
+template <class Hdr>
+int64_t reg_workspace_bytes(const l3c_net_config &c, const void *plan_host, const void *region_host) {
+    Hdr h;
+    RegionHeader g;
+    RegPlan q;
+    CODEC_TRY(reg_blobs(c, plan_host, -1, region_host, -1, &h, &g, &q));
+    return q.p.bytes;
 }
 
 // the size functions of an encode (bands 0: legacy): the file stride, or the workspace of a batch
@@ -994,5 +1210,33 @@ int l3c_decode_images(const l3c_decode_images_desc *d, l3c_stream_t main_stream,
     // the wrapped entry checks its own arguments (the side stream among them) before it enqueues anything, the scatter's are checked above
     CODEC_TRY(banded ? l3c_decode_batch_banded(&q, main_stream, side_stream) : l3c_decode_batch(&q, main_stream, side_stream));
     return l3c_u8_scatter(q.pixels, B, (int)H, (int)W, d->dst, d->dst_bytes, d->images_host, d->images, main_stream);
+}
+
+// ---- region decode -----------------------------------------------------------------------------------------------------------
+
+int64_t l3c_decode_region_plan_bytes(const l3c_net_config *cfg, const void *plan_host) {
+    CODEC_TRY(codec_config(cfg));
+    return l3c_plan::region_plan_bytes(cfg, plan_host, l3c::error_buffer(), 512);
+}
+
+int l3c_decode_region_plan(const l3c_net_config *cfg, const void *plan_host, int64_t plan_bytes, const uint16_t *padding_host,
+                           const l3c_region_box *box_host, void *region_host, int64_t region_bytes, l3c_region_info *info_out) {
+    CODEC_TRY(codec_config(cfg));
+    return l3c_plan::make_region_plan(cfg, plan_host, plan_bytes, padding_host, box_host, region_host, region_bytes, info_out, l3c::error_buffer(),
+                                      512);
+}
+
+int64_t l3c_decode_region_workspace_bytes(const l3c_net_config *cfg, const void *plan_host, const void *region_host) {
+    CODEC_TRY(codec_config(cfg));
+    bool banded;
+    CODEC_TRY(plan_is_banded(plan_host, &banded));
+    return banded ? reg_workspace_bytes<BandedHeader>(*cfg, plan_host, region_host) : reg_workspace_bytes<Header>(*cfg, plan_host, region_host);
+}
+
+int l3c_decode_region(const l3c_decode_region_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    bool banded;
+    CODEC_TRY(plan_is_banded(d->plan_host, &banded));
+    return banded ? reg_run<BandedHeader>(d, main_stream, side_stream) : reg_run<Header>(d, main_stream, side_stream);
 }
 }

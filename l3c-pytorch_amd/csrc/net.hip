@@ -1,4 +1,5 @@
-// net.hip -- the whole network behind two library calls: l3c_net_forward / l3c_net_get_p (include/l3c_hip.h).
+// net.hip -- the whole network behind two library calls: l3c_net_forward / l3c_net_get_p (include/l3c_hip.h), and the finest scale's
+// l3c_net_get_p on a row window: l3c_net_get_p_rows (the row arithmetic: csrc/codec_plan_region.h).
 //
 // A host loop over the layer schedule of modules/multiscale_network.py: the same entry points, with the descriptors ops.conv builds
 // for the same layer, in the same order -- so every kernel sees the same inputs and sums in the same order, and P is bit-identical to
@@ -10,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "codec_plan_region.h"
 #include "l3c_common.h"
 
 #define NET_FAIL(code, ...) (snprintf(l3c::error_buffer(), 512, __VA_ARGS__), (code))
@@ -333,6 +335,56 @@ GetPPlan getp_plan(const l3c_net_config &c, int net, int64_t B, int h, int w) {
     return p;
 }
 
+// l3c_net_get_p_rows: the decoder stage on half-resolution rows [a0 / 2, a1 / 2), the classifier on rows [c0, c1) of its features
+struct RowsPlan {
+    int64_t a0, a1;
+    bool cut;                                   // the decoder rows are not the whole frame: its inputs are row slices
+    int64_t body, bn, fuse, F, Fc, bytes;       // offsets (-1: not needed); `body`: one of the four decoder buffers at offset 0
+};
+
+RowsPlan rows_plan(const l3c_net_config &c, int64_t B, int h, int w, int c0, int c1) {
+    RowsPlan p{};
+    l3c_plan::region_decoder_rows(2ll * h, c0, c1, l3c_plan::region_apron_rows(c.dec_blocks), &p.a0, &p.a1);
+    p.cut = p.a0 != 0 || p.a1 != 2ll * h;
+    const int64_t ha = (p.a1 - p.a0) / 2, W = 2ll * w;
+    p.body = align_up(B * ha * w * c.Cf * 4);
+    int64_t at = align_up(3 * B * (c1 - c0) * W * c.Cf * 4);
+    if (at < 4 * p.body) at = 4 * p.body;
+    auto take = [&](bool needed, int64_t n) {
+        if (!needed) return (int64_t)-1;
+        const int64_t o = at;
+        at += align_up(n);
+        return o;
+    };
+    p.bn = take(p.cut, B * c.C * ha * w * 4);
+    p.fuse = take(p.cut && B > 1, B * ha * w * c.Cf * 4);
+    p.F = take(true, B * (p.a1 - p.a0) * W * c.Cf * 4);
+    p.Fc = take(B > 1 && (c0 != p.a0 || c1 != p.a1), B * (c1 - c0) * W * c.Cf * 4);
+    p.bytes = at;
+    return p;
+}
+
+// what both entries of the windowed step ask of the config and the window
+int check_rows(const l3c_net_config *cfg, int net, int64_t B, int h, int w, int c0, int c1) {
+    NET_TRY(check_config(cfg, true));
+    if (cfg->rgb_baseline) return NET_FAIL(L3C_ERR_UNSUPPORTED, "l3c_net_get_p_rows: the RGB baselines are not windowed");
+    L3C_REQUIRE(net == 0, "l3c_net_get_p_rows: only scale 0 is windowed (net must be 0)");
+    L3C_REQUIRE(h > 0 && w > 0 && h < 32768 && w < 32768, "bad shape");
+    NET_TRY(check_image(*cfg, B, 2ll * h, 2ll * w));
+    if (!(0 <= c0 && c0 < c1 && c1 <= 2 * h && c0 % 2 == 0 && c1 % 2 == 0))
+        return NET_FAIL(L3C_ERR_INVALID_ARG, "conv rows [%d, %d) must be even rows inside the %d frame rows", c0, c1, 2 * h);
+    if (c0 % l3c_plan::REGION_GRANULE || (c1 % l3c_plan::REGION_GRANULE && c1 != 2 * h))
+        return NET_FAIL(L3C_ERR_INVALID_ARG, "conv rows [%d, %d): c0 must be a multiple of 64, c1 a multiple of 64 or the frame's end %d", c0, c1, 2 * h);
+    return L3C_OK;
+}
+
+// rows [r0, r0 + rows) of `planes` planes of plane_rows rows of row_bytes bytes each -> dst, packed
+int copy_rows(float *dst, const float *src, int64_t planes, int64_t plane_rows, int64_t r0, int64_t rows, int64_t row_bytes, hipStream_t st) {
+    return l3c::check_hip(hipMemcpy2DAsync(dst, (size_t)(rows * row_bytes), reinterpret_cast<const char *>(src) + r0 * row_bytes,
+                                           (size_t)(plane_rows * row_bytes), (size_t)(rows * row_bytes), (size_t)planes, hipMemcpyDeviceToDevice, st),
+                          "hipMemcpy2DAsync");
+}
+
 }  // namespace
 
 extern "C" {
@@ -537,5 +589,65 @@ int l3c_net_get_p(const l3c_net_get_p_desc *d, l3c_stream_t stream) {
     float *F = d->F ? d->F : p.f_off >= 0 ? reinterpret_cast<float *>(ws + p.f_off) : d->P;   // F without a caller buffer: in P's memory
     NET_TRY(decoder(r, c, d->net, d->bn_q, d->fuse, d->h, d->w, region, p.body / 4, F));
     return prob(r, c, d->net, F, 2 * d->h, 2 * d->w, region, d->P);
+}
+
+int l3c_net_halo_rows(int dec_blocks) {
+    L3C_REQUIRE(dec_blocks >= 0 && dec_blocks <= MAX_BLOCKS, "dec_blocks must be 0 .. 64");
+    return (int)l3c_plan::region_halo_rows(dec_blocks);
+}
+
+int l3c_net_apron_rows(int dec_blocks) {
+    L3C_REQUIRE(dec_blocks >= 0 && dec_blocks <= MAX_BLOCKS, "dec_blocks must be 0 .. 64");
+    return (int)l3c_plan::region_apron_rows(dec_blocks);
+}
+
+int64_t l3c_net_get_p_rows_workspace_bytes(const l3c_net_config *cfg, int64_t B, int h, int w, int c0, int c1) {
+    NET_TRY(check_rows(cfg, 0, B, h, w, c0, c1));
+    return rows_plan(*cfg, B, h, w, c0, c1).bytes;
+}
+
+int l3c_net_get_p_rows(const l3c_net_get_p_rows_desc *d, l3c_stream_t stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    NET_TRY(check_rows(d->cfg_host, d->net, d->B, d->h, d->w, d->c0, d->c1));
+    const l3c_net_config &c = *d->cfg_host;
+    L3C_REQUIRE(d->packed && d->bn_q && d->P && d->workspace, "null pointer");
+    L3C_REQUIRE(d->fuse, "null pointer: fuse (the windowed step needs the coarser decoder's features)");
+    L3C_REQUIRE(aligned16(d->packed) && aligned16(d->bn_q) && aligned16(d->fuse) && aligned16(d->P) && aligned16(d->workspace),
+                "every pointer must be 16-byte aligned");
+    Layout L;
+    build_layout(c, L);
+    if (d->packed_bytes != L.bytes)
+        return NET_FAIL(L3C_ERR_INVALID_ARG, "packed_bytes %lld != l3c_net_packed_bytes %lld (packed for another config?)",
+                        (long long)d->packed_bytes, (long long)L.bytes);
+    const RowsPlan p = rows_plan(c, d->B, d->h, d->w, d->c0, d->c1);
+    if (d->workspace_bytes < p.bytes)
+        return NET_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)p.bytes);
+
+    // ---- everything checked: enqueue
+    const Run r{static_cast<const char *>(d->packed), &L, (int)d->B, stream};
+    const hipStream_t st = l3c::as_stream(stream);
+    char *ws = static_cast<char *>(d->workspace);
+    const int64_t B = d->B, h = d->h, w = d->w, W = 2 * w, ha = (p.a1 - p.a0) / 2, rows = d->c1 - d->c0;
+    const float *bn = d->bn_q, *fuse = d->fuse;
+    if (p.cut) {
+        float *g = reinterpret_cast<float *>(ws + p.bn);
+        NET_TRY(copy_rows(g, d->bn_q, B * c.C, h, p.a0 / 2, ha, w * 4, st));
+        bn = g;
+        fuse = d->fuse + (p.a0 / 2) * w * c.Cf;              // one image: the rows are contiguous where they lie
+        if (p.fuse >= 0) {
+            float *f = reinterpret_cast<float *>(ws + p.fuse);
+            NET_TRY(copy_rows(f, d->fuse, B, h, p.a0 / 2, ha, w * c.Cf * 4, st));
+            fuse = f;
+        }
+    }
+    float *F = reinterpret_cast<float *>(ws + p.F);
+    NET_TRY(decoder(r, c, 0, bn, fuse, (int)ha, (int)w, reinterpret_cast<float *>(ws), p.body / 4, F));
+    const float *Fw = F + (d->c0 - p.a0) * W * c.Cf;         // (likewise)
+    if (p.Fc >= 0) {
+        float *f = reinterpret_cast<float *>(ws + p.Fc);
+        NET_TRY(copy_rows(f, F, B, p.a1 - p.a0, d->c0 - p.a0, rows, W * c.Cf * 4, st));
+        Fw = f;
+    }
+    return prob(r, c, 0, Fw, (int)rows, (int)W, reinterpret_cast<float *>(ws), d->P);
 }
 }

@@ -7,6 +7,9 @@ byte for byte and either side decodes the other's.  L3C family, equally sized pa
 `Bitcoding(bp, bands=K)`); `decode_batch` reads either.  torch owns the memory and the streams, nothing else.  It has no other knobs, and
 no product path (Bitcoding, l3c.py, test.py, bench.py) reads it.
 
+`decode_region` returns a BOX of the pictures without decoding the rest of their finest record, as `Bitcoding.decode_region` does
+(l3c_decode_region_plan + l3c_decode_region: the region planner, the windowed network step and the finest step in the library).
+
 `encode_images` / `decode_images` take pictures as they come -- a list of host images, each of its own size, planar or interleaved RGB /
 RGBX / BGR(X) -- and leave padding and cropping to the library (l3c_encode_images / l3c_decode_images: l3c_u8_gather / l3c_u8_scatter driven
 by a table of l3c_u8_image entries, one call per group of images that pad to one shape).
@@ -21,8 +24,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._lib import CodecModel, DecodeBatchDesc, DecodeImagesDesc, EncodeBatchDesc, EncodeImagesDesc, ptr, stream
-from .bitcoding import container, upload
+from ._lib import CodecModel, DecodeBatchDesc, DecodeImagesDesc, DecodeRegionDesc, EncodeBatchDesc, EncodeImagesDesc, ptr, stream
+from .bitcoding import container, region, upload
 from .bitcoding.bitcoding import Bitcoding, _staging
 from .helpers import dataset_codec
 from .modules import schema
@@ -33,6 +36,8 @@ _PLAN_HEADER_WORDS = 26          # csrc/codec_plan.h: Header up to its records
 _PLAN_MAX_RECORDS = _lib.NET_MAX_SCALES + 1
 PLAN_BANDED_MAGIC = int.from_bytes(b'L3CBPLAN', 'little')
 _PLAN_BANDED_HEADER_WORDS = 24 + _PLAN_MAX_RECORDS     # csrc/codec_plan_banded.h: BandedHeader up to its records
+REGION_MAGIC = int.from_bytes(b'L3CRPLAN', 'little')
+_REGION_HEADER_WORDS = 48        # csrc/codec_plan_region.h: RegionHeader
 _RING = upload._H2DRing(3)
 
 
@@ -131,6 +136,30 @@ def parse_plan_banded(blob):
     return plan
 
 
+def parse_region_plan(blob):
+    """The blob l3c_decode_region_plan writes (layout: csrc/codec_plan_region.h) as a dict: the header's numbers, the pairs bands / sym_rows /
+    conv_rows / valid_rows / decoder_rows, the arrays src_offset / dst_offset / nbytes of the 3 S picked streams, `entries` = the (pixbase, hw,
+    pix0, length) int64 arrays of the S entries, and `crop` = the B l3c_u8_image records."""
+    raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+    w = raw[:8 * _REGION_HEADER_WORDS].view(np.int64)
+    names = ['magic', 'bytes', 'plan_magic', 'B', 'H', 'W', 'L', 'n']
+    plan = {n: int(w[i]) for i, n in enumerate(names)}
+    plan['padding'], plan['box'] = tuple(int(v) for v in w[8:12]), tuple(int(v) for v in w[12:16])
+    for i, n in enumerate(['bands', 'sym_rows', 'conv_rows', 'valid_rows', 'decoder_rows']):
+        plan[n] = (int(w[16 + 2 * i]), int(w[17 + 2 * i]))
+    for i, n in enumerate(['S', 'n_chunks', 'lag', 'max_nbytes', 'dst_bytes', 'streams_total', 'bytes_used', 'bytes_total']):
+        plan[n] = int(w[26 + i])
+    plan['cfg'] = [int(v) for v in w[34:43]]
+    src_off, dst_off, nb_off, ent_off, crop_off = (int(v) for v in w[43:48])
+    S, B = plan['S'], plan['B']
+    plan['src_offset'] = raw[src_off:src_off + 24 * S].view(np.int64).copy()
+    plan['dst_offset'] = raw[dst_off:dst_off + 24 * S].view(np.int64).copy()
+    plan['nbytes'] = raw[nb_off:nb_off + 12 * S].view(np.uint32).copy()
+    plan['entries'] = tuple(raw[ent_off + 8 * S * i:ent_off + 8 * S * (i + 1)].view(np.int64).copy() for i in range(4))
+    plan['crop'] = raw[crop_off:crop_off + IMAGE_DTYPE.itemsize * B].view(IMAGE_DTYPE).copy()
+    return plan
+
+
 def _plan_banded_bytes(cfg_ref, files):
     """l3c_decode_plan_banded_bytes of host byte strings: the size function reads the framing of file 0 and the signature of every file."""
     head = np.frombuffer(bytes(files[0]) + b''.join(bytes(f[:4]) for f in files[1:]) + b'\0' * 8, dtype=np.uint8)
@@ -161,6 +190,19 @@ def _check_plan(rc):
     msg = _lib.load().l3c_last_error().decode()
     if rc == -1:
         raise ValueError(msg)
+    raise _lib.L3CError('libl3c_hip: {} (status {})'.format(msg, rc))
+
+
+def _check_region(rc):
+    """The region entries' refusals as Bitcoding.decode_region raises them: ValueError for a bad argument, NotImplementedError for what is
+    outside the scope."""
+    if rc == 0:
+        return
+    msg = _lib.load().l3c_last_error().decode()
+    if rc == -1:
+        raise ValueError(msg)
+    if rc == -3:
+        raise NotImplementedError(msg)
     raise _lib.L3CError('libl3c_hip: {} (status {})'.format(msg, rc))
 
 
@@ -323,6 +365,78 @@ class NativeCodec(object):
         if seals is not None:
             container.check_frame_crcs(seals, ops.u8_crc32(pixels.view(-1), B, 3 * H.value * W.value).cpu().numpy())
         return pixels, [tuple(int(v) for v in p) for p in pads]
+
+    def decode_region(self, files, box, verify=True):
+        """The pixels of a BOX of B files of equally padded images, banded or legacy, without decoding the rest of their finest record
+        -> ((B, 3, y1 - y0, x1 - x0) uint8 on the GPU, region.RegionInfo): Bitcoding.decode_region as library calls (l3c_decode_plan[_banded],
+        l3c_decode_region_plan, l3c_decode_region).  box: (y0, y1) or (y0, y1, x0, x1) in the coordinates of the UNPADDED image.  Files,
+        plan blob and region blob cross PCIe in one copy from page-locked memory; the library's refusals are ValueError /
+        NotImplementedError with its message.  Sealed files: generation and model are checked (verify=True) before anything is enqueued;
+        a seal's CRC covers the whole frame and is NOT checked -- the info says so."""
+        lib = _lib.load()
+        if not files:
+            raise ValueError('decode_region: no files')
+        try:
+            box = tuple(int(v) for v in box)
+        except (TypeError, ValueError):
+            raise ValueError('box must be (y0, y1) or (y0, y1, x0, x1), got {!r}'.format(box))
+        if len(box) not in (2, 4):
+            raise ValueError('box must be (y0, y1) or (y0, y1, x0, x1), got {!r}'.format(box))
+        B = len(files)
+        sealed = sum(container.is_sealed(f) for f in files)
+        files, seals = self._split(files, verify)
+        banded = [container.is_banded(f) for f in files]
+        if any(banded) and not all(banded):
+            raise ValueError('decode_region: a batch mixes banded and legacy .l3c files')
+        if banded[0]:
+            plan_fn = lib.l3c_decode_plan_banded
+            n_plan = _plan_banded_bytes(self._cfg_ref, files)
+            _check_plan(min(n_plan, 0))
+        else:
+            plan_fn, n_plan = lib.l3c_decode_plan, _size(lib.l3c_decode_plan_bytes(self._cfg_ref, B))
+        offs = np.concatenate([[0], np.cumsum([len(f) for f in files])]).astype(np.int64)
+        plan_at = (int(offs[-1]) + 4 + 15) // 16 * 16
+        region_at = plan_at + (n_plan + 15) // 16 * 16
+        region_cap = 3 * n_plan + 4096          # at least l3c_decode_region_plan_bytes: every array of the region blob is shorter than the plan's
+        k, stage = _RING.take(region_at + region_cap)
+        st = stage.numpy()
+        for b, f in enumerate(files):
+            st[offs[b]:offs[b + 1]] = np.frombuffer(f, dtype=np.uint8)
+        st[offs[-1]:plan_at] = 0
+        H, W, pads = ctypes.c_int(), ctypes.c_int(), np.zeros((B, 4), dtype=np.uint16)
+        plan_host, region_host = stage.data_ptr() + plan_at, stage.data_ptr() + region_at
+        _check_plan(plan_fn(self._cfg_ref, stage.data_ptr(), offs.ctypes.data_as(ctypes.POINTER(_lib.c_i64)), B, plan_host, n_plan,
+                            ctypes.byref(H), ctypes.byref(W), pads.ctypes.data))
+        if len(box) == 2:
+            box = box + (0, W.value - int(pads[0, 0]) - int(pads[0, 1]))
+        cbox = _lib.RegionBox(*(min(max(v, -2 ** 31), 2 ** 31 - 1) for v in box))
+        info = _lib.RegionInfo()
+        n_max = lib.l3c_decode_region_plan_bytes(self._cfg_ref, plan_host)
+        _check_region(min(n_max, 0))
+        if n_max > region_cap:
+            raise _lib.L3CError('decode_region: a region blob of {} bytes beside a plan blob of {}'.format(n_max, n_plan))
+        _check_region(lib.l3c_decode_region_plan(self._cfg_ref, plan_host, n_plan, pads.ctypes.data, ctypes.byref(cbox), region_host, region_cap,
+                                                 ctypes.byref(info)))
+        n_region = int(st[region_at + 8:region_at + 16].view(np.int64)[0])      # word 1 of the header: the blob's size
+        dev = torch.empty(region_at + n_region, dtype=torch.uint8, device='cuda')
+        dev.copy_(stage[:region_at + n_region], non_blocking=True)
+        _RING.sent(k)
+        ws_bytes = lib.l3c_decode_region_workspace_bytes(self._cfg_ref, plan_host, region_host)
+        _check_region(min(ws_bytes, 0))
+        ws = _bytes(ws_bytes)
+        pixels = torch.empty(B, 3, info.out_rows, info.out_cols, dtype=torch.uint8, device='cuda')
+        side = self._side_stream(info.lag, [dev, ws, pixels, self.net.packed, self.targets_rgb])
+        d = DecodeRegionDesc(ctypes.pointer(self.model), ptr(dev), plan_host, dev.data_ptr() + plan_at, n_plan, region_host,
+                             dev.data_ptr() + region_at, n_region, ptr(pixels), ptr(ws), ws.numel())
+        _lib.call('l3c_decode_region', ctypes.byref(d), stream(), side)
+        check = seals is not None
+        pair = lambda a: (int(a[0]), int(a[1]))       # noqa: E731
+        return pixels, region.RegionInfo(box=tuple(box), bands=pair(info.bands), n_bands=int(info.n_bands), sym_rows=pair(info.sym_rows),
+                                         conv_rows=pair(info.conv_rows), valid_rows=pair(info.valid_rows), decoder_rows=pair(info.decoder_rows),
+                                         frame_rows=int(info.frame_rows), streams_used=int(info.streams_used),
+                                         streams_total=int(info.streams_total), bytes_used=int(info.bytes_used),
+                                         bytes_total=int(info.bytes_total), sealed=sealed, verified=('generation', 'model') if check else (),
+                                         pixel_crc_checked=False)
 
     def _split(self, files, verify):
         """-> (the files without their seals, the seals to verify after the decode or None); generation and model id are checked here."""
