@@ -1050,7 +1050,8 @@ int l3c_decode_images(const l3c_decode_images_desc *desc_host, l3c_stream_t main
  *   window pixels B 3 (c1 - c0) W | flags | scratch: max(l3c_net_get_p workspaces of the coarser records, their tables,
  *   l3c_net_get_p_rows_workspace_bytes, l3c_decode_rgb_entries_workspace_bytes) | 256
  * SEALS stay the caller's business, as for l3c_decode_batch: strip with l3c_seal_find before planning.  A seal's CRC covers the whole
- * frame: a region decode CANNOT check it (generation and model id can be checked as ever).
+ * frame: a region decode CANNOT check it (generation and model id can be checked as ever) unless the file is band-sealed ("band seals"
+ * below) -- and this entry does not check a band table either: it cuts the last band and keeps the window's pixels in its workspace.
  */
 typedef struct {
     int32_t y0, y1, x0, x1;         /* UNPADDED image coordinates: rows [y0, y1), columns [x0, x1) */
@@ -1106,7 +1107,7 @@ int l3c_decode_region(const l3c_decode_region_desc *desc_host, l3c_stream_t main
  * and the file's are non-zero -- both before anything is enqueued --; after the decode, l3c_u8_crc32 of `pixels` against the frame CRC.
  *
  * l3c_seal_find / l3c_seal_write are pure host code (csrc/seal.h: no HIP, compiles stand-alone).  l3c_seal_find returns 1: sealed
- * (*body_bytes_out = file_bytes - 24, *seal_out filled), 0: unsealed (*body_bytes_out = file_bytes), L3C_ERR_INVALID_ARG, "invalid file:
+ * (*body_bytes_out = file_bytes - 24 -- a band-sealed file, below: the size in front of its band table --, *seal_out filled), 0: unsealed (*body_bytes_out = file_bytes), L3C_ERR_INVALID_ARG, "invalid file:
  * seal ...": a recognised seal with an unknown version, non-zero flags or a wrong check word -- never treated as absent.  l3c_seal_write
  * stores the 24 bytes for a file whose 8 padding bytes are padding8_host.
  */
@@ -1181,6 +1182,70 @@ int l3c_u8_crc32_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_spa
  */
 int l3c_seal_append(uint8_t *files, int64_t file_stride, int64_t *file_bytes, const uint32_t *frame_crc, const uint16_t *padding,
                     uint64_t model_id, int64_t B, l3c_stream_t stream);
+
+/* ---- band seals: a CRC per band of the finest record (opt-in, banded files only; INTEGRATION.md "Band seals") ---------------------------- */
+
+/*
+ * The P of the finest scale depends on the coarser records alone, never on other pixels of that scale: a damaged byte in band j of the
+ * finest record spoils band j and nothing else.  A BAND SEAL (seal version 2) therefore carries one CRC-32 per band of the finest record,
+ * so that a region decode verifies exactly the bands it decoded and a full decode names the damaged bands:
+ *     body (the unsealed banded file) | BAND TABLE | the 24 seal bytes above with version = 2
+ *     BAND TABLE, little-endian, T = 20 + 12 n bytes:
+ *       0 'L3CT' | 4 u16 n | 6 u16 0 | 8 u32 L | 12 u32 crc[3][n] (channel-major) | 12 + 12 n u32 T | 16 + 12 n separator 46 E2 84 92
+ *   n, L         bands per channel and band length of the finest record; a reader rejects a table that states others than the record header
+ *   crc[c][j]    CRC-32 of bytes [c HW + j L, c HW + min((j + 1) L, HW)) of the padded planar frame
+ *   frame CRC    as in version 1; it must be the combination of the band CRCs (crc(A | B) = crc(A) x^(8 |B|) + crc(B) over GF(2))
+ *   check        CRC-32 of the 8 padding bytes, then the whole table, then seal bytes 0..19
+ * The table ends with the separator, so the recognition rule is the one above for both versions; T lies at file[-32:-28].
+ *
+ * l3c_seal_find_bands is l3c_seal_find that also hands out the table: *body_bytes_out is the size in front of the TABLE, bands_out->crc
+ * points INTO the file (12 n bytes, [3][n] little-endian words, unaligned); a version-1 seal gives n = 0.  "invalid file: seal ..." for a
+ * length field that is not 20 + 12 n with 1 <= n <= 1024, a table that would start in front of the body's last separator, a missing
+ * 'L3CT', a non-zero reserved field, a wrong check word, a version-2 seal on a legacy file, n or L other than the finest record's, a frame
+ * CRC that is not the combination of the band CRCs.  l3c_seal_find on a band-sealed file returns 1 with the same *body_bytes_out: a
+ * caller that knows version 1 alone goes on verifying the frame CRC.  l3c_seal_write_bands stores l3c_seal_bands_bytes(n) bytes.
+ */
+typedef struct {
+    int32_t n;                      /* bands per channel; 0: a version-1 seal */
+    uint32_t band_len;
+    const uint8_t *crc;             /* 12 n bytes inside the file: [3][n] little-endian words, unaligned */
+} l3c_seal_bands;
+int64_t l3c_seal_bands_bytes(int n);    /* 20 + 12 n + 24: table and seal */
+int l3c_seal_find_bands(const uint8_t *file_host, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out);
+int l3c_seal_write_bands(const l3c_seal *seal_host, const uint8_t *padding8_host, const uint32_t *band_crc_host, int n, uint32_t band_len,
+                         uint8_t *dst_host);
+
+/*
+ * l3c_u8_crc32_bands: the CRC-32 of every band of every plane of n_frames frames AND of every frame, the bytes read once, in two launches.
+ * Frame f is `planes` planes of plane_bytes bytes back to back at frames + f * frame_stride; band j of a plane is its bytes
+ * [j * band_bytes, min((j + 1) * band_bytes, plane_bytes)), n = ceil(plane_bytes / band_bytes) bands per plane.
+ * First launch: a WAVEFRONT per 16 KiB chunk of a band (four per block, no barrier behind the table staging): lane l loads bytes
+ * 16 l .. 16 l + 15 of every 1024-byte row and advances its four remainders by x^(8 * 1024) through the 4-bit tables of l3c_u8_crc32 in
+ * LDS, a bank per lane; a chunk's remainder, zero-filled to whole rows, goes to the workspace.  Second launch, a wavefront per frame: a
+ * lane finishes a band (its chunks, the fill undone, Z(length) added) and Horner-combines its share of a plane's band remainders; the
+ * wave combines planes into the frame's word.  Only two band lengths exist (the full band, a plane's last): their constants are
+ * computed on the host per call.  Integer only, no atomics, the same words whatever the launch geometry, no allocation, no host sync.
+ *   frames          4-byte aligned                                 frame_stride   % 4 == 0 and >= planes * plane_bytes
+ *   plane_bytes     > 0, % 4 == 0                                  band_bytes     > 0, % 4 == 0 (may exceed plane_bytes: n = 1)
+ *   band_crc_out    uint32 [n_frames][planes][n]                   frame_crc_out  uint32 [n_frames], or NULL
+ *   workspace       l3c_u8_crc32_bands_workspace_bytes(...) bytes, 16-byte aligned; garbage on entry
+ * planes in 1..1024, n_frames >= 1, n_frames * planes * n * chunks per band below 2^40.  Bytes between frames are never read into a result.
+ */
+int64_t l3c_u8_crc32_bands_workspace_bytes(int64_t n_frames, int planes, int64_t plane_bytes, int64_t band_bytes);
+int l3c_u8_crc32_bands(const uint8_t *frames, int64_t n_frames, int planes, int64_t plane_bytes, int64_t band_bytes, int64_t frame_stride,
+                       uint32_t *band_crc_out, uint32_t *frame_crc_out, void *workspace, int64_t workspace_bytes, l3c_stream_t stream);
+
+/*
+ * l3c_seal_append_bands: l3c_seal_append for band seals: the band table and the version-2 seal, l3c_seal_bands_bytes(n) bytes, behind
+ * every file on the device, file_bytes[b] grows by as much.  A wavefront per file: the lanes share the check word's 12 + 3 n words.  A
+ * band-sealed encode is l3c_encode_batch_banded, ONE l3c_u8_crc32_bands on desc.img (planes = 3, plane_bytes = H W, band_bytes = the
+ * finest record's band length), l3c_seal_append_bands -- no host round trip.  It needs file_stride >=
+ * l3c_encode_banded_file_stride(...) + l3c_seal_bands_bytes(n) rounded up to 32.
+ *   frame_crc   uint32 [B]          band_crc   uint32 [B][3][n]: the outputs of l3c_u8_crc32_bands          n in 1..1024, band_len > 0
+ * padding, model_id, file_bytes[b] == -1, a slot without room, B and file_stride: as for l3c_seal_append.
+ */
+int l3c_seal_append_bands(uint8_t *files, int64_t file_stride, int64_t *file_bytes, const uint32_t *frame_crc, const uint32_t *band_crc, int n,
+                          uint32_t band_len, const uint16_t *padding, uint64_t model_id, int64_t B, l3c_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -202,6 +202,11 @@ class Seal(ctypes.Structure):
     _fields_ = [('generation', ctypes.c_uint16), ('frame_crc', ctypes.c_uint32), ('model_id', ctypes.c_uint64)]
 
 
+class SealBands(ctypes.Structure):
+    """l3c_seal_bands (include/l3c_hip.h); crc points into the file."""
+    _fields_ = [('n', ctypes.c_int32), ('band_len', ctypes.c_uint32), ('crc', ctypes.c_void_p)]
+
+
 SEAL_BYTES = 24      # include/l3c_hip.h: L3C_SEAL_BYTES
 EPI_RELU, EPI_RESIDUAL, EPI_PIXEL_SHUFFLE = 1, 2, 4
 ABI_VERSION = 4      # include/l3c_hip.h: L3C_ABI_VERSION (4: grouped tables, l3c_decode_rgb, l3c_container_read; no canvas batches)
@@ -325,6 +330,12 @@ PROTOTYPES = {
     'l3c_u8_crc32_spans_workspace_bytes': (c_i64, [c_vp, c_i64]),
     'l3c_u8_crc32_spans': (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     'l3c_seal_append': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.c_uint64, c_i64, c_vp]),
+    'l3c_seal_bands_bytes': (c_i64, [c_int]),
+    'l3c_seal_find_bands': (c_int, [c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(Seal), ctypes.POINTER(SealBands)]),
+    'l3c_seal_write_bands': (c_int, [ctypes.POINTER(Seal), c_vp, c_vp, c_int, ctypes.c_uint32, c_vp]),
+    'l3c_u8_crc32_bands_workspace_bytes': (c_i64, [c_i64, c_int, c_i64, c_i64]),
+    'l3c_u8_crc32_bands': (c_int, [c_vp, c_i64, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'l3c_seal_append_bands': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_int, ctypes.c_uint32, c_vp, ctypes.c_uint64, c_i64, c_vp]),
 }
 
 # include/l3c_xcheck.h: the TEST-ONLY cross-check library (round-1/2 Winograd F(2x2,3x3) kernel); see load_xcheck()

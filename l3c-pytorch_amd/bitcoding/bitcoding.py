@@ -101,6 +101,8 @@ class EncodedBatch(object):
         self.coder_stream = None             # the side stream of the last `code` call (the natural place for the D2H of the files)
         self.frame_crc = None                # Bitcoding(seal=True): int32 (B,) device tensor, CRC-32 of every padded frame (ops.u8_crc32)
         self.seal = None                     # ... and (bitstream generation, model id) of the encoder: every whole file is then sealed
+        self.band_crc = None                 # Bitcoding(seal='bands'): int32 (B, 3, n) device tensor, CRC-32 of every band of the finest record's
+        self.band_len = None                 # ... planes (ops.u8_crc32_bands, with frame_crc from the same pass), and that record's band length
 
     def _coder_outputs(self):
         """(C, H, W, out, nbytes) of every coder group, nbytes reshaped to (B, streams per image of that group)."""
@@ -120,6 +122,8 @@ class EncodedBatch(object):
             nbytes.record_stream(cur)
         if self.frame_crc is not None:
             self.frame_crc.record_stream(cur)
+        if self.band_crc is not None:
+            self.band_crc.record_stream(cur)
         return self
 
     def total_payload_bytes(self):
@@ -193,11 +197,27 @@ class EncodedBatch(object):
 
     @staticmethod
     def _seals(encs, bodies):
-        """The seal of every file of `encs` (b'' for a batch encoded without): ONE D2H of the frame CRCs, the check words on the host."""
+        """The seal of every file of `encs` (b'' for a batch encoded without): ONE D2H of the frame CRCs (and the band CRCs of
+        seal='bands' batches), the band tables and check words on the host."""
         sealed = [e for e in encs if e.seal is not None]
-        crcs = iter(torch.cat([e.wait().frame_crc for e in sealed]).cpu().numpy().view(np.uint32).tolist()) if sealed else None
-        return [[container.make_seal(body, e.seal[0], next(crcs), e.seal[1]) if e.seal is not None else b'' for body in files]
-                for e, files in zip(encs, bodies)]
+        if not sealed:
+            return [[b''] * len(files) for files in bodies]
+        words = torch.cat([t.reshape(-1) for e in sealed for t in ((e.wait().frame_crc,) if e.band_crc is None else (e.frame_crc, e.band_crc))])
+        words, at, res = words.cpu().numpy().view(np.uint32), 0, []
+        for e, files in zip(encs, bodies):
+            if e.seal is None:
+                res.append([b''] * len(files))
+                continue
+            frame = words[at:at + e.B].tolist()
+            at += e.B
+            bands = [None] * e.B
+            if e.band_crc is not None:
+                assert e.band_len == e.banded_scales[-1][3], (e.band_len, e.banded_scales[-1][3])
+                per = e.band_crc[0].numel()
+                bands = [words[at + b * per:at + (b + 1) * per].reshape(3, -1) for b in range(e.B)]
+                at += e.B * per
+            res.append([container.make_seal(body, e.seal[0], frame[b], e.seal[1], bands[b], e.band_len) for b, body in enumerate(files)])
+        return res
 
     def _write_container(self, dst, offsets, padding_tuples):
         """Enqueue the assembly of this batch's files into `dst` at the (device, int64) byte `offsets`."""
@@ -297,11 +317,20 @@ class Bitcoding(object):
         seal: True = every whole file this object returns or writes (to_bytes, many_to_bytes, encode and its .partN files) ends with a
         24-byte SEAL (container.make_seal): the bitstream generation, the checkpoint's id and the CRC-32 of the padded frame, computed on the
         device (ops.u8_crc32) while the encode is enqueued; the body of a sealed file is the unsealed file.  The decoder verifies every
-        sealed file whatever this says (decode_batch)."""
+        sealed file whatever this says (decode_batch).
+        seal='bands' (banded files only: ValueError with bands=0): a BAND SEAL instead (container.make_seal with band_crcs; INTEGRATION.md
+        "Band seals"): in front of the 24 bytes a table of one CRC-32 per band of the finest record -- ops.u8_crc32_bands on the input
+        frames, the frame CRC from the same pass.  decode_batch then names the damaged bands and rows of a file that fails, and
+        decode_region verifies exactly the bands it decoded."""
+        if seal not in (False, True, 'bands'):
+            raise ValueError("seal must be False, True or 'bands', got {!r}".format(seal))
+        if seal == 'bands' and not bands:
+            raise ValueError("seal='bands' needs banded files: a band seal holds a CRC per band of the finest record (bands=K, K >= 1)")
         if bands and not 1 <= int(bands) <= MAX_BANDS:
             raise ValueError('bands must be 0 (legacy format) or in 1..{}, got {}'.format(MAX_BANDS, bands))
         self.bands = int(bands)
         self.seal = bool(seal)
+        self.seal_bands = seal == 'bands'
         self._model_id = None
         self.blueprint = blueprint
         self.auto_recurse = int(auto_recurse)
@@ -408,7 +437,11 @@ class Bitcoding(object):
         raw = out.raw
         K = net.config_ms.prob.K
         enc = EncodedBatch(B, (H, W), self.bands)
-        if self.seal:
+        if self.seal_bands:
+            enc.band_len = band_len(H * W, self.bands)
+            enc.band_crc, enc.frame_crc = ops.u8_crc32_bands(imgs.to('cuda').to(torch.uint8).contiguous().view(-1), B, H * W, enc.band_len)
+            enc.seal = (self.generation(), self.model_id())
+        elif self.seal:
             enc.frame_crc = ops.u8_crc32(imgs.to('cuda').to(torch.uint8).contiguous().view(-1), B, 3 * H * W)
             enc.seal = (self.generation(), self.model_id())
         for scale, dmll, uniform in self.iter_scale_dmll():
@@ -564,7 +597,11 @@ class Bitcoding(object):
         SEALED files (container.split_seal; a batch may mix sealed and unsealed ones): the seals are split off, then -- verify=True --
         every seal's generation and, where both sides state one, its model id are checked BEFORE anything is enqueued
         (container.SealError, reason 'generation' / 'model'); after the decode ops.u8_crc32 hashes the decoded frames on the device and ONE
-        D2H of B words is compared with the seals (SealError, reason 'pixels').  verify=False strips the seals and checks nothing."""
+        D2H of B words is compared with the seals (SealError, reason 'pixels').  verify=False strips the seals and checks nothing.
+        BAND-SEALED files among them (Bitcoding(seal='bands')): ONE ops.u8_crc32_bands on the decoded frames instead, one D2H; every
+        band-sealed file is compared band by band -- SealError('pixels') then carries .bands and .rows, the damaged bands and their
+        rows in the unpadded image; every other row is verified and can be fetched with decode_region --, the version-1 sealed files of
+        the batch against the same call's frame words."""
         split = [container.split_seal(f, view=True) for f in files]
         files, seals = [b for b, _ in split], [s for _, s in split]
         check = verify and any(s is not None for s in seals)
@@ -572,10 +609,22 @@ class Bitcoding(object):
             container.check_seals(seals, self.generation(), self.model_id)
         out, padding = self._decode_batch(files, torch.uint8 if check else out_dtype, None)
         if check:
-            B = out.shape[0]
-            container.check_frame_crcs(seals, ops.u8_crc32(out.view(-1), B, out.numel() // B).cpu().numpy())
+            self._check_pixels(seals, out, padding)
             out = out.to(out_dtype)
         return out, padding
+
+    @staticmethod
+    def _check_pixels(seals, out, padding):
+        """The decoded uint8 frames `out` (B, 3, H, W) against their seals: one hash call, one D2H; SealError('pixels')."""
+        B, _, H, W = out.shape
+        band_lens = {s.band_len for s in seals if s is not None and s.band_crcs is not None}
+        if not band_lens:
+            container.check_frame_crcs(seals, ops.u8_crc32(out.view(-1), B, out.numel() // B).cpu().numpy())
+            return
+        L, = band_lens                       # (the files of a batch share every record's band length: container.parse_batch)
+        bands, frames = ops.u8_crc32_bands(out.view(-1), B, H * W, L)
+        words = torch.cat([frames, bands.view(-1)]).cpu().numpy()
+        container.check_band_crcs(seals, words[B:].reshape(B, 3, -1), (H, W), padding, 0, words[:B])
 
     # ---- the walk over a file's scale records, coarse -> fine: what decode_batch (legacy and banded files) and the set decoder share -----
     # The headers are untrusted input: a wrong C / H / W would make the table and decoder kernels index P and the symbol buffers out of
@@ -680,7 +729,7 @@ class Bitcoding(object):
         complete record present but the finest; more than the data holds raises ValueError.  Only the bytes of the records decoded cross
         PCIe; nothing synchronises with the host."""
         total = self.n_predicted_scales() + 1
-        files = [f[:-container.SEAL_BYTES] if container.is_sealed(f) else f for f in files]     # a preview is not lossless: nothing to verify
+        files = [container.split_seal(f, view=True)[0] for f in files]     # a preview is not lossless: nothing to verify
         recs, framing, banded, n = container.parse_prefix(files, total + 1)
         if n > total:
             raise ValueError('invalid file: more than {} scale records, the model codes {}'.format(total, total))
@@ -712,7 +761,12 @@ class Bitcoding(object):
         LEGACY file is one band: its one entry per image is pixels [0, y1 W) -- the rows below the box are saved, the rows above are not.
         Every file still crosses PCIe whole (the banded framing interleaves length fields and payloads).
         SEALED files: generation and model are checked as decode_batch checks them (verify=True), before anything is enqueued; the frame CRC
-        covers the whole frame and is NOT checked -- the info says so.  L3C only: the RGB baselines raise NotImplementedError."""
+        covers the whole frame and is NOT checked -- the info says so.
+        BAND-SEALED files (Bitcoding(seal='bands')) and verify=True: the pixels ARE verified.  The plan then decodes the last band whole
+        (region_plan(cut=False): at most one band more), ops.sym_to_u8 turns the window into bytes and ONE ops.u8_crc32_spans hashes the
+        3 B (j1 - j0) decoded bands where they lie in it; the words are compared with the files' band tables: SealError('pixels') with
+        .bands and .rows, or info.verified = ('generation', 'model', 'bands') and info.pixel_crc_checked = True -- True exactly when every
+        sealed file of the call was checked this way.  L3C only: the RGB baselines raise NotImplementedError."""
         net = self.blueprint.net
         if net.config_ms.rgb_bicubic_baseline:
             raise NotImplementedError('decode_region: the RGB baselines are not windowed (every scale of theirs is an RGB scale)')
@@ -724,6 +778,8 @@ class Bitcoding(object):
         check = bool(verify and sealed)
         if check:
             container.check_seals(seals, self.generation(), self.model_id)
+        band_sealed = [s is not None and s.band_crcs is not None for s in seals]
+        check_bands = check and any(band_sealed)
         records, framing, banded = container.parse_batch(files)
         n_pred = self._n_predicted(len(records))
         self._check_coarsest(records[0], banded, int(framing.nbytes[0].max()))
@@ -739,7 +795,7 @@ class Bitcoding(object):
             C, H, W = record[:3]
             L = record[3] if banded else H * W
             n = n_bands(H * W, L)
-            plan = region.region_plan(H, W, L, rows, region.halo_rows(net.config_ms))
+            plan = region.region_plan(H, W, L, rows, region.halo_rows(net.config_ms), cut=not check_bands)
             c0, c1 = plan.conv_rows
             P = net.get_P_rows(0, bn, F, plan.conv_rows)
             if tuple(P.shape) != (B, c1 - c0, W, Kp):
@@ -764,6 +820,8 @@ class Bitcoding(object):
         sym = self._walk_records(records, framing, banded, streams, n_pred, len(records), None, finest)
         plan = found['plan']
         c0 = plan.conv_rows[0]
+        if check_bands:
+            self._check_region_bands(seals, sym, plan, records[-1], framing.padding)
         out = sym[:, :, rows[0] - c0:rows[1] - c0, cols[0]:cols[1]].to(out_dtype)
         left, _, top, _ = framing.padding[0]
         info = region.RegionInfo(box=(rows[0] - top, rows[1] - top, cols[0] - left, cols[1] - left), bands=plan.bands, n_bands=found['n'],
@@ -771,8 +829,25 @@ class Bitcoding(object):
                                  decoder_rows=region.decoder_rows(Hf, plan.conv_rows, region.apron_rows(net.config_ms)), frame_rows=Hf,
                                  streams_used=found['streams_used'], streams_total=int(framing.nbytes[-1].size),
                                  bytes_used=found['bytes_used'], bytes_total=int(framing.nbytes[-1].sum()), sealed=sealed,
-                                 verified=('generation', 'model') if check else (), pixel_crc_checked=False)
+                                 verified=(('generation', 'model', 'bands') if check_bands else ('generation', 'model')) if check else (),
+                                 pixel_crc_checked=check_bands and sum(band_sealed) == sealed)
         return out, info
+
+    @staticmethod
+    def _check_region_bands(seals, sym, plan, record, padding):
+        """decode_region on band-sealed files: the bands [j0, j1) the window holds WHOLE (region_plan(cut=False)) against the files' band
+        tables.  Band (b, c, j) lies at byte ((3 b + c)(c1 - c0) - c0) W + j L of the window's pixels, min(L, HW - j L) bytes long."""
+        _, H, W, L = record
+        B = sym.shape[0]
+        (j0, j1), (c0, c1) = plan.bands, plan.conv_rows
+        pixels = ops.sym_to_u8(sym.contiguous())
+        plane = np.arange(3 * B, dtype=np.int64)[:, None]
+        j = np.arange(j0, j1, dtype=np.int64)[None, :]
+        offsets = (plane * (c1 - c0) - c0) * W + j * L
+        lengths = np.broadcast_to(np.minimum(L, H * W - j * L), offsets.shape)
+        assert (offsets % 4 == 0).all() and (offsets >= 0).all(), (W, L, c0)      # W a multiple of the padding factor, L of 64
+        words = ops.u8_crc32_spans(pixels.view(-1), offsets.reshape(-1), lengths.reshape(-1)).cpu().numpy().reshape(B, 3, j1 - j0)
+        container.check_band_crcs(seals, words, (H, W), padding, j0)
 
     def _scale_symbols_of(self, banded):
         """The decoder of one scale record of a batch, by the files' format (the walk and the set decoder's coarsest scale)."""

@@ -333,21 +333,48 @@ def image_entry_table(hws, pixbase0=0):
 #     'L3CS' | u8 version = 1 | u8 flags = 0 | u16 bitstream generation | u32 frame CRC | u64 model id | u32 check
 # frame CRC: zlib.crc32 of the padded planar frame [3][H][W]; model id: 0 = not stated; check: zlib.crc32 of the file's 8 padding bytes
 # followed by seal bytes 0..19.  The parsers above never see a seal: callers split it off first.
+#
+# BAND SEALS (opt-in, Bitcoding(bands=K, seal='bands'); INTEGRATION.md "Band seals"), banded files only: seal version 2 with a BAND TABLE in
+# front of the 24 bytes, T = 20 + 12 n bytes:
+#     'L3CT' | u16 n | u16 0 | u32 L | u32 crc[3][n] (channel-major) | u32 T | separator 46 E2 84 92
+# n, L: bands per channel and band length of the finest record; crc[c][j]: zlib.crc32 of bytes [c HW + j L, c HW + min((j + 1) L, HW)) of
+# the padded planar frame.  The check word runs over the padding bytes, the whole table and seal bytes 0..19; the frame CRC stays and must
+# be the combination of the band CRCs (combine_band_crcs).  The recognition rule (is_sealed) is the same: the table ends with the separator.
 
 SEAL_SIGNATURE = b'L3CS'
 SEAL_VERSION = 1
+SEAL_VERSION_BANDS = 2
 SEAL_BYTES = 24
+TABLE_SIGNATURE = b'L3CT'
+
+
+def seal_bands_bytes(n):
+    """Bytes a band seal adds to a file of n bands per channel: the table and the 24 seal bytes."""
+    return 20 + 12 * int(n) + SEAL_BYTES
 
 
 class Seal(object):
-    def __init__(self, generation, frame_crc, model_id):
+    """band_len, band_crcs: None for a version-1 seal; for a band seal the finest record's band length and the (3, n) uint32 band CRCs."""
+
+    def __init__(self, generation, frame_crc, model_id, band_len=None, band_crcs=None):
         self.generation, self.frame_crc, self.model_id = int(generation), int(frame_crc), int(model_id)
+        self.band_len = None if band_crcs is None else int(band_len)
+        self.band_crcs = None if band_crcs is None else np.array(band_crcs, dtype=np.uint32).reshape(3, -1)
+
+    def _key(self):
+        return (self.generation, self.frame_crc, self.model_id, self.band_len, None if self.band_crcs is None else self.band_crcs.tobytes())
 
     def __eq__(self, other):
-        return isinstance(other, Seal) and (self.generation, self.frame_crc, self.model_id) == (other.generation, other.frame_crc, other.model_id)
+        return isinstance(other, Seal) and self._key() == other._key()
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = None
 
     def __repr__(self):
-        return 'Seal(generation={}, frame_crc=0x{:08x}, model_id=0x{:016x})'.format(self.generation, self.frame_crc, self.model_id)
+        bands = '' if self.band_crcs is None else ', band_len={}, band_crcs=<3 x {}>'.format(self.band_len, self.band_crcs.shape[1])
+        return 'Seal(generation={}, frame_crc=0x{:08x}, model_id=0x{:016x}{})'.format(self.generation, self.frame_crc, self.model_id, bands)
 
 
 class SealError(ValueError):
@@ -355,12 +382,16 @@ class SealError(ValueError):
     another bitstream generation), 'model' (by another checkpoint) -- both raised before anything is decoded --, 'pixels' (the decoded
     frame does not hash to the seal's CRC: a damaged payload, or a checkpoint the seal does not state).  index: the file's place in the call
     (the set readers: (entry, file), or the caller's key); failed: the places of ALL files known to have failed for that reason when the
-    error was raised, in call order -- `index` is the first of them."""
+    error was raised, in call order -- `index` is the first of them.
+    bands, rows: None, except on the 'pixels' error of band-sealed files (check_band_crcs): bands = {file: [(channel, band), ...]} the
+    bands whose pixels do not hash to their table word, rows = {file: (y0, y1)} their hull in rows of the UNPADDED image, None where they
+    lie in the padding rows alone.  Every row outside the hull decoded to the sealed pixels."""
 
-    def __init__(self, reason, index, message, failed=None):
+    def __init__(self, reason, index, message, failed=None, bands=None, rows=None):
         ValueError.__init__(self, message)
         self.reason, self.index = reason, index
         self.failed = [index] if failed is None else list(failed)
+        self.bands, self.rows = bands, rows
 
 
 def _padding_bytes(body):
@@ -371,35 +402,217 @@ def _padding_bytes(body):
 
 
 def is_sealed(data):
-    """Whether the file ends with a seal: at least 28 bytes, 'L3CS' 24 bytes before the end and the scale separator in front of it (every
-    unsealed file of either format ends with that separator).  A damaged seal still counts: split_seal raises for it."""
+    """Whether the file ends with a seal of either version: at least 28 bytes, 'L3CS' 24 bytes before the end and the scale separator in
+    front of it (every unsealed file of either format ends with that separator, and so does a band table).  A damaged seal still counts:
+    split_seal raises for it."""
     return len(data) >= SEAL_BYTES + 4 and bytes(data[-24:-20]) == SEAL_SIGNATURE and bytes(data[-28:-24]) == _MAGIC_VALUE_SEP
 
 
-def make_seal(body, generation, frame_crc, model_id=0):
-    """The 24 seal bytes for the unsealed file `body` (its padding fields go into the check word)."""
+_CRC_POLY = 0xEDB88320
+_X8_TABLES = {}
+
+
+def _x8_tables(nbytes):
+    """ "Times x^(8 nbytes) mod P" as four 256-entry tables, one per byte of the other factor (CRC registers are reflected: bit 31 is
+    x^0): a x^(8 nbytes) = t[0][a & 255] ^ t[1][a >> 8 & 255] ^ t[2][a >> 16 & 255] ^ t[3][a >> 24].  The arithmetic of csrc/crc_spans.h
+    (mulmod, powmod); kept per length: the files of a call share two."""
+    t = _X8_TABLES.get(nbytes)
+    if t is not None:
+        return t
+
+    def mul(a, b):
+        p = 0
+        for i in range(31, -1, -1):
+            if (a >> i) & 1:
+                p ^= b
+            b = (b >> 1) ^ (_CRC_POLY if b & 1 else 0)
+        return p
+    r, base, e = 0x80000000, 0x00800000, int(nbytes)          # 1, x^8
+    while e:
+        if e & 1:
+            r = mul(r, base)
+        base = mul(base, base)
+        e >>= 1
+    row = [0] * 32                                            # row[i]: what bit i of the other factor adds -- bit i is x^(31 - i)
+    for i in range(31, -1, -1):
+        row[i] = r
+        r = (r >> 1) ^ (_CRC_POLY if r & 1 else 0)
+    t = []
+    for byte in range(4):
+        tab = [0]
+        for bit in range(8):
+            tab += [v ^ row[8 * byte + bit] for v in tab]
+        t.append(tab)
+    if len(_X8_TABLES) >= 64:
+        _X8_TABLES.clear()
+    _X8_TABLES[nbytes] = t
+    return t
+
+
+def combine_band_crcs(crcs, L, HW):
+    """zlib.crc32 of a planar frame [3][HW] from the CRCs of its bands, crcs (3, n) with n = ceil(HW / L): the frame is the concatenation
+    of the bands in (channel, band) order, and crc(A | B) = crc(A) x^(8 |B|) + crc(B) over GF(2) (zlib's crc32_combine)."""
+    crcs = np.asarray(crcs).astype(np.int64) & 0xffffffff
+    n = n_bands(HW, L)
+    if crcs.shape != (3, n):
+        raise ValueError('combine_band_crcs: {} band CRCs for 3 x {} bands'.format(crcs.shape, n))
+    words = crcs.tolist()
+    (f0, f1, f2, f3), (l0, l1, l2, l3) = _x8_tables(int(L)), _x8_tables(int(HW - (n - 1) * L))
+    a = 0
+    for c in range(3):
+        row = words[c]
+        for j in range(n - 1):
+            a = f0[a & 255] ^ f1[a >> 8 & 255] ^ f2[a >> 16 & 255] ^ f3[a >> 24] ^ row[j]
+        a = l0[a & 255] ^ l1[a >> 8 & 255] ^ l2[a >> 16 & 255] ^ l3[a >> 24] ^ row[n - 1]
+    return a
+
+
+def _finest_header(body):
+    """(C, H, W, L) of the last scale record of a banded file, walked by the length fields alone (csrc/seal.h: finest_record); None where
+    the records do not end exactly with the data.  The parsers above do the full job later; this is what a seal's table is checked against."""
+    end, p, found = len(body), 14, None
+    if end < 14 or not is_banded(body):
+        return None
+    unpack = struct.unpack_from
+    while p < end:
+        if end - p < 9:
+            return None
+        C, H, W, L = unpack('<BHHI', body, p)
+        p += 9
+        if C == 0 or H * W == 0 or L == 0 or L % 64:
+            return None
+        n = n_bands(H * W, L)
+        if n > MAX_BANDS:
+            return None
+        for _ in range(C * n):
+            if end - p < 4:
+                return None
+            p += 4 + unpack('<I', body, p)[0]
+        if end - p < 4 or bytes(body[p:p + 4]) != _MAGIC_VALUE_SEP:
+            return None
+        p += 4
+        found = (C, H, W, L)
+    return found
+
+
+def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=None):
+    """The seal bytes for the unsealed file `body` (its padding fields go into the check word): 24 bytes, or with band_crcs ((3, n) words)
+    and band_len (the finest record's) the band table and the version-2 seal, seal_bands_bytes(n) bytes."""
     import zlib
-    head = SEAL_SIGNATURE + struct.pack('<BBHIQ', SEAL_VERSION, 0, generation, frame_crc & 0xffffffff, model_id)
-    return head + struct.pack('<I', zlib.crc32(_padding_bytes(body) + head) & 0xffffffff)
+    table = b''
+    if band_crcs is not None:
+        crcs = np.ascontiguousarray(np.asarray(band_crcs).astype(np.int64) & 0xffffffff, dtype='<u4').reshape(3, -1)
+        n = crcs.shape[1]
+        if not 1 <= n <= MAX_BANDS or band_len is None or int(band_len) <= 0:
+            raise ValueError('make_seal: a band seal needs 1..{} bands per channel and their length, got {} and {}'.format(MAX_BANDS, n, band_len))
+        if not is_banded(body):
+            raise ValueError('make_seal: a band seal needs a banded file')
+        T = 20 + 12 * n
+        table = TABLE_SIGNATURE + struct.pack('<HHI', n, 0, int(band_len)) + crcs.tobytes() + struct.pack('<I', T) + _MAGIC_VALUE_SEP
+    head = SEAL_SIGNATURE + struct.pack('<BBHIQ', SEAL_VERSION_BANDS if table else SEAL_VERSION, 0, generation, frame_crc & 0xffffffff, model_id)
+    return table + head + struct.pack('<I', zlib.crc32(_padding_bytes(body) + table + head) & 0xffffffff)
 
 
 def split_seal(data, view=False):
-    """-> (body, Seal or None): the file without its seal, as the parsers above expect it.  ValueError('invalid file: seal ...') for a
-    recognised seal with an unknown version, non-zero flags or a wrong check word: never silently treated as absent.
-    view=True: the body of a sealed file is a memoryview of `data`, not a copy (the decoders: a copy of every file is a millisecond per
-    10 MB on the host, more than the hash costs on the device); everything above reads either."""
+    """-> (body, Seal or None): the file without its seal (and band table), as the parsers above expect it.
+    ValueError('invalid file: seal ...') for a recognised seal with an unknown version, non-zero flags or a wrong check word, and for a band
+    seal whose table is not where its length field says, lacks its signature, has a non-zero reserved field, sits on a legacy file, states
+    another n or L than the finest record's header, or whose frame CRC is not the combination of its band CRCs: never silently treated as
+    absent.  view=True: the body of a sealed file is a memoryview of `data`, not a copy (the decoders: a copy of every file is a
+    millisecond per 10 MB on the host, more than the hash costs on the device); everything above reads either."""
     import zlib
     if not is_sealed(data):
         return data, None
-    body, s = (memoryview(data) if view else data)[:-SEAL_BYTES], bytes(data[-SEAL_BYTES:])
+    end, s = len(data) - SEAL_BYTES, bytes(data[-SEAL_BYTES:])
     version, flags, generation, frame_crc, model_id, check = struct.unpack('<BBHIQI', s[4:])
-    if version != SEAL_VERSION:
+    if version not in (SEAL_VERSION, SEAL_VERSION_BANDS):
         raise ValueError('invalid file: seal of an unknown version')
+    table = b''
+    if version == SEAL_VERSION_BANDS:
+        if not is_banded(data):
+            raise ValueError('invalid file: seal of an unknown version for a legacy file (version 2, the band seal, needs a banded file)')
+        if end < 20 + 12 + 4:
+            raise ValueError('invalid file: seal of an unknown version: 2 needs a band table, and the file is too short for one')
+        T, = struct.unpack('<I', bytes(data[end - 8:end - 4]))
+        n = (T - 20) // 12
+        if T < 20 or (T - 20) % 12 or not 1 <= n <= MAX_BANDS:
+            raise ValueError('invalid file: seal of an unknown version: 2 needs a band table, and its length field is not 20 + 12 n with '
+                             '1 <= n <= 1024')
+        if T > end - 14 - 4 or bytes(data[end - T - 4:end - T]) != _MAGIC_VALUE_SEP:
+            raise ValueError("invalid file: seal band table does not start behind the file's last scale separator")
+        table, end = bytes(data[end - T:end]), end - T
+        if table[:4] != TABLE_SIGNATURE:
+            raise ValueError("invalid file: seal band table without its 'L3CT' signature")
+        if table[6:8] != b'\0\0':
+            raise ValueError('invalid file: seal band table with a non-zero reserved field')
     if flags:
         raise ValueError('invalid file: seal with non-zero flags')
-    if check != zlib.crc32(_padding_bytes(body) + s[:20]) & 0xffffffff:
+    body = (memoryview(data) if view else data)[:end]
+    if check != zlib.crc32(_padding_bytes(body) + table + s[:20]) & 0xffffffff:
         raise ValueError('invalid file: seal check word does not match (damaged seal or padding fields)')
-    return body, Seal(generation, frame_crc, model_id)
+    if not table:
+        return body, Seal(generation, frame_crc, model_id)
+    n_stated, _, L = struct.unpack('<HHI', table[4:12])
+    if n_stated != n:
+        raise ValueError('invalid file: seal band table states another band count than its length')
+    finest = _finest_header(body)
+    if finest is None or finest[3] != L or n_bands(finest[1] * finest[2], L) != n:
+        raise ValueError("invalid file: seal band table does not match the bands of the file's finest scale record")
+    crcs = np.frombuffer(table[12:12 + 12 * n], dtype='<u4').reshape(3, n)
+    if combine_band_crcs(crcs, L, finest[1] * finest[2]) != frame_crc:
+        raise ValueError('invalid file: seal frame CRC is not the combination of its band CRCs')
+    return body, Seal(generation, frame_crc, model_id, L, crcs)
+
+
+def band_rows(j, L, frame_hw, padding):
+    """Rows [y0, y1) of the UNPADDED image that bands j (an int or a sequence) of length L of an H x W frame touch: their hull, or None when
+    they lie in the padding rows alone.  padding: (left, right, top, bottom)."""
+    H, W = frame_hw
+    js = [int(j)] if np.isscalar(j) else [int(v) for v in j]
+    top, bottom = int(padding[2]), int(padding[3])
+    r0 = min(js) * L // W
+    r1 = -(-min((max(js) + 1) * L, H * W) // W)
+    y0, y1 = max(r0 - top, 0), min(r1 - top, H - top - bottom)
+    return (y0, y1) if y0 < y1 else None
+
+
+def check_band_crcs(seals, words, frame_hw, paddings, first_band=0, frame_words=None):
+    """After the decode: the band CRCs of the decoded pixels against the tables.  seals: per file a Seal or None; words[i]: the (3, m) CRC
+    words of bands first_band .. first_band + m - 1 of decoded frame i (a full decode: all n; a region decode: the bands it decoded), ignored
+    for files without a band seal; frame_hw: the padded (H, W); paddings: per file (left, right, top, bottom).  frame_words: the frame
+    CRCs of the decoded frames, compared with the version-1 seals of the same call (None: those are not checked here).
+    SealError('pixels') names the first failing file, lists all, and carries .bands and .rows for the band-sealed ones."""
+    failed, bands, rows = [], {}, {}
+    words = (np.asarray(words).astype(np.int64) & 0xffffffff).astype(np.uint32)      # int32 or uint32 words, all files at once
+    for i, s in enumerate(seals):
+        if s is None:
+            continue
+        if s.band_crcs is None:
+            if frame_words is not None and (int(frame_words[i]) & 0xffffffff) != s.frame_crc:
+                failed.append(i)
+            continue
+        got = words[i]
+        want = s.band_crcs[:, first_band:first_band + got.shape[1]]
+        if got.shape != want.shape:
+            raise ValueError('check_band_crcs: file {}: {} words for bands {}.. of a 3 x {} table'.format(i, got.shape, first_band, s.band_crcs.shape[1]))
+        if np.array_equal(got, want):
+            continue
+        bad = [(int(c), int(first_band + j)) for c, j in zip(*np.nonzero(got != want))]
+        if bad:
+            failed.append(i)
+            bands[i] = bad
+            rows[i] = band_rows(sorted({j for _, j in bad}), s.band_len, frame_hw, paddings[i])
+    if failed:
+        i = failed[0]
+        if i in bands:
+            where = 'rows [{}, {})'.format(*rows[i]) if rows[i] else 'the padding rows'
+            msg = ('file {} decoded to pixels that do not hash to its band CRCs in {} band(s) (channel, band) {}: {} of the image are damaged (a '
+                   'damaged payload, or not the checkpoint that wrote it); every other row is verified'.format(
+                       i, len(bands[i]), bands[i][:6] + (['...'] if len(bands[i]) > 6 else []), where))
+        else:
+            msg = ('file {} decoded to pixels whose CRC-32 {:08x} is not the sealed {:08x}: damaged payload, or not the checkpoint that wrote '
+                   'it'.format(i, int(frame_words[i]) & 0xffffffff, seals[i].frame_crc))
+        raise SealError('pixels', i, msg, failed, bands or None, rows or None)
 
 
 def check_seals(seals, generation, model_id):

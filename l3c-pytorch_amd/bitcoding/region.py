@@ -117,7 +117,9 @@ class RegionInfo(object):
     record's bands per channel and the frame's rows; streams_used / streams_total and bytes_used / bytes_total: the band streams of the finest
     record the range decoder read, and their payload bytes, of all the record holds (summed over the batch; the coarser records are decoded
     whole and are not counted); verified: the seal fields that were checked ('generation', 'model'), empty for unsealed files or verify=False;
-    pixel_crc_checked: always False -- a seal's CRC covers the whole frame."""
+    ('bands' too where the decoded bands were hashed); pixel_crc_checked: True when every sealed file of the call is BAND-SEALED and the
+    bands the call decoded hashed to their table words (Bitcoding.decode_region, verify=True); False otherwise -- a version-1 seal's CRC
+    covers the whole frame."""
 
     FIELDS = ('box', 'bands', 'n_bands', 'sym_rows', 'conv_rows', 'valid_rows', 'decoder_rows', 'frame_rows', 'streams_used', 'streams_total', 'bytes_used',
               'bytes_total', 'sealed', 'verified', 'pixel_crc_checked')
@@ -134,8 +136,12 @@ class RegionInfo(object):
 
     def line(self):
         """One line for people (l3c.py dec --region)."""
-        seal = ('sealed: {} checked, pixel CRC not checked (it covers the whole frame)'.format(' and '.join(self.verified) or 'nothing')
-                if self.sealed else 'not sealed')
+        if self.sealed and self.pixel_crc_checked:
+            seal = 'band-sealed: generation and model checked, the CRCs of bands {}..{} of every channel checked: every decoded pixel is verified'.format(
+                self.bands[0], self.bands[1] - 1)
+        else:
+            seal = ('sealed: {} checked, pixel CRC not checked (it covers the whole frame)'.format(
+                ' and '.join(v for v in self.verified if v != 'bands') or 'nothing') if self.sealed else 'not sealed')
         return ('region rows [{}, {}) x columns [{}, {}): bands {}..{} of {}, symbol rows {}..{}, conv rows {}..{} and decoder rows {}..{} '
                 'of {}, {} of {} streams, {} of {} payload bytes of the finest record; {}'.format(
                     self.box[0], self.box[1], self.box[2], self.box[3], self.bands[0], self.bands[1] - 1, self.n_bands, self.sym_rows[0],

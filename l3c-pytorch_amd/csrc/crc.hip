@@ -1,4 +1,5 @@
-// crc.hip -- sealed files (include/l3c_hip.h: l3c_u8_crc32, l3c_seal_append, l3c_seal_find / l3c_seal_write; the format is csrc/seal.h).
+// crc.hip -- sealed files (include/l3c_hip.h: l3c_u8_crc32, l3c_seal_append, l3c_seal_find / l3c_seal_write; the format is csrc/seal.h) and band
+// seals (l3c_u8_crc32_bands, l3c_seal_append_bands, l3c_seal_find_bands / l3c_seal_write_bands: the second half of this file).
 //
 // l3c_u8_crc32: zlib's CRC-32 of n_items byte runs, integer only, the same words whatever the launch geometry, no atomics.
 //
@@ -33,10 +34,11 @@ namespace {
 
 using namespace l3c_crc;      // crc_spans.h: mulmod, powmod, the tile geometry, the constants of a run's length
 constexpr int MAX_GRID = 4096, DEPTH = 8;
+constexpr int BAND_GRID = 1024;      // blocks of the band chunk launch: four a CU, each stages the tables once for many chunks
 
-// [0]: MULK, [1]: MUL32 -- entry 16 k + n is (n << 4 k) times the constant
+// [0]: MULK, [1]: MUL32, [2]: MULW (a wavefront's row, l3c_u8_crc32_bands) -- entry 16 k + n is (n << 4 k) times the constant
 struct NibbleTables {
-    uint32_t v[2][128];
+    uint32_t v[3][128];
 };
 constexpr NibbleTables make_tables() {
     NibbleTables t{};
@@ -44,6 +46,7 @@ constexpr NibbleTables make_tables() {
         for (uint32_t n = 0; n < 16; ++n) {
             t.v[0][16 * k + n] = mulmod(n << (4 * k), K_ROW);
             t.v[1][16 * k + n] = mulmod(n << (4 * k), POLY);
+            t.v[2][16 * k + n] = mulmod(n << (4 * k), K_WROW);
         }
     return t;
 }
@@ -114,16 +117,16 @@ __device__ __forceinline__ u32x4 load_quad(const uint8_t *p) {
 
 // N whole rows from p on, straight-line code: up to DEPTH rows of loads in flight per thread -- 16 waves x DEPTH KiB per CU, what it takes to
 // hide the memory latency behind a row's arithmetic -- and, with no branch in between, a wait for exactly the load a row needs
-template <int N>
+template <int N, int STRIDE = ROW_BYTES>
 __device__ __forceinline__ void fold_rows(const uint32_t *tab, uint32_t (&a)[4], const uint8_t *p) {
     constexpr int D = N < DEPTH ? N : DEPTH;
     u32x4 q[D];
 #pragma unroll
-    for (int i = 0; i < D; ++i) q[i] = load_quad(p + i * ROW_BYTES);
+    for (int i = 0; i < D; ++i) q[i] = load_quad(p + i * STRIDE);
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         const u32x4 cur = q[i % D];
-        if (i + D < N) q[i % D] = load_quad(p + (i + D) * ROW_BYTES);
+        if (i + D < N) q[i % D] = load_quad(p + (i + D) * STRIDE);
         row_step(tab, a, cur);
     }
 }
@@ -313,6 +316,159 @@ __global__ __launch_bounds__(64) void seal_append_kernel(uint8_t *__restrict__ f
     file_bytes[b] = n + L3C_SEAL_BYTES;
 }
 
+// ---- l3c_u8_crc32_bands: every band of every plane of every frame, and every frame, from one pass over the bytes -------------------------
+//
+// A band is 64 bytes to a few hundred KiB, small next to the 128 KiB tile above, so the unit here is a WAVEFRONT on a chunk of WCHUNK
+// bytes of one band: rows of WROW = 64 x 16 bytes, lane l on bytes 16 l .. 16 l + 15 of every row, the row step through MULW (x^(8 WROW))
+// in LDS, a bank per lane as above.  The four waves of a block work on four chunks and never meet: no barrier behind the staging.
+// The constants of a band length (BandConsts) exist twice per call -- every band but a plane's last has one length -- and come from the
+// host; nothing is prepared on the device.
+struct BandConsts {
+    int64_t bytes;                    // of the band
+    int64_t chunks;                   // ceil(bytes / WCHUNK)
+    uint32_t k_last, unfill, z;       // as SpanConsts, for rows of WROW bytes and chunks of WCHUNK
+    uint32_t k_band;                  // x^(8 bytes): Horner over the bands of a plane
+};
+struct BandsCall {
+    BandConsts full, last;            // bands 0 .. n - 2 of a plane, band n - 1
+    int64_t n_frames, planes, n, cpb; // cpb: partial words per band (the chunks of the longest band)
+    int64_t plane_bytes, band_bytes, frame_stride;
+    uint32_t k_plane, z_frame;        // x^(8 plane_bytes), Z(planes * plane_bytes)
+};
+
+__global__ __launch_bounds__(THREADS) void u8_crc32_band_chunks_kernel(const uint8_t *__restrict__ frames, BandsCall g, int64_t units,
+                                                                      uint32_t *__restrict__ partial) {
+    __shared__ uint32_t lds[2 * 128 * 32];
+    const int t = threadIdx.x, lane = t & 63;
+    for (int i = 0; i < 32; ++i) {                                           // MULW, then MUL32
+        const int idx = i * THREADS + t;
+        lds[idx] = idx < 128 * 32 ? g_tables.v[2][idx >> 5] : g_tables.v[1][(idx >> 5) - 128];
+    }
+    const uint32_t shift = g_shifts.v[THREADS - 64 + lane];                  // x^(8 * 16 (63 - lane)): the bytes of a row behind the lane's 16
+    const uint32_t *mulw = lds + (t & 31), *mul32 = lds + 128 * 32 + (t & 31);
+    __syncthreads();
+    for (int64_t unit = (int64_t)blockIdx.x * (THREADS / 64) + (t >> 6); unit < units; unit += (int64_t)gridDim.x * (THREADS / 64)) {
+        const int64_t band = unit / g.cpb, chunk = unit - band * g.cpb;      // band: (frame, plane, j) flattened
+        const int64_t fp = band / g.n, j = band - fp * g.n, f = fp / g.planes, c = fp - f * g.planes;
+        const int64_t bytes = j + 1 < g.n ? g.full.bytes : g.last.bytes;
+        const int64_t chunk_at = chunk * WCHUNK;
+        if (chunk_at >= bytes) continue;                                     // a shorter last band: the word is never read
+        const uint8_t *base = frames + f * g.frame_stride + c * g.plane_bytes + j * g.band_bytes;
+        const int64_t left = bytes - chunk_at;
+        const int whole = left >= WCHUNK ? WROWS : (int)(left / WROW);
+        uint32_t a[4] = {0u, 0u, 0u, 0u};
+        const uint8_t *p = base + chunk_at + 16 * lane;
+        if (whole == WROWS) {
+            fold_rows<WROWS, WROW>(mulw, a, p);
+        } else {
+            int r = 0;
+            for (; r + 4 <= whole; r += 4) fold_rows<4, WROW>(mulw, a, p + r * WROW);
+            for (; r < whole; ++r) fold_rows<1, WROW>(mulw, a, p + r * WROW);
+            if (left > (int64_t)whole * WROW) row_step(mulw, a, load16(base, chunk_at + (int64_t)whole * WROW + 16 * lane, bytes));
+        }
+        uint32_t v = times(mul32, a[0]);
+        v = times(mul32, v ^ a[1]);
+        v = times(mul32, v ^ a[2]);
+        v = times(mul32, v ^ a[3]);
+        v = mulmod(v, shift);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d, 64);
+        if (lane == 0) partial[unit] = v;
+    }
+}
+
+// the remainder of one band from its chunks' (from a zero register, without Z)
+__device__ __forceinline__ uint32_t band_raw(const uint32_t *p, const BandConsts &k) {
+    uint32_t a = 0;
+    for (int64_t i = 0; i + 1 < k.chunks; ++i) a = mulmod(a, K_WCHUNK) ^ p[i];
+    if (k.chunks > 1) a = mulmod(a, k.k_last);
+    return mulmod(a ^ p[k.chunks - 1], k.unfill);
+}
+
+// Second launch, a wavefront per frame.  Per plane: lane l finishes its contiguous share of the full bands, stores their words, and runs
+// Horner over their remainders with x^(8 band_bytes), weighs it with the full bands behind the share, the wave XORs; lane 0 adds the last band
+// and the plane to the frame's remainder.  raw(A | B) = raw(A) x^(8 |B|) + raw(B); Z(frame length) once at the end.
+__global__ __launch_bounds__(64) void u8_crc32_bands_combine_kernel(const uint32_t *__restrict__ partial, BandsCall g, uint32_t *__restrict__ band_crc,
+                                                                    uint32_t *__restrict__ frame_crc) {
+    const int lane = threadIdx.x;
+    const int64_t full = g.n - 1, share = (full + 63) / 64;
+    const int64_t lo = lane * share < full ? lane * share : full, hi = lo + share < full ? lo + share : full;
+    const bool weigh = hi > lo && hi < full;
+    const uint32_t weight = weigh ? powmod(g.full.k_band, (uint64_t)(full - hi)) : ONE;
+    for (int64_t f = blockIdx.x; f < g.n_frames; f += gridDim.x) {
+        uint32_t frame = 0;
+        for (int64_t c = 0; c < g.planes; ++c) {
+            const int64_t band0 = (f * g.planes + c) * g.n;
+            uint32_t a = 0;
+            for (int64_t j = lo; j < hi; ++j) {
+                const uint32_t r = band_raw(partial + (band0 + j) * g.cpb, g.full);
+                band_crc[band0 + j] = r ^ g.full.z;
+                a = mulmod(a, g.full.k_band) ^ r;
+            }
+            if (weigh) a = mulmod(a, weight);
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) a ^= __shfl_xor(a, d, 64);
+            if (lane == 0) {
+                const uint32_t r = band_raw(partial + (band0 + full) * g.cpb, g.last);
+                band_crc[band0 + full] = r ^ g.last.z;
+                frame = mulmod(frame, g.k_plane) ^ mulmod(a, g.last.k_band) ^ r;
+            }
+        }
+        if (lane == 0 && frame_crc) frame_crc[f] = frame ^ g.z_frame;
+    }
+}
+
+// l3c_seal_append_bands, a wavefront per file.  The check word runs over M = 12 + 3 n little-endian words: the padding (2), the table
+// (5 + 3 n), seal words 0..4.  Lane l folds its contiguous share bit by bit, weighs it with x^(32 * words behind the share), the wave
+// XORs, Z(4 M) comes from the host.  Every lane stores the bytes of the words it walks: byte stores, a file ends anywhere.
+__global__ __launch_bounds__(64) void seal_append_bands_kernel(uint8_t *__restrict__ files, int64_t file_stride, int64_t *__restrict__ file_bytes,
+                                                               const uint32_t *__restrict__ frame_crc, const uint32_t *__restrict__ band_crc,
+                                                               int n, uint32_t band_len, const uint16_t *__restrict__ padding, uint64_t model_id,
+                                                               uint32_t generation, uint32_t z_check, int64_t B) {
+    const int lane = threadIdx.x;
+    const int M = 12 + 3 * n, T = 20 + 12 * n;
+    const int share = (M + 63) / 64;
+    const int lo = lane * share < M ? lane * share : M, hi = lo + share < M ? lo + share : M;
+    const uint32_t weight = powmod(POLY, (uint64_t)(M - hi));                      // POLY is x^32
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        const int64_t at = file_bytes[b];
+        if (at < 0) continue;
+        if (at > file_stride - (T + L3C_SEAL_BYTES)) {
+            if (lane == 0) file_bytes[b] = -1;
+            continue;
+        }
+        uint8_t *dst = files + b * file_stride + at;                              // word i of the message lies at dst + 4 (i - 2)
+        uint32_t a = 0;
+        for (int i = lo; i < hi; ++i) {
+            uint32_t w;
+            if (i < 2) w = padding ? (uint32_t)padding[4 * b + 2 * i] | (uint32_t)padding[4 * b + 2 * i + 1] << 16 : 0u;
+            else if (i == 2) w = 0x5443334Cu;                                      // 'L3CT'
+            else if (i == 3) w = (uint32_t)n;                                      // n, reserved = 0
+            else if (i == 4) w = band_len;
+            else if (i < 5 + 3 * n) w = band_crc[b * 3 * n + (i - 5)];
+            else if (i == 5 + 3 * n) w = (uint32_t)T;
+            else if (i == 6 + 3 * n) w = 0x9284E246u;                              // the separator 46 E2 84 92
+            else if (i == 7 + 3 * n) w = 0x5343334Cu;                              // 'L3CS'
+            else if (i == 8 + 3 * n) w = (uint32_t)l3c_sealing::VERSION_BANDS | generation << 16;
+            else if (i == 9 + 3 * n) w = frame_crc[b];
+            else if (i == 10 + 3 * n) w = (uint32_t)model_id;
+            else w = (uint32_t)(model_id >> 32);
+            if (i >= 2)
+                for (int k = 0; k < 4; ++k) dst[4 * (i - 2) + k] = (uint8_t)(w >> (8 * k));
+            a ^= w;
+            for (int k = 0; k < 32; ++k) a = (a >> 1) ^ (POLY & (0u - (a & 1u)));
+        }
+        a = mulmod(a, weight);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) a ^= __shfl_xor(a, d, 64);
+        if (lane == 0) {
+            const uint32_t check = a ^ z_check;
+            for (int k = 0; k < 4; ++k) dst[T + 20 + k] = (uint8_t)(check >> (8 * k));
+            file_bytes[b] = at + T + L3C_SEAL_BYTES;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -417,5 +573,104 @@ int l3c_seal_append(uint8_t *files, int64_t file_stride, int64_t *file_bytes, co
     hipLaunchKernelGGL(seal_append_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, l3c::as_stream(stream), files, file_stride, file_bytes,
                        frame_crc, padding, model_id, (uint32_t)L3C_BITSTREAM_GENERATION, B);
     return l3c::check_launch("seal_append_kernel");
+}
+
+int64_t l3c_seal_bands_bytes(int n) {
+    if (n < 1 || n > l3c_sealing::MAX_BANDS) return l3c::fail(L3C_ERR_INVALID_ARG, "%s", "n must be in 1..1024");
+    return l3c_sealing::table_bytes(n) + L3C_SEAL_BYTES;
+}
+
+int l3c_seal_find_bands(const uint8_t *file_host, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out) {
+    L3C_REQUIRE(file_host && file_bytes >= 0, "null pointer or negative size");
+    return l3c_sealing::find_bands(file_host, file_bytes, body_bytes_out, seal_out, bands_out, l3c::error_buffer(), 512);
+}
+
+int l3c_seal_write_bands(const l3c_seal *seal_host, const uint8_t *padding8_host, const uint32_t *band_crc_host, int n, uint32_t band_len,
+                         uint8_t *dst_host) {
+    L3C_REQUIRE(seal_host && padding8_host && band_crc_host && dst_host, "null pointer");
+    L3C_REQUIRE(n >= 1 && n <= l3c_sealing::MAX_BANDS && band_len > 0, "n must be in 1..1024 and band_len positive");
+    uint8_t *crc = dst_host + 12;                                            // the table's words, little-endian, where write_bands puts them
+    for (int i = 0; i < 3 * n; ++i) l3c_sealing::put(crc + 4 * i, band_crc_host[i], 4);
+    l3c_sealing::write_bands(*seal_host, padding8_host, crc, n, band_len, dst_host);
+    return L3C_OK;
+}
+
+namespace {
+// the constants of a band of `bytes` bytes
+BandConsts band_consts(int64_t bytes) {
+    BandConsts k{};
+    k.bytes = bytes;
+    k.chunks = (bytes + WCHUNK - 1) / WCHUNK;
+    const int64_t last_rows_bytes = (bytes - (k.chunks - 1) * WCHUNK + WROW - 1) / WROW * WROW;
+    k.k_last = powmod(X8, (uint64_t)last_rows_bytes);
+    k.unfill = powmod(X8_INV, (uint64_t)((k.chunks - 1) * WCHUNK + last_rows_bytes - bytes));
+    k.z = span_z(bytes);
+    k.k_band = powmod(X8, (uint64_t)bytes);
+    return k;
+}
+// the arguments of l3c_u8_crc32_bands that size its work -> units (partial words), or L3C_ERR_INVALID_ARG
+int64_t bands_call(int64_t n_frames, int planes, int64_t plane_bytes, int64_t band_bytes, BandsCall *g) {
+    if (n_frames < 1 || planes < 1 || planes > 1024 || plane_bytes < 4 || plane_bytes % 4 || band_bytes < 4 || band_bytes % 4)
+        return l3c::fail(L3C_ERR_INVALID_ARG, "%s", "bad sizes: n_frames >= 1, planes in 1..1024, plane_bytes and band_bytes positive multiples of 4");
+    const int64_t n = (plane_bytes - 1) / band_bytes + 1, longest = n > 1 ? band_bytes : plane_bytes;
+    const int64_t cpb = (longest - 1) / WCHUNK + 1;                          // n cpb < plane_bytes / 2 + 2: no overflow below
+    if (plane_bytes > INT64_MAX / 4 / planes || planes * n * cpb >= ((int64_t)1 << 40) / n_frames)
+        return l3c::fail(L3C_ERR_INVALID_ARG, "%s", "bad sizes: n_frames * planes * bands * chunks per band must stay below 2^40");
+    if (g) {
+        g->full = band_consts(longest);
+        g->last = band_consts(plane_bytes - (n - 1) * band_bytes);
+        g->n_frames = n_frames, g->planes = planes, g->n = n, g->cpb = cpb;
+        g->plane_bytes = plane_bytes, g->band_bytes = band_bytes;
+        g->k_plane = powmod(X8, (uint64_t)plane_bytes);
+        g->z_frame = span_z(planes * plane_bytes);
+    }
+    return n_frames * planes * n * cpb;
+}
+}  // namespace
+
+int64_t l3c_u8_crc32_bands_workspace_bytes(int64_t n_frames, int planes, int64_t plane_bytes, int64_t band_bytes) {
+    const int64_t units = bands_call(n_frames, planes, plane_bytes, band_bytes, nullptr);
+    return units < 0 ? units : (4 * units + 15) / 16 * 16 + 16;
+}
+
+int l3c_u8_crc32_bands(const uint8_t *frames, int64_t n_frames, int planes, int64_t plane_bytes, int64_t band_bytes, int64_t frame_stride,
+                       uint32_t *band_crc_out, uint32_t *frame_crc_out, void *workspace, int64_t workspace_bytes, l3c_stream_t stream) {
+    L3C_REQUIRE(frames && band_crc_out && workspace, "null pointer");
+    BandsCall g{};
+    const int64_t units = bands_call(n_frames, planes, plane_bytes, band_bytes, &g);
+    if (units < 0) return (int)units;
+    L3C_REQUIRE(frame_stride % 4 == 0 && frame_stride >= planes * plane_bytes, "frame_stride must be a multiple of 4 and at least planes * plane_bytes");
+    L3C_REQUIRE(n_frames == 1 || frame_stride <= INT64_MAX / n_frames, "n_frames * frame_stride overflows");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 3) == 0 && (reinterpret_cast<uintptr_t>(band_crc_out) & 3) == 0 &&
+                    (reinterpret_cast<uintptr_t>(frame_crc_out) & 3) == 0,
+                "frames, band_crc_out and frame_crc_out must be 4-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "the workspace must be 16-byte aligned");
+    L3C_REQUIRE(workspace_bytes >= (4 * units + 15) / 16 * 16 + 16, "workspace_bytes too small");
+    g.frame_stride = frame_stride;
+    const hipStream_t st = l3c::as_stream(stream);
+    uint32_t *partial = static_cast<uint32_t *>(workspace);
+    const int64_t blocks = (units + THREADS / 64 - 1) / (THREADS / 64);
+    hipLaunchKernelGGL(u8_crc32_band_chunks_kernel, dim3((unsigned)(blocks < BAND_GRID ? blocks : BAND_GRID)), dim3(THREADS), 0, st, frames, g, units,
+                       partial);
+    const int rc = l3c::check_launch("u8_crc32_band_chunks_kernel");
+    if (rc != L3C_OK) return rc;
+    hipLaunchKernelGGL(u8_crc32_bands_combine_kernel, dim3((unsigned)(n_frames < MAX_GRID ? n_frames : MAX_GRID)), dim3(64), 0, st, partial, g,
+                       band_crc_out, frame_crc_out);
+    return l3c::check_launch("u8_crc32_bands_combine_kernel");
+}
+
+int l3c_seal_append_bands(uint8_t *files, int64_t file_stride, int64_t *file_bytes, const uint32_t *frame_crc, const uint32_t *band_crc, int n,
+                          uint32_t band_len, const uint16_t *padding, uint64_t model_id, int64_t B, l3c_stream_t stream) {
+    L3C_REQUIRE(files && file_bytes && frame_crc && band_crc, "null pointer");
+    L3C_REQUIRE(B > 0 && B < 65536, "bad batch size (1 .. 65535)");
+    L3C_REQUIRE(n >= 1 && n <= l3c_sealing::MAX_BANDS && band_len > 0, "n must be in 1..1024 and band_len positive");
+    L3C_REQUIRE(file_stride > 0 && file_stride <= INT64_MAX / B, "bad file_stride");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(file_bytes) & 7) == 0 && (reinterpret_cast<uintptr_t>(frame_crc) & 3) == 0 &&
+                    (reinterpret_cast<uintptr_t>(band_crc) & 3) == 0 && (reinterpret_cast<uintptr_t>(padding) & 1) == 0,
+                "file_bytes, frame_crc, band_crc and padding must be aligned to their element size");
+    hipLaunchKernelGGL(seal_append_bands_kernel, dim3((unsigned)(B < MAX_GRID ? B : MAX_GRID)), dim3(64), 0, l3c::as_stream(stream), files, file_stride,
+                       file_bytes, frame_crc, band_crc, n, band_len, padding, model_id, (uint32_t)L3C_BITSTREAM_GENERATION,
+                       span_z(4 * (int64_t)(12 + 3 * n)), B);
+    return l3c::check_launch("seal_append_bands_kernel");
 }
 }

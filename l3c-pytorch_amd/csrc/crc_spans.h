@@ -51,6 +51,9 @@ L3C_CRC_HD constexpr uint32_t powmod(uint32_t base, uint64_t e) {
 
 constexpr uint32_t X8 = powmod(X1, 8), X8_INV = powmod(X_INV, 8);
 constexpr uint32_t K_ROW = powmod(X8, ROW_BYTES), K_TILE = powmod(X8, TILE_BYTES);
+// l3c_u8_crc32_bands: a wavefront's row (64 lanes x 16 bytes) and the chunk of a band one wavefront folds
+constexpr int WROW = 64 * 16, WROWS = 16, WCHUNK = WROWS * WROW;
+constexpr uint32_t K_WROW = powmod(X8, WROW), K_WCHUNK = powmod(X8, WCHUNK);
 static_assert(mulmod(X1, X_INV) == ONE && mulmod(X8, X8_INV) == ONE, "x^-1 mod P");
 static_assert(powmod(X1, 32) == POLY, "x^32 mod P is the polynomial's low part");
 

@@ -10,6 +10,15 @@
 // check = CRC-32 (zlib) of the file's 8 padding bytes -- file bytes 0..7, in a banded file ('L3CB') bytes 6..13 -- followed by seal bytes
 // 0..19.  A file is SEALED exactly when it has at least 28 bytes, bytes [-24, -20) are 'L3CS' and bytes [-28, -24) are the scale separator
 // every unsealed file ends with; a recognised seal that is damaged is an error, never "unsealed".
+//
+// Version 2, the BAND SEAL (banded files only): body | BAND TABLE | the 24 seal bytes with version = 2.  The table, T = 20 + 12 n bytes:
+//
+//     0 'L3CT' | 4 u16 n | 6 u16 0 | 8 u32 L | 12 u32 crc[3][n] (channel-major) | 12 + 12 n u32 T | 16 + 12 n separator 46 E2 84 92
+//
+// n, L: bands per channel and band length of the finest record; crc[c][j]: the CRC-32 of bytes [c HW + j L, c HW + min((j + 1) L, HW)) of
+// the padded planar frame.  The table ends with the separator, so the recognition rule above holds for both versions, and T lies at
+// file[-32:-28]: the table is found from the end.  check = CRC-32 of the 8 padding bytes, the whole table, seal bytes 0..19.  The frame CRC
+// stays in the seal and must be the combination of the band CRCs (crc32_combine's arithmetic, crc_spans.h).
 #ifndef L3C_SEAL_H_
 #define L3C_SEAL_H_
 
@@ -18,10 +27,12 @@
 #include <string.h>
 
 #include "../../include/l3c_hip.h"
+#include "crc_spans.h"
 
 namespace l3c_sealing {
 
-constexpr int VERSION = 1;
+constexpr int VERSION = 1, VERSION_BANDS = 2, MAX_BANDS = 1024;
+constexpr uint8_t TABLE_SIGNATURE[4] = {'L', '3', 'C', 'T'};
 constexpr uint8_t SIGNATURE[4] = {'L', '3', 'C', 'S'};
 constexpr uint8_t SEPARATOR[4] = {0x46, 0xE2, 0x84, 0x92};
 constexpr uint8_t BANDED_SIGNATURE[4] = {'L', '3', 'C', 'B'};
@@ -62,18 +73,110 @@ inline void write(const l3c_seal &s, const uint8_t *padding8, uint8_t *dst) {
     put(dst + 20, crc32(crc32(0, padding8, 8), dst, 20), 4);
 }
 
-// 1: sealed, 0: unsealed, L3C_ERR_INVALID_ARG (message in err): a recognised seal that is damaged
-inline int find(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, char *err, size_t cap) {
+// band table + seal of a band-sealed file: table_bytes(n) + L3C_SEAL_BYTES bytes behind the body
+constexpr int64_t table_bytes(int64_t n) { return 20 + 12 * n; }
+
+// zlib's crc32_combine over the bands of a frame of 3 planes of hw bytes: crc(A | B) = crc(A) x^(8 |B|) + crc(B), from crc() = 0.
+// crc: 12 n bytes, [3][n] little-endian words, unaligned
+inline uint32_t combine_bands(const uint8_t *crc, int64_t n, uint32_t band_len, int64_t hw) {
+    const uint32_t k_full = l3c_crc::powmod(l3c_crc::X8, band_len), k_last = l3c_crc::powmod(l3c_crc::X8, (uint64_t)(hw - (n - 1) * (int64_t)band_len));
+    uint32_t a = 0;
+    for (int c = 0; c < 3; ++c)
+        for (int64_t j = 0; j < n; ++j) a = l3c_crc::mulmod(a, j + 1 < n ? k_full : k_last) ^ (uint32_t)get(crc + 4 * (c * n + j), 4);
+    return a;
+}
+
+// The finest (last) scale record of the banded file in [0, body): its H W, band length and bands per channel, walked by the length fields.
+// false: not a banded file whose records end exactly at `body`.
+inline bool finest_record(const uint8_t *f, int64_t body, int64_t *hw_out, uint32_t *band_len_out, int64_t *n_out) {
+    if (body < 14 || memcmp(f, BANDED_SIGNATURE, 4) != 0) return false;
+    int64_t p = 14;
+    bool found = false;
+    while (p < body) {
+        if (body - p < 9) return false;
+        const int64_t C = f[p], hw = (int64_t)get(f + p + 1, 2) * (int64_t)get(f + p + 3, 2), L = (int64_t)get(f + p + 5, 4);
+        p += 9;
+        if (C == 0 || hw == 0 || L == 0 || L % 64) return false;
+        const int64_t n = (hw + L - 1) / L;
+        if (n > MAX_BANDS) return false;
+        for (int64_t k = 0; k < C * n; ++k) {
+            if (body - p < 4) return false;
+            const int64_t len = (int64_t)get(f + p, 4);
+            p += 4;
+            if (len > body - p) return false;
+            p += len;
+        }
+        if (body - p < 4 || memcmp(f + p, SEPARATOR, 4) != 0) return false;
+        p += 4;
+        *hw_out = hw, *band_len_out = (uint32_t)L, *n_out = n;
+        found = true;
+    }
+    return found;
+}
+
+// the band table for n bands per channel of length band_len and the seal of version 2 behind it: table_bytes(n) + 24 bytes at dst.
+// band_crc: 12 n bytes, [3][n] little-endian words (unaligned is fine)
+inline void write_bands(const l3c_seal &s, const uint8_t *padding8, const uint8_t *band_crc, int n, uint32_t band_len, uint8_t *dst) {
+    const int64_t T = table_bytes(n);
+    memcpy(dst, TABLE_SIGNATURE, 4);
+    put(dst + 4, (uint64_t)n, 2);
+    put(dst + 6, 0, 2);
+    put(dst + 8, band_len, 4);
+    memmove(dst + 12, band_crc, 12 * (size_t)n);
+    put(dst + 12 + 12 * n, (uint64_t)T, 4);
+    memcpy(dst + 16 + 12 * n, SEPARATOR, 4);
+    uint8_t *seal = dst + T;
+    memcpy(seal, SIGNATURE, 4);
+    seal[4] = VERSION_BANDS;
+    seal[5] = 0;
+    put(seal + 6, s.generation, 2);
+    put(seal + 8, s.frame_crc, 4);
+    put(seal + 12, s.model_id, 8);
+    put(seal + 20, crc32(crc32(0, padding8, 8), dst, T + 20), 4);
+}
+
+// 1: sealed, 0: unsealed, L3C_ERR_INVALID_ARG (message in err): a recognised seal that is damaged.  *body_bytes_out: the bytes in front of
+// the seal, in front of the band table where the seal has one.  bands_out (may be null): n = 0 for a version-1 seal.
+inline int find_bands(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out, char *err,
+                      size_t cap) {
     if (body_bytes_out) *body_bytes_out = file_bytes;
+    if (bands_out) bands_out->n = 0, bands_out->band_len = 0, bands_out->crc = nullptr;
     if (file_bytes < L3C_SEAL_BYTES + 4) return 0;
     const uint8_t *s = file + file_bytes - L3C_SEAL_BYTES;
     if (memcmp(s, SIGNATURE, 4) != 0 || memcmp(s - 4, SEPARATOR, 4) != 0) return 0;
-    const int64_t body = file_bytes - L3C_SEAL_BYTES;
-    const int64_t padding_at = memcmp(file, BANDED_SIGNATURE, 4) == 0 ? 6 : 0;
-    if (s[4] != VERSION) return fail(err, cap, "of an unknown version");
+    int64_t body = file_bytes - L3C_SEAL_BYTES;
+    const bool banded = memcmp(file, BANDED_SIGNATURE, 4) == 0;
+    const int64_t padding_at = banded ? 6 : 0;
+    if (s[4] != VERSION && s[4] != VERSION_BANDS) return fail(err, cap, "of an unknown version");
+    int64_t T = 0, n = 0;
+    if (s[4] == VERSION_BANDS) {
+        if (!banded) return fail(err, cap, "of an unknown version for a legacy file (version 2, the band seal, needs a banded file)");
+        if (body < 20 + 12 + 4) return fail(err, cap, "of an unknown version: 2 needs a band table, and the file is too short for one");
+        T = (int64_t)get(s - 8, 4);
+        n = (T - 20) / 12;
+        if (T < 20 || (T - 20) % 12 != 0 || n < 1 || n > MAX_BANDS)
+            return fail(err, cap, "of an unknown version: 2 needs a band table, and its length field is not 20 + 12 n with 1 <= n <= 1024");
+        if (T > body - 14 - 4 || memcmp(file + body - T - 4, SEPARATOR, 4) != 0)
+            return fail(err, cap, "band table does not start behind the file's last scale separator");
+        body -= T;
+        const uint8_t *t = file + body;
+        if (memcmp(t, TABLE_SIGNATURE, 4) != 0) return fail(err, cap, "band table without its 'L3CT' signature");
+        if (get(t + 6, 2) != 0) return fail(err, cap, "band table with a non-zero reserved field");
+    }
     if (s[5] != 0) return fail(err, cap, "with non-zero flags");
     if (padding_at + 8 > body) return fail(err, cap, "on a file too short for its padding fields");
-    if (get(s + 20, 4) != crc32(crc32(0, file + padding_at, 8), s, 20)) return fail(err, cap, "check word does not match (damaged seal or padding fields)");
+    if (get(s + 20, 4) != crc32(crc32(crc32(0, file + padding_at, 8), file + body, T), s, 20))
+        return fail(err, cap, "check word does not match (damaged seal or padding fields)");
+    if (T) {
+        const uint8_t *t = file + body;
+        int64_t hw = 0, rec_n = 0;
+        uint32_t rec_len = 0;
+        if ((int64_t)get(t + 4, 2) != n) return fail(err, cap, "band table states another band count than its length");
+        if (!finest_record(file, body, &hw, &rec_len, &rec_n) || rec_n != n || rec_len != (uint32_t)get(t + 8, 4))
+            return fail(err, cap, "band table does not match the bands of the file's finest scale record");
+        if ((uint32_t)get(s + 8, 4) != combine_bands(t + 12, n, rec_len, hw)) return fail(err, cap, "frame CRC is not the combination of its band CRCs");
+        if (bands_out) bands_out->n = (int32_t)n, bands_out->band_len = rec_len, bands_out->crc = t + 12;
+    }
     if (body_bytes_out) *body_bytes_out = body;
     if (seal_out) {
         seal_out->generation = (uint16_t)get(s + 6, 2);
@@ -81,6 +184,10 @@ inline int find(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out
         seal_out->model_id = get(s + 12, 8);
     }
     return 1;
+}
+
+inline int find(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, char *err, size_t cap) {
+    return find_bands(file, file_bytes, body_bytes_out, seal_out, nullptr, err, cap);
 }
 
 }  // namespace l3c_sealing

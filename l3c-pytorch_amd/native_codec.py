@@ -210,11 +210,17 @@ class NativeCodec(object):
     def __init__(self, blueprint, bands=0, seal=False):
         """bands: 0 = encode writes the legacy format; K in 1..1024 = banded files, as Bitcoding(bp, bands=K).  decode_batch reads either.
         seal: True = every file the encoders return ends with a seal, as Bitcoding(bp, seal=True); the decoders verify sealed files whatever
-        this says."""
+        this says.  seal='bands' (with bands=K; ValueError with bands=0): BAND-SEALED files, as Bitcoding(bp, bands=K, seal='bands'), byte for
+        byte: l3c_encode_batch_banded, ONE l3c_u8_crc32_bands on the input frames, l3c_seal_append_bands -- no host round trip."""
+        if seal not in (False, True, 'bands'):
+            raise ValueError("seal must be False, True or 'bands', got {!r}".format(seal))
+        if seal == 'bands' and not bands:
+            raise ValueError("seal='bands' needs banded files: a band seal holds a CRC per band of the finest record (bands=K, K >= 1)")
         if bands and not 1 <= int(bands) <= container.MAX_BANDS:
             raise ValueError('bands must be 0 (legacy format) or in 1..{}, got {}'.format(container.MAX_BANDS, bands))
         self.bands = int(bands)
         self.seal = bool(seal)
+        self.seal_bands = seal == 'bands'
         self._network, self._model_id = blueprint.net, None
         _lib.require_gpu()
         self.net = NativeNet(blueprint.net)
@@ -234,7 +240,12 @@ class NativeCodec(object):
     # ---- sizes ---------------------------------------------------------------------------------------------------------------
 
     def file_stride(self, H, W):
-        """The slot of one file: the library's stride, and with seal=True the 32 bytes more that l3c_seal_append asks for."""
+        """The slot of one file: the library's stride, and with seal=True the 32 bytes more that l3c_seal_append asks for; with
+        seal='bands' l3c_seal_bands_bytes(n) rounded up to 32."""
+        if self.seal_bands:
+            n = container.n_bands(H * W, container.band_len(H * W, self.bands))
+            return (_size(_lib.load().l3c_encode_banded_file_stride(self._cfg_ref, H, W, self.bands)) +
+                    (_size(_lib.load().l3c_seal_bands_bytes(n)) + 31) // 32 * 32)
         if self.bands:
             return _size(_lib.load().l3c_encode_banded_file_stride(self._cfg_ref, H, W, self.bands)) + 32 * self.seal
         return _size(_lib.load().l3c_encode_file_stride(self._cfg_ref, H, W)) + 32 * self.seal
@@ -286,7 +297,11 @@ class NativeCodec(object):
             _lib.call('l3c_encode_batch_banded', ctypes.byref(d), self.bands, stream())
         else:
             _lib.call('l3c_encode_batch', ctypes.byref(d), stream())
-        if self.seal:
+        if self.seal_bands:
+            L = container.band_len(H * W, self.bands)
+            band_crc, frame_crc = ops.u8_crc32_bands(imgs.view(-1), B, H * W, L)
+            ops.seal_append_bands(files, file_bytes, frame_crc, band_crc, L, pads, self.model_id())
+        elif self.seal:
             ops.seal_append(files, file_bytes, ops.u8_crc32(imgs.view(-1), B, 3 * H * W), pads, self.model_id())
         return files, file_bytes
 
@@ -317,7 +332,8 @@ class NativeCodec(object):
         sym: optional int16 (B,3,H,W) device tensor that receives the same values.
         Sealed files (a batch may mix sealed and unsealed ones): as Bitcoding.decode_batch -- container.SealError('generation' / 'model')
         before anything is enqueued, l3c_u8_crc32 on `pixels` and one D2H of B words after, SealError('pixels'); verify=False strips the
-        seals and checks nothing."""
+        seals and checks nothing.  Band-sealed files among them: ONE l3c_u8_crc32_bands on `pixels` instead, every band-sealed file compared
+        band by band (SealError('pixels') with .bands and .rows), the version-1 sealed ones against the same call's frame words."""
         lib = _lib.load()
         B = len(files)
         files, seals = self._split(files, verify)
@@ -362,9 +378,10 @@ class NativeCodec(object):
                 t.record_stream(side)
         d = DecodeBatchDesc(ctypes.pointer(self.model), ptr(dev), plan_host, ptr(dev) + plan_at, n_plan, ptr(pixels), ptr(sym), ptr(ws), ws.numel())
         _lib.call(decode_fn, ctypes.byref(d), stream(), side.cuda_stream if side is not None else None)
+        pads = [tuple(int(v) for v in p) for p in pads]
         if seals is not None:
-            container.check_frame_crcs(seals, ops.u8_crc32(pixels.view(-1), B, 3 * H.value * W.value).cpu().numpy())
-        return pixels, [tuple(int(v) for v in p) for p in pads]
+            Bitcoding._check_pixels(seals, pixels, pads)
+        return pixels, pads
 
     def decode_region(self, files, box, verify=True):
         """The pixels of a BOX of B files of equally padded images, banded or legacy, without decoding the rest of their finest record
@@ -372,7 +389,9 @@ class NativeCodec(object):
         l3c_decode_region_plan, l3c_decode_region).  box: (y0, y1) or (y0, y1, x0, x1) in the coordinates of the UNPADDED image.  Files,
         plan blob and region blob cross PCIe in one copy from page-locked memory; the library's refusals are ValueError /
         NotImplementedError with its message.  Sealed files: generation and model are checked (verify=True) before anything is enqueued;
-        a seal's CRC covers the whole frame and is NOT checked -- the info says so."""
+        a seal's CRC covers the whole frame and is NOT checked -- the info says so.  A BAND-SEALED file is treated here as a version-1
+        sealed one: generation and model checked, pixel_crc_checked False (l3c_decode_region plans the cut last band and keeps the window's
+        pixels in its workspace; Bitcoding.decode_region verifies the decoded bands)."""
         lib = _lib.load()
         if not files:
             raise ValueError('decode_region: no files')
@@ -438,9 +457,26 @@ class NativeCodec(object):
                                          bytes_total=int(info.bytes_total), sealed=sealed, verified=('generation', 'model') if check else (),
                                          pixel_crc_checked=False)
 
+    @staticmethod
+    def _split_seal(f):
+        """container.split_seal(f, view=True) through the library (l3c_seal_find_bands: the same checks and messages; a band seal's table
+        is checked against the finest record and the frame CRC in microseconds where the Python reader takes a tenth of a millisecond)."""
+        if not container.is_sealed(f):
+            return f, None
+        lib = _lib.load()
+        buf = np.frombuffer(f, dtype=np.uint8)
+        body, seal, bands = ctypes.c_int64(), _lib.Seal(), _lib.SealBands()
+        rc = lib.l3c_seal_find_bands(buf.ctypes.data, buf.size, ctypes.byref(body), ctypes.byref(seal), ctypes.byref(bands))
+        if rc != 1:
+            raise ValueError(lib.l3c_last_error().decode())
+        crcs = None
+        if bands.n:
+            crcs = np.frombuffer(f, dtype='<u4', count=3 * bands.n, offset=bands.crc - buf.ctypes.data).reshape(3, bands.n)
+        return memoryview(f)[:body.value], container.Seal(seal.generation, seal.frame_crc, seal.model_id, bands.band_len if bands.n else None, crcs)
+
     def _split(self, files, verify):
         """-> (the files without their seals, the seals to verify after the decode or None); generation and model id are checked here."""
-        split = [container.split_seal(f, view=True) for f in files]
+        split = [self._split_seal(f) for f in files]
         seals = [s for _, s in split]
         if not verify or all(s is None for s in seals):
             return [b for b, _ in split], None

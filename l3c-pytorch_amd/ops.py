@@ -856,3 +856,35 @@ def seal_append(files, file_bytes, frame_crc, padding=None, model_id=0):
     B, stride = files.shape
     call('l3c_seal_append', ptr(files, torch.uint8), stride, ptr(file_bytes, torch.int64), ptr(frame_crc, torch.int32), ptr(padding, torch.int16),
          int(model_id), B, stream())
+
+
+def u8_crc32_bands(frames, n_frames, plane_bytes, band_bytes, planes=3, frame_stride=None, frame_crc=True, workspace=None):
+    """l3c_u8_crc32_bands: zlib.crc32 of every band of every plane of n_frames frames -- band j of a plane is its bytes
+    [j band_bytes, min((j + 1) band_bytes, plane_bytes)) -- and of every frame, the bytes read once, in two launches.  frames: contiguous
+    uint8 device tensor, frame f at f * frame_stride (default: back to back).  -> (int32 (n_frames, planes, n), int32 (n_frames,) or None
+    with frame_crc=False) device tensors holding the CRC words (view them as uint32 on the host); no host synchronisation."""
+    frame_stride = planes * plane_bytes if frame_stride is None else frame_stride
+    if frames.dtype != torch.uint8 or not frames.is_contiguous() or n_frames < 1 or planes < 1 or plane_bytes < 1 or band_bytes < 1 \
+            or frames.numel() < (n_frames - 1) * frame_stride + planes * plane_bytes:
+        raise ValueError('u8_crc32_bands: {} frames of {} planes of {} bytes, {} apart, do not fit a {} tensor of {} elements'.format(
+            n_frames, planes, plane_bytes, frame_stride, frames.dtype, frames.numel()))
+    n_ws = _lib.load().l3c_u8_crc32_bands_workspace_bytes(n_frames, planes, plane_bytes, band_bytes)
+    _lib.check(min(n_ws, 0))
+    ws = torch.empty(n_ws, dtype=torch.uint8, device=frames.device) if workspace is None else workspace
+    n = -(-plane_bytes // band_bytes)
+    bands = torch.empty((n_frames, planes, n), dtype=torch.int32, device=frames.device)
+    whole = torch.empty(n_frames, dtype=torch.int32, device=frames.device) if frame_crc else None
+    call('l3c_u8_crc32_bands', ptr(frames, torch.uint8), n_frames, planes, plane_bytes, band_bytes, frame_stride, ptr(bands, torch.int32),
+         ptr(whole, torch.int32), ptr(ws, torch.uint8), ws.numel(), stream())
+    return bands, whole
+
+
+def seal_append_bands(files, file_bytes, frame_crc, band_crc, band_len, padding=None, model_id=0):
+    """l3c_seal_append_bands: the band table and this build's version-2 seal behind every file of a banded encode, in place.  files uint8
+    (B, file_stride), file_bytes int64 (B,), frame_crc int32 (B,) and band_crc int32 (B, 3, n) (u8_crc32_bands of the padded frames),
+    padding int16 (B, 4) device tensor or None -- all on the device."""
+    B, stride = files.shape
+    if band_crc.dim() != 3 or band_crc.shape[0] != B or band_crc.shape[1] != 3 or not band_crc.is_contiguous():
+        raise ValueError('seal_append_bands: band_crc must be a contiguous (B, 3, n) tensor, got {}'.format(tuple(band_crc.shape)))
+    call('l3c_seal_append_bands', ptr(files, torch.uint8), stride, ptr(file_bytes, torch.int64), ptr(frame_crc, torch.int32),
+         ptr(band_crc, torch.int32), band_crc.shape[2], int(band_len), ptr(padding, torch.int16), int(model_id), B, stream())

@@ -192,10 +192,12 @@ class MultiscaleTester(object):
         # --write_to_files works for --recursive too (the reference raises NotImplementedError, :187-188): the `.l3c` layout carries
         # one more scale record per recursion.  Finished files are written by worker threads.
         self.file_writer = AsyncFileWriter() if getattr(flags, 'write_to_files', None) else None
+        if getattr(flags, 'seal_bands', False) and not int(getattr(flags, 'bands', 0) or 0):
+            raise ValueError('--seal-bands needs --bands: a band seal holds a CRC per band of a banded file')
         self.bc = Bitcoding(self.blueprint, times=self.times if getattr(flags, 'write_to_files', None) else None,
                             compare_with_theory=bool(getattr(flags, 'compare_theory', False)), auto_recurse=self.recursive,
                             file_writer=self.file_writer, bands=int(getattr(flags, 'bands', 0) or 0),
-                            seal=bool(getattr(flags, 'seal', False)))
+                            seal='bands' if getattr(flags, 'seal_bands', False) else bool(getattr(flags, 'seal', False)))
         self.max_batch = int(getattr(flags, 'batch', None) or 8)
         self.io_threads = int(getattr(flags, 'io_threads', None) or 4)
         exp_name = os.path.basename(experiment_dir)
@@ -511,7 +513,7 @@ class MultiscaleTester(object):
         from .. import _lib
         # the container has no version field (reference bitcoding.py:326-375): say which decoder generation reads this file
         print('---\nSaved: {}  (bitstream generation {}, include/l3c_hip.h{})'.format(pout, _lib.load().l3c_bitstream_generation(),
-                                                                                 '; sealed' if self.bc.seal else ''))
+                                                                                 '; band-sealed' if self.bc.seal_bands else '; sealed' if self.bc.seal else ''))
         return bpsp
 
     def decode(self, pin, png_out_p, region=None):
@@ -539,10 +541,15 @@ class MultiscaleTester(object):
                 _, seal = container.split_seal(fin.read())
             decoded = self.bc.decode(pin, verify=verify)
         except container.SealError as e:
+            if e.rows:                                  # a band-sealed file: the damage is located
+                where = next(iter(e.rows.values()))
+                raise DecodeError('seal: {}\ndamaged rows: {}; dec --region Y0:Y1 outside them returns verified pixels'.format(
+                    e, 'the padding alone' if where is None else '[{}, {})'.format(*where)))
             raise DecodeError('seal: {}'.format(e))
         self._write_img(decoded, png_out_p)
         if seal is not None:
-            print('seal: ok (generation {})'.format(seal.generation) if verify else 'seal: not verified (--no-verify)')
+            bands = '' if seal.band_crcs is None else ', {} band CRCs'.format(seal.band_crcs.size)
+            print('seal: ok (generation {}{})'.format(seal.generation, bands) if verify else 'seal: not verified (--no-verify)')
         print('---\nDecoded: {}'.format(png_out_p))
 
     def preview(self, pin, png_out_p, records=None, max_bytes=None):

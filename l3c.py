@@ -68,6 +68,9 @@ def main(argv=None):
     enc.add_argument('--seal', action='store_true',
                      help='write a SEALED file: 24 bytes behind the last record that state the bitstream generation, the checkpoint and the '
                           'CRC-32 of the image, so that dec refuses to return wrong pixels')
+    enc.add_argument('--seal-bands', dest='seal_bands', action='store_true',
+                     help='with --bands: write a BAND-SEALED file, a seal with one CRC-32 per band of the finest record in front of it: dec then '
+                          'names the damaged rows of a file that fails, and dec --region verifies the pixels it returns')
     dec.add_argument('img_p')
     dec.add_argument('out_p_png')
     dec.add_argument('--no-verify', dest='no_verify', action='store_true', help='do not check the seal of a sealed file')
