@@ -31,24 +31,36 @@ def regimes(rgb):
     return [r for r in REGIMES if rgb or r != 'lambda']
 
 
-def targets32(rgb):
-    """The Lp fp32 bin edges the coder evaluates the CDF at (the oracle's), as numpy."""
-    x_min, x_max, L = alphabet(rgb)
+def targets_of(alpha):
+    """The Lp fp32 bin edges the coder evaluates the CDF at (the oracle's), as numpy; alpha = (x_min, x_max, L)."""
+    x_min, x_max, L = alpha
     return ocdf.coding_targets(x_min, x_max, L).numpy()
 
 
-def values_of(sym, rgb):
-    """Symbols -> the fp32 values the head is conditioned on / scores (Spec.to_bn: two rounded fp32 operations)."""
-    x_min, x_max, L = alphabet(rgb)
+def values_at(sym, alpha):
+    """Symbols -> the fp32 values the head is conditioned on / scores (Spec.to_bn: two rounded fp32 operations); alpha = (x_min, x_max, L)."""
+    x_min, x_max, L = alpha
     bw = np.float32((x_max - x_min) / (L - 1))
     return (sym.astype(np.float32) * bw + np.float32(x_min)).astype(np.float32)
+
+
+def targets32(rgb):
+    """`targets_of` on the alphabet of the RGB scale / the bottleneck scales."""
+    return targets_of(alphabet(rgb))
+
+
+def values_of(sym, rgb):
+    """`values_at` on the alphabet of the RGB scale / the bottleneck scales."""
+    return values_at(sym, alphabet(rgb))
 
 
 # ---- value regimes -----------------------------------------------------------------------------------------------------------
 
 
-def make_P(regime, rgb, B, H, W, C, K, rng):
-    """-> P (B, Kp, H, W) fp32.
+def make_P(regime, rgb, B, H, W, C, K, rng, alpha=None):
+    """-> P (B, Kp, H, W) fp32.  alpha: (x_min, x_max, L) of a head that is not one of the two shipped ones (`benign`, `sharp`, `lambda` only):
+    on a bottleneck-style head `benign` then draws mu from the range widened by a tenth of its span on either side and log_sigma from
+    U(-9, -1 + log(bin width / (2 / 24))) -- sigma up to 4.4 bins, as on the shipped alphabet, where both are the figures below.
       benign    logits N(0,1); mu U(-20, 280) | U(-1.2, 1.2); log_sigma U(-9, 2) | U(-9, -1); lambda N(0,1)
       sharp     log_sigma U(-12, -6) (mostly at the -7 clamp); means on multiples of half a bin width: the bin edges themselves (the
                 coder's fp32 targets: sigmoid(0) = .5 exactly) and the bin centres
@@ -62,20 +74,25 @@ def make_P(regime, rgb, B, H, W, C, K, rng):
       lambda    lambdas drawn from {-90, -30, 0, 17, 30} (sigmoid saturated to 0 and to 1)                               RGB only"""
     if regime not in regimes(rgb):
         raise ValueError('regime {!r} is not defined for rgb={}'.format(regime, rgb))
-    x_min, x_max, L = alphabet(rgb)
+    if alpha is not None and tuple(alpha) != alphabet(rgb) and (rgb or regime not in ('benign', 'sharp')):
+        raise ValueError('regime {!r} is not defined for the alphabet {} (rgb={})'.format(regime, alpha, rgb))
+    x_min, x_max, L = alphabet(rgb) if alpha is None else alpha
     span = x_max - x_min
     shape = (B, C, K, H, W)
     logit = rng.randn(*shape)
     if rgb:
         mu = rng.uniform(-20, 280, size=shape)
         ls = rng.uniform(-9, 2, size=shape)
-    else:
+    elif (x_min, x_max, L) == alphabet(False):
         mu = rng.uniform(-1.2, 1.2, size=shape)
         ls = rng.uniform(-9, -1, size=shape)
+    else:
+        mu = rng.uniform(x_min - 0.1 * span, x_max + 0.1 * span, size=shape)
+        ls = rng.uniform(-9, -1 + np.log(span / (L - 1) / (2 / 24)), size=shape)
     lam = rng.randn(*shape)
     if regime == 'sharp':
         ls = rng.uniform(-12, -6, size=shape)
-        t = targets32(rgb).astype(np.float64)
+        t = targets_of((x_min, x_max, L)).astype(np.float64)
         grid = np.sort(np.concatenate([t, x_min + np.arange(L) * (span / (L - 1))]))        # edges and centres
         mu = grid[rng.randint(0, grid.size, size=shape)]
     elif regime == 'wide':
@@ -101,9 +118,9 @@ def make_P(regime, rgb, B, H, W, C, K, rng):
     return np.stack(parts, axis=1).reshape(B, len(parts) * C * K, H, W).astype(np.float32)
 
 
-def make_sym(rgb, B, H, W, C, rng):
+def make_sym(rgb, B, H, W, C, rng, alpha=None):
     """int16 symbols (B, C, H, W) with 0 and L-1 at some pixels of every channel (the first and the last pixel of image 0)."""
-    L = alphabet(rgb)[2]
+    L = (alphabet(rgb) if alpha is None else alpha)[2]
     sym = rng.randint(0, L, size=(B, C, H, W)).astype(np.int16)
     flat = sym.reshape(B, C, H * W)
     flat[0, :, 0] = L - 1
@@ -111,11 +128,12 @@ def make_sym(rgb, B, H, W, C, rng):
     return sym
 
 
-def near_sym(P, rgb, C, K, rng, far_every=16):
+def near_sym(P, rgb, C, K, rng, far_every=16, alpha=None):
     """Symbols where the mixture has its mass: channel by channel the value nearest to the (coupled, fp64) mean of a randomly picked
     component (picked with the mixture's own weights), clipped to the alphabet (`offrange`: the edge symbols).  Every `far_every`-th pixel keeps a uniformly random symbol (0:
     none); in every channel the first pixel of image 0 gets L-1 and the last pixel of the last image gets 0."""
-    x_min, x_max, L = alphabet(rgb)
+    alpha = alphabet(rgb) if alpha is None else alpha
+    x_min, x_max, L = alpha
     B, _, H, W = P.shape
     bw = (x_max - x_min) / (L - 1)
     sym = rng.randint(0, L, size=(B, C, H, W)).astype(np.int16)
@@ -124,7 +142,7 @@ def near_sym(P, rgb, C, K, rng, far_every=16):
         far[far_every - 1::far_every] = True
     far = far.reshape(1, H, W)
     for c in range(C):
-        pi, mu, _ = params64(P, values_of(sym, rgb), rgb, C, K, c)
+        pi, mu, _ = params64(P, values_at(sym, alpha), rgb, C, K, c)
         k = (rng.uniform(size=(B, 1, H, W)) > np.cumsum(pi, axis=1)).sum(axis=1, keepdims=True).clip(0, K - 1)   # k ~ pi
         near = np.clip(np.rint((np.take_along_axis(mu, k, 1)[:, 0] - x_min) / bw), 0, L - 1).astype(np.int16)
         sym[:, c] = np.where(far, sym[:, c], near)
@@ -144,6 +162,53 @@ def head_case(regime, rgb, H, W, B=2, K=10, far_every=16):
     rng = np.random.RandomState(10000 * REGIMES.index(regime) + 100 * H + W + (5000 if rgb else 0))
     P = make_P(regime, rgb, B, H, W, C, K, rng)
     return P, near_sym(P, rgb, C, K, rng, far_every), C, K
+
+
+# The heads of tests/test_gpu_head_shapes.py: (C, K, rgb, alphabet), each there for what its Kp = (4 | 3) C K and its C do in
+# csrc/dmll_kernels.hip (the fill form of the P tile: Kp % 4 and q = Kp / 4 | Kp / 2; the threads per block: 320 iff C == 5; the turns of the
+# compute loop: 64 C items; the kMaxK register arrays: K = 1 and K = 16; the LDS limit of the 64-pixel tile: 64 (Kp + 1) floats in 64 KiB, Kp <= 255).  The last row
+# is the one tile that fills the limit to the byte.
+HEAD_SHAPES = (
+    (3, 1, True, (0.0, 255.0, 256)),      # Kp 12: K = 1; 16-byte fill at q = 3; window rows
+    (3, 5, True, (0.0, 255.0, 256)),      # Kp 60: 16-byte fill at q = 15
+    (3, 16, True, (0.0, 255.0, 256)),     # Kp 192: K = kMaxK with coupling; the largest RGB tile; the mean kernel's extra LDS
+    (1, 1, False, (-1.0, 1.0, 2)),        # Kp 3: the smallest of everything; odd Kp
+    (1, 2, False, (-1.0, 1.0, 25)),       # Kp 6: half fill at q = 3, nearly every piece straddles rows
+    (3, 2, False, (-1.0, 1.0, 7)),        # Kp 18: half fill at q = 9
+    (2, 7, False, (-2.0, 3.0, 64)),       # Kp 42: half fill at q = 21; an asymmetric range
+    (5, 3, False, (-1.0, 1.0, 25)),       # Kp 45: 320 threads with the 4-byte fill
+    (5, 4, False, (-1.0, 1.0, 25)),       # Kp 60: 320 threads on the run-time interval kernel, 16-byte fill
+    (5, 16, False, (-1.0, 1.0, 259)),     # Kp 240: 320 threads; K = kMaxK; the largest tile of an even Kp; Lp = 260
+    (7, 6, False, (-1.0, 1.0, 25)),       # Kp 126: half fill at q = 63; 448 items: 1.75 turns on 256 threads
+    (8, 10, False, (-1.0, 1.0, 25)),      # Kp 240: 512 items: two full turns
+    (17, 5, False, (-1.0, 1.0, 25)),      # Kp 255: the largest tile the limit admits, 65 536 bytes exactly; 1088 items: 4.25 turns
+)
+SHAPE_REGIMES = ('benign', 'sharp', 'lambda')      # `lambda`: the RGB shapes only
+
+
+def shape_regimes(rgb):
+    return [r for r in SHAPE_REGIMES if rgb or r != 'lambda']
+
+
+def mean_regimes(rgb, K):
+    """The regimes l3c_dmll_mean is judged in at a head shape: all of shape_regimes, except `sharp` at K = 1 -- with a single component the
+    mean IS that component's mu, which `sharp` puts on bin edges: an exact rounding tie at a fifth to a half of the pixels, each of them
+    excused by the rule (the cap on the excused share is about inputs; with K > 1 the weighted sum leaves the grid)."""
+    return [r for r in shape_regimes(rgb) if not (K == 1 and r == 'sharp')]
+
+
+def shape_id(C, K, rgb, alpha):
+    return 'C{}K{}{}L{}'.format(C, K, 'rgb' if rgb else 'z', alpha[2])
+
+
+def shape_case(C, K, rgb, alpha, regime, H, W, B=3, far_every=16):
+    """`head_case` for any head: the inputs of one (shape, alphabet, regime, size) case, the same on the CPU and on the GPU side:
+    P (B, Kp, H, W) fp32, sym int16 (B, C, H, W)."""
+    if regime not in shape_regimes(rgb):
+        raise ValueError('regime {!r} is not one of the shape cases (rgb={})'.format(regime, rgb))
+    rng = np.random.RandomState(1000003 * REGIMES.index(regime) + 100019 * C + 5003 * K + 307 * alpha[2] + 100 * H + W + (5000 if rgb else 0))
+    P = make_P(regime, rgb, B, H, W, C, K, rng, alpha=alpha)
+    return P, near_sym(P, rgb, C, K, rng, far_every, alpha=alpha)
 
 
 def tie_case(Lp, K):
@@ -305,10 +370,11 @@ def _softplus64(a):
     return np.logaddexp(0.0, a)
 
 
-def nll64(P, x, rgb, C, K, return_clamped=False):
+def nll64(P, x, rgb, C, K, return_clamped=False, alpha=None):
     """forward() of the reference's loss in fp64 from fp32 P (B, Kp, H, W) and fp32 values x (B, C, H, W) -> (B, C, H, W) nats
-    [, mask: every component of the element sits at the 1e-12 clamp of the bin's mass]."""
-    x_min, x_max, L = alphabet(rgb)
+    [, mask: every component of the element sits at the 1e-12 clamp of the bin's mass].  alpha: (x_min, x_max, L) of a head that is not one of
+    the two shipped ones."""
+    x_min, x_max, L = alphabet(rgb) if alpha is None else alpha
     half = (x_max - x_min) / (L - 1) / 2
     l, K_ = _split(P, rgb, C)
     assert K_ == K
@@ -347,6 +413,29 @@ def nll_tolerance(ref32, ref64):
     exceeds 1e-3: must stay below 2 % of the case)."""
     slack = 4 * np.abs(ref32.astype(np.float64) - ref64)
     return 2e-5 + 2e-5 * np.abs(ref32) + slack, float((slack > NLL_SLACK_CAP).mean())
+
+
+# ---- the mixture's mean as symbols -------------------------------------------------------------------------------------------------
+
+MEAN_EXCUSED_CAP = 0.02
+
+
+def mean_rule64(P, got, rgb, C, K, alpha, c):
+    """The rule of tests/test_gpu_preview.py::test_mean_kernel_against_fp64 for channel c of the symbols `got` (B, C, H, W) an implementation
+    of l3c_dmll_mean returned: fp64 from P, conditioned on `got`'s own earlier channels.  -> (want, excused), (B, H, W) each: a pixel is
+    excused iff fp64's scaled mean t is within bound / bw + 1e-6 of a rounding tie, with
+        bound = sum_k (PI_BOUND + 16 u pi_k) (|mu_k| + |a_k| + |b_k|)         a, b: the two coupling terms, u = 2^-24;
+    everywhere else the symbol must EQUAL want = clip(rint(t), 0, L-1).  The excused share is capped (MEAN_EXCUSED_CAP), not tolerated."""
+    x_min, x_max, L = alpha
+    bw = (x_max - x_min) / (L - 1)
+    x = values_at(np.asarray(got), alpha)
+    l, _ = _split(P, rgb, C)
+    pi, mu, _ = params64(P, x, rgb, C, K, c)
+    a, b = _coupling64(l, x, rgb, c)
+    t = (np.clip((pi * mu).sum(axis=1), x_min, x_max) - x_min) / bw
+    bound = ((PI_BOUND + 16 * U32 * pi) * (np.abs(l[:, 1, c]) + np.abs(a) + np.abs(b))).sum(axis=1)
+    excused = np.abs(np.abs(t - np.floor(t)) - 0.5) <= bound / bw + 1e-6
+    return np.clip(np.rint(t), 0, L - 1).astype(np.int64), excused
 
 
 # ---- the thin convolutions ---------------------------------------------------------------------------------------------------

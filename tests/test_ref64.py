@@ -131,6 +131,95 @@ def test_exact_ties_go_to_the_even_entry_in_the_oracle(Lp, K):
     assert np.array_equal(ref64.as_u16(table), want)
 
 
+# ---- the heads of tests/test_gpu_head_shapes.py: every (C, K, alphabet) of ref64.HEAD_SHAPES ---------------------------------------
+
+SHAPE_W = 165          # B = 3, H = 1: the size at which the -m gpu file checks every shape against fp64
+SHAPE_CASES = [pytest.param(C, K, rgb, alpha, regime, id='{}-{}'.format(ref64.shape_id(C, K, rgb, alpha), regime))
+               for (C, K, rgb, alpha) in ref64.HEAD_SHAPES for regime in ref64.shape_regimes(rgb)]
+
+
+def test_shape_builders_leave_the_shipped_cases_alone():
+    """head_case draws what it drew before the alphabet was threaded through (make_P with and without `alpha` on the shipped alphabets), and
+    the shape table is the one the kernels' forms were chosen for: Kp of every row."""
+    for rgb in (True, False):
+        for regime in ref64.shape_regimes(rgb):
+            P, sym, C, K = ref64.head_case(regime, rgb, 5, 13)
+            rng = np.random.RandomState(10000 * ref64.REGIMES.index(regime) + 100 * 5 + 13 + (5000 if rgb else 0))
+            P2 = ref64.make_P(regime, rgb, 2, 5, 13, C, K, rng, alpha=ref64.alphabet(rgb))
+            assert P.tobytes() == P2.tobytes()
+            assert np.array_equal(sym, ref64.near_sym(P2, rgb, C, K, rng, alpha=ref64.alphabet(rgb)))
+        assert np.array_equal(ref64.targets32(rgb), ref64.targets_of(ref64.alphabet(rgb)))
+    assert [(4 if rgb else 3) * C * K for C, K, rgb, _ in ref64.HEAD_SHAPES] == [12, 60, 192, 3, 6, 18, 42, 45, 60, 240, 126, 240, 255]
+    assert [a[2] + 1 for _, _, _, a in ref64.HEAD_SHAPES] == [257, 257, 257, 3, 26, 8, 65, 26, 26, 260, 26, 26, 26]
+
+
+@pytest.mark.parametrize('C,K,rgb,alpha,regime', SHAPE_CASES)
+def test_oracle_meets_the_rules_at_every_head_shape(C, K, rgb, alpha, regime):
+    """The oracle on the inputs of tests/test_gpu_head_shapes.py, through the rules that file applies to the kernels: parameters within
+    PI_BOUND / mu_bound64 / the exact clamp; its table through check_entries on its own parameters, the two shares pooled over the channels
+    of the case and inside the caps; rows that increase in fp64 increase; the NLL inside nll_tolerance with the slack term above 1e-3 on
+    < 2 %; both edge symbols occur."""
+    spec = odmll.Spec(rgb, alpha[0], alpha[1], alpha[2])
+    t = ref64.targets_of(alpha)
+    Lp = t.shape[0]
+    P, sym = ref64.shape_case(C, K, rgb, alpha, regime, 1, SHAPE_W)
+    assert P.shape == (3, (4 if rgb else 3) * C * K, 1, SHAPE_W) and sym.min() == 0 and sym.max() == alpha[2] - 1
+    x = ref64.values_at(sym, alpha)
+    assert np.array_equal(x, spec.to_bn(torch.from_numpy(sym)).numpy())
+    pooled, intervals = ref64.EntryStats(), ref64.EntryStats()
+    worst_pi = worst_mu = 0.0
+    for c in range(C):
+        pi, mu, ls = [v.numpy() for v in odmll.params_for_channel(spec, torch.from_numpy(P), c, C, torch.from_numpy(x))]
+        pi64, mu64, ls64 = ref64.params64(P, x, rgb, C, K, c)
+        assert (ls.astype(np.float64) == ls64).all()
+        worst_pi = max(worst_pi, np.abs(pi - pi64).max() / ref64.PI_BOUND)
+        worst_mu = max(worst_mu, (np.abs(mu - mu64) / np.maximum(ref64.mu_bound64(P, x, rgb, C, K, c), 1e-300)).max())
+        table = ocdf.mixture_cdf_table(*(torch.from_numpy(v) for v in (pi, t, mu, ls))).numpy()
+        what = '{} {} c{}'.format(ref64.shape_id(C, K, rgb, alpha), regime, c)
+        ref64.check_entries(table, pi, mu, ls, t, what=what, stats=pooled)
+        inc64 = ref64.rows_increasing(ref64.entries64(ref64.cdf64(pi, mu, ls, t), Lp))
+        assert ref64.rows_increasing(ref64.as_u16(table))[inc64].all(), what
+        # the two entries per symbol an encoder reads: where the mixture has its mass, few of them saturated
+        idx = np.stack([sym[:, c], sym[:, c] + 1], axis=-1).astype(np.int64)
+        ref64.check_entries(np.take_along_axis(ref64.as_u16(table), idx, -1), pi, mu, ls, t, index=idx, what=what + ' intervals', stats=intervals)
+    print('   |pi - pi64| / PI_BOUND <= {:.3f}, |mu - mu64| / bound <= {:.3f}; table: {}; intervals: {}'.format(worst_pi, worst_mu, pooled, intervals))
+    assert worst_pi <= 1 and worst_mu <= 1, (worst_pi, worst_mu)
+    pooled.assert_caps((C, K, rgb, alpha, regime, 'table'))
+    intervals.assert_caps((C, K, rgb, alpha, regime, 'intervals'))
+    ref32 = odmll.nll(spec, torch.from_numpy(x), torch.from_numpy(P)).numpy()
+    tol, share = ref64.nll_tolerance(ref32, ref64.nll64(P, x, rgb, C, K, alpha=alpha))
+    print('   nll: slack term above 1e-3 on {:.3%} of {} elements'.format(share, ref32.size))
+    assert np.isfinite(ref32).all() and share < ref64.NLL_SLACK_SHARE, share
+
+
+def _mean32(spec, P, C):
+    """The mixture's mean as symbols in fp32 torch, channel by channel on its own estimates (what l3c_dmll_mean computes)."""
+    Pt = torch.from_numpy(P)
+    B, _, H, W = P.shape
+    sym = torch.zeros(B, C, H, W, dtype=torch.long)
+    for c in range(C):
+        pi, mu, _ = odmll.params_for_channel(spec, Pt, c, C, spec.to_bn(sym))
+        sym[:, c] = spec.to_sym((pi * mu).sum(dim=1))
+    return sym.numpy()
+
+
+@pytest.mark.parametrize('C,K,rgb,alpha', [pytest.param(*s, id=ref64.shape_id(*s)) for s in ref64.HEAD_SHAPES])
+def test_fp32_mean_meets_the_excuse_rule_at_every_head_shape(C, K, rgb, alpha):
+    """ref64.mean_rule64 on a plain fp32 statement of the estimator: no symbol differs from fp64's outside the excused pixels, and those
+    stay below 2 % of the shape's (pixel, channel) items (regimes pooled)."""
+    spec = odmll.Spec(rgb, alpha[0], alpha[1], alpha[2])
+    n = n_excused = 0
+    for regime in ref64.mean_regimes(rgb, K):
+        P, _ = ref64.shape_case(C, K, rgb, alpha, regime, 1, SHAPE_W)
+        got = _mean32(spec, P, C)
+        for c in range(C):
+            want, excused = ref64.mean_rule64(P, got, rgb, C, K, alpha, c)
+            assert not ((got[:, c] != want) & ~excused).any(), (regime, c)
+            n, n_excused = n + excused.size, n_excused + int(excused.sum())
+    print('   mean: excused {:.3%} of {}'.format(n_excused / n, n))
+    assert n_excused <= ref64.MEAN_EXCUSED_CAP * n, (n_excused, n)
+
+
 def test_quantise_argmin_is_the_oracles_quantiser():
     from oracle import net as onet
     rng = np.random.RandomState(0)
