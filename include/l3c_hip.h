@@ -436,6 +436,28 @@ int l3c_dmll_sample(const float *P, const float *u_mix, const float *u_logistic,
 int l3c_dmll_mean(const float *P, int64_t B, int64_t HW, int C, int K, int rgb, float x_min, float x_max, int L,
                   int16_t *sym_out, l3c_stream_t stream);
 
+/*
+ * CONCEALMENT (INTEGRATION.md "Salvage decode"): the estimator of l3c_dmll_mean on pixel SPANS of decoded RGB symbols, conditioned on the
+ * channels that are kept.  RGB scale only: C = 3, lambda-coupled, P [B][HW][12 K].  Per pixel of a span, channels in the order R, G, B:
+ *   bit c of `replace` clear   x_c = sym_c * bin_width + x_min of the symbol already in `sym`; that symbol is read, never written
+ *   bit c set                  sym_c = the snapped m_c of l3c_dmll_mean, its coupling evaluated on the x_c' of the channels below -- kept or
+ *                              estimated --, x_c = sym_c * bin_width + x_min; sym_c is stored
+ * The device code is l3c_dmll_mean's: a span with replace == 7 gives, bit for bit, what l3c_dmll_mean gives on those pixels.
+ * One launch serves all spans: a block takes 64 pixels of one span (grid.y = the span, grid.x = the tiles of the longest).  Nothing outside
+ * the spans is read from `sym` or written, and no record of P outside them is fetched.  Overlapping spans are the caller's error.
+ *   spans_host   the table on the host, validated before anything is launched (an error names the span)
+ *   spans        the caller's device copy of the same table, 8-byte aligned
+ *   span         0 <= image < B, pix0 % 64 == 0 and >= 0, npix >= 0, pix0 + npix <= HW, replace < 8, reserved == 0
+ *   sym          int16 planar [B][3][HW], in/out
+ * n_spans in 0 .. 65535.  n_spans == 0, or every span empty or with replace == 0: success, nothing is launched.
+ */
+typedef struct l3c_conceal_span {
+    int64_t image, pix0, npix;
+    uint32_t replace, reserved;     /* replace: bit c set = channel c is overwritten */
+} l3c_conceal_span;
+int l3c_dmll_conceal(const float *P, int64_t B, int64_t HW, int K, float x_min, float x_max, int L, const l3c_conceal_span *spans_host,
+                     const l3c_conceal_span *spans, int64_t n_spans, int16_t *sym /* in/out, planar [B][3][HW] */, l3c_stream_t stream);
+
 /* ---- convolution stack (replaces the cuDNN convs behind modules/{net,edsr,head,prob_clf}.py) ---------------------- */
 
 /*
@@ -909,11 +931,18 @@ int l3c_encode_batch_banded(const l3c_encode_batch_desc *desc_host, int bands, l
  * l3c_sym_to_bn, l3c_net_get_p, l3c_dmll_cdf_table_ragged + l3c_ac_decode_chunks (ragged) over all B n bands, up to 8 channels per call;
  * the RGB record l3c_decode_rgb_banded on zeroed symbols, window mode 1; l3c_sym_to_u8.  side_stream must be a stream of its own whenever
  * the plan says lag 2; main_stream is ordered after the last pixel.
+ *
+ * l3c_decode_batch_banded_p_offset: where that call leaves the finest record's P [B][H W][12 K] -- the last thing written to the single P
+ * area of its workspace -- as a byte offset from the workspace pointer rounded up to the next multiple of 256 (the base the decode itself
+ * works from; a 256-byte aligned workspace: from the pointer).  A multiple of 256; valid until the workspace is reused.  Pure host code
+ * on the plan l3c_decode_batch_banded_workspace_bytes reads; a negative status for a bad plan.  With desc.sym, the caller then holds what
+ * l3c_dmll_conceal needs (INTEGRATION.md "Salvage decode").
  */
 int64_t l3c_decode_plan_banded_bytes(const l3c_net_config *cfg_host, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B);
 int l3c_decode_plan_banded(const l3c_net_config *cfg_host, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B,
                            void *plan_host, int64_t plan_bytes, int *H_out, int *W_out, uint16_t *padding_host_out);
 int64_t l3c_decode_batch_banded_workspace_bytes(const l3c_net_config *cfg_host, const void *plan_host);
+int64_t l3c_decode_batch_banded_p_offset(const l3c_net_config *cfg_host, const void *plan_host);
 int l3c_decode_batch_banded(const l3c_decode_batch_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
 
 /* ---- pictures as they come: any size and layout, padded and cropped on the device ----------------------------------------------------- */

@@ -254,6 +254,7 @@ PROTOTYPES = {
     'l3c_dmll_cdf_table': (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     'l3c_dmll_sample': (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
     'l3c_dmll_mean': (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_int, c_vp, c_vp]),
+    'l3c_dmll_conceal': (c_int, [c_vp, c_i64, c_i64, c_int, c_f32, c_f32, c_int, c_vp, c_vp, c_i64, c_vp, c_vp]),
     'l3c_dmll_nll': (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_int, c_vp, c_vp]),
     'l3c_conv_packed_words': (c_i64, [c_int, c_int, c_int]),
     'l3c_conv_pack_weights': (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp]),
@@ -304,6 +305,7 @@ PROTOTYPES = {
     'l3c_decode_plan_banded': (c_int, [ctypes.POINTER(NetConfig), c_vp, ctypes.POINTER(c_i64), c_i64, c_vp, c_i64, ctypes.POINTER(c_int),
                                        ctypes.POINTER(c_int), c_vp]),
     'l3c_decode_batch_banded_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
+    'l3c_decode_batch_banded_p_offset': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
     'l3c_decode_batch_banded': (c_int, [ctypes.POINTER(DecodeBatchDesc), c_vp, c_vp]),
     'l3c_image_padding': (c_int, [c_int, c_int, c_int, c_vp]),
     'l3c_image_table_check': (c_int, [c_vp, c_i64, c_int, c_int, c_i64]),

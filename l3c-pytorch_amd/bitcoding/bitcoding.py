@@ -626,6 +626,67 @@ class Bitcoding(object):
         words = torch.cat([frames, bands.view(-1)]).cpu().numpy()
         container.check_band_crcs(seals, words[B:].reshape(B, 3, -1), (H, W), padding, 0, words[:B])
 
+    def decode_salvage(self, files, out_dtype=torch.uint8):
+        """decode_batch(verify=True) that CONCEALS what does not verify instead of raising -> ((B,3,H,W) out_dtype on the GPU, list of padding
+        tuples, container.SalvageInfo).  The pre-decode checks still raise (SealError 'generation' / 'model' are not damage), and so does
+        an invalid file.  The decode is decode_batch's; this entry point alone keeps the finest scale's P and the int16 symbols alive past
+        the CRC check: ONE ops.u8_crc32_bands and its D2H, container.failing_bands, then for every band position j of a band-sealed file
+        with a failing channel one span (file, j L, min(L, HW - j L), mask of the failing channels) of ONE ops.dmll_conceal call -- the
+        mixture's mean, conditioned on the channels of the pixel that verified -- and one ops.sym_to_u8.  Every verified pixel comes back
+        exact; info says which is which (concealed, rows, lost, unverified).  An intact batch: no conceal launch, the pixels of
+        decode_batch.  Legacy files among banded ones are refused as decode_batch refuses them."""
+        split = [container.split_seal(f, view=True) for f in files]
+        files, seals = [b for b, _ in split], [s for _, s in split]
+        if any(s is not None for s in seals):
+            container.check_seals(seals, self.generation(), self.model_id)
+        records, framing, banded = container.parse_batch(files)
+        n_pred = self._n_predicted(len(records))
+        self._check_coarsest(records[0], banded, int(framing.nbytes[0].max()))
+        streams = upload._upload_streams(files, framing)
+        kept = {}
+        sym = self._walk_records(records, framing, banded, streams, n_pred, len(records), None, keep_finest=kept)
+        dmll = kept['dmll']
+        pixels, info = self._salvage(seals, sym.to(torch.uint8), sym, kept['P'], framing.padding, self.blueprint.net.config_ms.prob.K,
+                                     (dmll.x_min, dmll.x_max, dmll.L))
+        return pixels.to(out_dtype), framing.padding, info
+
+    @staticmethod
+    def _salvage(seals, pixels, sym, P, padding, K, alphabet):
+        """The decoded uint8 frames `pixels` (B, 3, H, W) against their seals, as _check_pixels -- one hash call, one D2H --, then the
+        concealment of what failed in `sym` (int16, the same values) from P (the finest scale's, a tensor or a device pointer)
+        -> (pixels, container.SalvageInfo); `pixels` itself where nothing was concealed."""
+        B, _, H, W = pixels.shape
+        HW = H * W
+        unverified = [i for i, s in enumerate(seals) if s is None]
+        band_lens = {s.band_len for s in seals if s is not None and s.band_crcs is not None}
+        if not band_lens:
+            lost = []
+            if len(unverified) < B:
+                crcs = ops.u8_crc32(pixels.view(-1), B, pixels.numel() // B).cpu().numpy()
+                lost = [i for i, s in enumerate(seals) if s is not None and (int(crcs[i]) & 0xffffffff) != s.frame_crc]
+            return pixels, container.SalvageInfo({}, {}, lost, unverified, {}, B)
+        L, = band_lens                       # (the files of a batch share every record's band length: container.parse_batch)
+        bands, frames = ops.u8_crc32_bands(pixels.view(-1), B, HW, L)
+        words = torch.cat([frames, bands.view(-1)]).cpu().numpy()
+        failed, concealed, rows = container.failing_bands(seals, words[B:].reshape(B, 3, -1), (H, W), padding, 0, words[:B])
+        n = container.n_bands(HW, L)
+        lost, spans = [], []
+        for i in failed:
+            if i not in concealed:           # a version-1 seal: the frame CRC says that something is wrong, not where
+                lost.append(i)
+                continue
+            masks = {}
+            for c, j in concealed[i]:
+                masks[j] = masks.get(j, 0) | (1 << c)
+            if len(masks) == n:
+                lost.append(i)
+            spans += [(i, j * L, min(L, HW - j * L), m) for j, m in sorted(masks.items())]
+        if spans:
+            ops.dmll_conceal(P, sym, spans, K, *alphabet)
+            pixels = ops.sym_to_u8(sym)
+        total = {i: 3 * n for i, s in enumerate(seals) if s is not None and s.band_crcs is not None}
+        return pixels, container.SalvageInfo(concealed, rows, lost, unverified, total, B)
+
     # ---- the walk over a file's scale records, coarse -> fine: what decode_batch (legacy and banded files) and the set decoder share -----
     # The headers are untrusted input: a wrong C / H / W would make the table and decoder kernels index P and the symbol buffers out of
     # bounds (the reference fails with a shape error here, bitcoding.py:248-266).  What needs only the framing is checked before the first
@@ -688,13 +749,14 @@ class Bitcoding(object):
         streams = upload._upload_streams(files, framing)
         return self._walk_records(records, framing, banded, streams, n_pred, len(records), side).to(out_dtype), framing.padding
 
-    def _walk_records(self, records, framing, banded, streams, n_pred, n_decoded, side, finest=None):
+    def _walk_records(self, records, framing, banded, streams, n_pred, n_decoded, side, finest=None, keep_finest=None):
         """The walk over the n_pred + 1 scale records of B files, coarse -> fine, on the current stream -> the finest scale's symbols
         (B, 3, H, W) int16.  records / framing / banded: what container.parse_batch or parse_prefix gave, streams: the files on the device
         (upload._upload_streams).  The first n_decoded records are decoded by the range decoder; every record past them takes the MEAN of
         the mixture the network predicts for it (ops.dmll_mean) in the shape the network predicts.  side: see _rgb_schedule.
         finest (decode_region): the walk ends BEFORE the finest record and returns finest(k, dmll, record, hw, bn, F) -- the record's index,
-        loss and header, the (H, W) of the record before it, and the decoder's inputs for it."""
+        loss and header, the (H, W) of the record before it, and the decoder's inputs for it.
+        keep_finest (decode_salvage): a dict that receives the finest scale's P and loss; every other caller lets P go with the walk."""
         B = len(framing.padding)
         symbols = self._scale_symbols_of(banded)
         K = self.blueprint.net.config_ms.prob.K
@@ -716,6 +778,8 @@ class Bitcoding(object):
             hw = (H, W)
             if scale > 0:                                               # the finest scale's symbols ARE the pixel values (to_bn of the RGB scale: x 1 + 0)
                 bn = self._next_input(sym, dmll)
+        if keep_finest is not None:
+            keep_finest['P'], keep_finest['dmll'] = P, dmll
         return sym
 
     def decode_preview(self, files, records=None, out_dtype=torch.uint8):

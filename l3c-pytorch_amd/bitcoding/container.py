@@ -394,6 +394,54 @@ class SealError(ValueError):
         self.bands, self.rows = bands, rows
 
 
+class SalvageInfo(object):
+    """What decode_salvage (Bitcoding, NativeCodec) returned for B files: which pixels are verified and which are estimates.
+    concealed: {file: [(channel, band), ...]} the bands of band-sealed files whose decoded pixels did not hash to their table word, the
+    pairs and order of SealError.bands; their pixels are the mixture's mean, conditioned on the channels of the same pixels that did
+    verify (ops.dmll_conceal).  rows: {file: (y0, y1) or None} their hull in rows of the UNPADDED image (None: the padding rows alone), as
+    SealError.rows; every row outside it is verified, exact.  lost: files of which NOTHING verified -- a band-sealed file with a failing
+    channel in every band position (concealed all the same: its coarse records are as likely the cause), or a version-1 sealed file whose
+    frame CRC fails (it cannot be localised: its pixels are left as decoded).  unverified: the unsealed files.  bands_total: {file: 3 n}
+    for the band-sealed files; n_files: B."""
+
+    FIELDS = ('concealed', 'rows', 'lost', 'unverified', 'bands_total', 'n_files')
+
+    def __init__(self, concealed, rows, lost, unverified, bands_total, n_files):
+        self.concealed, self.rows, self.lost, self.unverified = concealed, rows, list(lost), list(unverified)
+        self.bands_total, self.n_files = bands_total, int(n_files)
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f in self.FIELDS}
+
+    def __eq__(self, other):
+        return isinstance(other, SalvageInfo) and self.as_dict() == other.as_dict()
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = None
+
+    def __repr__(self):
+        return 'SalvageInfo({})'.format(', '.join('{}={!r}'.format(f, getattr(self, f)) for f in self.FIELDS))
+
+    def line(self):
+        """One line for people (l3c.py dec --salvage)."""
+        tag = (lambda i: 'file {}: '.format(i)) if self.n_files > 1 else (lambda i: '')
+        said = []
+        for i in sorted(set(self.concealed) | set(self.lost)):
+            if i in self.concealed:
+                where = 'rows [{}, {})'.format(*self.rows[i]) if self.rows.get(i) else 'the padding rows'
+                what = '{} concealed ({} of {} bands)'.format(where, len(self.concealed[i]), self.bands_total[i])
+                what += (': LOST, no band position verified, every pixel is an estimate' if i in self.lost else ', every other row verified')
+            else:
+                what = 'LOST, the frame CRC fails and the seal has no band table to locate the damage: pixels as decoded, none verified'
+            said.append(tag(i) + what)
+        tail = '; not sealed: file(s) {}'.format(self.unverified) if self.unverified and self.n_files > 1 else ''
+        if not said:
+            return 'not sealed: nothing to verify' if len(self.unverified) == self.n_files else 'seal: ok' + tail
+        return 'salvaged: ' + '; '.join(said) + tail
+
+
 def _padding_bytes(body):
     at = 6 if is_banded(body) else 0
     if len(body) < at + 8:
@@ -576,12 +624,14 @@ def band_rows(j, L, frame_hw, padding):
     return (y0, y1) if y0 < y1 else None
 
 
-def check_band_crcs(seals, words, frame_hw, paddings, first_band=0, frame_words=None):
-    """After the decode: the band CRCs of the decoded pixels against the tables.  seals: per file a Seal or None; words[i]: the (3, m) CRC
-    words of bands first_band .. first_band + m - 1 of decoded frame i (a full decode: all n; a region decode: the bands it decoded), ignored
-    for files without a band seal; frame_hw: the padded (H, W); paddings: per file (left, right, top, bottom).  frame_words: the frame
-    CRCs of the decoded frames, compared with the version-1 seals of the same call (None: those are not checked here).
-    SealError('pixels') names the first failing file, lists all, and carries .bands and .rows for the band-sealed ones."""
+def failing_bands(seals, words, frame_hw, paddings, first_band=0, frame_words=None):
+    """After the decode: the band CRCs of the decoded pixels against the tables, WITHOUT raising (decode_salvage; check_band_crcs raises on
+    the same findings).  seals: per file a Seal or None; words[i]: the (3, m) CRC words of bands first_band .. first_band + m - 1 of
+    decoded frame i (a full decode: all n; a region decode: the bands it decoded), ignored for files without a band seal; frame_hw: the
+    padded (H, W); paddings: per file (left, right, top, bottom).  frame_words: the frame CRCs of the decoded frames, compared with the
+    version-1 seals of the same call (None: those are not checked here).
+    -> (failed, bands, rows): the files that failed, in call order; bands = {file: [(channel, band), ...]} and rows = {file: (y0, y1) or
+    None} for the band-sealed ones among them (SealError.bands, .rows)."""
     failed, bands, rows = [], {}, {}
     words = (np.asarray(words).astype(np.int64) & 0xffffffff).astype(np.uint32)      # int32 or uint32 words, all files at once
     for i, s in enumerate(seals):
@@ -602,6 +652,13 @@ def check_band_crcs(seals, words, frame_hw, paddings, first_band=0, frame_words=
             failed.append(i)
             bands[i] = bad
             rows[i] = band_rows(sorted({j for _, j in bad}), s.band_len, frame_hw, paddings[i])
+    return failed, bands, rows
+
+
+def check_band_crcs(seals, words, frame_hw, paddings, first_band=0, frame_words=None):
+    """failing_bands, raising: SealError('pixels') names the first failing file, lists all, and carries .bands and .rows for the
+    band-sealed ones."""
+    failed, bands, rows = failing_bands(seals, words, frame_hw, paddings, first_band, frame_words)
     if failed:
         i = failed[0]
         if i in bands:

@@ -533,14 +533,19 @@ int plan_recheck(const l3c_net_config &c, void *plan_host) {
     return CODEC_FAIL(L3C_ERR_INVALID_ARG, "invalid file: %lld x %lld pixels: %s", (long long)h.H, (long long)h.W, why);
 }
 
+// a size or an offset of the decode's workspace, from the checked plan
 template <class Hdr>
-int64_t dec_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) {
+int64_t dec_plan_field(const l3c_net_config *cfg, const void *plan_host, int64_t DecPlan::*field) {
     CODEC_TRY(codec_config(cfg));
     Hdr h;
     CODEC_TRY(check_blob_of(*cfg, plan_host, -1, &h));
     DecPlan p;
     CODEC_TRY(dec_plan(*cfg, h, &p));
-    return p.bytes;
+    return p.*field;
+}
+template <class Hdr>
+int64_t dec_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) {
+    return dec_plan_field<Hdr>(cfg, plan_host, &DecPlan::bytes);
 }
 
 template <class Hdr>
@@ -1112,6 +1117,11 @@ int l3c_decode_plan_banded(const l3c_net_config *cfg, const uint8_t *files_host,
 
 int64_t l3c_decode_batch_banded_workspace_bytes(const l3c_net_config *cfg, const void *plan_host) {
     return dec_workspace_bytes<BandedHeader>(cfg, plan_host);
+}
+
+// (every record's P goes to the one P area, coarse to fine: the finest record's is what a finished decode leaves there)
+int64_t l3c_decode_batch_banded_p_offset(const l3c_net_config *cfg, const void *plan_host) {
+    return dec_plan_field<BandedHeader>(cfg, plan_host, &DecPlan::P);
 }
 
 int l3c_decode_batch_banded(const l3c_decode_batch_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {

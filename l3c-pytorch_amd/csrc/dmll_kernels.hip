@@ -763,6 +763,40 @@ __device__ __forceinline__ float mean_to_sym(float m, const MeanSnap &s) {
     return fminf(fmaxf(rintf((v - s.x_min) / s.bin_width), 0.0f), s.top);
 }
 
+// One (pixel, channel) item: the normalised sums of its px record.  A0, A1: the weights of the values of R and G (channel 2) or of R alone
+// (channel 1: A0), zero where the channel is not coupled.
+struct MeanSums {
+    float S, A0, A1;
+};
+__device__ __forceinline__ MeanSums mean_sums(const float *__restrict__ px, int c, int K, int CK, int rgb) {
+    float mx = px[c * K];
+    for (int k = 1; k < K; ++k) mx = fmaxf(mx, px[c * K + k]);
+    float denom = 0.0f, s = 0.0f, a0 = 0.0f, a1 = 0.0f;
+    for (int k = 0; k < K; ++k) {
+        const float e = expf(px[c * K + k] - mx);
+        denom = denom + e;
+        s = s + e * px[CK + c * K + k];
+        if (rgb && c == 1) {
+            a0 = a0 + e * sigmoid_f(px[3 * CK + k]);
+        } else if (rgb && c == 2) {
+            a0 = a0 + e * sigmoid_f(px[3 * CK + K + k]);
+            a1 = a1 + e * sigmoid_f(px[3 * CK + 2 * K + k]);
+        }
+    }
+    return MeanSums{s / denom, a0 / denom, a1 / denom};
+}
+// The ordered steps of RGB pixel p on the sums of its three items ([3][kHeadPix] each): R, then G on R's value, then B on both.  q: in, the
+// symbols of the channels whose bit of `replace` is CLEAR (kept: their value conditions the channels above, their sums are not read);
+// out, the symbols of all three.  replace == 7 is the plain estimator.
+__device__ __forceinline__ void rgb_mean_steps(const float *s_S, const float *s_A0, const float *s_A1, int p, const MeanSnap &snap,
+                                               unsigned replace, float q[3]) {
+    if (replace & 1u) q[0] = mean_to_sym(s_S[p], snap);
+    const float x0 = q[0] * snap.bin_width + snap.x_min;
+    if (replace & 2u) q[1] = mean_to_sym(s_S[kHeadPix + p] + x0 * s_A0[kHeadPix + p], snap);
+    const float x1 = q[1] * snap.bin_width + snap.x_min;
+    if (replace & 4u) q[2] = mean_to_sym(s_S[2 * kHeadPix + p] + (x0 * s_A0[2 * kHeadPix + p] + x1 * s_A1[2 * kHeadPix + p]), snap);
+}
+
 template <int NT>
 __global__ __launch_bounds__(NT) void dmll_mean_kernel(const float *__restrict__ P, int64_t HW, int C, int K, int rgb, MeanSnap snap,
                                                         int16_t *__restrict__ sym_out, TileDiv dv) {
@@ -780,27 +814,13 @@ __global__ __launch_bounds__(NT) void dmll_mean_kernel(const float *__restrict__
     for (int w = tid; w < kHeadPix * C; w += NT) {
         const int p = w % kHeadPix, c = w / kHeadPix;
         if (p >= npix) continue;
-        const float *px = tile + p * ld;
-        float mx = px[c * K];
-        for (int k = 1; k < K; ++k) mx = fmaxf(mx, px[c * K + k]);
-        float denom = 0.0f, s = 0.0f, a0 = 0.0f, a1 = 0.0f;
-        for (int k = 0; k < K; ++k) {
-            const float e = expf(px[c * K + k] - mx);
-            denom = denom + e;
-            s = s + e * px[CK + c * K + k];
-            if (rgb && c == 1) {
-                a0 = a0 + e * sigmoid_f(px[3 * CK + k]);
-            } else if (rgb && c == 2) {
-                a0 = a0 + e * sigmoid_f(px[3 * CK + K + k]);
-                a1 = a1 + e * sigmoid_f(px[3 * CK + 2 * K + k]);
-            }
-        }
+        const MeanSums m = mean_sums(tile + p * ld, c, K, CK, rgb);
         if (rgb) {
-            s_S[c * kHeadPix + p] = s / denom;
-            s_A0[c * kHeadPix + p] = a0 / denom;
-            s_A1[c * kHeadPix + p] = a1 / denom;
+            s_S[c * kHeadPix + p] = m.S;
+            s_A0[c * kHeadPix + p] = m.A0;
+            s_A1[c * kHeadPix + p] = m.A1;
         } else {
-            sym_out[(b * C + c) * HW + pix0 + p] = (int16_t)mean_to_sym(s / denom, snap);
+            sym_out[(b * C + c) * HW + pix0 + p] = (int16_t)mean_to_sym(m.S, snap);
         }
     }
     if (!rgb) return;
@@ -808,14 +828,58 @@ __global__ __launch_bounds__(NT) void dmll_mean_kernel(const float *__restrict__
     if (tid < npix) {       // C == 3: R, then G on R's estimate, then B on both
         const int p = tid;
         int16_t *out = sym_out + b * 3 * HW + pix0 + p;
-        const float q0 = mean_to_sym(s_S[p], snap);
-        const float x0 = q0 * snap.bin_width + snap.x_min;
-        const float q1 = mean_to_sym(s_S[kHeadPix + p] + x0 * s_A0[kHeadPix + p], snap);
-        const float x1 = q1 * snap.bin_width + snap.x_min;
-        const float q2 = mean_to_sym(s_S[2 * kHeadPix + p] + (x0 * s_A0[2 * kHeadPix + p] + x1 * s_A1[2 * kHeadPix + p]), snap);
-        out[0] = (int16_t)q0;
-        out[HW] = (int16_t)q1;
-        out[2 * HW] = (int16_t)q2;
+        float q[3] = {0.0f, 0.0f, 0.0f};
+        rgb_mean_steps(s_S, s_A0, s_A1, p, snap, 7u, q);
+        out[0] = (int16_t)q[0];
+        out[HW] = (int16_t)q[1];
+        out[2 * HW] = (int16_t)q[2];
+    }
+}
+
+// ---- concealment: the same estimator on pixel SPANS, conditioned on the channels that are kept (salvage decode) ---------
+// A span is pixels [pix0, pix0 + npix) of one image and a mask of the channels to overwrite.  Per pixel, channels in the order R, G, B: a
+// channel whose bit is clear keeps its symbol, and its VALUE (sym * bin_width + x_min) conditions the channels above it; a channel whose
+// bit is set takes the snapped mean of rgb_mean_steps.  mean_sums and rgb_mean_steps are dmll_mean_kernel's: replace == 7 is that kernel
+// on those pixels, bit for bit.  blockIdx.y is the span, blockIdx.x its tile of kHeadPix pixels (grid.x covers the longest span: the
+// surplus blocks of a shorter one, and every block of a span that replaces nothing, leave at once, uniformly).  Nothing outside the
+// spans is read from sym or written, no record of P outside them is fetched; a kept channel is read, never written.
+template <int NT>
+__global__ __launch_bounds__(NT) void dmll_conceal_kernel(const float *__restrict__ P, int64_t HW, int K, MeanSnap snap,
+                                                           const l3c_conceal_span *__restrict__ spans, int16_t *__restrict__ sym, TileDiv dv) {
+    extern __shared__ __attribute__((aligned(16))) float tile[];   // [kHeadPix][Kp + 1], then S, A0, A1: [3][kHeadPix] each
+    const int CK = 3 * K, Kp = 4 * CK;
+    const int ld = Kp + 1;
+    float *s_S = tile + kHeadPix * ld, *s_A0 = s_S + 3 * kHeadPix, *s_A1 = s_A0 + 3 * kHeadPix;
+    const l3c_conceal_span sp = spans[blockIdx.y];
+    const int64_t off = (int64_t)blockIdx.x * kHeadPix;
+    if (sp.replace == 0u || off >= sp.npix) return;
+    const int64_t pix0 = sp.pix0 + off;
+    const int npix = (int)((sp.npix - off) < kHeadPix ? (sp.npix - off) : kHeadPix);
+    const int tid = threadIdx.x;
+    int16_t *px_sym = sym + sp.image * 3 * HW + pix0 + tid;
+    // the kept channels' symbols: asked for before the tile, so that they arrive under its fill
+    float q[3] = {0.0f, 0.0f, 0.0f};
+    if (tid < npix) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            if (!(sp.replace >> c & 1u)) q[c] = (float)px_sym[c * HW];
+    }
+    fill_tile<NT>(tile, P + (sp.image * HW + pix0) * Kp, npix, Kp, ld, dv, tid);
+    __syncthreads();
+    for (int w = tid; w < kHeadPix * 3; w += NT) {
+        const int p = w % kHeadPix, c = w / kHeadPix;
+        if (p >= npix || !(sp.replace >> c & 1u)) continue;      // (a kept channel's sums are never read)
+        const MeanSums m = mean_sums(tile + p * ld, c, K, CK, 1);
+        s_S[c * kHeadPix + p] = m.S;
+        s_A0[c * kHeadPix + p] = m.A0;
+        s_A1[c * kHeadPix + p] = m.A1;
+    }
+    __syncthreads();
+    if (tid < npix) {
+        rgb_mean_steps(s_S, s_A0, s_A1, tid, snap, sp.replace, q);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            if (sp.replace >> c & 1u) px_sym[c * HW] = (int16_t)q[c];
     }
 }
 
@@ -1009,5 +1073,38 @@ int l3c_dmll_mean(const float *P, int64_t B, int64_t HW, int C, int K, int rgb, 
         hipLaunchKernelGGL(dmll_mean_kernel<256>, grid, dim3(256), lds, l3c::as_stream(stream), P, HW, C, K, rgb, snap, sym_out,
                            tile_div(Kp, kHeadPix));
     return l3c::check_launch("dmll_mean_kernel");
+}
+
+static_assert(sizeof(l3c_conceal_span) == 32, "the span table is read as it is passed: 32 bytes a span");
+
+int l3c_dmll_conceal(const float *P, int64_t B, int64_t HW, int K, float x_min, float x_max, int L, const l3c_conceal_span *spans_host,
+                     const l3c_conceal_span *spans, int64_t n_spans, int16_t *sym, l3c_stream_t stream) {
+    L3C_REQUIRE(n_spans >= 0 && n_spans < 65536, "n_spans out of range (0 .. 65535)");
+    if (n_spans == 0) return L3C_OK;
+    L3C_REQUIRE(P && spans_host && spans && sym, "null pointer");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(spans) & 7) == 0, "spans must be 8-byte aligned");
+    L3C_REQUIRE(B > 0 && B < 65536 && HW > 0 && HW <= (int64_t)0x7fffffff * kHeadPix, "bad shape");
+    L3C_REQUIRE(K > 0 && K <= kMaxK, "K out of range (1..16)");
+    L3C_REQUIRE(L >= 2 && L <= 32768 && x_min < x_max, "alphabet out of range (2 <= L <= 32768, x_min < x_max)");
+    int64_t longest = 0;
+    for (int64_t i = 0; i < n_spans; ++i) {
+        const l3c_conceal_span &s = spans_host[i];
+        const char *why = s.image < 0 || s.image >= B                       ? "image outside the batch"
+                          : s.pix0 < 0 || s.pix0 % kHeadPix != 0            ? "pix0 is not a non-negative multiple of 64"
+                          : s.npix < 0 || s.pix0 > HW || s.npix > HW - s.pix0 ? "pixels outside the image (npix >= 0, pix0 + npix <= HW)"
+                          : s.replace >= 8u                                  ? "replace must be below 8"
+                          : s.reserved != 0u                                 ? "reserved must be 0"
+                                                                             : nullptr;
+        if (why) return l3c::fail(L3C_ERR_INVALID_ARG, "bad span: %s (span %lld)", why, (long long)i);
+        if (s.replace && s.npix > longest) longest = s.npix;
+    }
+    if (longest == 0) return L3C_OK;      // every span empty or keeping all three channels: nothing to write
+    const int Kp = 12 * K;
+    const size_t lds = ((size_t)kHeadPix * (Kp + 1) + 9 * kHeadPix) * sizeof(float);
+    L3C_REQUIRE(lds <= 64 * 1024, "Kp too large for the LDS tile");
+    const MeanSnap snap{x_min, x_max, (float)(((double)x_max - (double)x_min) / (double)(L - 1)), (float)(L - 1)};      // as l3c_dmll_mean
+    const dim3 grid((unsigned)((longest + kHeadPix - 1) / kHeadPix), (unsigned)n_spans);
+    hipLaunchKernelGGL(dmll_conceal_kernel<256>, grid, dim3(256), lds, l3c::as_stream(stream), P, HW, K, snap, spans, sym, tile_div(Kp, kHeadPix));
+    return l3c::check_launch("dmll_conceal_kernel");
 }
 }

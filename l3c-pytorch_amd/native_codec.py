@@ -222,6 +222,7 @@ class NativeCodec(object):
         self.seal = bool(seal)
         self.seal_bands = seal == 'bands'
         self._network, self._model_id = blueprint.net, None
+        self._losses = blueprint.losses
         _lib.require_gpu()
         self.net = NativeNet(blueprint.net)
         self.cfg = self.net.cfg
@@ -334,9 +335,34 @@ class NativeCodec(object):
         before anything is enqueued, l3c_u8_crc32 on `pixels` and one D2H of B words after, SealError('pixels'); verify=False strips the
         seals and checks nothing.  Band-sealed files among them: ONE l3c_u8_crc32_bands on `pixels` instead, every band-sealed file compared
         band by band (SealError('pixels') with .bands and .rows), the version-1 sealed ones against the same call's frame words."""
+        files, seals = self._split(files, verify)
+        pixels, pads = self._decode_bodies(files, workspace, sym)
+        if seals is not None:
+            Bitcoding._check_pixels(seals, pixels, pads)
+        return pixels, pads
+
+    def decode_salvage(self, files, workspace=None):
+        """Bitcoding.decode_salvage as library calls -> ((B,3,H,W) uint8 on the GPU, padding tuples, container.SalvageInfo): the same
+        pixels and the same info.  l3c_decode_batch_banded with desc.sym; the finest record's P is what that call leaves in its workspace
+        (l3c_decode_batch_banded_p_offset), so after ONE l3c_u8_crc32_bands and its D2H the bands that fail are concealed by ONE
+        l3c_dmll_conceal on workspace + offset and the symbols, and one l3c_sym_to_u8.  SealError('generation' / 'model') and invalid
+        files raise as in decode_batch; an intact batch launches no conceal kernel."""
+        split = [self._split_seal(f) for f in files]
+        files, seals = [b for b, _ in split], [s for _, s in split]
+        if any(s is not None for s in seals):
+            container.check_seals(seals, self.generation(), self.model_id)
+        kept = {}
+        pixels, pads = self._decode_bodies(files, workspace, None, kept)
+        loss = self._losses.loss_dmol_rgb
+        pixels, info = Bitcoding._salvage(seals, pixels, kept['sym'], kept.get('P'), pads, self.cfg.K, (loss.x_min, loss.x_max, loss.L))
+        return pixels, pads, info
+
+    def _decode_bodies(self, files, workspace, sym, keep=None):
+        """decode_batch behind the seals: the unsealed files -> (pixels, padding tuples), enqueued on the current stream.
+        keep (decode_salvage): a dict that receives 'sym', the int16 symbols, 'ws', the workspace, and -- banded files -- 'P', the device
+        address of the finest record's P in it, valid while 'ws' is held and not reused."""
         lib = _lib.load()
         B = len(files)
-        files, seals = self._split(files, verify)
         banded = [container.is_banded(f) for f in files]
         if any(banded) and not all(banded):
             raise ValueError('decode_batch: a batch mixes banded and legacy .l3c files')
@@ -367,6 +393,11 @@ class NativeCodec(object):
         lag = int(np.frombuffer(stage.numpy()[plan_at + 88:plan_at + 96].tobytes(), dtype=np.int64)[0])      # word 11 of either header
         ws = _bytes(ws_bytes) if workspace is None else workspace
         pixels = torch.empty(B, 3, H.value, W.value, dtype=torch.uint8, device='cuda')
+        if keep is not None:
+            sym = torch.empty(B, 3, H.value, W.value, dtype=torch.int16, device='cuda')
+            keep.update(sym=sym, ws=ws)
+            if banded:      # (the plan is read here: its staging buffer goes back to the ring with this call)
+                keep['P'] = (ws.data_ptr() + 255) // 256 * 256 + _size(lib.l3c_decode_batch_banded_p_offset(self._cfg_ref, plan_host))
         if sym is not None and (sym.dtype != torch.int16 or tuple(sym.shape) != tuple(pixels.shape) or not sym.is_contiguous()):
             raise ValueError('sym must be a contiguous int16 tensor of shape {}'.format(tuple(pixels.shape)))
         side = None
@@ -378,10 +409,7 @@ class NativeCodec(object):
                 t.record_stream(side)
         d = DecodeBatchDesc(ctypes.pointer(self.model), ptr(dev), plan_host, ptr(dev) + plan_at, n_plan, ptr(pixels), ptr(sym), ptr(ws), ws.numel())
         _lib.call(decode_fn, ctypes.byref(d), stream(), side.cuda_stream if side is not None else None)
-        pads = [tuple(int(v) for v in p) for p in pads]
-        if seals is not None:
-            Bitcoding._check_pixels(seals, pixels, pads)
-        return pixels, pads
+        return pixels, [tuple(int(v) for v in p) for p in pads]
 
     def decode_region(self, files, box, verify=True):
         """The pixels of a BOX of B files of equally padded images, banded or legacy, without decoding the rest of their finest record

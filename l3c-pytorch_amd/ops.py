@@ -689,6 +689,41 @@ def dmll_mean(P_nhwc, C, K, rgb, x_min, x_max, L):
     return out
 
 
+CONCEAL_SPAN_DTYPE = np.dtype([('image', '<i8'), ('pix0', '<i8'), ('npix', '<i8'), ('replace', '<u4'), ('reserved', '<u4')])      # l3c_conceal_span
+
+
+def conceal_spans(spans):
+    """[(image, pix0, npix, replace mask), ...] -> the host table of l3c_dmll_conceal (CONCEAL_SPAN_DTYPE)."""
+    table = np.zeros(len(spans), dtype=CONCEAL_SPAN_DTYPE)
+    for i, (image, pix0, npix, replace) in enumerate(spans):
+        table[i] = (image, pix0, npix, replace, 0)
+    return table
+
+
+def dmll_conceal(P, sym, spans, K, x_min, x_max, L):
+    """l3c_dmll_conceal, in place on `sym`: P (B,H,W,12 K) fp32 or a device pointer to it, sym int16 (B,3,H,W) contiguous, spans a list of
+    (image, pix0, npix, replace mask) or a CONCEAL_SPAN_DTYPE array -- pixels [pix0, pix0 + npix) of image `image`, pix0 a multiple of 64;
+    the channels whose bit of the mask is set take the snapped mean of the mixture, conditioned on the channels that are kept.  The table
+    is checked on the host and goes up through upload_small.  One launch, no host synchronisation; no spans: nothing is called."""
+    table = spans if isinstance(spans, np.ndarray) else conceal_spans(spans)
+    if table.dtype != CONCEAL_SPAN_DTYPE or table.ndim != 1:
+        raise ValueError('dmll_conceal: spans must be a 1-d array of CONCEAL_SPAN_DTYPE, got {} {}'.format(table.dtype, table.shape))
+    B, C, H, W = sym.shape
+    if sym.dtype != torch.int16 or C != 3 or not sym.is_contiguous():
+        raise ValueError('dmll_conceal: sym must be a contiguous int16 (B,3,H,W) tensor, got {} {}'.format(sym.dtype, tuple(sym.shape)))
+    if isinstance(P, torch.Tensor):
+        if tuple(P.shape) != (B, H, W, 12 * K):
+            raise ValueError('dmll_conceal: P {} beside sym {} at K = {}'.format(tuple(P.shape), tuple(sym.shape), K))
+        P = ptr(P, torch.float32)
+    if not len(table):
+        return sym
+    table = np.ascontiguousarray(table)
+    table_d = upload_small(table.view(np.int64))
+    call('l3c_dmll_conceal', P, B, H * W, int(K), float(x_min), float(x_max), int(L), table.ctypes.data, ptr(table_d, torch.int64), len(table),
+         ptr(sym, torch.int16), stream())
+    return sym
+
+
 # ---- arithmetic coder -------------------------------------------------------------------------------------------------
 
 

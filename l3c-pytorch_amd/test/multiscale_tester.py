@@ -516,8 +516,9 @@ class MultiscaleTester(object):
                                                                                  '; band-sealed' if self.bc.seal_bands else '; sealed' if self.bc.seal else ''))
         return bpsp
 
-    def decode(self, pin, png_out_p, region=None):
-        """region: a box (y0, y1) or (y0, y1, x0, x1) of the image -- only that box is decoded (Bitcoding.decode_region) and written."""
+    def decode(self, pin, png_out_p, region=None, salvage=False):
+        """region: a box (y0, y1) or (y0, y1, x0, x1) of the image -- only that box is decoded (Bitcoding.decode_region) and written.
+        salvage: Bitcoding.decode_salvage -- the picture is written whatever the pixel CRCs say, and SalvageInfo.line() is printed."""
         pout_dir = os.path.dirname(os.path.abspath(png_out_p))
         if not os.path.isdir(pout_dir):
             raise DecodeError('png_out_p directory ({}) does not exists!'.format(pout_dir))
@@ -525,6 +526,25 @@ class MultiscaleTester(object):
             raise DecodeError('png_out_p must end in .png, got {}'.format(png_out_p))
         from ..bitcoding import container
         verify = not getattr(self.flags, 'no_verify', False)
+        if salvage:
+            if region is not None:
+                raise DecodeError('--salvage decodes the whole image: it does not go with --region')
+            try:
+                with open(pin, 'rb') as fin:
+                    decoded, padding, info = self.bc.decode_salvage([fin.read()])
+            except container.SealError as e:
+                raise DecodeError('seal: {}'.format(e))
+            except (ValueError, NotImplementedError) as e:
+                raise DecodeError(str(e))
+            if any(padding[0]):
+                from ..helpers import pad
+                decoded = pad.undo_pad(decoded, *padding[0])
+            self._write_img(decoded, png_out_p)
+            print(info.line())
+            if info.lost:
+                print('*** the file is LOST: nothing of it verified')
+            print('---\nDecoded: {}'.format(png_out_p))
+            return
         if region is not None:
             try:
                 decoded, info = self.bc.decode(pin, verify=verify, region=region)

@@ -2,7 +2,7 @@
 """Encoder / decoder CLI -- same arguments as the reference's src/l3c.py:74-125:
 
     python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] enc IMG_P OUT_P [--overwrite]
-    python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] dec [--region Y0:Y1[,X0:X1]] IMG_P OUT_P_PNG
+    python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] dec [--region Y0:Y1[,X0:X1]] [--salvage] IMG_P OUT_P_PNG
     python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] preview IMG_P OUT_P_PNG [--records R] [--bytes N]
 
 Everything runs on the MI355X path; `--device cpu` is refused (there is no CPU back end in this build).
@@ -77,6 +77,9 @@ def main(argv=None):
     dec.add_argument('--region', type=parse_region, default=None, metavar='Y0:Y1[,X0:X1]',
                      help='decode only rows [Y0, Y1) (and columns [X0, X1)) of the image: of a banded file only the bands and rows that '
                           'box needs are decoded; OUT_P_PNG receives the box')
+    dec.add_argument('--salvage', action='store_true',
+                     help='a damaged BAND-SEALED file: write the picture all the same -- every verified pixel exact, the damaged bands '
+                          'concealed by the mean of the predicted distribution -- and say which rows are which')
     pre = mode.add_parser('preview', help='Picture from the coarse scale records of a file: preview IMG_P OUT_P_PNG [--records R] [--bytes N]')
     pre.add_argument('img_p')
     pre.add_argument('out_p_png')
@@ -103,7 +106,7 @@ def main(argv=None):
             return 1
     else:
         try:
-            tester.decode(flags.img_p, flags.out_p_png, flags.region)
+            tester.decode(flags.img_p, flags.out_p_png, flags.region, flags.salvage)
         except DecodeError as e:
             print('*** DecodeError:', e)
             return 1
