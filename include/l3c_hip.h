@@ -1276,6 +1276,94 @@ int l3c_u8_crc32_bands(const uint8_t *frames, int64_t n_frames, int planes, int6
 int l3c_seal_append_bands(uint8_t *files, int64_t file_stride, int64_t *file_bytes, const uint32_t *frame_crc, const uint32_t *band_crc, int n,
                           uint32_t band_len, const uint16_t *padding, uint64_t model_id, int64_t B, l3c_stream_t stream);
 
+/* ---- parity bands: rebuild a damaged band of the finest record (opt-in, band-sealed files only; INTEGRATION.md "Parity bands") ----------- */
+
+/*
+ * A band seal turns damage into ERASURES: l3c_u8_crc32_bands says which (channel, band) of the finest record failed.  Seal version 3 adds an
+ * XOR parity over that record's band payloads (about 95 % of a file's bytes), RAID-5 style: one parity stream per group of G bands restores
+ * one erased band per group exactly.
+ *     body (the unsealed banded file) | PARITY SECTION | BAND TABLE (as in version 2) | the 24 seal bytes with version = 3
+ *     PARITY SECTION, little-endian, S = 16 + 12 m + sum(plen) bytes:
+ *       0 'L3CP' | 4 u16 G | 6 u16 m | 8 u32 plen[3][m] (channel-major) | 8 + 12 m the 3 m parity payloads, (c, g) order, back to back |
+ *       S - 8 u32 S | S - 4 separator 46 E2 84 92
+ *   n, G, m      n the bands per channel of the finest record, G in 1..n, m = ceil(n / G)
+ *   groups       INTERLEAVED: group g of channel c holds the bands { j : j % m == g }; a channel's bands lie back to back in the file, so a
+ *                burst over adjacent bands hits different groups
+ *   payload      of (c, g): the XOR of its members' payloads, each zero-extended to plen[c][g], the longest member's byte count
+ *   check        CRC-32 of the 8 padding bytes, section bytes [0, 8 + 12 m), the section's last 8 bytes, the band table, seal bytes 0..19.
+ *                The parity PAYLOADS are not under it: a damaged parity stream must not make an intact file unreadable; it can only make a
+ *                repair fail, which the band CRCs of the repaired pixels notice.
+ * The section ends with the separator: the band table still starts behind one, and the recognition rule is unchanged.  A reader rejects,
+ * "invalid file: seal ...": a section that does not start behind the body's last separator or lacks 'L3CP', an S other than 16 + 12 m +
+ * sum(plen), G or m inconsistent with the finest record's n, a plen[c][g] that is not the largest length field of its members, a
+ * version-3 seal on a legacy file, and everything a version-2 seal is rejected for.
+ *
+ * l3c_seal_find_parity is l3c_seal_find_bands that also hands out the section: *body_bytes_out is the size in front of the SECTION;
+ * parity_out->plen and ->payloads point INTO the file (unaligned); versions 1 and 2 give m = 0.  l3c_seal_find and l3c_seal_find_bands
+ * accept version 3 and return the same *body_bytes_out: every reader of band-sealed files reads a version-3 file as the band-sealed file
+ * it contains.  l3c_seal_write_parity stores l3c_seal_parity_bytes(n, m, payload bytes) bytes: section, table and seal.
+ *
+ * THE REPAIR (Bitcoding.decode_repair; INTEGRATION.md "Parity bands") decodes as the salvage decode does, keeps the finest P and the symbols,
+ * and goes in rounds.  The erasure of a failing band position is its lowest failing channel c; a group (file, c, g) is rebuilt when it
+ * holds exactly one erasure and every other member verifies at channel c.  A round: the parity payloads needed go up, ONE l3c_u8_xor_spans
+ * rebuilds every payload of the round in the decoders' aligned form, the positions' symbols are zeroed, ONE l3c_decode_rgb_entries decodes
+ * them against the kept P, l3c_sym_to_u8, and ONE l3c_u8_crc32_spans hashes their bands again.  Rounds repeat while one verified a band
+ * more; a payload counts as repaired only when all three channels of its position verify, and what still fails is concealed
+ * (l3c_dmll_conceal).
+ * NOT BUILT: the encoder side and the repair in l3c_encode_batch_banded / l3c_decode_batch_banded callers (NativeCodec), repair in the set
+ * readers and in the region decode, protection of the coarser records and of the framing (a damaged length field is an invalid file),
+ * verification of parity payloads that were never needed.
+ */
+typedef struct {
+    int32_t G, m;                   /* bands per group, groups per channel; m == 0: no parity section */
+    const uint8_t *plen;            /* 12 m bytes inside the file: [3][m] little-endian words, unaligned */
+    const uint8_t *payloads;        /* the 3 m parity payloads, (c, g) order, back to back */
+    int64_t payload_bytes;          /* sum of plen */
+} l3c_seal_parity;
+int64_t l3c_seal_parity_bytes(int n, int m, int64_t payload_bytes);    /* 16 + 12 m + payload_bytes + 20 + 12 n + 24 */
+int l3c_seal_find_parity(const uint8_t *file_host, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
+                         l3c_seal_parity *parity_out);
+int l3c_seal_write_parity(const l3c_seal *seal_host, const uint8_t *padding8_host, const uint32_t *band_crc_host, int n, uint32_t band_len, int G,
+                          const uint32_t *plen_host, const uint8_t *payloads_host, uint8_t *dst_host);
+
+/*
+ * The two kernels share one device fold (csrc/parity.hip): a block XORs a 4096-byte tile of ONE output stream over the stream's members,
+ * grid.y = the output stream.  A thread owns 16 bytes of the tile: one 16-byte load per member where the member is 16-byte aligned, dword
+ * loads otherwise; nothing at or behind a member's 4-byte-rounded end is read, the bytes of its last dword behind its length count as
+ * zero; 16-byte stores where the slot is 16-byte aligned, dword stores otherwise.  Every argument is checked before the launch; no
+ * allocation, no host synchronisation, no atomics.
+ *
+ * l3c_band_parity: the encoder side, lengths known on the device alone.  `scale`: the finest record's coder output, the two groups of
+ * l3c_ac_band_intervals as l3c_container_write_banded takes them (C must be 3); band j < n - 1 of stream s = b 3 + c is row s (n - 1) + j
+ * of out_full, band n - 1 row s of out_last.
+ *   parity          uint8 [B][3][m][parity_stride], m = ceil(n / G): bytes [0, ((parity_nbytes + 3) / 4) * 4) of a slot are written, the
+ *                   rest of the slot is the caller's and is not written
+ *   parity_nbytes   uint32 [B][3][m]: the longest member's byte count, or L3C_AC_OVERRUN when a member reported L3C_AC_OVERRUN -- such
+ *                   a member is not read and the slot is not written (that file is already -1)
+ *   parity_stride   % 16 == 0 and >= max(stride_full, stride_last); the coder strides % 4 == 0; G in 1..n; B * 3 * m <= 65535
+ * l3c_band_parity_groups: m for n and G, or L3C_ERR_INVALID_ARG.
+ */
+int l3c_band_parity_groups(int n, int G);
+int l3c_band_parity(const l3c_banded_scale *scale_host, int64_t B, int G, uint8_t *parity, int64_t parity_stride, uint32_t *parity_nbytes,
+                    l3c_stream_t stream);
+
+/*
+ * l3c_u8_xor_spans: the repair side, lengths known on the host.  Output slot g = bytes [out_spans[g].offset, ...) of `out` receives the XOR
+ * of the spans [group_first[g], group_first[g + 1]) of `spans` inside `data`, each cut or zero-extended to out_spans[g].bytes, followed by
+ * zero bytes up to ((bytes + 3) / 4) * 4 + 4: the aligned, zero-padded form l3c_container_read produces and the range decoders read.  A
+ * group of one member is a copy; a group of none is zeros.  n_groups == 0 is a success with nothing launched.
+ *   spans_host, out_spans_host, group_first_host    the tables on the host, validated before anything is launched
+ *   spans, out_spans, group_first                   the caller's device copies of the same tables, 8-byte aligned
+ *   span            offset % 4 == 0 and >= 0, bytes >= 0; the span's 4-byte-rounded end must lie inside data_bytes
+ *   out span        offset % 4 == 0 and >= 0, bytes >= 0, offset + ((bytes + 3) / 4) * 4 + 4 <= out_bytes; slots must not overlap
+ *                   (not checked) and `out` must not overlap `data`
+ *   group_first     [n_groups + 1], ascending from 0 to n_spans; n_groups <= 65535
+ * data and out 4-byte aligned (16-byte aligned data, out and offsets: the full load rate).
+ */
+int l3c_u8_xor_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, int64_t n_spans,
+                     const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups, const l3c_u8_span *out_spans_host,
+                     const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

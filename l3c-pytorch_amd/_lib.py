@@ -207,6 +207,11 @@ class SealBands(ctypes.Structure):
     _fields_ = [('n', ctypes.c_int32), ('band_len', ctypes.c_uint32), ('crc', ctypes.c_void_p)]
 
 
+class SealParity(ctypes.Structure):
+    """l3c_seal_parity (include/l3c_hip.h); plen and payloads point into the file."""
+    _fields_ = [('G', ctypes.c_int32), ('m', ctypes.c_int32), ('plen', ctypes.c_void_p), ('payloads', ctypes.c_void_p), ('payload_bytes', c_i64)]
+
+
 SEAL_BYTES = 24      # include/l3c_hip.h: L3C_SEAL_BYTES
 EPI_RELU, EPI_RESIDUAL, EPI_PIXEL_SHUFFLE = 1, 2, 4
 ABI_VERSION = 4      # include/l3c_hip.h: L3C_ABI_VERSION (4: grouped tables, l3c_decode_rgb, l3c_container_read; no canvas batches)
@@ -338,6 +343,12 @@ PROTOTYPES = {
     'l3c_u8_crc32_bands_workspace_bytes': (c_i64, [c_i64, c_int, c_i64, c_i64]),
     'l3c_u8_crc32_bands': (c_int, [c_vp, c_i64, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'l3c_seal_append_bands': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_int, ctypes.c_uint32, c_vp, ctypes.c_uint64, c_i64, c_vp]),
+    'l3c_seal_parity_bytes': (c_i64, [c_int, c_int, c_i64]),
+    'l3c_seal_find_parity': (c_int, [c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(Seal), ctypes.POINTER(SealBands), ctypes.POINTER(SealParity)]),
+    'l3c_seal_write_parity': (c_int, [ctypes.POINTER(Seal), c_vp, c_vp, c_int, ctypes.c_uint32, c_int, c_vp, c_vp, c_vp]),
+    'l3c_band_parity_groups': (c_int, [c_int, c_int]),
+    'l3c_band_parity': (c_int, [ctypes.POINTER(BandedScale), c_i64, c_int, c_vp, c_i64, c_vp, c_vp]),
+    'l3c_u8_xor_spans': (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 # include/l3c_xcheck.h: the TEST-ONLY cross-check library (round-1/2 Winograd F(2x2,3x3) kernel); see load_xcheck()

@@ -103,6 +103,8 @@ class EncodedBatch(object):
         self.seal = None                     # ... and (bitstream generation, model id) of the encoder: every whole file is then sealed
         self.band_crc = None                 # Bitcoding(seal='bands'): int32 (B, 3, n) device tensor, CRC-32 of every band of the finest record's
         self.band_len = None                 # ... planes (ops.u8_crc32_bands, with frame_crc from the same pass), and that record's band length
+        self.parity_group = 0                # Bitcoding(parity=G): the group size asked for (the seal states min(G, n)) ...
+        self.parity = None                   # ... and (uint8 (B, 3, m, stride), int32 (B, 3, m)) of ops.band_parity on the finest record's coder output
 
     def _coder_outputs(self):
         """(C, H, W, out, nbytes) of every coder group, nbytes reshaped to (B, streams per image of that group)."""
@@ -124,6 +126,9 @@ class EncodedBatch(object):
             self.frame_crc.record_stream(cur)
         if self.band_crc is not None:
             self.band_crc.record_stream(cur)
+        if self.parity is not None:
+            for t in self.parity:
+                t.record_stream(cur)
         return self
 
     def total_payload_bytes(self):
@@ -198,11 +203,20 @@ class EncodedBatch(object):
     @staticmethod
     def _seals(encs, bodies):
         """The seal of every file of `encs` (b'' for a batch encoded without): ONE D2H of the frame CRCs (and the band CRCs of
-        seal='bands' batches), the band tables and check words on the host."""
+        seal='bands' batches, and the parity lengths and slots of parity=G batches), the band tables, parity sections and check words on
+        the host."""
         sealed = [e for e in encs if e.seal is not None]
         if not sealed:
             return [[b''] * len(files) for files in bodies]
-        words = torch.cat([t.reshape(-1) for e in sealed for t in ((e.wait().frame_crc,) if e.band_crc is None else (e.frame_crc, e.band_crc))])
+
+        def parts(e):
+            e.wait()
+            if e.band_crc is None:
+                return (e.frame_crc,)
+            if e.parity is None:
+                return (e.frame_crc, e.band_crc)
+            return (e.frame_crc, e.band_crc, e.parity[1], e.parity[0].view(torch.int32))      # (the slots' stride is a multiple of 16)
+        words = torch.cat([t.reshape(-1) for e in sealed for t in parts(e)])
         words, at, res = words.cpu().numpy().view(np.uint32), 0, []
         for e, files in zip(encs, bodies):
             if e.seal is None:
@@ -216,7 +230,18 @@ class EncodedBatch(object):
                 per = e.band_crc[0].numel()
                 bands = [words[at + b * per:at + (b + 1) * per].reshape(3, -1) for b in range(e.B)]
                 at += e.B * per
-            res.append([container.make_seal(body, e.seal[0], frame[b], e.seal[1], bands[b], e.band_len) for b, body in enumerate(files)])
+            parity = [None] * e.B
+            if e.parity is not None:
+                slots, lens = e.parity
+                m, stride = slots.shape[2], slots.shape[3]
+                nb = EncodedBatch._checked_nbytes(words[at:at + lens.numel()].view(np.int32)).reshape(e.B, 3, m)
+                at += lens.numel()
+                host = words[at:at + slots.numel() // 4].view(np.uint8).reshape(e.B, 3, m, stride)
+                at += slots.numel() // 4
+                G = min(e.parity_group, bands[0].shape[1])
+                parity = [(G, [[host[b, c, g, :nb[b, c, g]].tobytes() for g in range(m)] for c in range(3)]) for b in range(e.B)]
+            res.append([container.make_seal(body, e.seal[0], frame[b], e.seal[1], bands[b], e.band_len, parity=parity[b])
+                        for b, body in enumerate(files)])
         return res
 
     def _write_container(self, dst, offsets, padding_tuples):
@@ -295,7 +320,7 @@ class EncodedBatch(object):
 
 class Bitcoding(object):
     def __init__(self, blueprint, times=None, compare_with_theory=False, coder_cus=0, auto_recurse=0, file_writer=None,
-                 coder_streams=4, forward_streams=3, decode_overlap=None, rgb_window='auto', bands=0, seal=False):
+                 coder_streams=4, forward_streams=3, decode_overlap=None, rgb_window='auto', bands=0, seal=False, parity=0):
         """coder_streams: side streams the range-coder launches rotate over; forward_streams: streams `encode_many` spreads the forward
         passes of a heterogeneous set over (used when the HIP runtime runs with >= 8 hardware queues -- helpers/runtime.py; the package
         does NOT ask for them on import: applications that code image sets call l3c_pytorch_amd.configure_hip_queues() before their
@@ -321,9 +346,19 @@ class Bitcoding(object):
         seal='bands' (banded files only: ValueError with bands=0): a BAND SEAL instead (container.make_seal with band_crcs; INTEGRATION.md
         "Band seals"): in front of the 24 bytes a table of one CRC-32 per band of the finest record -- ops.u8_crc32_bands on the input
         frames, the frame CRC from the same pass.  decode_batch then names the damaged bands and rows of a file that fails, and
-        decode_region verifies exactly the bands it decoded."""
+        decode_region verifies exactly the bands it decoded.
+        parity=G (G >= 1; needs seal='bands': ValueError otherwise; INTEGRATION.md "Parity bands"): seal version 3 -- in front of the band table
+        an XOR parity over the band payloads of the finest record, one parity stream per group of min(G, n) bands of a channel
+        (ops.band_parity on the coder's output, enqueued with the encode), about 1 / G of the file's size.  decode_repair then rebuilds
+        one damaged band per group bit-exactly; every other reader reads the file as the band-sealed file it contains.  0: every byte
+        written is the band-sealed file's."""
         if seal not in (False, True, 'bands'):
             raise ValueError("seal must be False, True or 'bands', got {!r}".format(seal))
+        if isinstance(parity, bool) or not isinstance(parity, int) or parity < 0:
+            raise ValueError('parity must be 0 or a group size >= 1, got {!r}'.format(parity))
+        if parity and seal != 'bands':
+            raise ValueError("parity needs seal='bands': the band seal is what turns damage into erasures of known position")
+        self.parity = parity
         if seal == 'bands' and not bands:
             raise ValueError("seal='bands' needs banded files: a band seal holds a CRC per band of the finest record (bands=K, K >= 1)")
         if bands and not 1 <= int(bands) <= MAX_BANDS:
@@ -441,6 +476,7 @@ class Bitcoding(object):
             enc.band_len = band_len(H * W, self.bands)
             enc.band_crc, enc.frame_crc = ops.u8_crc32_bands(imgs.to('cuda').to(torch.uint8).contiguous().view(-1), B, H * W, enc.band_len)
             enc.seal = (self.generation(), self.model_id())
+            enc.parity_group = self.parity
         elif self.seal:
             enc.frame_crc = ops.u8_crc32(imgs.to('cuda').to(torch.uint8).contiguous().view(-1), B, 3 * H * W)
             enc.seal = (self.generation(), self.model_id())
@@ -481,6 +517,14 @@ class Bitcoding(object):
                         owners.append((enc, (C, Hs, Ws), 1))
                         groups.append((iv, enc.B * C, Hs * Ws))
             results, ws = ops.ac_encode_groups(groups)
+            g, finest = 0, {}
+            for enc, shape, n_groups in owners:                 # (coarse -> fine: the last record of a batch is its finest)
+                finest[id(enc)] = (enc, shape, results[g:g + n_groups])
+                g += n_groups
+            for enc, shape, coded in finest.values():
+                if enc.parity_group:                             # behind the coder on its stream: nothing waits
+                    _, Hs, Ws, L = shape
+                    enc.parity = ops.band_parity(enc.B, Hs, Ws, L, coded, min(enc.parity_group, n_bands(Hs * Ws, L)))
             done = torch.cuda.Event()
             done.record(side)
         g = 0
@@ -651,10 +695,11 @@ class Bitcoding(object):
         return pixels.to(out_dtype), framing.padding, info
 
     @staticmethod
-    def _salvage(seals, pixels, sym, P, padding, K, alphabet):
+    def _salvage(seals, pixels, sym, P, padding, K, alphabet, words=None):
         """The decoded uint8 frames `pixels` (B, 3, H, W) against their seals, as _check_pixels -- one hash call, one D2H --, then the
         concealment of what failed in `sym` (int16, the same values) from P (the finest scale's, a tensor or a device pointer)
-        -> (pixels, container.SalvageInfo); `pixels` itself where nothing was concealed."""
+        -> (pixels, container.SalvageInfo); `pixels` itself where nothing was concealed.  words (decode_repair): the hash call's words as
+        _band_words returns them, already on the host: nothing is hashed here."""
         B, _, H, W = pixels.shape
         HW = H * W
         unverified = [i for i, s in enumerate(seals) if s is None]
@@ -666,8 +711,8 @@ class Bitcoding(object):
                 lost = [i for i, s in enumerate(seals) if s is not None and (int(crcs[i]) & 0xffffffff) != s.frame_crc]
             return pixels, container.SalvageInfo({}, {}, lost, unverified, {}, B)
         L, = band_lens                       # (the files of a batch share every record's band length: container.parse_batch)
-        bands, frames = ops.u8_crc32_bands(pixels.view(-1), B, HW, L)
-        words = torch.cat([frames, bands.view(-1)]).cpu().numpy()
+        if words is None:
+            words = Bitcoding._band_words(pixels, L)
         failed, concealed, rows = container.failing_bands(seals, words[B:].reshape(B, 3, -1), (H, W), padding, 0, words[:B])
         n = container.n_bands(HW, L)
         lost, spans = [], []
@@ -686,6 +731,145 @@ class Bitcoding(object):
             pixels = ops.sym_to_u8(sym)
         total = {i: 3 * n for i, s in enumerate(seals) if s is not None and s.band_crcs is not None}
         return pixels, container.SalvageInfo(concealed, rows, lost, unverified, total, B)
+
+    @staticmethod
+    def _band_words(pixels, L):
+        """The frame words (B) and band words (B 3 n) of the uint8 frames `pixels` (B, 3, H, W) on the host: one hash call, one D2H."""
+        B, _, H, W = pixels.shape
+        bands, frames = ops.u8_crc32_bands(pixels.view(-1), B, H * W, L)
+        return torch.cat([frames, bands.view(-1)]).cpu().numpy()
+
+    def decode_repair(self, files, out_dtype=torch.uint8):
+        """decode_salvage that first REBUILDS what the parity of a version-3 file (Bitcoding(parity=G)) can rebuild, bit-exactly
+        -> ((B,3,H,W) out_dtype on the GPU, list of padding tuples, container.RepairInfo).
+        The decode, the hash call and container.failing_bands are decode_salvage's; an intact batch makes the same library calls: no
+        parity is uploaded, no XOR kernel launched.  A failing band position's ERASURE is its lowest failing channel c (the channels below
+        verified, so with the right P that payload is the damaged one).  A group (file, c, g) -- the bands { j : j % m == g } of channel
+        c -- is rebuilt when it holds exactly one erasure and every other member verifies at channel c.  A ROUND: the parity payloads
+        of those groups go up (a small H2D), ONE ops.u8_xor_spans rebuilds every payload of the round from its parity stream and the
+        group's other members (which are on the device already) in the decoders' aligned form, the positions' symbols are zeroed, ONE
+        ops.decode_rgb_entries decodes them against the kept P, ops.sym_to_u8, and ONE ops.u8_crc32_spans hashes their bands again.
+        Rounds repeat while one verified a band more and failures remain (a band whose other channel is damaged too, in another group,
+        takes a second round); no payload is rebuilt twice.  The band CRCs stay the arbiter: a payload counts as repaired only when all
+        three channels of its position verify.  What still fails is concealed as decode_salvage conceals it (info.salvage).
+        info.files: per file the HEALED file -- the rebuilt payloads spliced in at their framing offsets, the same length, section, table
+        and seal --, None where nothing was repaired.  Files without parity, intact files and unsealed files: decode_salvage."""
+        raw = files
+        split = [container.split_seal(f, view=True) for f in files]
+        files, seals = [b for b, _ in split], [s for _, s in split]
+        if any(s is not None for s in seals):
+            container.check_seals(seals, self.generation(), self.model_id)
+        records, framing, banded = container.parse_batch(files)
+        n_pred = self._n_predicted(len(records))
+        self._check_coarsest(records[0], banded, int(framing.nbytes[0].max()))
+        streams = upload._upload_streams(files, framing)
+        kept = {}
+        sym = self._walk_records(records, framing, banded, streams, n_pred, len(records), None, keep_finest=kept)
+        dmll = kept['dmll']
+        K = self.blueprint.net.config_ms.prob.K
+        pixels, B = sym.to(torch.uint8), len(files)
+        band_lens = {s.band_len for s in seals if s is not None and s.band_crcs is not None}
+        words, repaired, healed, rounds = None, {}, [None] * B, 0
+        if band_lens:
+            L, = band_lens
+            words = self._band_words(pixels, L)
+            if any(s is not None and s.parity is not None for s in seals):
+                pixels, repaired, healed, rounds = self._repair(raw, seals, records[-1], framing, streams, pixels, sym, kept['P'], dmll, K, words)
+        pixels, salvage = self._salvage(seals, pixels, sym, kept['P'], framing.padding, K, (dmll.x_min, dmll.x_max, dmll.L), words)
+        rows = {i: container.band_rows(sorted({j for _, j in got}), seals[i].band_len, records[-1][1:3], framing.padding[i])
+                for i, got in repaired.items()}
+        return pixels.to(out_dtype), framing.padding, container.RepairInfo(repaired, rows, salvage, healed, rounds)
+
+    def _repair(self, raw, seals, record, framing, streams, pixels, sym, P, dmll, K, words):
+        """The rounds of decode_repair on the finest record (C, H, W, L) of B decoded files; `words` (_band_words) is updated in place
+        with the words of the bands hashed again -> (pixels, {file: [(c, j)]} repaired, healed files, rounds run)."""
+        C, H, W, L = record
+        B, HW = len(seals), H * W
+        n = n_bands(HW, L)
+        band_words = words[B:].reshape(B, 3, n)                              # (a view: what _salvage reads afterwards)
+        k = len(framing.offset) - 1
+        buf, _, _ = streams.scale(k)
+        o_h, l_h = streams.scale_host(k)                                     # stream (c n + j) B + b
+        at = o_h.reshape(3, n, B).transpose(2, 0, 1).copy()                  # [b, c, j]: where the payload lies in `work`
+        lens = l_h.reshape(3, n, B).transpose(2, 0, 1).astype(np.int64)
+        work, tried, rebuilt, rounds = buf, set(), [], 0
+        al16 = lambda v: (int(v) + 15) // 16 * 16                            # noqa: E731
+        Kp = P.shape[-1]
+        while True:
+            _, failing, _ = container.failing_bands(seals, band_words, (H, W), framing.padding)
+            jobs = []                                                        # (file, c, j) to rebuild this round
+            for i, bad in failing.items():
+                if seals[i].parity is None:
+                    continue
+                bad, m = set(bad), seals[i].parity_groups
+                erasures = {}
+                for j in sorted({j for _, j in bad}):
+                    c = min(c for c, jj in bad if jj == j)
+                    erasures.setdefault((c, j % m), []).append(j)
+                for (c, g), js in sorted(erasures.items()):
+                    j = js[0]
+                    if len(js) == 1 and (i, c, j) not in tried and all((c, o) not in bad for o in range(g, n, m) if o != j):
+                        jobs.append((i, c, j))
+            if not jobs:
+                break
+            rounds += 1
+            tried.update(jobs)
+            # `work` grows by this round's region: the parity payloads (uploaded), then the output slots, all 16-byte aligned
+            base = al16(work.numel())
+            p_at, o_at, pos = [], [], base
+            for i, c, j in jobs:
+                p_at.append(pos)
+                pos = al16(pos + len(seals[i].parity[c][j % seals[i].parity_groups]) + 4)
+            src_end = pos
+            for i, c, j in jobs:
+                o_at.append(pos)
+                pos = al16(pos + (lens[i, c, j] + 3) // 4 * 4 + 4)
+            up = np.zeros(pos - work.numel(), dtype=np.uint8)
+            for (i, c, j), a in zip(jobs, p_at):
+                p = seals[i].parity[c][j % seals[i].parity_groups]
+                up[a - work.numel():a - work.numel() + len(p)] = np.frombuffer(p, dtype=np.uint8)
+            work = torch.cat([work, ops.upload_small(up)])
+            offs, lns, first = [], [], [0]
+            for (i, c, j), a in zip(jobs, p_at):
+                m = seals[i].parity_groups
+                others = [o for o in range(j % m, n, m) if o != j]
+                offs += [a] + [int(at[i, c, o]) for o in others]
+                lns += [len(seals[i].parity[c][j % m])] + [int(lens[i, c, o]) for o in others]
+                first.append(len(offs))
+            ops.u8_xor_spans(work[:src_end], offs, lns, first, work[src_end:], [a - src_end for a in o_at], [int(lens[i, c, j]) for i, c, j in jobs])
+            for (i, c, j), a in zip(jobs, o_at):
+                at[i, c, j] = a
+            # the positions of the round, decoded again: their symbols zeroed, one entry each
+            spots = sorted({(i, j) for i, _, j in jobs})
+            flat = sym.view(B, 3, HW)
+            for i, j in spots:
+                flat[i, :, j * L:min((j + 1) * L, HW)] = 0
+            e_i = np.asarray([i for i, _ in spots], dtype=np.int64)
+            e_j = np.asarray([j for _, j in spots], dtype=np.int64)
+            length = np.minimum(L, HW - e_j * L)
+            chunks = max(1, min(self.RGB_BAND_CHUNKS, int(length.min()) // 64))
+            hold = ops.decode_rgb_entries(P.view(-1, Kp), self._targets(dmll), sym.view(-1), work, at[e_i, :, e_j].T, lens[e_i, :, e_j].T,
+                                          e_i * HW, np.full(len(spots), HW, dtype=np.int64), e_j * L, length, chunks, K,
+                                          *self._rgb_schedule(len(spots), None))
+            pixels = ops.sym_to_u8(sym)
+            plane = (e_i[None, :] * 3 + np.arange(3, dtype=np.int64)[:, None])           # (3, S)
+            again = ops.u8_crc32_spans(pixels.view(-1), (plane * HW + e_j[None, :] * L).reshape(-1), np.broadcast_to(length, plane.shape).reshape(-1))
+            band_words[e_i[None, :], np.arange(3)[:, None], e_j[None, :]] = again.cpu().numpy().view(words.dtype).reshape(3, -1)
+            del hold
+            rebuilt += jobs
+        _, failing, _ = container.failing_bands(seals, band_words, (H, W), framing.padding)
+        repaired, healed = {}, [None] * B
+        for i, c, j in rebuilt:
+            if all((cc, j) not in failing.get(i, ()) for cc in range(3)):
+                repaired.setdefault(i, []).append((c, j))
+        for i, got in repaired.items():
+            got.sort()
+            f = bytearray(raw[i])
+            for c, j in got:
+                a, nb, to = int(at[i, c, j]), int(lens[i, c, j]), int(framing.offset[k][i, c * n + j])
+                f[to:to + nb] = work[a:a + nb].cpu().numpy().tobytes()
+            healed[i] = bytes(f)
+        return pixels, repaired, healed, rounds
 
     # ---- the walk over a file's scale records, coarse -> fine: what decode_batch (legacy and banded files) and the set decoder share -----
     # The headers are untrusted input: a wrong C / H / W would make the table and decoder kernels index P and the symbol buffers out of

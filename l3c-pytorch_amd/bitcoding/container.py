@@ -341,11 +341,23 @@ def image_entry_table(hws, pixbase0=0):
 # the padded planar frame.  The check word runs over the padding bytes, the whole table and seal bytes 0..19; the frame CRC stays and must
 # be the combination of the band CRCs (combine_band_crcs).  The recognition rule (is_sealed) is the same: the table ends with the separator.
 
+#
+# PARITY BANDS (opt-in, Bitcoding(bands=K, seal='bands', parity=G); INTEGRATION.md "Parity bands"): seal version 3, a band seal with a PARITY
+# SECTION between the body and the band table, S = 16 + 12 m + sum(plen) bytes:
+#     'L3CP' | u16 G | u16 m | u32 plen[3][m] (channel-major) | the 3 m parity payloads, (c, g) order, back to back | u32 S | separator
+# m = ceil(n / G) groups per channel of the finest record's n bands; group g of channel c holds the bands { j : j % m == g } (interleaved:
+# adjacent bands lie in different groups), its parity payload is the XOR of its members' payloads, each zero-extended to plen[c][g], the
+# longest member's byte count (band_parity).  The check word runs over the padding bytes, the section's head (bytes [0, 8 + 12 m)), its
+# last 8 bytes, the band table and seal bytes 0..19 -- NOT over the parity payloads: a damaged parity stream can only make a repair fail,
+# which the band CRCs then notice.  The section ends with the separator, so the band table still starts behind one.
+
 SEAL_SIGNATURE = b'L3CS'
 SEAL_VERSION = 1
 SEAL_VERSION_BANDS = 2
+SEAL_VERSION_PARITY = 3
 SEAL_BYTES = 24
 TABLE_SIGNATURE = b'L3CT'
+PARITY_SIGNATURE = b'L3CP'
 
 
 def seal_bands_bytes(n):
@@ -354,15 +366,27 @@ def seal_bands_bytes(n):
 
 
 class Seal(object):
-    """band_len, band_crcs: None for a version-1 seal; for a band seal the finest record's band length and the (3, n) uint32 band CRCs."""
+    """band_len, band_crcs: None for a version-1 seal; for a band seal the finest record's band length and the (3, n) uint32 band CRCs.
+    parity_group, parity: None but for a version-3 seal: G, and parity[c][g] the parity payload of group g of channel c (m = ceil(n / G)
+    groups per channel; bytes, or views of the file split_seal read them from)."""
 
-    def __init__(self, generation, frame_crc, model_id, band_len=None, band_crcs=None):
+    def __init__(self, generation, frame_crc, model_id, band_len=None, band_crcs=None, parity_group=None, parity=None):
         self.generation, self.frame_crc, self.model_id = int(generation), int(frame_crc), int(model_id)
         self.band_len = None if band_crcs is None else int(band_len)
         self.band_crcs = None if band_crcs is None else np.array(band_crcs, dtype=np.uint32).reshape(3, -1)
+        self.parity_group = None if parity is None else int(parity_group)
+        self.parity = None if parity is None else [list(row) for row in parity]
+
+    @property
+    def parity_groups(self):
+        """m, the parity streams per channel; 0 without parity."""
+        return 0 if self.parity is None else len(self.parity[0])
 
     def _key(self):
-        return (self.generation, self.frame_crc, self.model_id, self.band_len, None if self.band_crcs is None else self.band_crcs.tobytes())
+        key = (self.generation, self.frame_crc, self.model_id, self.band_len, None if self.band_crcs is None else self.band_crcs.tobytes())
+        if self.parity is not None:
+            key += (self.parity_group, tuple(bytes(p) for row in self.parity for p in row))
+        return key
 
     def __eq__(self, other):
         return isinstance(other, Seal) and self._key() == other._key()
@@ -374,6 +398,8 @@ class Seal(object):
 
     def __repr__(self):
         bands = '' if self.band_crcs is None else ', band_len={}, band_crcs=<3 x {}>'.format(self.band_len, self.band_crcs.shape[1])
+        if self.parity is not None:
+            bands += ', parity_group={}, parity=<3 x {}>'.format(self.parity_group, self.parity_groups)
         return 'Seal(generation={}, frame_crc=0x{:08x}, model_id=0x{:016x}{})'.format(self.generation, self.frame_crc, self.model_id, bands)
 
 
@@ -440,6 +466,38 @@ class SalvageInfo(object):
         if not said:
             return 'not sealed: nothing to verify' if len(self.unverified) == self.n_files else 'seal: ok' + tail
         return 'salvaged: ' + '; '.join(said) + tail
+
+
+class RepairInfo(object):
+    """What Bitcoding.decode_repair returned for B files.  repaired: {file: [(channel, band), ...]} the band payloads of the finest record
+    that were rebuilt from the file's parity and whose band position then verified in all three channels: those pixels are the encoder's,
+    bit for bit.  rows: {file: (y0, y1) or None} their hull in rows of the UNPADDED image (band_rows).  salvage: the SalvageInfo of what
+    was left after the repair -- decode_salvage's own when nothing was repairable.  files: per file the healed file's bytes (the rebuilt
+    payloads spliced in at their framing offsets; the same length, parity section, table and seal), None where nothing was repaired.
+    rounds: the repair rounds that ran (0: no parity was uploaded, no XOR kernel launched)."""
+
+    def __init__(self, repaired, rows, salvage, files, rounds=0):
+        self.repaired, self.rows, self.salvage, self.files, self.rounds = repaired, rows, salvage, list(files), int(rounds)
+
+    def __repr__(self):
+        return 'RepairInfo(repaired={!r}, rows={!r}, rounds={}, healed files={}, salvage={!r})'.format(
+            self.repaired, self.rows, self.rounds, [i for i, f in enumerate(self.files) if f is not None], self.salvage)
+
+    def line(self):
+        """One line for people (l3c.py dec --repair)."""
+        if not self.repaired:
+            return self.salvage.line()
+        tag = (lambda i: 'file {}: '.format(i)) if self.salvage.n_files > 1 else (lambda i: '')
+        said = []
+        for i in sorted(self.repaired):
+            where = 'rows [{}, {})'.format(*self.rows[i]) if self.rows.get(i) else 'the padding rows'
+            k = len(self.repaired[i])
+            said.append('{}{} restored ({} payload{})'.format(tag(i), where, k, '' if k == 1 else 's'))
+        rest = self.salvage.line()
+        if self.salvage.concealed or self.salvage.lost:
+            return 'repaired: ' + '; '.join(said) + '; ' + rest
+        tail = rest[len('seal: ok'):] if rest.startswith('seal: ok') else ''        # (the unsealed files of a mixed batch)
+        return 'repaired: ' + '; '.join(said) + ', every row verified' + tail
 
 
 def _padding_bytes(body):
@@ -518,6 +576,12 @@ def combine_band_crcs(crcs, L, HW):
 def _finest_header(body):
     """(C, H, W, L) of the last scale record of a banded file, walked by the length fields alone (csrc/seal.h: finest_record); None where
     the records do not end exactly with the data.  The parsers above do the full job later; this is what a seal's table is checked against."""
+    found = _finest_record(body)
+    return None if found is None else found[0]
+
+
+def _finest_record(body):
+    """_finest_header's walk -> ((C, H, W, L), the position of the record's first length field), or None."""
     end, p, found = len(body), 14, None
     if end < 14 or not is_banded(body):
         return None
@@ -532,6 +596,7 @@ def _finest_header(body):
         n = n_bands(H * W, L)
         if n > MAX_BANDS:
             return None
+        first = p
         for _ in range(C * n):
             if end - p < 4:
                 return None
@@ -539,15 +604,72 @@ def _finest_header(body):
         if end - p < 4 or bytes(body[p:p + 4]) != _MAGIC_VALUE_SEP:
             return None
         p += 4
-        found = (C, H, W, L)
+        found = ((C, H, W, L), first)
     return found
 
 
-def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=None):
+def parity_groups(n, G):
+    """m = ceil(n / G): the parity streams per channel for n bands in groups of G; ValueError unless 1 <= G <= n."""
+    n, G = int(n), int(G)
+    if not 1 <= G <= n:
+        raise ValueError('parity: the group size must be in 1..n = {}, got {}'.format(n, G))
+    return -(-n // G)
+
+
+def band_parity(payloads, G):
+    """The parity payloads of ONE channel (the reference the kernels are tested against): payloads, the n band payloads of the channel
+    (bytes-like, any lengths), in groups of G -> the m = ceil(n / G) parity payloads as bytes; group g is the XOR of the bands
+    { j : j % m == g }, each zero-extended to the longest of them."""
+    n = len(payloads)
+    m = parity_groups(n, G)
+    res = []
+    for g in range(m):
+        members = [np.frombuffer(bytes(p), dtype=np.uint8) for p in payloads[g::m]]
+        acc = np.zeros(max(len(a) for a in members), dtype=np.uint8)
+        for a in members:
+            acc[:len(a)] ^= a
+        res.append(acc.tobytes())
+    return res
+
+
+def parity_section_bytes(plens):
+    """S of a parity section whose payload lengths are plens ((3, m))."""
+    plens = np.asarray(plens, dtype=np.int64).reshape(3, -1)
+    return 16 + 12 * plens.shape[1] + int(plens.sum())
+
+
+def _band_lengths_of_finest(body, first, C, n):
+    """The (C, n) length fields of the record whose first length field lies at `first` (as _finest_record found it)."""
+    lens, p = np.zeros((C, n), dtype=np.int64), first
+    for c in range(C):
+        for j in range(n):
+            lens[c, j], = struct.unpack_from('<I', body, p)
+            p += 4 + int(lens[c, j])
+    return lens
+
+
+def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=None, parity=None):
     """The seal bytes for the unsealed file `body` (its padding fields go into the check word): 24 bytes, or with band_crcs ((3, n) words)
-    and band_len (the finest record's) the band table and the version-2 seal, seal_bands_bytes(n) bytes."""
+    and band_len (the finest record's) the band table and the version-2 seal, seal_bands_bytes(n) bytes.
+    parity = (G, payloads) on top of a band seal, payloads[c][g] the parity payload of group g of channel c (band_parity per channel): the
+    parity section in front of the table and the version-3 seal."""
     import zlib
-    table = b''
+    table, section, checked = b'', b'', b''
+    if parity is not None:
+        if band_crcs is None:
+            raise ValueError('make_seal: parity needs a band seal (band_crcs and band_len)')
+        G, rows = parity
+        n = np.asarray(band_crcs).reshape(3, -1).shape[1]
+        m = parity_groups(n, G)
+        if len(rows) != 3 or any(len(row) != m for row in rows):
+            raise ValueError('make_seal: parity needs 3 x {} payloads for {} bands in groups of {}'.format(m, n, G))
+        rows = [[bytes(p) for p in row] for row in rows]
+        head = PARITY_SIGNATURE + struct.pack('<HH', int(G), m) + b''.join(struct.pack('<I', len(p)) for row in rows for p in row)
+        S = 16 + 12 * m + sum(len(p) for row in rows for p in row)
+        if S >= 1 << 32:
+            raise ValueError('make_seal: parity section of {} bytes'.format(S))
+        tail = struct.pack('<I', S) + _MAGIC_VALUE_SEP
+        section, checked = head + b''.join(p for row in rows for p in row) + tail, head + tail
     if band_crcs is not None:
         crcs = np.ascontiguousarray(np.asarray(band_crcs).astype(np.int64) & 0xffffffff, dtype='<u4').reshape(3, -1)
         n = crcs.shape[1]
@@ -557,8 +679,9 @@ def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=
             raise ValueError('make_seal: a band seal needs a banded file')
         T = 20 + 12 * n
         table = TABLE_SIGNATURE + struct.pack('<HHI', n, 0, int(band_len)) + crcs.tobytes() + struct.pack('<I', T) + _MAGIC_VALUE_SEP
-    head = SEAL_SIGNATURE + struct.pack('<BBHIQ', SEAL_VERSION_BANDS if table else SEAL_VERSION, 0, generation, frame_crc & 0xffffffff, model_id)
-    return table + head + struct.pack('<I', zlib.crc32(_padding_bytes(body) + table + head) & 0xffffffff)
+    version = SEAL_VERSION_PARITY if section else SEAL_VERSION_BANDS if table else SEAL_VERSION
+    head = SEAL_SIGNATURE + struct.pack('<BBHIQ', version, 0, generation, frame_crc & 0xffffffff, model_id)
+    return section + table + head + struct.pack('<I', zlib.crc32(_padding_bytes(body) + checked + table + head) & 0xffffffff)
 
 
 def split_seal(data, view=False):
@@ -573,19 +696,20 @@ def split_seal(data, view=False):
         return data, None
     end, s = len(data) - SEAL_BYTES, bytes(data[-SEAL_BYTES:])
     version, flags, generation, frame_crc, model_id, check = struct.unpack('<BBHIQI', s[4:])
-    if version not in (SEAL_VERSION, SEAL_VERSION_BANDS):
+    if version not in (SEAL_VERSION, SEAL_VERSION_BANDS, SEAL_VERSION_PARITY):
         raise ValueError('invalid file: seal of an unknown version')
-    table = b''
-    if version == SEAL_VERSION_BANDS:
+    table, checked, section_at, m = b'', b'', None, 0
+    if version != SEAL_VERSION:
         if not is_banded(data):
-            raise ValueError('invalid file: seal of an unknown version for a legacy file (version 2, the band seal, needs a banded file)')
+            raise ValueError('invalid file: seal of an unknown version for a legacy file (version {}, needs a banded file)'.format(
+                '2, the band seal' if version == SEAL_VERSION_BANDS else '3, the parity seal'))
         if end < 20 + 12 + 4:
-            raise ValueError('invalid file: seal of an unknown version: 2 needs a band table, and the file is too short for one')
+            raise ValueError('invalid file: seal of an unknown version: {} needs a band table, and the file is too short for one'.format(version))
         T, = struct.unpack('<I', bytes(data[end - 8:end - 4]))
         n = (T - 20) // 12
         if T < 20 or (T - 20) % 12 or not 1 <= n <= MAX_BANDS:
-            raise ValueError('invalid file: seal of an unknown version: 2 needs a band table, and its length field is not 20 + 12 n with '
-                             '1 <= n <= 1024')
+            raise ValueError('invalid file: seal of an unknown version: {} needs a band table, and its length field is not 20 + 12 n with '
+                             '1 <= n <= 1024'.format(version))
         if T > end - 14 - 4 or bytes(data[end - T - 4:end - T]) != _MAGIC_VALUE_SEP:
             raise ValueError("invalid file: seal band table does not start behind the file's last scale separator")
         table, end = bytes(data[end - T:end]), end - T
@@ -593,23 +717,50 @@ def split_seal(data, view=False):
             raise ValueError("invalid file: seal band table without its 'L3CT' signature")
         if table[6:8] != b'\0\0':
             raise ValueError('invalid file: seal band table with a non-zero reserved field')
+    if version == SEAL_VERSION_PARITY:
+        S, = struct.unpack('<I', bytes(data[end - 8:end - 4]))           # (the separator at [end - 4, end) is the one the table starts behind)
+        if S < 16 + 12 or S > end - 14 - 4 or bytes(data[end - S - 4:end - S]) != _MAGIC_VALUE_SEP:
+            raise ValueError("invalid file: seal parity section does not start behind the file's last scale separator")
+        section_at, end = end - S, end - S
+        if bytes(data[section_at:section_at + 4]) != PARITY_SIGNATURE:
+            raise ValueError("invalid file: seal parity section without its 'L3CP' signature")
+        G, m = struct.unpack('<HH', bytes(data[section_at + 4:section_at + 8]))
+        if m < 1 or 16 + 12 * m > S:
+            raise ValueError('invalid file: seal parity section is too short for its {} x 3 length fields'.format(m))
+        plen = np.frombuffer(bytes(data[section_at + 8:section_at + 8 + 12 * m]), dtype='<u4').astype(np.int64).reshape(3, m)
+        if S != 16 + 12 * m + int(plen.sum()):
+            raise ValueError('invalid file: seal parity section length is not 16 + 12 m + the sum of its payload lengths')
+        checked = bytes(data[section_at:section_at + 8 + 12 * m]) + bytes(data[section_at + S - 8:section_at + S])
     if flags:
         raise ValueError('invalid file: seal with non-zero flags')
     body = (memoryview(data) if view else data)[:end]
-    if check != zlib.crc32(_padding_bytes(body) + table + s[:20]) & 0xffffffff:
+    if check != zlib.crc32(_padding_bytes(body) + checked + table + s[:20]) & 0xffffffff:
         raise ValueError('invalid file: seal check word does not match (damaged seal or padding fields)')
     if not table:
         return body, Seal(generation, frame_crc, model_id)
     n_stated, _, L = struct.unpack('<HHI', table[4:12])
     if n_stated != n:
         raise ValueError('invalid file: seal band table states another band count than its length')
-    finest = _finest_header(body)
+    finest, first = _finest_record(body) or (None, None)
     if finest is None or finest[3] != L or n_bands(finest[1] * finest[2], L) != n:
         raise ValueError("invalid file: seal band table does not match the bands of the file's finest scale record")
     crcs = np.frombuffer(table[12:12 + 12 * n], dtype='<u4').reshape(3, n)
     if combine_band_crcs(crcs, L, finest[1] * finest[2]) != frame_crc:
         raise ValueError('invalid file: seal frame CRC is not the combination of its band CRCs')
-    return body, Seal(generation, frame_crc, model_id, L, crcs)
+    if section_at is None:
+        return body, Seal(generation, frame_crc, model_id, L, crcs)
+    if finest[0] != 3 or not 1 <= G <= n or m != -(-n // G):
+        raise ValueError("invalid file: seal parity section does not match the bands of the file's finest scale record")
+    lens = _band_lengths_of_finest(body, first, 3, n)
+    if any(int(plen[c, g]) != int(lens[c, g::m].max()) for c in range(3) for g in range(m)):
+        raise ValueError("invalid file: seal parity section states a payload length that is not its longest member's")
+    view, at, rows = memoryview(data), section_at + 8 + 12 * m, []
+    for c in range(3):
+        rows.append([])
+        for g in range(m):
+            rows[c].append(view[at:at + int(plen[c, g])])
+            at += int(plen[c, g])
+    return body, Seal(generation, frame_crc, model_id, L, crcs, G, rows)
 
 
 def band_rows(j, L, frame_hw, padding):

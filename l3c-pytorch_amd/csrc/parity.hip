@@ -1,0 +1,186 @@
+// parity.hip -- parity bands (include/l3c_hip.h: l3c_band_parity, l3c_u8_xor_spans; the format is csrc/seal.h, version 3).
+//
+// Both kernels are streaming XORs over byte streams of different lengths and share one fold: a block owns a TILE of 4096 bytes of ONE
+// output stream (grid.y = the stream), a thread 16 bytes of it, and walks the stream's members, eight at a time (fold_members): one 16-byte
+// load per member where the member starts 16-byte aligned and the 16 bytes lie in front of its 4-byte-rounded end, dword loads otherwise (the
+// coder's rows are only guaranteed a stride that is a multiple of 4).  Nothing at or behind a member's 4-byte-rounded end is read; the bytes
+// of its last dword behind its length are masked to zero (the coder's slots hold garbage there), so every member counts as zero-extended.
+// A wave reads 1 KiB of a member per step; the members of a group are independent loads, issued eight deep.
+// Stores are 16 bytes where the slot is 16-byte aligned and the 16 bytes lie inside what the call writes, dwords otherwise; nothing outside
+// that range is written.  No atomics, no LDS, no allocation, no host synchronisation.
+#include "l3c_common.h"
+#include "parity_plan.h"
+
+namespace {
+
+using namespace l3c_parity;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+struct Member {
+    const uint8_t *p;      // 4-byte aligned
+    int64_t len;           // bytes that count; the rest of the last dword is masked
+};
+
+// bytes [off, off + 16) of a member as four dwords, zero at and behind its 4-byte-rounded end (the bytes of its last dword behind `len`
+// still as they lie in memory: mask16); off % 16 == 0
+__device__ __forceinline__ u32x4 load16(const Member &m, int64_t off) {
+    const int64_t end4 = (m.len + 3) & ~(int64_t)3;
+    u32x4 q = {0u, 0u, 0u, 0u};
+    if (off + 16 <= end4 && (reinterpret_cast<uintptr_t>(m.p) & 15) == 0) {
+        q = *reinterpret_cast<const u32x4 *>(m.p + off);
+    } else if (off < end4) {
+        if (off < end4) q.x = *reinterpret_cast<const uint32_t *>(m.p + off);
+        if (off + 4 < end4) q.y = *reinterpret_cast<const uint32_t *>(m.p + off + 4);
+        if (off + 8 < end4) q.z = *reinterpret_cast<const uint32_t *>(m.p + off + 8);
+        if (off + 12 < end4) q.w = *reinterpret_cast<const uint32_t *>(m.p + off + 12);
+    }
+    return q;
+}
+
+// the dwords of load16 with the bytes at and behind `len` cleared
+__device__ __forceinline__ u32x4 mask16(u32x4 q, int64_t len, int64_t off) {
+    uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int64_t keep = len - (off + 4 * i);                  // bytes of dword i that belong to the member
+        if (keep < 4) w[i] = keep <= 0 ? 0u : w[i] & (0xFFFFFFFFu >> (8 * (4 - (int)keep)));
+    }
+    return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// The XOR over members 0 .. count - 1 (member(k) -> Member, uniform over the block) of their bytes [off, off + 16).  DEPTH members at a time:
+// their descriptors are read first, then their loads issued, then folded -- two memory latencies per DEPTH members, not per member; a
+// group's members are independent streams, so that is all the latency there is to hide.
+constexpr int DEPTH = 8;
+template <typename F>
+__device__ __forceinline__ u32x4 fold_members(int64_t count, int64_t off, F member) {
+    u32x4 acc = {0u, 0u, 0u, 0u};
+    for (int64_t k = 0; k < count; k += DEPTH) {
+        Member m[DEPTH];
+        u32x4 q[DEPTH];
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) m[u] = k + u < count ? member(k + u) : Member{nullptr, 0};
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) q[u] = load16(m[u], off);
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) acc ^= mask16(q[u], m[u].len, off);
+    }
+    return acc;
+}
+
+// bytes [off, off + 16) of the slot at dst, as far as they lie in front of `end` (a multiple of 4); off % 16 == 0
+__device__ __forceinline__ void store16(uint8_t *dst, int64_t off, int64_t end, u32x4 v) {
+    if (off + 16 <= end && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        *reinterpret_cast<u32x4 *>(dst + off) = v;
+        return;
+    }
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (off + 4 * i < end) *reinterpret_cast<uint32_t *>(dst + off + 4 * i) = w[i];
+}
+
+// band j of stream s (= b 3 + c) of the finest record's coder output
+__device__ __forceinline__ const uint8_t *band_row(const l3c_banded_scale &sc, int64_t n, int64_t s, int64_t j) {
+    return j + 1 < n ? sc.out_full + (s * (n - 1) + j) * sc.stride_full : sc.out_last + s * sc.stride_last;
+}
+__device__ __forceinline__ uint32_t band_nbytes(const l3c_banded_scale &sc, int64_t n, int64_t s, int64_t j) {
+    return j + 1 < n ? sc.nbytes_full[s * (n - 1) + j] : sc.nbytes_last[s];
+}
+
+// grid (tiles of the longest possible stream, B 3 m): block (x, y) folds tile x of parity stream y = s m + g, the bands j = g, g + m, .. < n
+__global__ __launch_bounds__(THREADS) void band_parity_kernel(l3c_banded_scale sc, int64_t n, int64_t m, uint8_t *__restrict__ parity,
+                                                             int64_t parity_stride, uint32_t *__restrict__ parity_nbytes) {
+    const int64_t y = blockIdx.y, s = y / m, g = y - s * m;
+    const int64_t count = (n - g + m - 1) / m;
+    uint32_t plen = 0;
+    bool overrun = false;
+    for (int64_t k = 0; k < count; ++k) {                          // uniform over the block: scalar loads, independent of each other
+        const uint32_t len = band_nbytes(sc, n, s, g + k * m);
+        overrun |= len == L3C_AC_OVERRUN;
+        plen = len > plen ? len : plen;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) parity_nbytes[y] = overrun ? L3C_AC_OVERRUN : plen;
+    if (overrun) return;
+    const int64_t end4 = ((int64_t)plen + 3) & ~(int64_t)3;
+    const int64_t off = (int64_t)blockIdx.x * TILE_BYTES + 16 * threadIdx.x;
+    if (off >= end4) return;
+    const u32x4 acc = fold_members(count, off, [&](int64_t k) {
+        const int64_t j = g + k * m;
+        return Member{band_row(sc, n, s, j), (int64_t)band_nbytes(sc, n, s, j)};
+    });
+    store16(parity + y * parity_stride, off, end4, acc);
+}
+
+// grid (tiles of the longest slot, n_groups): block (x, g) folds tile x of output slot g
+__global__ __launch_bounds__(THREADS) void u8_xor_spans_kernel(const uint8_t *__restrict__ data, const l3c_u8_span *__restrict__ spans,
+                                                              const int64_t *__restrict__ group_first,
+                                                              const l3c_u8_span *__restrict__ out_spans, uint8_t *__restrict__ out) {
+    const int64_t g = blockIdx.y;
+    const l3c_u8_span slot = out_spans[g];
+    const int64_t end = slot_bytes(slot.bytes);                    // the payload rounded up to 4, then 4 zero bytes
+    const int64_t off = (int64_t)blockIdx.x * TILE_BYTES + 16 * threadIdx.x;
+    if (off >= end) return;
+    const int64_t k0 = group_first[g];
+    const u32x4 acc = fold_members(group_first[g + 1] - k0, off, [&](int64_t k) {
+        const l3c_u8_span src = spans[k0 + k];
+        return Member{data + src.offset, src.bytes < slot.bytes ? src.bytes : slot.bytes};
+    });
+    store16(out + slot.offset, off, end, acc);
+}
+
+}  // namespace
+
+extern "C" {
+
+int l3c_band_parity_groups(int n, int G) {
+    L3C_REQUIRE(n >= 1 && n <= 1024 && G >= 1 && G <= n, "n must be in 1..1024 and G in 1..n");
+    return (n + G - 1) / G;
+}
+
+int l3c_band_parity(const l3c_banded_scale *scale_host, int64_t B, int G, uint8_t *parity, int64_t parity_stride, uint32_t *parity_nbytes,
+                    l3c_stream_t stream) {
+    L3C_REQUIRE(scale_host && parity && parity_nbytes, "null pointer");
+    const l3c_banded_scale sc = *scale_host;
+    L3C_REQUIRE(sc.C == 3 && sc.H > 0 && sc.W > 0, "the parity covers the finest record: C must be 3, H and W positive");
+    L3C_REQUIRE(sc.band_len > 0 && sc.band_len % 64 == 0, "band_len must be a positive multiple of 64");
+    const int64_t hw = (int64_t)sc.H * sc.W, n = (hw + sc.band_len - 1) / sc.band_len;
+    L3C_REQUIRE(n <= 1024, "more than 1024 bands per channel");
+    L3C_REQUIRE(G >= 1 && G <= n, "G must be in 1..n");
+    const int64_t m = (n + G - 1) / G;
+    L3C_REQUIRE(B >= 1 && B <= MAX_STREAMS / (3 * m), "bad batch size: B * 3 * m must be in 1..65535");
+    L3C_REQUIRE(sc.out_last && sc.nbytes_last && (n == 1 || (sc.out_full && sc.nbytes_full)), "null pointer in the scale");
+    L3C_REQUIRE(sc.stride_last > 0 && sc.stride_last % 4 == 0 && (n == 1 || (sc.stride_full > 0 && sc.stride_full % 4 == 0)),
+                "the coder strides must be positive multiples of 4");
+    const int64_t longest = n > 1 && sc.stride_full > sc.stride_last ? sc.stride_full : sc.stride_last;
+    L3C_REQUIRE(parity_stride % 16 == 0 && parity_stride >= longest, "parity_stride must be a multiple of 16 and at least the coder strides");
+    L3C_REQUIRE(parity_stride <= INT64_MAX / MAX_STREAMS && tiles_of(longest) <= 0x7fffffff, "stride out of range");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(sc.out_last) & 3) == 0 && (reinterpret_cast<uintptr_t>(sc.out_full) & 3) == 0 &&
+                    (reinterpret_cast<uintptr_t>(sc.nbytes_last) & 3) == 0 && (reinterpret_cast<uintptr_t>(sc.nbytes_full) & 3) == 0 &&
+                    (reinterpret_cast<uintptr_t>(parity_nbytes) & 3) == 0,
+                "the coder outputs and the length arrays must be 4-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(parity) & 15) == 0, "parity must be 16-byte aligned");
+    hipLaunchKernelGGL(band_parity_kernel, dim3((unsigned)tiles_of(longest), (unsigned)(B * 3 * m)), dim3(THREADS), 0, l3c::as_stream(stream), sc, n, m,
+                       parity, parity_stride, parity_nbytes);
+    return l3c::check_launch("band_parity_kernel");
+}
+
+int l3c_u8_xor_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, int64_t n_spans,
+                     const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups, const l3c_u8_span *out_spans_host,
+                     const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream) {
+    L3C_REQUIRE(n_groups >= 0, "n_groups must not be negative");
+    if (n_groups == 0) return L3C_OK;
+    const int64_t tiles = check_xor_spans(spans_host, n_spans, group_first_host, n_groups, out_spans_host, data_bytes, out_bytes, l3c::error_buffer(), 512);
+    if (tiles < 0) return (int)tiles;
+    L3C_REQUIRE(out && group_first && out_spans && (n_spans == 0 || (data && spans)), "null pointer");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(data) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0, "data and out must be 4-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(spans) & 7) == 0 && (reinterpret_cast<uintptr_t>(group_first) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(out_spans) & 7) == 0,
+                "spans, group_first and out_spans (the device tables) must be 8-byte aligned");
+    L3C_REQUIRE(n_spans == 0 || out + out_bytes <= data || data + data_bytes <= out, "out must not overlap data");
+    hipLaunchKernelGGL(u8_xor_spans_kernel, dim3((unsigned)tiles, (unsigned)n_groups), dim3(THREADS), 0, l3c::as_stream(stream), data, spans,
+                       group_first, out_spans, out);
+    return l3c::check_launch("u8_xor_spans_kernel");
+}
+}

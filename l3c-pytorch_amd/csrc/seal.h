@@ -19,6 +19,14 @@
 // the padded planar frame.  The table ends with the separator, so the recognition rule above holds for both versions, and T lies at
 // file[-32:-28]: the table is found from the end.  check = CRC-32 of the 8 padding bytes, the whole table, seal bytes 0..19.  The frame CRC
 // stays in the seal and must be the combination of the band CRCs (crc32_combine's arithmetic, crc_spans.h).
+//
+// Version 3, PARITY BANDS: body | PARITY SECTION | BAND TABLE | the 24 seal bytes with version = 3.  The section, S = 16 + 12 m + sum(plen):
+//
+//     0 'L3CP' | 4 u16 G | 6 u16 m | 8 u32 plen[3][m] (channel-major) | 8 + 12 m the 3 m parity payloads, (c, g) order | S - 8 u32 S | S - 4 separator
+//
+// m = ceil(n / G); group g of channel c holds the bands { j : j % m == g }; its payload is the XOR of the members' payloads, each
+// zero-extended to plen[c][g], the longest member's byte count.  check = CRC-32 of the 8 padding bytes, section bytes [0, 8 + 12 m), the
+// section's last 8 bytes, the band table, seal bytes 0..19: the parity payloads are NOT under it.
 #ifndef L3C_SEAL_H_
 #define L3C_SEAL_H_
 
@@ -31,8 +39,9 @@
 
 namespace l3c_sealing {
 
-constexpr int VERSION = 1, VERSION_BANDS = 2, MAX_BANDS = 1024;
+constexpr int VERSION = 1, VERSION_BANDS = 2, VERSION_PARITY = 3, MAX_BANDS = 1024;
 constexpr uint8_t TABLE_SIGNATURE[4] = {'L', '3', 'C', 'T'};
+constexpr uint8_t PARITY_SIGNATURE[4] = {'L', '3', 'C', 'P'};
 constexpr uint8_t SIGNATURE[4] = {'L', '3', 'C', 'S'};
 constexpr uint8_t SEPARATOR[4] = {0x46, 0xE2, 0x84, 0x92};
 constexpr uint8_t BANDED_SIGNATURE[4] = {'L', '3', 'C', 'B'};
@@ -62,6 +71,15 @@ inline int fail(char *err, size_t cap, const char *what) {
     return L3C_ERR_INVALID_ARG;
 }
 
+// `what` is a format with one %d
+inline int fail_d(char *err, size_t cap, const char *what, int d) {
+    if (err && cap) {
+        const int at = snprintf(err, cap, "invalid file: seal ");
+        if (at > 0 && (size_t)at < cap) snprintf(err + at, cap - (size_t)at, what, d);
+    }
+    return L3C_ERR_INVALID_ARG;
+}
+
 // seal bytes 0..19 of `s`, then the check word over padding8 | those bytes
 inline void write(const l3c_seal &s, const uint8_t *padding8, uint8_t *dst) {
     memcpy(dst, SIGNATURE, 4);
@@ -88,7 +106,8 @@ inline uint32_t combine_bands(const uint8_t *crc, int64_t n, uint32_t band_len, 
 
 // The finest (last) scale record of the banded file in [0, body): its H W, band length and bands per channel, walked by the length fields.
 // false: not a banded file whose records end exactly at `body`.
-inline bool finest_record(const uint8_t *f, int64_t body, int64_t *hw_out, uint32_t *band_len_out, int64_t *n_out) {
+inline bool finest_record(const uint8_t *f, int64_t body, int64_t *hw_out, uint32_t *band_len_out, int64_t *n_out, int64_t *C_out = nullptr,
+                          int64_t *first_len_at_out = nullptr) {
     if (body < 14 || memcmp(f, BANDED_SIGNATURE, 4) != 0) return false;
     int64_t p = 14;
     bool found = false;
@@ -99,6 +118,8 @@ inline bool finest_record(const uint8_t *f, int64_t body, int64_t *hw_out, uint3
         if (C == 0 || hw == 0 || L == 0 || L % 64) return false;
         const int64_t n = (hw + L - 1) / L;
         if (n > MAX_BANDS) return false;
+        if (C_out) *C_out = C;
+        if (first_len_at_out) *first_len_at_out = p;
         for (int64_t k = 0; k < C * n; ++k) {
             if (body - p < 4) return false;
             const int64_t len = (int64_t)get(f + p, 4);
@@ -135,46 +156,126 @@ inline void write_bands(const l3c_seal &s, const uint8_t *padding8, const uint8_
     put(seal + 20, crc32(crc32(0, padding8, 8), dst, T + 20), 4);
 }
 
+// parity section + band table + seal of a version-3 file: section_bytes(m, payload bytes) + table_bytes(n) + L3C_SEAL_BYTES bytes behind the body
+constexpr int64_t section_bytes(int64_t m, int64_t payload_bytes) { return 16 + 12 * m + payload_bytes; }
+
+// The section for m groups per channel (plen: [3][m] host words, payloads: the 3 m parity payloads back to back, (c, g) order), the band
+// table and the seal of version 3 behind it, at dst.  dst must not overlap band_crc or payloads.
+inline void write_parity(const l3c_seal &s, const uint8_t *padding8, const uint8_t *band_crc, int n, uint32_t band_len, int G, int m,
+                         const uint32_t *plen, const uint8_t *payloads, uint8_t *dst) {
+    int64_t sum = 0;
+    for (int i = 0; i < 3 * m; ++i) sum += plen[i];
+    const int64_t S = section_bytes(m, sum), T = table_bytes(n), head = 8 + 12 * (int64_t)m;
+    memcpy(dst, PARITY_SIGNATURE, 4);
+    put(dst + 4, (uint64_t)G, 2);
+    put(dst + 6, (uint64_t)m, 2);
+    for (int i = 0; i < 3 * m; ++i) put(dst + 8 + 4 * i, plen[i], 4);
+    if (sum) memcpy(dst + head, payloads, (size_t)sum);
+    put(dst + S - 8, (uint64_t)S, 4);
+    memcpy(dst + S - 4, SEPARATOR, 4);
+    uint8_t *t = dst + S;
+    memcpy(t, TABLE_SIGNATURE, 4);
+    put(t + 4, (uint64_t)n, 2);
+    put(t + 6, 0, 2);
+    put(t + 8, band_len, 4);
+    memmove(t + 12, band_crc, 12 * (size_t)n);
+    put(t + 12 + 12 * n, (uint64_t)T, 4);
+    memcpy(t + 16 + 12 * n, SEPARATOR, 4);
+    uint8_t *seal = t + T;
+    memcpy(seal, SIGNATURE, 4);
+    seal[4] = VERSION_PARITY;
+    seal[5] = 0;
+    put(seal + 6, s.generation, 2);
+    put(seal + 8, s.frame_crc, 4);
+    put(seal + 12, s.model_id, 8);
+    put(seal + 20, crc32(crc32(crc32(crc32(0, padding8, 8), dst, head), dst + S - 8, 8), t, T + 20), 4);
+}
+
 // 1: sealed, 0: unsealed, L3C_ERR_INVALID_ARG (message in err): a recognised seal that is damaged.  *body_bytes_out: the bytes in front of
-// the seal, in front of the band table where the seal has one.  bands_out (may be null): n = 0 for a version-1 seal.
-inline int find_bands(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out, char *err,
-                      size_t cap) {
+// the seal, in front of the band table where the seal has one, in front of the parity section where it has one.  bands_out (may be null):
+// n = 0 for a version-1 seal.  parity_out (may be null): m = 0 unless the seal is of version 3.
+inline int find_parity(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
+                       l3c_seal_parity *parity_out, char *err, size_t cap) {
     if (body_bytes_out) *body_bytes_out = file_bytes;
     if (bands_out) bands_out->n = 0, bands_out->band_len = 0, bands_out->crc = nullptr;
+    if (parity_out) parity_out->G = 0, parity_out->m = 0, parity_out->plen = nullptr, parity_out->payloads = nullptr, parity_out->payload_bytes = 0;
     if (file_bytes < L3C_SEAL_BYTES + 4) return 0;
     const uint8_t *s = file + file_bytes - L3C_SEAL_BYTES;
     if (memcmp(s, SIGNATURE, 4) != 0 || memcmp(s - 4, SEPARATOR, 4) != 0) return 0;
     int64_t body = file_bytes - L3C_SEAL_BYTES;
     const bool banded = memcmp(file, BANDED_SIGNATURE, 4) == 0;
     const int64_t padding_at = banded ? 6 : 0;
-    if (s[4] != VERSION && s[4] != VERSION_BANDS) return fail(err, cap, "of an unknown version");
-    int64_t T = 0, n = 0;
-    if (s[4] == VERSION_BANDS) {
-        if (!banded) return fail(err, cap, "of an unknown version for a legacy file (version 2, the band seal, needs a banded file)");
-        if (body < 20 + 12 + 4) return fail(err, cap, "of an unknown version: 2 needs a band table, and the file is too short for one");
+    const int version = s[4];
+    if (version != VERSION && version != VERSION_BANDS && version != VERSION_PARITY) return fail(err, cap, "of an unknown version");
+    int64_t T = 0, n = 0, S = 0, m = 0, G = 0, table_at = 0;
+    if (version != VERSION) {
+        if (!banded)
+            return fail(err, cap, version == VERSION_BANDS ? "of an unknown version for a legacy file (version 2, the band seal, needs a banded file)"
+                                                           : "of an unknown version for a legacy file (version 3, the parity seal, needs a banded file)");
+        if (body < 20 + 12 + 4) return fail_d(err, cap, "of an unknown version: %d needs a band table, and the file is too short for one", version);
         T = (int64_t)get(s - 8, 4);
         n = (T - 20) / 12;
         if (T < 20 || (T - 20) % 12 != 0 || n < 1 || n > MAX_BANDS)
-            return fail(err, cap, "of an unknown version: 2 needs a band table, and its length field is not 20 + 12 n with 1 <= n <= 1024");
+            return fail_d(err, cap, "of an unknown version: %d needs a band table, and its length field is not 20 + 12 n with 1 <= n <= 1024", version);
         if (T > body - 14 - 4 || memcmp(file + body - T - 4, SEPARATOR, 4) != 0)
             return fail(err, cap, "band table does not start behind the file's last scale separator");
         body -= T;
+        table_at = body;
         const uint8_t *t = file + body;
         if (memcmp(t, TABLE_SIGNATURE, 4) != 0) return fail(err, cap, "band table without its 'L3CT' signature");
         if (get(t + 6, 2) != 0) return fail(err, cap, "band table with a non-zero reserved field");
     }
+    if (version == VERSION_PARITY) {
+        S = (int64_t)get(file + body - 8, 4);                  // (the separator at [body - 4, body) is the one the table starts behind)
+        if (S < 16 + 12 || S > body - 14 - 4 || memcmp(file + body - S - 4, SEPARATOR, 4) != 0)
+            return fail(err, cap, "parity section does not start behind the file's last scale separator");
+        body -= S;
+        const uint8_t *p = file + body;
+        if (memcmp(p, PARITY_SIGNATURE, 4) != 0) return fail(err, cap, "parity section without its 'L3CP' signature");
+        G = (int64_t)get(p + 4, 2), m = (int64_t)get(p + 6, 2);
+        if (m < 1 || 16 + 12 * m > S) return fail_d(err, cap, "parity section is too short for its %d x 3 length fields", (int)m);
+        int64_t sum = 0;
+        for (int64_t i = 0; i < 3 * m; ++i) sum += (int64_t)get(p + 8 + 4 * i, 4);
+        if (S != section_bytes(m, sum)) return fail(err, cap, "parity section length is not 16 + 12 m + the sum of its payload lengths");
+    }
     if (s[5] != 0) return fail(err, cap, "with non-zero flags");
     if (padding_at + 8 > body) return fail(err, cap, "on a file too short for its padding fields");
-    if (get(s + 20, 4) != crc32(crc32(crc32(0, file + padding_at, 8), file + body, T), s, 20))
-        return fail(err, cap, "check word does not match (damaged seal or padding fields)");
+    {
+        uint32_t c = crc32(0, file + padding_at, 8);
+        if (S) c = crc32(crc32(c, file + body, 8 + 12 * m), file + body + S - 8, 8);
+        if (get(s + 20, 4) != crc32(crc32(c, file + table_at, T), s, 20))
+            return fail(err, cap, "check word does not match (damaged seal or padding fields)");
+    }
     if (T) {
-        const uint8_t *t = file + body;
-        int64_t hw = 0, rec_n = 0;
+        const uint8_t *t = file + table_at;
+        int64_t hw = 0, rec_n = 0, rec_C = 0, first = 0;
         uint32_t rec_len = 0;
         if ((int64_t)get(t + 4, 2) != n) return fail(err, cap, "band table states another band count than its length");
-        if (!finest_record(file, body, &hw, &rec_len, &rec_n) || rec_n != n || rec_len != (uint32_t)get(t + 8, 4))
+        if (!finest_record(file, body, &hw, &rec_len, &rec_n, &rec_C, &first) || rec_n != n || rec_len != (uint32_t)get(t + 8, 4))
             return fail(err, cap, "band table does not match the bands of the file's finest scale record");
         if ((uint32_t)get(s + 8, 4) != combine_bands(t + 12, n, rec_len, hw)) return fail(err, cap, "frame CRC is not the combination of its band CRCs");
+        if (S) {
+            const uint8_t *p = file + body;
+            if (rec_C != 3 || G < 1 || G > n || m != (n + G - 1) / G)
+                return fail(err, cap, "parity section does not match the bands of the file's finest scale record");
+            // every plen[c][g] against the length fields of its members, band j of channel c in group j % m (finest_record has walked them)
+            int64_t at = first;
+            for (int64_t c = 0; c < 3; ++c) {
+                uint32_t longest[MAX_BANDS];
+                for (int64_t g = 0; g < m; ++g) longest[g] = 0;
+                for (int64_t j = 0; j < n; ++j) {
+                    const uint32_t len = (uint32_t)get(file + at, 4);
+                    at += 4 + (int64_t)len;
+                    if (len > longest[j % m]) longest[j % m] = len;
+                }
+                for (int64_t g = 0; g < m; ++g)
+                    if ((uint32_t)get(p + 8 + 4 * (c * m + g), 4) != longest[g])
+                        return fail(err, cap, "parity section states a payload length that is not its longest member's");
+            }
+            if (parity_out)
+                parity_out->G = (int32_t)G, parity_out->m = (int32_t)m, parity_out->plen = p + 8, parity_out->payloads = p + 8 + 12 * m,
+                parity_out->payload_bytes = S - 16 - 12 * m;
+        }
         if (bands_out) bands_out->n = (int32_t)n, bands_out->band_len = rec_len, bands_out->crc = t + 12;
     }
     if (body_bytes_out) *body_bytes_out = body;
@@ -186,8 +287,13 @@ inline int find_bands(const uint8_t *file, int64_t file_bytes, int64_t *body_byt
     return 1;
 }
 
+inline int find_bands(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out, char *err,
+                      size_t cap) {
+    return find_parity(file, file_bytes, body_bytes_out, seal_out, bands_out, nullptr, err, cap);
+}
+
 inline int find(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, char *err, size_t cap) {
-    return find_bands(file, file_bytes, body_bytes_out, seal_out, nullptr, err, cap);
+    return find_parity(file, file_bytes, body_bytes_out, seal_out, nullptr, nullptr, err, cap);
 }
 
 }  // namespace l3c_sealing

@@ -923,3 +923,58 @@ def seal_append_bands(files, file_bytes, frame_crc, band_crc, band_len, padding=
         raise ValueError('seal_append_bands: band_crc must be a contiguous (B, 3, n) tensor, got {}'.format(tuple(band_crc.shape)))
     call('l3c_seal_append_bands', ptr(files, torch.uint8), stride, ptr(file_bytes, torch.int64), ptr(frame_crc, torch.int32),
          ptr(band_crc, torch.int32), band_crc.shape[2], int(band_len), ptr(padding, torch.int16), int(model_id), B, stream())
+
+
+def banded_scale_desc(C, H, W, L, groups):
+    """l3c_banded_scale of one record of a banded encode: groups = [(out, nbytes) of the full bands (absent when n == 1), of the last bands],
+    the results of ac_encode_groups on band_intervals."""
+    (out_f, nb_f), (out_l, nb_l) = (groups[0] if len(groups) == 2 else (None, None)), groups[-1]
+    return _lib.BandedScale(ptr(out_f, torch.uint8), ptr(nb_f, torch.int32), out_f.shape[1] if out_f is not None else 0,
+                            ptr(out_l, torch.uint8), ptr(nb_l, torch.int32), out_l.shape[1], C, H, W, L)
+
+
+def band_parity(B, H, W, L, groups, G, out=None):
+    """l3c_band_parity: the XOR parity of the finest record's band payloads (3 channels; `groups` as banded_scale_desc takes them), bands
+    { j : j % m == g } of a channel in group g, m = ceil(n / G) -> (parity uint8 (B, 3, m, stride), nbytes int32 (B, 3, m)) on the device:
+    bytes [0, nbytes) of a slot are the parity payload (the bytes behind its 4-byte-rounded length are not written), nbytes -1 where a
+    member overran.  out: (parity, nbytes) tensors of the caller's instead of new ones.  No host synchronisation."""
+    n = -(-(H * W) // L)
+    m = _lib.load().l3c_band_parity_groups(n, int(G))
+    _lib.check(min(m, 0))
+    dev = groups[-1][0].device
+    if out is None:
+        stride = -(-max(g[0].shape[1] for g in groups) // 16) * 16
+        out = (torch.empty((B, 3, m, stride), dtype=torch.uint8, device=dev), torch.empty((B, 3, m), dtype=torch.int32, device=dev))
+    parity, nbytes = out
+    if tuple(parity.shape[:3]) != (B, 3, m) or tuple(nbytes.shape) != (B, 3, m):
+        raise ValueError('band_parity: out must be (B, 3, m, stride) and (B, 3, m) with m = {}, got {} and {}'.format(
+            m, tuple(parity.shape), tuple(nbytes.shape)))
+    stride = parity.shape[3]
+    desc = banded_scale_desc(3, H, W, L, groups)
+    call('l3c_band_parity', ctypes.byref(desc), B, int(G), ptr(parity, torch.uint8), stride, ptr(nbytes, torch.int32), stream())
+    return parity, nbytes
+
+
+def u8_xor_spans(data, offsets, lengths, group_first, out, out_offsets, out_lengths):
+    """l3c_u8_xor_spans: slot g of `out` -- bytes [out_offsets[g], ...) -- receives the XOR of the spans data[offsets[k]:offsets[k] +
+    lengths[k]], k in [group_first[g], group_first[g + 1]), each cut or zero-extended to out_lengths[g], then zero bytes up to
+    ((out_lengths[g] + 3) // 4) * 4 + 4.  data, out: contiguous uint8 device tensors that do not overlap; the tables: host integer sequences
+    (offsets multiples of 4), checked on the host, uploaded through upload_small.  No groups: nothing is launched.  No host synchronisation."""
+    group_first = np.ascontiguousarray(group_first, dtype=np.int64)
+    n_groups = group_first.shape[0] - 1
+    if n_groups <= 0:
+        return out
+    spans = np.zeros(len(offsets), dtype=SPAN_DTYPE)
+    spans['offset'], spans['bytes'] = offsets, lengths
+    slots = np.zeros(n_groups, dtype=SPAN_DTYPE)
+    slots['offset'], slots['bytes'] = out_offsets, out_lengths
+    if data.dtype != torch.uint8 or out.dtype != torch.uint8 or not data.is_contiguous() or not out.is_contiguous():
+        raise ValueError('u8_xor_spans: data and out must be contiguous uint8 tensors')
+    # ONE upload for the three tables, each 8-byte aligned
+    table = np.concatenate([spans.view(np.int64), slots.view(np.int64), group_first])
+    table_d = upload_small(table)
+    a, b = 2 * spans.shape[0], 2 * spans.shape[0] + 2 * n_groups
+    call('l3c_u8_xor_spans', ptr(data, torch.uint8), data.numel(), spans.ctypes.data, ptr(table_d[:a], torch.int64) if a else None, spans.shape[0],
+         group_first.ctypes.data, ptr(table_d[b:], torch.int64), n_groups, slots.ctypes.data, ptr(table_d[a:b], torch.int64),
+         ptr(out, torch.uint8), out.numel(), stream())
+    return out

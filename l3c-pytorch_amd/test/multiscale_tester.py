@@ -194,10 +194,13 @@ class MultiscaleTester(object):
         self.file_writer = AsyncFileWriter() if getattr(flags, 'write_to_files', None) else None
         if getattr(flags, 'seal_bands', False) and not int(getattr(flags, 'bands', 0) or 0):
             raise ValueError('--seal-bands needs --bands: a band seal holds a CRC per band of a banded file')
+        if getattr(flags, 'parity', 0) and not getattr(flags, 'seal_bands', False):
+            raise ValueError('--parity needs --bands --seal-bands: the band seal is what locates the damage the parity repairs')
         self.bc = Bitcoding(self.blueprint, times=self.times if getattr(flags, 'write_to_files', None) else None,
                             compare_with_theory=bool(getattr(flags, 'compare_theory', False)), auto_recurse=self.recursive,
                             file_writer=self.file_writer, bands=int(getattr(flags, 'bands', 0) or 0),
-                            seal='bands' if getattr(flags, 'seal_bands', False) else bool(getattr(flags, 'seal', False)))
+                            seal='bands' if getattr(flags, 'seal_bands', False) else bool(getattr(flags, 'seal', False)),
+                            parity=int(getattr(flags, 'parity', 0) or 0))
         self.max_batch = int(getattr(flags, 'batch', None) or 8)
         self.io_threads = int(getattr(flags, 'io_threads', None) or 4)
         exp_name = os.path.basename(experiment_dir)
@@ -513,12 +516,15 @@ class MultiscaleTester(object):
         from .. import _lib
         # the container has no version field (reference bitcoding.py:326-375): say which decoder generation reads this file
         print('---\nSaved: {}  (bitstream generation {}, include/l3c_hip.h{})'.format(pout, _lib.load().l3c_bitstream_generation(),
-                                                                                 '; band-sealed' if self.bc.seal_bands else '; sealed' if self.bc.seal else ''))
+                                                                                 ('; band-sealed, parity over groups of {}'.format(self.bc.parity) if self.bc.parity else
+                                                                                  '; band-sealed' if self.bc.seal_bands else '; sealed' if self.bc.seal else '')))
         return bpsp
 
-    def decode(self, pin, png_out_p, region=None, salvage=False):
+    def decode(self, pin, png_out_p, region=None, salvage=False, repair=False, write_repaired=None):
         """region: a box (y0, y1) or (y0, y1, x0, x1) of the image -- only that box is decoded (Bitcoding.decode_region) and written.
-        salvage: Bitcoding.decode_salvage -- the picture is written whatever the pixel CRCs say, and SalvageInfo.line() is printed."""
+        salvage: Bitcoding.decode_salvage -- the picture is written whatever the pixel CRCs say, and SalvageInfo.line() is printed.
+        repair: Bitcoding.decode_repair -- salvage that first rebuilds what the file's parity bands can rebuild; RepairInfo.line() is
+        printed, and the healed file goes to write_repaired when something was repaired."""
         pout_dir = os.path.dirname(os.path.abspath(png_out_p))
         if not os.path.isdir(pout_dir):
             raise DecodeError('png_out_p directory ({}) does not exists!'.format(pout_dir))
@@ -526,12 +532,12 @@ class MultiscaleTester(object):
             raise DecodeError('png_out_p must end in .png, got {}'.format(png_out_p))
         from ..bitcoding import container
         verify = not getattr(self.flags, 'no_verify', False)
-        if salvage:
+        if salvage or repair:
             if region is not None:
-                raise DecodeError('--salvage decodes the whole image: it does not go with --region')
+                raise DecodeError('--{} decodes the whole image: it does not go with --region'.format('repair' if repair else 'salvage'))
             try:
                 with open(pin, 'rb') as fin:
-                    decoded, padding, info = self.bc.decode_salvage([fin.read()])
+                    decoded, padding, info = (self.bc.decode_repair if repair else self.bc.decode_salvage)([fin.read()])
             except container.SealError as e:
                 raise DecodeError('seal: {}'.format(e))
             except (ValueError, NotImplementedError) as e:
@@ -541,6 +547,12 @@ class MultiscaleTester(object):
                 decoded = pad.undo_pad(decoded, *padding[0])
             self._write_img(decoded, png_out_p)
             print(info.line())
+            if repair:
+                if write_repaired and info.files[0] is not None:
+                    with open(write_repaired, 'wb') as fout:
+                        fout.write(info.files[0])
+                    print('Repaired file: {}'.format(write_repaired))
+                info = info.salvage
             if info.lost:
                 print('*** the file is LOST: nothing of it verified')
             print('---\nDecoded: {}'.format(png_out_p))

@@ -2,7 +2,7 @@
 """Encoder / decoder CLI -- same arguments as the reference's src/l3c.py:74-125:
 
     python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] enc IMG_P OUT_P [--overwrite]
-    python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] dec [--region Y0:Y1[,X0:X1]] [--salvage] IMG_P OUT_P_PNG
+    python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] dec [--region Y0:Y1[,X0:X1]] [--salvage] [--repair [--write-repaired OUT.l3c]] IMG_P OUT_P_PNG
     python l3c.py LOG_DIR LOG_DATE [--device auto|gpu|cpu] [-i ITR] preview IMG_P OUT_P_PNG [--records R] [--bytes N]
 
 Everything runs on the MI355X path; `--device cpu` is refused (there is no CPU back end in this build).
@@ -21,6 +21,7 @@ from l3c_pytorch_amd.test.multiscale_tester import DecodeError, EncodeError, Mul
 
 # `enc --bands` without a value: the smallest band count within 5 % of the fastest one-image decode (profiles/r07_banded_latency.log)
 DEFAULT_BANDS = 64
+DEFAULT_PARITY = 16
 
 
 def parse_device_flag(flag):
@@ -71,6 +72,10 @@ def main(argv=None):
     enc.add_argument('--seal-bands', dest='seal_bands', action='store_true',
                      help='with --bands: write a BAND-SEALED file, a seal with one CRC-32 per band of the finest record in front of it: dec then '
                           'names the damaged rows of a file that fails, and dec --region verifies the pixels it returns')
+    enc.add_argument('--parity', type=int, nargs='?', const=DEFAULT_PARITY, default=0, metavar='G',
+                     help='with --bands --seal-bands: add PARITY BANDS, an XOR parity stream per group of G bands of the finest record (about '
+                          '1 / G more bytes; the flag alone: {}): dec --repair then rebuilds one damaged band per group, bit for '
+                          'bit'.format(DEFAULT_PARITY))
     dec.add_argument('img_p')
     dec.add_argument('out_p_png')
     dec.add_argument('--no-verify', dest='no_verify', action='store_true', help='do not check the seal of a sealed file')
@@ -80,6 +85,11 @@ def main(argv=None):
     dec.add_argument('--salvage', action='store_true',
                      help='a damaged BAND-SEALED file: write the picture all the same -- every verified pixel exact, the damaged bands '
                           'concealed by the mean of the predicted distribution -- and say which rows are which')
+    dec.add_argument('--repair', action='store_true',
+                     help='a damaged file written with --parity: rebuild the damaged bands from the parity, bit for bit, where one band per '
+                          'group is damaged; what cannot be rebuilt is concealed as --salvage conceals it; says which rows are which')
+    dec.add_argument('--write-repaired', dest='write_repaired', default=None, metavar='OUT.l3c',
+                     help='with --repair: write the healed file (the rebuilt payloads spliced in) when something was repaired')
     pre = mode.add_parser('preview', help='Picture from the coarse scale records of a file: preview IMG_P OUT_P_PNG [--records R] [--bytes N]')
     pre.add_argument('img_p')
     pre.add_argument('out_p_png')
@@ -106,7 +116,9 @@ def main(argv=None):
             return 1
     else:
         try:
-            tester.decode(flags.img_p, flags.out_p_png, flags.region, flags.salvage)
+            if flags.write_repaired and not flags.repair:
+                raise DecodeError('--write-repaired needs --repair')
+            tester.decode(flags.img_p, flags.out_p_png, flags.region, flags.salvage, flags.repair, flags.write_repaired)
         except DecodeError as e:
             print('*** DecodeError:', e)
             return 1
