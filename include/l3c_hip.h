@@ -1327,6 +1327,38 @@ int l3c_seal_write_parity(const l3c_seal *seal_host, const uint8_t *padding8_hos
                           const uint32_t *plen_host, const uint8_t *payloads_host, uint8_t *dst_host);
 
 /*
+ * R PARITY STREAMS PER GROUP (Bitcoding(parity=G, parity_streams=R), R in 2..4): any R damaged bands of a group come back exactly, and a
+ * damaged parity row still leaves R - 1 usable.  The arithmetic is GF(2^8), polynomial 0x11D, alpha = 0x02: member k of group g of a channel is
+ * band j = g + k m, its evaluation point x_k = alpha^k, and
+ *     row r (0 <= r < R) of the group = XOR over its members k of (x_k)^r d_k,     every d_k zero-extended to plen[c][g]
+ * so row 0 is the XOR parity above, byte for byte.  Distinct points need G <= 255.  One-byte members 0x01, 0x02, 0x80 give rows 0x83, 0x3F,
+ * 0xE1, 0x96.  Any t <= R erased members are solvable from any t CONSECUTIVE rows r0 .. r0 + t - 1 (a diagonal times a Vandermonde matrix).
+ * The seal version stays 3; the section is of a second kind, S = 20 + 12 m + R sum(plen) bytes:
+ *       0 'L3CQ' | 4 u16 G | 6 u16 m | 8 u16 R | 10 u16 0 | 12 u32 plen[3][m] | 12 + 12 m the 3 m R payloads, (c, g, r) order, plen[c][g] bytes
+ *       each | S - 8 u32 S | S - 4 separator
+ *   check        the padding bytes, section bytes [0, 12 + 12 m), the section's last 8 bytes, the band table, seal bytes 0..19
+ *   R = 1        is never written as 'L3CQ': l3c_seal_write_parity_rs with R = 1 stores l3c_seal_write_parity's bytes
+ * A reader rejects R outside 2..4, a non-zero reserved field, G > 255, an S other than 20 + 12 m + R sum(plen), and everything an 'L3CP'
+ * section is rejected for.  l3c_seal_find_parity_rs hands out either kind ('L3CP': R = 1; payload_bytes = R sum(plen)).  l3c_seal_find,
+ * l3c_seal_find_bands and l3c_seal_find_parity accept an 'L3CQ' file and return the body size in front of the section and the band table;
+ * l3c_seal_find_parity gives m = 0: every other reader reads the file as the band-sealed file it contains.
+ * The repair rebuilds a group (file, c, g) that holds 1..R erasures while every other member verifies: the rows r0 .. r0 + t - 1 go up,
+ * the t x t system is inverted on the host, and each rebuilt payload is ONE linear combination (one l3c_u8_gf_spans group) of those rows and
+ * the present members.  r0 = 0 first; where the positions still fail and t < R, r0 = 1 .. R - t in later rounds.
+ */
+typedef struct {
+    int32_t G, m, R;                /* bands per group, groups per channel (0: no parity section), parity streams per group */
+    const uint8_t *plen;            /* 12 m bytes inside the file: [3][m] little-endian words, unaligned */
+    const uint8_t *payloads;        /* the 3 m R parity payloads, (c, g, r) order, back to back */
+    int64_t payload_bytes;          /* R times the sum of plen */
+} l3c_seal_parity_rs;
+int64_t l3c_seal_parity_rs_bytes(int n, int m, int R, int64_t payload_bytes);  /* section (either kind) + 20 + 12 n + 24; payload_bytes = R sum(plen) */
+int l3c_seal_find_parity_rs(const uint8_t *file_host, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
+                            l3c_seal_parity_rs *parity_out);
+int l3c_seal_write_parity_rs(const l3c_seal *seal_host, const uint8_t *padding8_host, const uint32_t *band_crc_host, int n, uint32_t band_len, int G,
+                             int R, const uint32_t *plen_host, const uint8_t *payloads_host, uint8_t *dst_host);
+
+/*
  * The two kernels share one device fold (csrc/parity.hip): a block XORs a 4096-byte tile of ONE output stream over the stream's members,
  * grid.y = the output stream.  A thread owns 16 bytes of the tile: one 16-byte load per member where the member is 16-byte aligned, dword
  * loads otherwise; nothing at or behind a member's 4-byte-rounded end is read, the bytes of its last dword behind its length count as
@@ -1363,6 +1395,25 @@ int l3c_band_parity(const l3c_banded_scale *scale_host, int64_t B, int G, uint8_
 int l3c_u8_xor_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, int64_t n_spans,
                      const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups, const l3c_u8_span *out_spans_host,
                      const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream);
+
+/*
+ * The same two kernels over GF(2^8) (polynomial 0x11D, alpha = 0x02; the 'L3CQ' section above), four packed bytes per dword, no table, no LDS.
+ *
+ * l3c_band_parity_rs: l3c_band_parity for R in 1..4 rows per group.  A block reads each member's bytes ONCE for all R rows: Horner over the
+ * members from the last to the first, acc_r = alpha^r acc_r ^ d_k.
+ *   parity          uint8 [B][3][m][R][parity_stride]: row r of group (b, c, g); what is written of a slot is as in l3c_band_parity
+ *   parity_nbytes   uint32 [B][3][m]: one length for the R rows of a group, or L3C_AC_OVERRUN -- then none of its R slots is written
+ *   G               in 1..n, and <= 255 when R > 1; B * 3 * m <= 65535; everything else as l3c_band_parity
+ *
+ * l3c_u8_gf_spans: l3c_u8_xor_spans with one coefficient per span: slot g = XOR over its spans k of coef[k] * span k.  coef_host: the n_spans
+ * bytes on the host, coef: the caller's device copy (no alignment asked).  coef = 1 everywhere gives l3c_u8_xor_spans' bytes; a span with
+ * coef = 0 contributes nothing and is not read.  Tables, cut / zero-extension, output form, alignment and the no-overlap rule: l3c_u8_xor_spans'.
+ */
+int l3c_band_parity_rs(const l3c_banded_scale *scale_host, int64_t B, int G, int R, uint8_t *parity, int64_t parity_stride, uint32_t *parity_nbytes,
+                       l3c_stream_t stream);
+int l3c_u8_gf_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, const uint8_t *coef_host,
+                    const uint8_t *coef, int64_t n_spans, const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups,
+                    const l3c_u8_span *out_spans_host, const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream);
 
 #ifdef __cplusplus
 }

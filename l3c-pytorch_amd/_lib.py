@@ -212,6 +212,12 @@ class SealParity(ctypes.Structure):
     _fields_ = [('G', ctypes.c_int32), ('m', ctypes.c_int32), ('plen', ctypes.c_void_p), ('payloads', ctypes.c_void_p), ('payload_bytes', c_i64)]
 
 
+class SealParityRS(ctypes.Structure):
+    """l3c_seal_parity_rs (include/l3c_hip.h); plen and payloads point into the file."""
+    _fields_ = [('G', ctypes.c_int32), ('m', ctypes.c_int32), ('R', ctypes.c_int32), ('plen', ctypes.c_void_p), ('payloads', ctypes.c_void_p),
+                ('payload_bytes', c_i64)]
+
+
 SEAL_BYTES = 24      # include/l3c_hip.h: L3C_SEAL_BYTES
 EPI_RELU, EPI_RESIDUAL, EPI_PIXEL_SHUFFLE = 1, 2, 4
 ABI_VERSION = 4      # include/l3c_hip.h: L3C_ABI_VERSION (4: grouped tables, l3c_decode_rgb, l3c_container_read; no canvas batches)
@@ -346,9 +352,14 @@ PROTOTYPES = {
     'l3c_seal_parity_bytes': (c_i64, [c_int, c_int, c_i64]),
     'l3c_seal_find_parity': (c_int, [c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(Seal), ctypes.POINTER(SealBands), ctypes.POINTER(SealParity)]),
     'l3c_seal_write_parity': (c_int, [ctypes.POINTER(Seal), c_vp, c_vp, c_int, ctypes.c_uint32, c_int, c_vp, c_vp, c_vp]),
+    'l3c_seal_parity_rs_bytes': (c_i64, [c_int, c_int, c_int, c_i64]),
+    'l3c_seal_find_parity_rs': (c_int, [c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(Seal), ctypes.POINTER(SealBands), ctypes.POINTER(SealParityRS)]),
+    'l3c_seal_write_parity_rs': (c_int, [ctypes.POINTER(Seal), c_vp, c_vp, c_int, ctypes.c_uint32, c_int, c_int, c_vp, c_vp, c_vp]),
     'l3c_band_parity_groups': (c_int, [c_int, c_int]),
     'l3c_band_parity': (c_int, [ctypes.POINTER(BandedScale), c_i64, c_int, c_vp, c_i64, c_vp, c_vp]),
     'l3c_u8_xor_spans': (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'l3c_band_parity_rs': (c_int, [ctypes.POINTER(BandedScale), c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp]),
+    'l3c_u8_gf_spans': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 # include/l3c_xcheck.h: the TEST-ONLY cross-check library (round-1/2 Winograd F(2x2,3x3) kernel); see load_xcheck()

@@ -105,6 +105,7 @@ class EncodedBatch(object):
         self.band_len = None                 # ... planes (ops.u8_crc32_bands, with frame_crc from the same pass), and that record's band length
         self.parity_group = 0                # Bitcoding(parity=G): the group size asked for (the seal states min(G, n)) ...
         self.parity = None                   # ... and (uint8 (B, 3, m, stride), int32 (B, 3, m)) of ops.band_parity on the finest record's coder output
+        self.parity_streams = 1              # Bitcoding(parity_streams=R): R > 1 -> (uint8 (B, 3, m, R, stride), int32 (B, 3, m)) of ops.band_parity_rs
 
     def _coder_outputs(self):
         """(C, H, W, out, nbytes) of every coder group, nbytes reshaped to (B, streams per image of that group)."""
@@ -233,13 +234,17 @@ class EncodedBatch(object):
             parity = [None] * e.B
             if e.parity is not None:
                 slots, lens = e.parity
-                m, stride = slots.shape[2], slots.shape[3]
+                m, stride, R = slots.shape[2], slots.shape[-1], e.parity_streams
                 nb = EncodedBatch._checked_nbytes(words[at:at + lens.numel()].view(np.int32)).reshape(e.B, 3, m)
                 at += lens.numel()
-                host = words[at:at + slots.numel() // 4].view(np.uint8).reshape(e.B, 3, m, stride)
+                host = words[at:at + slots.numel() // 4].view(np.uint8).reshape(slots.shape)
                 at += slots.numel() // 4
                 G = min(e.parity_group, bands[0].shape[1])
-                parity = [(G, [[host[b, c, g, :nb[b, c, g]].tobytes() for g in range(m)] for c in range(3)]) for b in range(e.B)]
+                if R == 1:
+                    parity = [(G, [[host[b, c, g, :nb[b, c, g]].tobytes() for g in range(m)] for c in range(3)]) for b in range(e.B)]
+                else:
+                    parity = [(G, [[[host[b, c, g, r, :nb[b, c, g]].tobytes() for r in range(R)] for g in range(m)] for c in range(3)])
+                              for b in range(e.B)]
             res.append([container.make_seal(body, e.seal[0], frame[b], e.seal[1], bands[b], e.band_len, parity=parity[b])
                         for b, body in enumerate(files)])
         return res
@@ -320,7 +325,7 @@ class EncodedBatch(object):
 
 class Bitcoding(object):
     def __init__(self, blueprint, times=None, compare_with_theory=False, coder_cus=0, auto_recurse=0, file_writer=None,
-                 coder_streams=4, forward_streams=3, decode_overlap=None, rgb_window='auto', bands=0, seal=False, parity=0):
+                 coder_streams=4, forward_streams=3, decode_overlap=None, rgb_window='auto', bands=0, seal=False, parity=0, parity_streams=1):
         """coder_streams: side streams the range-coder launches rotate over; forward_streams: streams `encode_many` spreads the forward
         passes of a heterogeneous set over (used when the HIP runtime runs with >= 8 hardware queues -- helpers/runtime.py; the package
         does NOT ask for them on import: applications that code image sets call l3c_pytorch_amd.configure_hip_queues() before their
@@ -351,7 +356,10 @@ class Bitcoding(object):
         an XOR parity over the band payloads of the finest record, one parity stream per group of min(G, n) bands of a channel
         (ops.band_parity on the coder's output, enqueued with the encode), about 1 / G of the file's size.  decode_repair then rebuilds
         one damaged band per group bit-exactly; every other reader reads the file as the band-sealed file it contains.  0: every byte
-        written is the band-sealed file's."""
+        written is the band-sealed file's.
+        parity_streams=R (1..4; R > 1 needs parity=G, and min(G, bands) <= 255: ValueError otherwise): R parity rows per group over GF(2^8)
+        (ops.band_parity_rs; container.rs_parity), the 'L3CQ' section, about R / G of the file's size.  decode_repair then rebuilds up to R
+        damaged bands per group, and a damaged parity row still leaves R - 1 usable.  1: every byte written is today's 'L3CP' file's."""
         if seal not in (False, True, 'bands'):
             raise ValueError("seal must be False, True or 'bands', got {!r}".format(seal))
         if isinstance(parity, bool) or not isinstance(parity, int) or parity < 0:
@@ -359,6 +367,13 @@ class Bitcoding(object):
         if parity and seal != 'bands':
             raise ValueError("parity needs seal='bands': the band seal is what turns damage into erasures of known position")
         self.parity = parity
+        if isinstance(parity_streams, bool) or not isinstance(parity_streams, int) or not 1 <= parity_streams <= container.MAX_PARITY_STREAMS:
+            raise ValueError('parity_streams must be in 1..{}, got {!r}'.format(container.MAX_PARITY_STREAMS, parity_streams))
+        if parity_streams > 1 and not parity:
+            raise ValueError('parity_streams > 1 needs parity=G: the rows are computed over the parity groups')
+        if parity_streams > 1:
+            container.check_parity_streams(parity_streams, parity, int(bands))
+        self.parity_streams = parity_streams
         if seal == 'bands' and not bands:
             raise ValueError("seal='bands' needs banded files: a band seal holds a CRC per band of the finest record (bands=K, K >= 1)")
         if bands and not 1 <= int(bands) <= MAX_BANDS:
@@ -476,7 +491,7 @@ class Bitcoding(object):
             enc.band_len = band_len(H * W, self.bands)
             enc.band_crc, enc.frame_crc = ops.u8_crc32_bands(imgs.to('cuda').to(torch.uint8).contiguous().view(-1), B, H * W, enc.band_len)
             enc.seal = (self.generation(), self.model_id())
-            enc.parity_group = self.parity
+            enc.parity_group, enc.parity_streams = self.parity, self.parity_streams
         elif self.seal:
             enc.frame_crc = ops.u8_crc32(imgs.to('cuda').to(torch.uint8).contiguous().view(-1), B, 3 * H * W)
             enc.seal = (self.generation(), self.model_id())
@@ -524,7 +539,12 @@ class Bitcoding(object):
             for enc, shape, coded in finest.values():
                 if enc.parity_group:                             # behind the coder on its stream: nothing waits
                     _, Hs, Ws, L = shape
-                    enc.parity = ops.band_parity(enc.B, Hs, Ws, L, coded, min(enc.parity_group, n_bands(Hs * Ws, L)))
+                    G = min(enc.parity_group, n_bands(Hs * Ws, L))
+                    if enc.parity_streams > 1:
+                        container.check_parity_streams(enc.parity_streams, G, G)
+                        enc.parity = ops.band_parity_rs(enc.B, Hs, Ws, L, coded, G, enc.parity_streams)
+                    else:
+                        enc.parity = ops.band_parity(enc.B, Hs, Ws, L, coded, G)
             done = torch.cuda.Event()
             done.record(side)
         g = 0
@@ -752,6 +772,11 @@ class Bitcoding(object):
         Rounds repeat while one verified a band more and failures remain (a band whose other channel is damaged too, in another group,
         takes a second round); no payload is rebuilt twice.  The band CRCs stay the arbiter: a payload counts as repaired only when all
         three channels of its position verify.  What still fails is concealed as decode_salvage conceals it (info.salvage).
+        Files with R = 2..4 parity rows per group ('L3CQ', Bitcoding(parity_streams=R)): a group is rebuilt when it holds t = 1..R erasures
+        and every other member verifies.  The rows r0 .. r0 + t - 1 go up, container.rs_repair_coefficients inverts the t x t system on the
+        host, and every rebuilt payload is one group of ONE ops.u8_gf_spans call per round (the 'L3CP' files of the batch keep their ONE
+        ops.u8_xor_spans call).  r0 = 0 first; where the group's positions still fail and t < R, a later round takes r0 = 1 .. R - t -- what
+        survives a damaged parity row.  No (group, erasure set, window) is tried twice.
         info.files: per file the HEALED file -- the rebuilt payloads spliced in at their framing offsets, the same length, section, table
         and seal --, None where nothing was repaired.  Files without parity, intact files and unsealed files: decode_salvage."""
         raw = files
@@ -797,46 +822,83 @@ class Bitcoding(object):
         Kp = P.shape[-1]
         while True:
             _, failing, _ = container.failing_bands(seals, band_words, (H, W), framing.padding)
-            jobs = []                                                        # (file, c, j) to rebuild this round
+            jobs = []                                                        # (file, c, j) to rebuild this round from an 'L3CP' section
+            rs_groups = []                                                   # (file, c, g, erased bands, r0) from an 'L3CQ' section
             for i, bad in failing.items():
                 if seals[i].parity is None:
                     continue
-                bad, m = set(bad), seals[i].parity_groups
+                bad, m, R = set(bad), seals[i].parity_groups, seals[i].parity_streams
                 erasures = {}
                 for j in sorted({j for _, j in bad}):
                     c = min(c for c, jj in bad if jj == j)
                     erasures.setdefault((c, j % m), []).append(j)
                 for (c, g), js in sorted(erasures.items()):
-                    j = js[0]
-                    if len(js) == 1 and (i, c, j) not in tried and all((c, o) not in bad for o in range(g, n, m) if o != j):
-                        jobs.append((i, c, j))
-            if not jobs:
+                    if len(js) > R or any((c, o) in bad for o in range(g, n, m) if o not in js):
+                        continue
+                    if R == 1:
+                        if (i, c, js[0]) not in tried:
+                            jobs.append((i, c, js[0]))
+                        continue
+                    # a window of len(js) consecutive rows, r0 = 0 first; a later one only where an earlier one left the positions failing
+                    r0 = next((r for r in range(R - len(js) + 1) if (i, c, g, tuple(js), r) not in tried), None)
+                    if r0 is not None:
+                        rs_groups.append((i, c, g, tuple(js), r0))
+            if not jobs and not rs_groups:
                 break
             rounds += 1
             tried.update(jobs)
+            tried.update(rs_groups)
+            rs_jobs = [(i, c, j) for i, c, g, js, r0 in rs_groups for j in js]
             # `work` grows by this round's region: the parity payloads (uploaded), then the output slots, all 16-byte aligned
             base = al16(work.numel())
-            p_at, o_at, pos = [], [], base
+            p_at, q_at, o_at, pos = [], [], [], base
             for i, c, j in jobs:
                 p_at.append(pos)
                 pos = al16(pos + len(seals[i].parity[c][j % seals[i].parity_groups]) + 4)
+            for i, c, g, js, r0 in rs_groups:                                # the rows r0 .. r0 + t - 1 of the group, one after the other
+                q_at.append([])
+                for r in range(r0, r0 + len(js)):
+                    q_at[-1].append(pos)
+                    pos = al16(pos + len(seals[i].parity[c][g][r]) + 4)
             src_end = pos
-            for i, c, j in jobs:
+            for i, c, j in jobs + rs_jobs:
                 o_at.append(pos)
                 pos = al16(pos + (lens[i, c, j] + 3) // 4 * 4 + 4)
+            rs_out = o_at[len(jobs)] if rs_jobs else pos                     # the slots of the 'L3CQ' jobs lie behind those of the 'L3CP' jobs
             up = np.zeros(pos - work.numel(), dtype=np.uint8)
             for (i, c, j), a in zip(jobs, p_at):
                 p = seals[i].parity[c][j % seals[i].parity_groups]
                 up[a - work.numel():a - work.numel() + len(p)] = np.frombuffer(p, dtype=np.uint8)
+            for (i, c, g, js, r0), ats in zip(rs_groups, q_at):
+                for r, a in zip(range(r0, r0 + len(js)), ats):
+                    p = seals[i].parity[c][g][r]
+                    up[a - work.numel():a - work.numel() + len(p)] = np.frombuffer(p, dtype=np.uint8)
             work = torch.cat([work, ops.upload_small(up)])
-            offs, lns, first = [], [], [0]
-            for (i, c, j), a in zip(jobs, p_at):
-                m = seals[i].parity_groups
-                others = [o for o in range(j % m, n, m) if o != j]
-                offs += [a] + [int(at[i, c, o]) for o in others]
-                lns += [len(seals[i].parity[c][j % m])] + [int(lens[i, c, o]) for o in others]
-                first.append(len(offs))
-            ops.u8_xor_spans(work[:src_end], offs, lns, first, work[src_end:], [a - src_end for a in o_at], [int(lens[i, c, j]) for i, c, j in jobs])
+            if jobs:
+                offs, lns, first = [], [], [0]
+                for (i, c, j), a in zip(jobs, p_at):
+                    m = seals[i].parity_groups
+                    others = [o for o in range(j % m, n, m) if o != j]
+                    offs += [a] + [int(at[i, c, o]) for o in others]
+                    lns += [len(seals[i].parity[c][j % m])] + [int(lens[i, c, o]) for o in others]
+                    first.append(len(offs))
+                ops.u8_xor_spans(work[:src_end], offs, lns, first, work[src_end:rs_out], [a - src_end for a in o_at[:len(jobs)]],
+                                 [int(lens[i, c, j]) for i, c, j in jobs])
+            if rs_jobs:
+                # every rebuilt payload is ONE linear combination of the uploaded rows and the group's present members
+                offs, lns, coefs, first = [], [], [], [0]
+                for (i, c, g, js, r0), ats in zip(rs_groups, q_at):
+                    m = seals[i].parity_groups
+                    present = [o for o in range(g, n, m) if o not in js]
+                    solved = container.rs_repair_coefficients([(j - g) // m for j in js], [(o - g) // m for o in present], r0)
+                    for rows, members in solved:
+                        offs += list(ats) + [int(at[i, c, o]) for o in present]
+                        lns += [len(seals[i].parity[c][g][r]) for r in range(r0, r0 + len(js))] + [int(lens[i, c, o]) for o in present]
+                        coefs += list(rows) + list(members)
+                        first.append(len(offs))
+                ops.u8_gf_spans(work[:src_end], offs, lns, coefs, first, work[rs_out:], [a - rs_out for a in o_at[len(jobs):]],
+                                [int(lens[i, c, j]) for i, c, j in rs_jobs])
+            jobs = jobs + rs_jobs
             for (i, c, j), a in zip(jobs, o_at):
                 at[i, c, j] = a
             # the positions of the round, decoded again: their symbols zeroed, one entry each
@@ -859,7 +921,7 @@ class Bitcoding(object):
             rebuilt += jobs
         _, failing, _ = container.failing_bands(seals, band_words, (H, W), framing.padding)
         repaired, healed = {}, [None] * B
-        for i, c, j in rebuilt:
+        for i, c, j in sorted(set(rebuilt)):                                 # (a payload tried with a second window is listed twice)
             if all((cc, j) not in failing.get(i, ()) for cc in range(3)):
                 repaired.setdefault(i, []).append((c, j))
         for i, got in repaired.items():

@@ -350,6 +350,12 @@ def image_entry_table(hws, pixbase0=0):
 # longest member's byte count (band_parity).  The check word runs over the padding bytes, the section's head (bytes [0, 8 + 12 m)), its
 # last 8 bytes, the band table and seal bytes 0..19 -- NOT over the parity payloads: a damaged parity stream can only make a repair fail,
 # which the band CRCs then notice.  The section ends with the separator, so the band table still starts behind one.
+#
+# R = 2..4 PARITY STREAMS PER GROUP (Bitcoding(parity=G, parity_streams=R)): the same seal version with a section of a second kind,
+# S = 20 + 12 m + R sum(plen) bytes:
+#     'L3CQ' | u16 G | u16 m | u16 R | u16 0 | u32 plen[3][m] | the 3 m R payloads, (c, g, r) order, plen[c][g] bytes each | u32 S | separator
+# Row r of a group is the XOR over its members k (band g + k m) of alpha^(k r) d_k in GF(2^8), polynomial 0x11D, alpha = 0x02 (rs_parity);
+# row 0 is the 'L3CP' payload; G <= 255.  The check word covers section bytes [0, 12 + 12 m) and the last 8.  R = 1 is always 'L3CP'.
 
 SEAL_SIGNATURE = b'L3CS'
 SEAL_VERSION = 1
@@ -358,6 +364,7 @@ SEAL_VERSION_PARITY = 3
 SEAL_BYTES = 24
 TABLE_SIGNATURE = b'L3CT'
 PARITY_SIGNATURE = b'L3CP'
+PARITY_RS_SIGNATURE = b'L3CQ'
 
 
 def seal_bands_bytes(n):
@@ -368,14 +375,22 @@ def seal_bands_bytes(n):
 class Seal(object):
     """band_len, band_crcs: None for a version-1 seal; for a band seal the finest record's band length and the (3, n) uint32 band CRCs.
     parity_group, parity: None but for a version-3 seal: G, and parity[c][g] the parity payload of group g of channel c (m = ceil(n / G)
-    groups per channel; bytes, or views of the file split_seal read them from)."""
+    groups per channel; bytes, or views of the file split_seal read them from).
+    parity_streams: None without parity, 1 for an 'L3CP' section, R = 2..4 for an 'L3CQ' section -- then parity[c][g] is the LIST of the
+    group's R row payloads (rs_parity), all plen[c][g] bytes long."""
 
-    def __init__(self, generation, frame_crc, model_id, band_len=None, band_crcs=None, parity_group=None, parity=None):
+    def __init__(self, generation, frame_crc, model_id, band_len=None, band_crcs=None, parity_group=None, parity=None, parity_streams=None):
         self.generation, self.frame_crc, self.model_id = int(generation), int(frame_crc), int(model_id)
         self.band_len = None if band_crcs is None else int(band_len)
         self.band_crcs = None if band_crcs is None else np.array(band_crcs, dtype=np.uint32).reshape(3, -1)
         self.parity_group = None if parity is None else int(parity_group)
-        self.parity = None if parity is None else [list(row) for row in parity]
+        self.parity_streams = None if parity is None else int(parity_streams or 1)
+        if parity is None:
+            self.parity = None
+        elif self.parity_streams == 1:
+            self.parity = [list(row) for row in parity]
+        else:
+            self.parity = [[list(rows) for rows in row] for row in parity]
 
     @property
     def parity_groups(self):
@@ -384,8 +399,10 @@ class Seal(object):
 
     def _key(self):
         key = (self.generation, self.frame_crc, self.model_id, self.band_len, None if self.band_crcs is None else self.band_crcs.tobytes())
-        if self.parity is not None:
+        if self.parity is not None and self.parity_streams == 1:
             key += (self.parity_group, tuple(bytes(p) for row in self.parity for p in row))
+        elif self.parity is not None:
+            key += (self.parity_group, self.parity_streams, tuple(bytes(p) for row in self.parity for rows in row for p in rows))
         return key
 
     def __eq__(self, other):
@@ -400,6 +417,8 @@ class Seal(object):
         bands = '' if self.band_crcs is None else ', band_len={}, band_crcs=<3 x {}>'.format(self.band_len, self.band_crcs.shape[1])
         if self.parity is not None:
             bands += ', parity_group={}, parity=<3 x {}>'.format(self.parity_group, self.parity_groups)
+            if self.parity_streams > 1:
+                bands += ', parity_streams={}'.format(self.parity_streams)
         return 'Seal(generation={}, frame_crc=0x{:08x}, model_id=0x{:016x}{})'.format(self.generation, self.frame_crc, self.model_id, bands)
 
 
@@ -632,10 +651,114 @@ def band_parity(payloads, G):
     return res
 
 
-def parity_section_bytes(plens):
-    """S of a parity section whose payload lengths are plens ((3, m))."""
+def parity_section_bytes(plens, R=1):
+    """S of a parity section whose payload lengths are plens ((3, m)); R > 1: of the 'L3CQ' section with R rows per group."""
     plens = np.asarray(plens, dtype=np.int64).reshape(3, -1)
-    return 16 + 12 * plens.shape[1] + int(plens.sum())
+    if R == 1:
+        return 16 + 12 * plens.shape[1] + int(plens.sum())
+    return 20 + 12 * plens.shape[1] + int(R) * int(plens.sum())
+
+
+# ---- GF(2^8), polynomial 0x11D, alpha = 0x02: the arithmetic of the 'L3CQ' section (R parity rows per group; csrc/parity.hip on the device) ----
+
+MAX_PARITY_STREAMS = 4
+MAX_RS_GROUP = 255                  # the points alpha^k of a group's members must be distinct
+
+
+def _gf_tables():
+    exp, log, v = np.zeros(510, dtype=np.uint8), np.zeros(256, dtype=np.int64), 1
+    for i in range(255):
+        exp[i] = exp[i + 255] = v
+        log[v] = i
+        v <<= 1
+        if v & 0x100:
+            v ^= 0x11D
+    return exp, log
+
+
+_GF_EXP, _GF_LOG = _gf_tables()
+
+
+def gf_mul(a, b):
+    """a b in GF(2^8) mod 0x11D; a, b ints or uint8 arrays (broadcast)."""
+    if np.isscalar(a) and np.isscalar(b):
+        return 0 if a == 0 or b == 0 else int(_GF_EXP[_GF_LOG[a] + _GF_LOG[b]])
+    a, b = np.asarray(a, dtype=np.uint8), np.asarray(b, dtype=np.uint8)
+    return np.where((a == 0) | (b == 0), np.uint8(0), _GF_EXP[_GF_LOG[a] + _GF_LOG[b]]).astype(np.uint8)
+
+
+def gf_pow_alpha(e):
+    """alpha^e, e >= 0."""
+    return int(_GF_EXP[int(e) % 255])
+
+
+def gf_inv(a):
+    if a == 0:
+        raise ZeroDivisionError('gf_inv(0)')
+    return int(_GF_EXP[255 - _GF_LOG[a]])
+
+
+def check_parity_streams(R, G, n):
+    """R, the parity rows per group, for n bands in groups of G; ValueError unless R in 1..4 and, for R > 1, min(G, n) <= 255."""
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 1 <= R <= MAX_PARITY_STREAMS:
+        raise ValueError('parity_streams must be in 1..{}, got {!r}'.format(MAX_PARITY_STREAMS, R))
+    if R > 1 and min(int(G), int(n)) > MAX_RS_GROUP:
+        raise ValueError('parity_streams > 1 needs groups of at most {} bands (distinct points in GF(2^8)), got min(G, n) = {}'.format(
+            MAX_RS_GROUP, min(int(G), int(n))))
+    return int(R)
+
+
+def rs_parity(payloads, G, R):
+    """The R parity rows per group of ONE channel (the reference the kernels are tested against): payloads, the n band payloads of the
+    channel, in groups of G -> [m][R] bytes; row r of group g is the XOR over its members k (band g + k m) of alpha^(k r) d_k, each d_k
+    zero-extended to the longest member.  Row 0 is band_parity's payload."""
+    n = len(payloads)
+    m = parity_groups(n, G)
+    R = check_parity_streams(R, G, n)
+    res = []
+    for g in range(m):
+        members = [np.frombuffer(bytes(p), dtype=np.uint8) for p in payloads[g::m]]
+        rows = [np.zeros(max(len(a) for a in members), dtype=np.uint8) for _ in range(R)]
+        for k, a in enumerate(members):
+            for r in range(R):
+                rows[r][:len(a)] ^= gf_mul(a, np.uint8(gf_pow_alpha(k * r)))
+        res.append([row.tobytes() for row in rows])
+    return res
+
+
+def rs_repair_coefficients(erased_ks, present_ks, r0=0):
+    """The erased members of a group from the parity rows r0 .. r0 + t - 1 (t = len(erased_ks)) and the present members: member k has
+    the point x_k = alpha^k, row r = XOR_k x_k^r d_k, so  sum_e x_e^r d_e = P_r ^ sum_p x_p^r d_p  for the t rows; the t x t matrix
+    (x_e^(r0 + i)) is a diagonal times a Vandermonde matrix and is inverted here.
+    -> per erased member (in erased_ks' order) a pair (row coefficients [t], member coefficients [len(present_ks)]):
+    d_e = XOR_i rows[i] P_(r0 + i)  ^  XOR_p members[p] d_p."""
+    erased, present, t = [int(k) for k in erased_ks], [int(k) for k in present_ks], len(erased_ks)
+    if t < 1 or len(set(erased)) != t or set(erased) & set(present) or any(not 0 <= k < MAX_RS_GROUP for k in erased + present):
+        raise ValueError('rs_repair_coefficients: distinct members in 0..254, got erased {} and present {}'.format(erased, present))
+    # Gauss-Jordan on [A | I], A[i][e] = x_e^(r0 + i)
+    A = [[gf_pow_alpha(k * (r0 + i)) for k in erased] + [int(i == c) for c in range(t)] for i in range(t)]
+    for col in range(t):
+        piv = next((i for i in range(col, t) if A[i][col]), None)
+        if piv is None:
+            raise ValueError('rs_repair_coefficients: singular system for erased {} and rows {}..{}'.format(erased, r0, r0 + t - 1))
+        A[col], A[piv] = A[piv], A[col]
+        inv = gf_inv(A[col][col])
+        A[col] = [gf_mul(inv, v) for v in A[col]]
+        for i in range(t):
+            if i != col and A[i][col]:
+                f = A[i][col]
+                A[i] = [v ^ gf_mul(f, w) for v, w in zip(A[i], A[col])]
+    res = []
+    for e in range(t):
+        rows = A[e][t:]                                               # row e of the inverse: the weight of P_(r0 + i) in d_e
+        members = []
+        for k in present:
+            w = 0
+            for i in range(t):
+                w ^= gf_mul(rows[i], gf_pow_alpha(k * (r0 + i)))
+            members.append(w)
+        res.append((rows, members))
+    return res
 
 
 def _band_lengths_of_finest(body, first, C, n):
@@ -652,7 +775,8 @@ def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=
     """The seal bytes for the unsealed file `body` (its padding fields go into the check word): 24 bytes, or with band_crcs ((3, n) words)
     and band_len (the finest record's) the band table and the version-2 seal, seal_bands_bytes(n) bytes.
     parity = (G, payloads) on top of a band seal, payloads[c][g] the parity payload of group g of channel c (band_parity per channel): the
-    parity section in front of the table and the version-3 seal."""
+    parity section in front of the table and the version-3 seal.  payloads[c][g] a LIST of R payloads of one length (rs_parity per channel):
+    the 'L3CQ' section for R = 2..4; a list of one is written as the 'L3CP' section of its payload."""
     import zlib
     table, section, checked = b'', b'', b''
     if parity is not None:
@@ -663,13 +787,25 @@ def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=
         m = parity_groups(n, G)
         if len(rows) != 3 or any(len(row) != m for row in rows):
             raise ValueError('make_seal: parity needs 3 x {} payloads for {} bands in groups of {}'.format(m, n, G))
-        rows = [[bytes(p) for p in row] for row in rows]
-        head = PARITY_SIGNATURE + struct.pack('<HH', int(G), m) + b''.join(struct.pack('<I', len(p)) for row in rows for p in row)
-        S = 16 + 12 * m + sum(len(p) for row in rows for p in row)
+        R = len(rows[0][0]) if isinstance(rows[0][0], (list, tuple)) else None     # rows[c][g]: a payload ('L3CP'), or the list of R row payloads
+        if R is not None:
+            check_parity_streams(R, G, n)
+            if any(not isinstance(p, (list, tuple)) or len(p) != R or len({len(q) for q in p}) != 1 for row in rows for p in row):
+                raise ValueError('make_seal: parity needs {} row payloads of one length in every group'.format(R))
+            rows = [[p[0] for p in row] for row in rows] if R == 1 else [[[bytes(q) for q in p] for p in row] for row in rows]
+        if R is None or R == 1:
+            rows = [[bytes(p) for p in row] for row in rows]
+            head = PARITY_SIGNATURE + struct.pack('<HH', int(G), m) + b''.join(struct.pack('<I', len(p)) for row in rows for p in row)
+            S = 16 + 12 * m + sum(len(p) for row in rows for p in row)
+            payload = b''.join(p for row in rows for p in row)
+        else:
+            head = PARITY_RS_SIGNATURE + struct.pack('<HHHH', int(G), m, R, 0) + b''.join(struct.pack('<I', len(p[0])) for row in rows for p in row)
+            S = 20 + 12 * m + R * sum(len(p[0]) for row in rows for p in row)
+            payload = b''.join(q for row in rows for p in row for q in p)
         if S >= 1 << 32:
             raise ValueError('make_seal: parity section of {} bytes'.format(S))
         tail = struct.pack('<I', S) + _MAGIC_VALUE_SEP
-        section, checked = head + b''.join(p for row in rows for p in row) + tail, head + tail
+        section, checked = head + payload + tail, head + tail
     if band_crcs is not None:
         crcs = np.ascontiguousarray(np.asarray(band_crcs).astype(np.int64) & 0xffffffff, dtype='<u4').reshape(3, -1)
         n = crcs.shape[1]
@@ -722,15 +858,25 @@ def split_seal(data, view=False):
         if S < 16 + 12 or S > end - 14 - 4 or bytes(data[end - S - 4:end - S]) != _MAGIC_VALUE_SEP:
             raise ValueError("invalid file: seal parity section does not start behind the file's last scale separator")
         section_at, end = end - S, end - S
-        if bytes(data[section_at:section_at + 4]) != PARITY_SIGNATURE:
+        rs = bytes(data[section_at:section_at + 4]) == PARITY_RS_SIGNATURE
+        if not rs and bytes(data[section_at:section_at + 4]) != PARITY_SIGNATURE:
             raise ValueError("invalid file: seal parity section without its 'L3CP' signature")
         G, m = struct.unpack('<HH', bytes(data[section_at + 4:section_at + 8]))
-        if m < 1 or 16 + 12 * m > S:
+        fields_at, R = (12 if rs else 8), 1                              # where plen starts inside the section
+        if m < 1 or fields_at + 8 + 12 * m > S:
             raise ValueError('invalid file: seal parity section is too short for its {} x 3 length fields'.format(m))
-        plen = np.frombuffer(bytes(data[section_at + 8:section_at + 8 + 12 * m]), dtype='<u4').astype(np.int64).reshape(3, m)
-        if S != 16 + 12 * m + int(plen.sum()):
+        if rs:
+            R, reserved = struct.unpack('<HH', bytes(data[section_at + 8:section_at + 12]))
+            if not 2 <= R <= MAX_PARITY_STREAMS:
+                raise ValueError("invalid file: seal parity section states {} parity streams, an 'L3CQ' section holds 2..4".format(R))
+            if reserved:
+                raise ValueError('invalid file: seal parity section with a non-zero reserved field')
+        plen = np.frombuffer(bytes(data[section_at + fields_at:section_at + fields_at + 12 * m]), dtype='<u4').astype(np.int64).reshape(3, m)
+        if not rs and S != 16 + 12 * m + int(plen.sum()):
             raise ValueError('invalid file: seal parity section length is not 16 + 12 m + the sum of its payload lengths')
-        checked = bytes(data[section_at:section_at + 8 + 12 * m]) + bytes(data[section_at + S - 8:section_at + S])
+        if rs and S != 20 + 12 * m + R * int(plen.sum()):
+            raise ValueError('invalid file: seal parity section length is not 20 + 12 m + R times the sum of its payload lengths')
+        checked = bytes(data[section_at:section_at + fields_at + 12 * m]) + bytes(data[section_at + S - 8:section_at + S])
     if flags:
         raise ValueError('invalid file: seal with non-zero flags')
     body = (memoryview(data) if view else data)[:end]
@@ -751,16 +897,19 @@ def split_seal(data, view=False):
         return body, Seal(generation, frame_crc, model_id, L, crcs)
     if finest[0] != 3 or not 1 <= G <= n or m != -(-n // G):
         raise ValueError("invalid file: seal parity section does not match the bands of the file's finest scale record")
+    if R > 1 and G > MAX_RS_GROUP:
+        raise ValueError('invalid file: seal parity section with more than one stream over groups of more than 255 bands')
     lens = _band_lengths_of_finest(body, first, 3, n)
     if any(int(plen[c, g]) != int(lens[c, g::m].max()) for c in range(3) for g in range(m)):
         raise ValueError("invalid file: seal parity section states a payload length that is not its longest member's")
-    view, at, rows = memoryview(data), section_at + 8 + 12 * m, []
+    view, at, rows = memoryview(data), section_at + fields_at + 12 * m, []
     for c in range(3):
         rows.append([])
         for g in range(m):
-            rows[c].append(view[at:at + int(plen[c, g])])
-            at += int(plen[c, g])
-    return body, Seal(generation, frame_crc, model_id, L, crcs, G, rows)
+            k = int(plen[c, g])
+            rows[c].append(view[at:at + k] if R == 1 else [view[at + r * k:at + (r + 1) * k] for r in range(R)])
+            at += R * k
+    return body, Seal(generation, frame_crc, model_id, L, crcs, G, rows, R)
 
 
 def band_rows(j, L, frame_hw, padding):

@@ -8,6 +8,11 @@
 // A wave reads 1 KiB of a member per step; the members of a group are independent loads, issued eight deep.
 // Stores are 16 bytes where the slot is 16-byte aligned and the 16 bytes lie inside what the call writes, dwords otherwise; nothing outside
 // that range is written.  No atomics, no LDS, no allocation, no host synchronisation.
+//
+// l3c_band_parity_rs and l3c_u8_gf_spans are the same two kernels over GF(2^8) (polynomial 0x11D, alpha = 0x02: the 'L3CQ' section of
+// csrc/seal.h), with the same loads, masks and stores.  The only field operation is "times alpha" on four packed bytes (xtime: 5 VALU
+// instructions per dword): the encoder keeps R accumulators and applies Horner's rule over the members, so a member is loaded once for all
+// rows; the repair side multiplies each member by a coefficient that is uniform over the block, by shift and add under scalar branches.
 #include "l3c_common.h"
 #include "parity_plan.h"
 
@@ -130,6 +135,104 @@ __global__ __launch_bounds__(THREADS) void u8_xor_spans_kernel(const uint8_t *__
     store16(out + slot.offset, off, end, acc);
 }
 
+// ---- GF(2^8), polynomial 0x11D, alpha = 0x02, on four packed bytes per dword ------------------------------------------------------------------
+
+// alpha times each byte of v: the byte shifted left, 0x1D added where its top bit was set
+__device__ __forceinline__ uint32_t xtime(uint32_t v) { return ((v & 0x7f7f7f7fu) << 1) ^ (((v >> 7) & 0x01010101u) * 0x1du); }
+__device__ __forceinline__ u32x4 xtime(u32x4 q) { return u32x4{xtime(q.x), xtime(q.y), xtime(q.z), xtime(q.w)}; }
+
+// c times each byte of q, c uniform over the block: shift and add, one uniform branch per bit of c
+__device__ __forceinline__ u32x4 gf_scale(u32x4 q, uint32_t c) {
+    u32x4 r = {0u, 0u, 0u, 0u};
+    while (c) {
+        if (c & 1u) r ^= q;
+        c >>= 1;
+        if (c) q = xtime(q);
+    }
+    return r;
+}
+
+// band_parity_kernel for R rows per group: row r = XOR over members k of alpha^(k r) d_k, by Horner from the last member to the first,
+// acc_r = alpha^r acc_r ^ d_k -- every member is loaded once for all rows.  Members eight at a time as in fold_members, the batches taken from
+// the top; the batch that holds the last member is filled up with empty members ABOVE it, where every acc is still zero.
+// grid (tiles, B 3 m); the slot of row r of stream y is parity + (y R + r) parity_stride
+template <int R>
+__global__ __launch_bounds__(THREADS) void band_parity_rs_kernel(l3c_banded_scale sc, int64_t n, int64_t m, uint8_t *__restrict__ parity,
+                                                                int64_t parity_stride, uint32_t *__restrict__ parity_nbytes) {
+    const int64_t y = blockIdx.y, s = y / m, g = y - s * m;
+    const int64_t count = (n - g + m - 1) / m;
+    uint32_t plen = 0;
+    bool overrun = false;
+    for (int64_t k = 0; k < count; ++k) {
+        const uint32_t len = band_nbytes(sc, n, s, g + k * m);
+        overrun |= len == L3C_AC_OVERRUN;
+        plen = len > plen ? len : plen;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) parity_nbytes[y] = overrun ? L3C_AC_OVERRUN : plen;
+    if (overrun) return;
+    const int64_t end4 = ((int64_t)plen + 3) & ~(int64_t)3;
+    const int64_t off = (int64_t)blockIdx.x * TILE_BYTES + 16 * threadIdx.x;
+    if (off >= end4) return;
+    u32x4 acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = u32x4{0u, 0u, 0u, 0u};
+    for (int64_t k0 = (count - 1) / DEPTH * DEPTH; k0 >= 0; k0 -= DEPTH) {
+        Member mem[DEPTH];
+        u32x4 q[DEPTH];
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) {
+            const int64_t j = g + (k0 + u) * m;
+            mem[u] = k0 + u < count ? Member{band_row(sc, n, s, j), (int64_t)band_nbytes(sc, n, s, j)} : Member{nullptr, 0};
+        }
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) q[u] = load16(mem[u], off);
+#pragma unroll
+        for (int u = DEPTH - 1; u >= 0; --u) {
+            const u32x4 d = mask16(q[u], mem[u].len, off);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+#pragma unroll
+                for (int i = 0; i < r; ++i) acc[r] = xtime(acc[r]);
+                acc[r] ^= d;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) store16(parity + (y * R + r) * parity_stride, off, end4, acc[r]);
+}
+
+// u8_xor_spans_kernel with a coefficient per span: slot g = XOR of coef[k] * span k.  A span with coef 0 becomes an empty member: not read.
+__global__ __launch_bounds__(THREADS) void u8_gf_spans_kernel(const uint8_t *__restrict__ data, const l3c_u8_span *__restrict__ spans,
+                                                             const uint8_t *__restrict__ coef, const int64_t *__restrict__ group_first,
+                                                             const l3c_u8_span *__restrict__ out_spans, uint8_t *__restrict__ out) {
+    const int64_t g = blockIdx.y;
+    const l3c_u8_span slot = out_spans[g];
+    const int64_t end = slot_bytes(slot.bytes);
+    const int64_t off = (int64_t)blockIdx.x * TILE_BYTES + 16 * threadIdx.x;
+    if (off >= end) return;
+    const int64_t k0 = group_first[g], count = group_first[g + 1] - k0;
+    u32x4 acc = {0u, 0u, 0u, 0u};
+    for (int64_t k = 0; k < count; k += DEPTH) {
+        Member mem[DEPTH];
+        uint32_t c[DEPTH];
+        u32x4 q[DEPTH];
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) {
+            c[u] = k + u < count ? coef[k0 + k + u] : 0u;
+            mem[u] = Member{nullptr, 0};
+            if (c[u]) {
+                const l3c_u8_span src = spans[k0 + k + u];
+                mem[u] = Member{data + src.offset, src.bytes < slot.bytes ? src.bytes : slot.bytes};
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) q[u] = load16(mem[u], off);
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) acc ^= gf_scale(mask16(q[u], mem[u].len, off), c[u]);
+    }
+    store16(out + slot.offset, off, end, acc);
+}
+
 }  // namespace
 
 extern "C" {
@@ -139,8 +242,9 @@ int l3c_band_parity_groups(int n, int G) {
     return (n + G - 1) / G;
 }
 
-int l3c_band_parity(const l3c_banded_scale *scale_host, int64_t B, int G, uint8_t *parity, int64_t parity_stride, uint32_t *parity_nbytes,
-                    l3c_stream_t stream) {
+// the argument checks of l3c_band_parity and l3c_band_parity_rs, all before the launch -> L3C_OK with n, m and the longest coder stride
+static int check_band_parity(const l3c_banded_scale *scale_host, int64_t B, int G, int R, const uint8_t *parity, int64_t parity_stride,
+                             const uint32_t *parity_nbytes, int64_t *n_out, int64_t *m_out, int64_t *longest_out) {
     L3C_REQUIRE(scale_host && parity && parity_nbytes, "null pointer");
     const l3c_banded_scale sc = *scale_host;
     L3C_REQUIRE(sc.C == 3 && sc.H > 0 && sc.W > 0, "the parity covers the finest record: C must be 3, H and W positive");
@@ -148,6 +252,8 @@ int l3c_band_parity(const l3c_banded_scale *scale_host, int64_t B, int G, uint8_
     const int64_t hw = (int64_t)sc.H * sc.W, n = (hw + sc.band_len - 1) / sc.band_len;
     L3C_REQUIRE(n <= 1024, "more than 1024 bands per channel");
     L3C_REQUIRE(G >= 1 && G <= n, "G must be in 1..n");
+    L3C_REQUIRE(R >= 1 && R <= 4, "R must be in 1..4");
+    L3C_REQUIRE(R == 1 || G <= 255, "more than one parity stream needs groups of at most 255 bands");
     const int64_t m = (n + G - 1) / G;
     L3C_REQUIRE(B >= 1 && B <= MAX_STREAMS / (3 * m), "bad batch size: B * 3 * m must be in 1..65535");
     L3C_REQUIRE(sc.out_last && sc.nbytes_last && (n == 1 || (sc.out_full && sc.nbytes_full)), "null pointer in the scale");
@@ -155,15 +261,40 @@ int l3c_band_parity(const l3c_banded_scale *scale_host, int64_t B, int G, uint8_
                 "the coder strides must be positive multiples of 4");
     const int64_t longest = n > 1 && sc.stride_full > sc.stride_last ? sc.stride_full : sc.stride_last;
     L3C_REQUIRE(parity_stride % 16 == 0 && parity_stride >= longest, "parity_stride must be a multiple of 16 and at least the coder strides");
-    L3C_REQUIRE(parity_stride <= INT64_MAX / MAX_STREAMS && tiles_of(longest) <= 0x7fffffff, "stride out of range");
+    L3C_REQUIRE(parity_stride <= INT64_MAX / (MAX_STREAMS * 4) && tiles_of(longest) <= 0x7fffffff, "stride out of range");
     L3C_REQUIRE((reinterpret_cast<uintptr_t>(sc.out_last) & 3) == 0 && (reinterpret_cast<uintptr_t>(sc.out_full) & 3) == 0 &&
                     (reinterpret_cast<uintptr_t>(sc.nbytes_last) & 3) == 0 && (reinterpret_cast<uintptr_t>(sc.nbytes_full) & 3) == 0 &&
                     (reinterpret_cast<uintptr_t>(parity_nbytes) & 3) == 0,
                 "the coder outputs and the length arrays must be 4-byte aligned");
     L3C_REQUIRE((reinterpret_cast<uintptr_t>(parity) & 15) == 0, "parity must be 16-byte aligned");
-    hipLaunchKernelGGL(band_parity_kernel, dim3((unsigned)tiles_of(longest), (unsigned)(B * 3 * m)), dim3(THREADS), 0, l3c::as_stream(stream), sc, n, m,
-                       parity, parity_stride, parity_nbytes);
+    *n_out = n, *m_out = m, *longest_out = longest;
+    return L3C_OK;
+}
+
+int l3c_band_parity(const l3c_banded_scale *scale_host, int64_t B, int G, uint8_t *parity, int64_t parity_stride, uint32_t *parity_nbytes,
+                    l3c_stream_t stream) {
+    int64_t n, m, longest;
+    const int rc = check_band_parity(scale_host, B, G, 1, parity, parity_stride, parity_nbytes, &n, &m, &longest);
+    if (rc != L3C_OK) return rc;
+    hipLaunchKernelGGL(band_parity_kernel, dim3((unsigned)tiles_of(longest), (unsigned)(B * 3 * m)), dim3(THREADS), 0, l3c::as_stream(stream),
+                       *scale_host, n, m, parity, parity_stride, parity_nbytes);
     return l3c::check_launch("band_parity_kernel");
+}
+
+int l3c_band_parity_rs(const l3c_banded_scale *scale_host, int64_t B, int G, int R, uint8_t *parity, int64_t parity_stride, uint32_t *parity_nbytes,
+                       l3c_stream_t stream) {
+    int64_t n, m, longest;
+    const int rc = check_band_parity(scale_host, B, G, R, parity, parity_stride, parity_nbytes, &n, &m, &longest);
+    if (rc != L3C_OK) return rc;
+    const dim3 grid((unsigned)tiles_of(longest), (unsigned)(B * 3 * m));
+    const hipStream_t st = l3c::as_stream(stream);
+    switch (R) {
+    case 1: hipLaunchKernelGGL(band_parity_rs_kernel<1>, grid, dim3(THREADS), 0, st, *scale_host, n, m, parity, parity_stride, parity_nbytes); break;
+    case 2: hipLaunchKernelGGL(band_parity_rs_kernel<2>, grid, dim3(THREADS), 0, st, *scale_host, n, m, parity, parity_stride, parity_nbytes); break;
+    case 3: hipLaunchKernelGGL(band_parity_rs_kernel<3>, grid, dim3(THREADS), 0, st, *scale_host, n, m, parity, parity_stride, parity_nbytes); break;
+    default: hipLaunchKernelGGL(band_parity_rs_kernel<4>, grid, dim3(THREADS), 0, st, *scale_host, n, m, parity, parity_stride, parity_nbytes); break;
+    }
+    return l3c::check_launch("band_parity_rs_kernel");
 }
 
 int l3c_u8_xor_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, int64_t n_spans,
@@ -182,5 +313,23 @@ int l3c_u8_xor_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span 
     hipLaunchKernelGGL(u8_xor_spans_kernel, dim3((unsigned)tiles, (unsigned)n_groups), dim3(THREADS), 0, l3c::as_stream(stream), data, spans,
                        group_first, out_spans, out);
     return l3c::check_launch("u8_xor_spans_kernel");
+}
+
+int l3c_u8_gf_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, const uint8_t *coef_host,
+                    const uint8_t *coef, int64_t n_spans, const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups,
+                    const l3c_u8_span *out_spans_host, const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream) {
+    L3C_REQUIRE(n_groups >= 0, "n_groups must not be negative");
+    if (n_groups == 0) return L3C_OK;
+    const int64_t tiles = check_xor_spans(spans_host, n_spans, group_first_host, n_groups, out_spans_host, data_bytes, out_bytes, l3c::error_buffer(), 512);
+    if (tiles < 0) return (int)tiles;
+    L3C_REQUIRE(out && group_first && out_spans && (n_spans == 0 || (data && spans && coef_host && coef)), "null pointer");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(data) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0, "data and out must be 4-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(spans) & 7) == 0 && (reinterpret_cast<uintptr_t>(group_first) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(out_spans) & 7) == 0,
+                "spans, group_first and out_spans (the device tables) must be 8-byte aligned");
+    L3C_REQUIRE(n_spans == 0 || out + out_bytes <= data || data + data_bytes <= out, "out must not overlap data");
+    hipLaunchKernelGGL(u8_gf_spans_kernel, dim3((unsigned)tiles, (unsigned)n_groups), dim3(THREADS), 0, l3c::as_stream(stream), data, spans, coef,
+                       group_first, out_spans, out);
+    return l3c::check_launch("u8_gf_spans_kernel");
 }
 }

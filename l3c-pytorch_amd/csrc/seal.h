@@ -27,6 +27,15 @@
 // m = ceil(n / G); group g of channel c holds the bands { j : j % m == g }; its payload is the XOR of the members' payloads, each
 // zero-extended to plen[c][g], the longest member's byte count.  check = CRC-32 of the 8 padding bytes, section bytes [0, 8 + 12 m), the
 // section's last 8 bytes, the band table, seal bytes 0..19: the parity payloads are NOT under it.
+//
+// Version 3 with R = 2..4 parity streams per group carries a section of a second kind, S = 20 + 12 m + R sum(plen):
+//
+//     0 'L3CQ' | 4 u16 G | 6 u16 m | 8 u16 R | 10 u16 0 | 12 u32 plen[3][m] | 12 + 12 m the 3 m R payloads, (c, g, r) order, plen[c][g] bytes each | S - 8 u32 S | S - 4 separator
+//
+// Row r of group g is the XOR over its members k (band j = g + k m) of (alpha^k)^r d_k in GF(2^8), polynomial 0x11D, alpha = 0x02; row 0 is the
+// 'L3CP' payload.  G <= 255 so that the points alpha^k of a group are distinct.  check covers section bytes [0, 12 + 12 m) and the last 8.
+// R = 1 is always written as 'L3CP'.  find_parity reports an 'L3CQ' section as m = 0 (the band-sealed file it contains); find_parity_rs
+// reports both kinds, 'L3CP' as R = 1.
 #ifndef L3C_SEAL_H_
 #define L3C_SEAL_H_
 
@@ -42,6 +51,8 @@ namespace l3c_sealing {
 constexpr int VERSION = 1, VERSION_BANDS = 2, VERSION_PARITY = 3, MAX_BANDS = 1024;
 constexpr uint8_t TABLE_SIGNATURE[4] = {'L', '3', 'C', 'T'};
 constexpr uint8_t PARITY_SIGNATURE[4] = {'L', '3', 'C', 'P'};
+constexpr uint8_t PARITY_RS_SIGNATURE[4] = {'L', '3', 'C', 'Q'};
+constexpr int MAX_PARITY_STREAMS = 4, MAX_RS_GROUP = 255;
 constexpr uint8_t SIGNATURE[4] = {'L', '3', 'C', 'S'};
 constexpr uint8_t SEPARATOR[4] = {0x46, 0xE2, 0x84, 0x92};
 constexpr uint8_t BANDED_SIGNATURE[4] = {'L', '3', 'C', 'B'};
@@ -191,14 +202,53 @@ inline void write_parity(const l3c_seal &s, const uint8_t *padding8, const uint8
     put(seal + 20, crc32(crc32(crc32(crc32(0, padding8, 8), dst, head), dst + S - 8, 8), t, T + 20), 4);
 }
 
+// an 'L3CQ' section of R streams: rs_section_bytes(m, R, sum of plen)
+constexpr int64_t rs_section_bytes(int64_t m, int64_t R, int64_t plen_sum) { return 20 + 12 * m + R * plen_sum; }
+
+// write_parity for R parity streams per group (payloads: (c, g, r) order, plen[c][g] bytes each).  R == 1 writes the 'L3CP' section of
+// write_parity, R in 2..4 the 'L3CQ' one.
+inline void write_parity_rs(const l3c_seal &s, const uint8_t *padding8, const uint8_t *band_crc, int n, uint32_t band_len, int G, int m, int R,
+                            const uint32_t *plen, const uint8_t *payloads, uint8_t *dst) {
+    if (R == 1) return write_parity(s, padding8, band_crc, n, band_len, G, m, plen, payloads, dst);
+    int64_t sum = 0;
+    for (int i = 0; i < 3 * m; ++i) sum += plen[i];
+    const int64_t S = rs_section_bytes(m, R, sum), T = table_bytes(n), head = 12 + 12 * (int64_t)m;
+    memcpy(dst, PARITY_RS_SIGNATURE, 4);
+    put(dst + 4, (uint64_t)G, 2);
+    put(dst + 6, (uint64_t)m, 2);
+    put(dst + 8, (uint64_t)R, 2);
+    put(dst + 10, 0, 2);
+    for (int i = 0; i < 3 * m; ++i) put(dst + 12 + 4 * i, plen[i], 4);
+    if (sum) memcpy(dst + head, payloads, (size_t)(R * sum));
+    put(dst + S - 8, (uint64_t)S, 4);
+    memcpy(dst + S - 4, SEPARATOR, 4);
+    uint8_t *t = dst + S;
+    memcpy(t, TABLE_SIGNATURE, 4);
+    put(t + 4, (uint64_t)n, 2);
+    put(t + 6, 0, 2);
+    put(t + 8, band_len, 4);
+    memmove(t + 12, band_crc, 12 * (size_t)n);
+    put(t + 12 + 12 * n, (uint64_t)T, 4);
+    memcpy(t + 16 + 12 * n, SEPARATOR, 4);
+    uint8_t *seal = t + T;
+    memcpy(seal, SIGNATURE, 4);
+    seal[4] = VERSION_PARITY;
+    seal[5] = 0;
+    put(seal + 6, s.generation, 2);
+    put(seal + 8, s.frame_crc, 4);
+    put(seal + 12, s.model_id, 8);
+    put(seal + 20, crc32(crc32(crc32(crc32(0, padding8, 8), dst, head), dst + S - 8, 8), t, T + 20), 4);
+}
+
 // 1: sealed, 0: unsealed, L3C_ERR_INVALID_ARG (message in err): a recognised seal that is damaged.  *body_bytes_out: the bytes in front of
 // the seal, in front of the band table where the seal has one, in front of the parity section where it has one.  bands_out (may be null):
-// n = 0 for a version-1 seal.  parity_out (may be null): m = 0 unless the seal is of version 3.
-inline int find_parity(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
-                       l3c_seal_parity *parity_out, char *err, size_t cap) {
+// n = 0 for a version-1 seal.  parity_out (may be null): m = 0 unless the seal is of version 3; R = 1 for an 'L3CP' section, 2..4 for 'L3CQ'.
+inline int find_parity_rs(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
+                          l3c_seal_parity_rs *parity_out, char *err, size_t cap) {
     if (body_bytes_out) *body_bytes_out = file_bytes;
     if (bands_out) bands_out->n = 0, bands_out->band_len = 0, bands_out->crc = nullptr;
-    if (parity_out) parity_out->G = 0, parity_out->m = 0, parity_out->plen = nullptr, parity_out->payloads = nullptr, parity_out->payload_bytes = 0;
+    if (parity_out)
+        parity_out->G = 0, parity_out->m = 0, parity_out->R = 0, parity_out->plen = nullptr, parity_out->payloads = nullptr, parity_out->payload_bytes = 0;
     if (file_bytes < L3C_SEAL_BYTES + 4) return 0;
     const uint8_t *s = file + file_bytes - L3C_SEAL_BYTES;
     if (memcmp(s, SIGNATURE, 4) != 0 || memcmp(s - 4, SEPARATOR, 4) != 0) return 0;
@@ -207,7 +257,7 @@ inline int find_parity(const uint8_t *file, int64_t file_bytes, int64_t *body_by
     const int64_t padding_at = banded ? 6 : 0;
     const int version = s[4];
     if (version != VERSION && version != VERSION_BANDS && version != VERSION_PARITY) return fail(err, cap, "of an unknown version");
-    int64_t T = 0, n = 0, S = 0, m = 0, G = 0, table_at = 0;
+    int64_t T = 0, n = 0, S = 0, m = 0, G = 0, R = 0, fields_at = 8, table_at = 0;      // fields_at: where plen starts inside the section
     if (version != VERSION) {
         if (!banded)
             return fail(err, cap, version == VERSION_BANDS ? "of an unknown version for a legacy file (version 2, the band seal, needs a banded file)"
@@ -231,18 +281,27 @@ inline int find_parity(const uint8_t *file, int64_t file_bytes, int64_t *body_by
             return fail(err, cap, "parity section does not start behind the file's last scale separator");
         body -= S;
         const uint8_t *p = file + body;
-        if (memcmp(p, PARITY_SIGNATURE, 4) != 0) return fail(err, cap, "parity section without its 'L3CP' signature");
-        G = (int64_t)get(p + 4, 2), m = (int64_t)get(p + 6, 2);
-        if (m < 1 || 16 + 12 * m > S) return fail_d(err, cap, "parity section is too short for its %d x 3 length fields", (int)m);
+        const bool rs = memcmp(p, PARITY_RS_SIGNATURE, 4) == 0;
+        if (!rs && memcmp(p, PARITY_SIGNATURE, 4) != 0) return fail(err, cap, "parity section without its 'L3CP' signature");
+        G = (int64_t)get(p + 4, 2), m = (int64_t)get(p + 6, 2), R = 1;
+        if (rs) fields_at = 12;
+        if (m < 1 || fields_at + 8 + 12 * m > S) return fail_d(err, cap, "parity section is too short for its %d x 3 length fields", (int)m);
+        if (rs) {
+            R = (int64_t)get(p + 8, 2);
+            if (R < 2 || R > MAX_PARITY_STREAMS) return fail_d(err, cap, "parity section states %d parity streams, an 'L3CQ' section holds 2..4", (int)R);
+            if (get(p + 10, 2) != 0) return fail(err, cap, "parity section with a non-zero reserved field");
+        }
         int64_t sum = 0;
-        for (int64_t i = 0; i < 3 * m; ++i) sum += (int64_t)get(p + 8 + 4 * i, 4);
-        if (S != section_bytes(m, sum)) return fail(err, cap, "parity section length is not 16 + 12 m + the sum of its payload lengths");
+        for (int64_t i = 0; i < 3 * m; ++i) sum += (int64_t)get(p + fields_at + 4 * i, 4);
+        if (!rs && S != section_bytes(m, sum)) return fail(err, cap, "parity section length is not 16 + 12 m + the sum of its payload lengths");
+        if (rs && S != rs_section_bytes(m, R, sum))
+            return fail(err, cap, "parity section length is not 20 + 12 m + R times the sum of its payload lengths");
     }
     if (s[5] != 0) return fail(err, cap, "with non-zero flags");
     if (padding_at + 8 > body) return fail(err, cap, "on a file too short for its padding fields");
     {
         uint32_t c = crc32(0, file + padding_at, 8);
-        if (S) c = crc32(crc32(c, file + body, 8 + 12 * m), file + body + S - 8, 8);
+        if (S) c = crc32(crc32(c, file + body, fields_at + 12 * m), file + body + S - 8, 8);
         if (get(s + 20, 4) != crc32(crc32(c, file + table_at, T), s, 20))
             return fail(err, cap, "check word does not match (damaged seal or padding fields)");
     }
@@ -258,6 +317,7 @@ inline int find_parity(const uint8_t *file, int64_t file_bytes, int64_t *body_by
             const uint8_t *p = file + body;
             if (rec_C != 3 || G < 1 || G > n || m != (n + G - 1) / G)
                 return fail(err, cap, "parity section does not match the bands of the file's finest scale record");
+            if (R > 1 && G > MAX_RS_GROUP) return fail(err, cap, "parity section with more than one stream over groups of more than 255 bands");
             // every plen[c][g] against the length fields of its members, band j of channel c in group j % m (finest_record has walked them)
             int64_t at = first;
             for (int64_t c = 0; c < 3; ++c) {
@@ -269,12 +329,12 @@ inline int find_parity(const uint8_t *file, int64_t file_bytes, int64_t *body_by
                     if (len > longest[j % m]) longest[j % m] = len;
                 }
                 for (int64_t g = 0; g < m; ++g)
-                    if ((uint32_t)get(p + 8 + 4 * (c * m + g), 4) != longest[g])
+                    if ((uint32_t)get(p + fields_at + 4 * (c * m + g), 4) != longest[g])
                         return fail(err, cap, "parity section states a payload length that is not its longest member's");
             }
             if (parity_out)
-                parity_out->G = (int32_t)G, parity_out->m = (int32_t)m, parity_out->plen = p + 8, parity_out->payloads = p + 8 + 12 * m,
-                parity_out->payload_bytes = S - 16 - 12 * m;
+                parity_out->G = (int32_t)G, parity_out->m = (int32_t)m, parity_out->R = (int32_t)R, parity_out->plen = p + fields_at,
+                parity_out->payloads = p + fields_at + 12 * m, parity_out->payload_bytes = S - fields_at - 8 - 12 * m;
         }
         if (bands_out) bands_out->n = (int32_t)n, bands_out->band_len = rec_len, bands_out->crc = t + 12;
     }
@@ -285,6 +345,20 @@ inline int find_parity(const uint8_t *file, int64_t file_bytes, int64_t *body_by
         seal_out->model_id = get(s + 12, 8);
     }
     return 1;
+}
+
+// find_parity_rs for callers that know the 'L3CP' section alone: an 'L3CQ' file reads as the band-sealed file it contains, m = 0
+inline int find_parity(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
+                       l3c_seal_parity *parity_out, char *err, size_t cap) {
+    l3c_seal_parity_rs rs;
+    const int rc = find_parity_rs(file, file_bytes, body_bytes_out, seal_out, bands_out, &rs, err, cap);
+    if (parity_out) {
+        parity_out->G = 0, parity_out->m = 0, parity_out->plen = nullptr, parity_out->payloads = nullptr, parity_out->payload_bytes = 0;
+        if (rc == 1 && rs.R == 1)
+            parity_out->G = rs.G, parity_out->m = rs.m, parity_out->plen = rs.plen, parity_out->payloads = rs.payloads,
+            parity_out->payload_bytes = rs.payload_bytes;
+    }
+    return rc;
 }
 
 inline int find_bands(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out, char *err,

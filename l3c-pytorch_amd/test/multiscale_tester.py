@@ -200,7 +200,7 @@ class MultiscaleTester(object):
                             compare_with_theory=bool(getattr(flags, 'compare_theory', False)), auto_recurse=self.recursive,
                             file_writer=self.file_writer, bands=int(getattr(flags, 'bands', 0) or 0),
                             seal='bands' if getattr(flags, 'seal_bands', False) else bool(getattr(flags, 'seal', False)),
-                            parity=int(getattr(flags, 'parity', 0) or 0))
+                            parity=int(getattr(flags, 'parity', 0) or 0), parity_streams=int(getattr(flags, 'parity_streams', 1) or 1))
         self.max_batch = int(getattr(flags, 'batch', None) or 8)
         self.io_threads = int(getattr(flags, 'io_threads', None) or 4)
         exp_name = os.path.basename(experiment_dir)

@@ -76,6 +76,9 @@ def main(argv=None):
                      help='with --bands --seal-bands: add PARITY BANDS, an XOR parity stream per group of G bands of the finest record (about '
                           '1 / G more bytes; the flag alone: {}): dec --repair then rebuilds one damaged band per group, bit for '
                           'bit'.format(DEFAULT_PARITY))
+    enc.add_argument('--parity-streams', dest='parity_streams', type=int, default=1, choices=(1, 2, 3, 4), metavar='R',
+                     help='with --parity: R parity streams per group over GF(2^8) instead of one (about R / G more bytes): dec --repair then '
+                          'rebuilds up to R damaged bands per group, and a damaged parity stream leaves R - 1 usable')
     dec.add_argument('img_p')
     dec.add_argument('out_p_png')
     dec.add_argument('--no-verify', dest='no_verify', action='store_true', help='do not check the seal of a sealed file')
