@@ -104,8 +104,8 @@ class EncodedBatch(object):
         self.band_crc = None                 # Bitcoding(seal='bands'): int32 (B, 3, n) device tensor, CRC-32 of every band of the finest record's
         self.band_len = None                 # ... planes (ops.u8_crc32_bands, with frame_crc from the same pass), and that record's band length
         self.parity_group = 0                # Bitcoding(parity=G): the group size asked for (the seal states min(G, n)) ...
-        self.parity = None                   # ... and (uint8 (B, 3, m, stride), int32 (B, 3, m)) of ops.band_parity on the finest record's coder output
-        self.parity_streams = 1              # Bitcoding(parity_streams=R): R > 1 -> (uint8 (B, 3, m, R, stride), int32 (B, 3, m)) of ops.band_parity_rs
+        self.parity = None                   # ... and (uint8 (B, 3, m, R, stride), int32 (B, 3, m)) on the finest record's coder output: of
+        self.parity_streams = 1              # ops.band_parity_rs for Bitcoding(parity_streams=R) above 1, a view of ops.band_parity's slots for R = 1
 
     def _coder_outputs(self):
         """(C, H, W, out, nbytes) of every coder group, nbytes reshaped to (B, streams per image of that group)."""
@@ -234,17 +234,14 @@ class EncodedBatch(object):
             parity = [None] * e.B
             if e.parity is not None:
                 slots, lens = e.parity
-                m, stride, R = slots.shape[2], slots.shape[-1], e.parity_streams
+                m, R = slots.shape[2], slots.shape[3]
                 nb = EncodedBatch._checked_nbytes(words[at:at + lens.numel()].view(np.int32)).reshape(e.B, 3, m)
                 at += lens.numel()
                 host = words[at:at + slots.numel() // 4].view(np.uint8).reshape(slots.shape)
                 at += slots.numel() // 4
                 G = min(e.parity_group, bands[0].shape[1])
-                if R == 1:
-                    parity = [(G, [[host[b, c, g, :nb[b, c, g]].tobytes() for g in range(m)] for c in range(3)]) for b in range(e.B)]
-                else:
-                    parity = [(G, [[[host[b, c, g, r, :nb[b, c, g]].tobytes() for r in range(R)] for g in range(m)] for c in range(3)])
-                              for b in range(e.B)]
+                parity = [(G, [[[host[b, c, g, r, :nb[b, c, g]].tobytes() for r in range(R)] for g in range(m)] for c in range(3)])
+                          for b in range(e.B)]
             res.append([container.make_seal(body, e.seal[0], frame[b], e.seal[1], bands[b], e.band_len, parity=parity[b])
                         for b, body in enumerate(files)])
         return res
@@ -544,7 +541,8 @@ class Bitcoding(object):
                         container.check_parity_streams(enc.parity_streams, G, G)
                         enc.parity = ops.band_parity_rs(enc.B, Hs, Ws, L, coded, G, enc.parity_streams)
                     else:
-                        enc.parity = ops.band_parity(enc.B, Hs, Ws, L, coded, G)
+                        slots, nb = ops.band_parity(enc.B, Hs, Ws, L, coded, G)
+                        enc.parity = (slots.unsqueeze(3), nb)
             done = torch.cuda.Event()
             done.record(side)
         g = 0
@@ -699,6 +697,15 @@ class Bitcoding(object):
         mixture's mean, conditioned on the channels of the pixel that verified -- and one ops.sym_to_u8.  Every verified pixel comes back
         exact; info says which is which (concealed, rows, lost, unverified).  An intact batch: no conceal launch, the pixels of
         decode_batch.  Legacy files among banded ones are refused as decode_batch refuses them."""
+        seals, records, framing, streams, sym, P, dmll = self._decode_keeping_finest(files)
+        pixels, info = self._salvage(seals, sym.to(torch.uint8), sym, P, framing.padding, self.blueprint.net.config_ms.prob.K,
+                                     (dmll.x_min, dmll.x_max, dmll.L))
+        return pixels.to(out_dtype), framing.padding, info
+
+    def _decode_keeping_finest(self, files):
+        """What decode_salvage and decode_repair open with: the seals split off and checked (SealError 'generation' / 'model'), the files
+        parsed and uploaded, decode_batch's walk with the finest scale's P and mixture kept
+        -> (seals, records, framing, streams, int16 symbols (B, 3, H, W), P, dmll)."""
         split = [container.split_seal(f, view=True) for f in files]
         files, seals = [b for b, _ in split], [s for _, s in split]
         if any(s is not None for s in seals):
@@ -709,10 +716,7 @@ class Bitcoding(object):
         streams = upload._upload_streams(files, framing)
         kept = {}
         sym = self._walk_records(records, framing, banded, streams, n_pred, len(records), None, keep_finest=kept)
-        dmll = kept['dmll']
-        pixels, info = self._salvage(seals, sym.to(torch.uint8), sym, kept['P'], framing.padding, self.blueprint.net.config_ms.prob.K,
-                                     (dmll.x_min, dmll.x_max, dmll.L))
-        return pixels.to(out_dtype), framing.padding, info
+        return seals, records, framing, streams, sym, kept['P'], kept['dmll']
 
     @staticmethod
     def _salvage(seals, pixels, sym, P, padding, K, alphabet, words=None):
@@ -779,18 +783,7 @@ class Bitcoding(object):
         survives a damaged parity row.  No (group, erasure set, window) is tried twice.
         info.files: per file the HEALED file -- the rebuilt payloads spliced in at their framing offsets, the same length, section, table
         and seal --, None where nothing was repaired.  Files without parity, intact files and unsealed files: decode_salvage."""
-        raw = files
-        split = [container.split_seal(f, view=True) for f in files]
-        files, seals = [b for b, _ in split], [s for _, s in split]
-        if any(s is not None for s in seals):
-            container.check_seals(seals, self.generation(), self.model_id)
-        records, framing, banded = container.parse_batch(files)
-        n_pred = self._n_predicted(len(records))
-        self._check_coarsest(records[0], banded, int(framing.nbytes[0].max()))
-        streams = upload._upload_streams(files, framing)
-        kept = {}
-        sym = self._walk_records(records, framing, banded, streams, n_pred, len(records), None, keep_finest=kept)
-        dmll = kept['dmll']
+        seals, records, framing, streams, sym, P, dmll = self._decode_keeping_finest(files)
         K = self.blueprint.net.config_ms.prob.K
         pixels, B = sym.to(torch.uint8), len(files)
         band_lens = {s.band_len for s in seals if s is not None and s.band_crcs is not None}
@@ -799,8 +792,8 @@ class Bitcoding(object):
             L, = band_lens
             words = self._band_words(pixels, L)
             if any(s is not None and s.parity is not None for s in seals):
-                pixels, repaired, healed, rounds = self._repair(raw, seals, records[-1], framing, streams, pixels, sym, kept['P'], dmll, K, words)
-        pixels, salvage = self._salvage(seals, pixels, sym, kept['P'], framing.padding, K, (dmll.x_min, dmll.x_max, dmll.L), words)
+                pixels, repaired, healed, rounds = self._repair(files, seals, records[-1], framing, streams, pixels, sym, P, dmll, K, words)
+        pixels, salvage = self._salvage(seals, pixels, sym, P, framing.padding, K, (dmll.x_min, dmll.x_max, dmll.L), words)
         rows = {i: container.band_rows(sorted({j for _, j in got}), seals[i].band_len, records[-1][1:3], framing.padding[i])
                 for i, got in repaired.items()}
         return pixels.to(out_dtype), framing.padding, container.RepairInfo(repaired, rows, salvage, healed, rounds)
@@ -822,8 +815,8 @@ class Bitcoding(object):
         Kp = P.shape[-1]
         while True:
             _, failing, _ = container.failing_bands(seals, band_words, (H, W), framing.padding)
-            jobs = []                                                        # (file, c, j) to rebuild this round from an 'L3CP' section
-            rs_groups = []                                                   # (file, c, g, erased bands, r0) from an 'L3CQ' section
+            # (file, c, g, erased bands, r0): rows r0 .. r0 + t - 1 of the group rebuild its t erased bands; one row ('L3CP'): t = 1, r0 = 0
+            groups = []
             for i, bad in failing.items():
                 if seals[i].parity is None:
                     continue
@@ -835,70 +828,55 @@ class Bitcoding(object):
                 for (c, g), js in sorted(erasures.items()):
                     if len(js) > R or any((c, o) in bad for o in range(g, n, m) if o not in js):
                         continue
-                    if R == 1:
-                        if (i, c, js[0]) not in tried:
-                            jobs.append((i, c, js[0]))
-                        continue
                     # a window of len(js) consecutive rows, r0 = 0 first; a later one only where an earlier one left the positions failing
                     r0 = next((r for r in range(R - len(js) + 1) if (i, c, g, tuple(js), r) not in tried), None)
                     if r0 is not None:
-                        rs_groups.append((i, c, g, tuple(js), r0))
-            if not jobs and not rs_groups:
+                        groups.append((i, c, g, tuple(js), r0))
+            if not groups:
                 break
             rounds += 1
-            tried.update(jobs)
-            tried.update(rs_groups)
-            rs_jobs = [(i, c, j) for i, c, g, js, r0 in rs_groups for j in js]
-            # `work` grows by this round's region: the parity payloads (uploaded), then the output slots, all 16-byte aligned
-            base = al16(work.numel())
-            p_at, q_at, o_at, pos = [], [], [], base
-            for i, c, j in jobs:
-                p_at.append(pos)
-                pos = al16(pos + len(seals[i].parity[c][j % seals[i].parity_groups]) + 4)
-            for i, c, g, js, r0 in rs_groups:                                # the rows r0 .. r0 + t - 1 of the group, one after the other
-                q_at.append([])
-                for r in range(r0, r0 + len(js)):
-                    q_at[-1].append(pos)
-                    pos = al16(pos + len(seals[i].parity[c][g][r]) + 4)
+            tried.update(groups)
+            groups.sort(key=lambda group: seals[group[0]].parity_streams > 1)    # (stable) the files of one row first: the XOR call's part
+            jobs = [(i, c, j) for i, c, g, js, r0 in groups for j in js]
+            # `work` grows by this round's region: the groups' parity rows (uploaded), then the output slots, all 16-byte aligned
+            taken = [seals[i].rows(c, g)[r0:r0 + len(js)] for i, c, g, js, r0 in groups]
+            row_at, o_at, pos = [], [], al16(work.numel())
+            for rows in taken:
+                row_at.append([])
+                for p in rows:
+                    row_at[-1].append(pos)
+                    pos = al16(pos + len(p) + 4)
             src_end = pos
-            for i, c, j in jobs + rs_jobs:
+            for i, c, j in jobs:
                 o_at.append(pos)
                 pos = al16(pos + (lens[i, c, j] + 3) // 4 * 4 + 4)
-            rs_out = o_at[len(jobs)] if rs_jobs else pos                     # the slots of the 'L3CQ' jobs lie behind those of the 'L3CP' jobs
             up = np.zeros(pos - work.numel(), dtype=np.uint8)
-            for (i, c, j), a in zip(jobs, p_at):
-                p = seals[i].parity[c][j % seals[i].parity_groups]
-                up[a - work.numel():a - work.numel() + len(p)] = np.frombuffer(p, dtype=np.uint8)
-            for (i, c, g, js, r0), ats in zip(rs_groups, q_at):
-                for r, a in zip(range(r0, r0 + len(js)), ats):
-                    p = seals[i].parity[c][g][r]
+            for rows, ats in zip(taken, row_at):
+                for p, a in zip(rows, ats):
                     up[a - work.numel():a - work.numel() + len(p)] = np.frombuffer(p, dtype=np.uint8)
             work = torch.cat([work, ops.upload_small(up)])
-            if jobs:
-                offs, lns, first = [], [], [0]
-                for (i, c, j), a in zip(jobs, p_at):
-                    m = seals[i].parity_groups
-                    others = [o for o in range(j % m, n, m) if o != j]
-                    offs += [a] + [int(at[i, c, o]) for o in others]
-                    lns += [len(seals[i].parity[c][j % m])] + [int(lens[i, c, o]) for o in others]
-                    first.append(len(offs))
-                ops.u8_xor_spans(work[:src_end], offs, lns, first, work[src_end:rs_out], [a - src_end for a in o_at[:len(jobs)]],
-                                 [int(lens[i, c, j]) for i, c, j in jobs])
-            if rs_jobs:
-                # every rebuilt payload is ONE linear combination of the uploaded rows and the group's present members
-                offs, lns, coefs, first = [], [], [], [0]
-                for (i, c, g, js, r0), ats in zip(rs_groups, q_at):
-                    m = seals[i].parity_groups
-                    present = [o for o in range(g, n, m) if o not in js]
+            # every rebuilt payload is ONE linear combination of its group's uploaded rows and present members; with one row every weight is 1
+            offs, lns, coefs, first = [], [], [], [0]
+            for (i, c, g, js, r0), rows, ats in zip(groups, taken, row_at):
+                m = seals[i].parity_groups
+                present = [o for o in range(g, n, m) if o not in js]
+                if seals[i].parity_streams == 1:
+                    solved = [([1], [1] * len(present))]
+                else:
                     solved = container.rs_repair_coefficients([(j - g) // m for j in js], [(o - g) // m for o in present], r0)
-                    for rows, members in solved:
-                        offs += list(ats) + [int(at[i, c, o]) for o in present]
-                        lns += [len(seals[i].parity[c][g][r]) for r in range(r0, r0 + len(js))] + [int(lens[i, c, o]) for o in present]
-                        coefs += list(rows) + list(members)
-                        first.append(len(offs))
-                ops.u8_gf_spans(work[:src_end], offs, lns, coefs, first, work[rs_out:], [a - rs_out for a in o_at[len(jobs):]],
-                                [int(lens[i, c, j]) for i, c, j in rs_jobs])
-            jobs = jobs + rs_jobs
+                for row_weights, member_weights in solved:
+                    offs += ats + [int(at[i, c, o]) for o in present]
+                    lns += [len(p) for p in rows] + [int(lens[i, c, o]) for o in present]
+                    coefs += list(row_weights) + list(member_weights)
+                    first.append(len(offs))
+            # ... the slots of the files of one row by ONE XOR call, the others by ONE call with the coefficients
+            nx = sum(1 for i, _, _ in jobs if seals[i].parity_streams == 1)
+            sx, gf_out, out_lens = first[nx], (o_at[nx] if nx < len(jobs) else pos), [int(lens[i, c, j]) for i, c, j in jobs]
+            if nx:
+                ops.u8_xor_spans(work[:src_end], offs[:sx], lns[:sx], first[:nx + 1], work[src_end:gf_out], [a - src_end for a in o_at[:nx]], out_lens[:nx])
+            if nx < len(jobs):
+                ops.u8_gf_spans(work[:src_end], offs[sx:], lns[sx:], coefs[sx:], [f - sx for f in first[nx:]], work[gf_out:],
+                                [a - gf_out for a in o_at[nx:]], out_lens[nx:])
             for (i, c, j), a in zip(jobs, o_at):
                 at[i, c, j] = a
             # the positions of the round, decoded again: their symbols zeroed, one entry each

@@ -356,6 +356,9 @@ def image_entry_table(hws, pixbase0=0):
 #     'L3CQ' | u16 G | u16 m | u16 R | u16 0 | u32 plen[3][m] | the 3 m R payloads, (c, g, r) order, plen[c][g] bytes each | u32 S | separator
 # Row r of a group is the XOR over its members k (band g + k m) of alpha^(k r) d_k in GF(2^8), polynomial 0x11D, alpha = 0x02 (rs_parity);
 # row 0 is the 'L3CP' payload; G <= 255.  The check word covers section bytes [0, 12 + 12 m) and the last 8.  R = 1 is always 'L3CP'.
+#
+# The code below knows ONE section of R rows per group: 'L3CP' is R = 1, and differs in its signature and the length of its head
+# (_SECTION_KINDS) alone.  A Seal keeps the rows as [c][g][r]; band_parity is rs_parity with one row.
 
 SEAL_SIGNATURE = b'L3CS'
 SEAL_VERSION = 1
@@ -365,6 +368,11 @@ SEAL_BYTES = 24
 TABLE_SIGNATURE = b'L3CT'
 PARITY_SIGNATURE = b'L3CP'
 PARITY_RS_SIGNATURE = b'L3CQ'
+_SECTION_KINDS = {PARITY_SIGNATURE: 8, PARITY_RS_SIGNATURE: 12}        # signature -> where plen starts inside the section
+
+
+def _section_signature(R):
+    return PARITY_SIGNATURE if R == 1 else PARITY_RS_SIGNATURE
 
 
 def seal_bands_bytes(n):
@@ -377,7 +385,7 @@ class Seal(object):
     parity_group, parity: None but for a version-3 seal: G, and parity[c][g] the parity payload of group g of channel c (m = ceil(n / G)
     groups per channel; bytes, or views of the file split_seal read them from).
     parity_streams: None without parity, 1 for an 'L3CP' section, R = 2..4 for an 'L3CQ' section -- then parity[c][g] is the LIST of the
-    group's R row payloads (rs_parity), all plen[c][g] bytes long."""
+    group's R row payloads (rs_parity), all plen[c][g] bytes long.  rows(c, g): the group's row payloads as a list in either case."""
 
     def __init__(self, generation, frame_crc, model_id, band_len=None, band_crcs=None, parity_group=None, parity=None, parity_streams=None):
         self.generation, self.frame_crc, self.model_id = int(generation), int(frame_crc), int(model_id)
@@ -385,24 +393,23 @@ class Seal(object):
         self.band_crcs = None if band_crcs is None else np.array(band_crcs, dtype=np.uint32).reshape(3, -1)
         self.parity_group = None if parity is None else int(parity_group)
         self.parity_streams = None if parity is None else int(parity_streams or 1)
-        if parity is None:
-            self.parity = None
-        elif self.parity_streams == 1:
-            self.parity = [list(row) for row in parity]
-        else:
-            self.parity = [[list(rows) for rows in row] for row in parity]
+        # the rows in ONE shape, [c][g][r]; `parity` in the documented one
+        self._rows = None if parity is None else [[list(p) if isinstance(p, (list, tuple)) else [p] for p in row] for row in parity]
+        self.parity = self._rows if parity is None or self.parity_streams > 1 else [[p[0] for p in row] for row in self._rows]
 
     @property
     def parity_groups(self):
         """m, the parity streams per channel; 0 without parity."""
         return 0 if self.parity is None else len(self.parity[0])
 
+    def rows(self, c, g):
+        """The parity_streams row payloads of group g of channel c, row 0 first."""
+        return self._rows[c][g]
+
     def _key(self):
         key = (self.generation, self.frame_crc, self.model_id, self.band_len, None if self.band_crcs is None else self.band_crcs.tobytes())
-        if self.parity is not None and self.parity_streams == 1:
-            key += (self.parity_group, tuple(bytes(p) for row in self.parity for p in row))
-        elif self.parity is not None:
-            key += (self.parity_group, self.parity_streams, tuple(bytes(p) for row in self.parity for rows in row for p in rows))
+        if self.parity is not None:
+            key += (self.parity_group, self.parity_streams, tuple(bytes(p) for row in self._rows for rows in row for p in rows))
         return key
 
     def __eq__(self, other):
@@ -638,25 +645,14 @@ def parity_groups(n, G):
 def band_parity(payloads, G):
     """The parity payloads of ONE channel (the reference the kernels are tested against): payloads, the n band payloads of the channel
     (bytes-like, any lengths), in groups of G -> the m = ceil(n / G) parity payloads as bytes; group g is the XOR of the bands
-    { j : j % m == g }, each zero-extended to the longest of them."""
-    n = len(payloads)
-    m = parity_groups(n, G)
-    res = []
-    for g in range(m):
-        members = [np.frombuffer(bytes(p), dtype=np.uint8) for p in payloads[g::m]]
-        acc = np.zeros(max(len(a) for a in members), dtype=np.uint8)
-        for a in members:
-            acc[:len(a)] ^= a
-        res.append(acc.tobytes())
-    return res
+    { j : j % m == g }, each zero-extended to the longest of them: rs_parity's row 0."""
+    return [rows[0] for rows in rs_parity(payloads, G, 1)]
 
 
 def parity_section_bytes(plens, R=1):
     """S of a parity section whose payload lengths are plens ((3, m)); R > 1: of the 'L3CQ' section with R rows per group."""
     plens = np.asarray(plens, dtype=np.int64).reshape(3, -1)
-    if R == 1:
-        return 16 + 12 * plens.shape[1] + int(plens.sum())
-    return 20 + 12 * plens.shape[1] + int(R) * int(plens.sum())
+    return _SECTION_KINDS[_section_signature(R)] + 12 * plens.shape[1] + int(R) * int(plens.sum()) + 8
 
 
 # ---- GF(2^8), polynomial 0x11D, alpha = 0x02: the arithmetic of the 'L3CQ' section (R parity rows per group; csrc/parity.hip on the device) ----
@@ -787,21 +783,15 @@ def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=
         m = parity_groups(n, G)
         if len(rows) != 3 or any(len(row) != m for row in rows):
             raise ValueError('make_seal: parity needs 3 x {} payloads for {} bands in groups of {}'.format(m, n, G))
-        R = len(rows[0][0]) if isinstance(rows[0][0], (list, tuple)) else None     # rows[c][g]: a payload ('L3CP'), or the list of R row payloads
-        if R is not None:
-            check_parity_streams(R, G, n)
-            if any(not isinstance(p, (list, tuple)) or len(p) != R or len({len(q) for q in p}) != 1 for row in rows for p in row):
-                raise ValueError('make_seal: parity needs {} row payloads of one length in every group'.format(R))
-            rows = [[p[0] for p in row] for row in rows] if R == 1 else [[[bytes(q) for q in p] for p in row] for row in rows]
-        if R is None or R == 1:
-            rows = [[bytes(p) for p in row] for row in rows]
-            head = PARITY_SIGNATURE + struct.pack('<HH', int(G), m) + b''.join(struct.pack('<I', len(p)) for row in rows for p in row)
-            S = 16 + 12 * m + sum(len(p) for row in rows for p in row)
-            payload = b''.join(p for row in rows for p in row)
-        else:
-            head = PARITY_RS_SIGNATURE + struct.pack('<HHHH', int(G), m, R, 0) + b''.join(struct.pack('<I', len(p[0])) for row in rows for p in row)
-            S = 20 + 12 * m + R * sum(len(p[0]) for row in rows for p in row)
-            payload = b''.join(q for row in rows for p in row for q in p)
+        listed = isinstance(rows[0][0], (list, tuple))                             # rows[c][g]: a payload, or the list of R row payloads
+        R = check_parity_streams(len(rows[0][0]) if listed else 1, G, n)
+        if listed and any(not isinstance(p, (list, tuple)) or len(p) != R or len({len(q) for q in p}) != 1 for row in rows for p in row):
+            raise ValueError('make_seal: parity needs {} row payloads of one length in every group'.format(R))
+        rows = [[[bytes(q) for q in (p if listed else [p])] for p in row] for row in rows]                # [c][g][r]
+        fields = (int(G), m) if R == 1 else (int(G), m, R, 0)
+        head = _section_signature(R) + struct.pack('<{}H'.format(len(fields)), *fields) + b''.join(struct.pack('<I', len(p[0])) for row in rows for p in row)
+        payload = b''.join(q for row in rows for p in row for q in p)
+        S = len(head) + len(payload) + 8
         if S >= 1 << 32:
             raise ValueError('make_seal: parity section of {} bytes'.format(S))
         tail = struct.pack('<I', S) + _MAGIC_VALUE_SEP
@@ -855,14 +845,14 @@ def split_seal(data, view=False):
             raise ValueError('invalid file: seal band table with a non-zero reserved field')
     if version == SEAL_VERSION_PARITY:
         S, = struct.unpack('<I', bytes(data[end - 8:end - 4]))           # (the separator at [end - 4, end) is the one the table starts behind)
-        if S < 16 + 12 or S > end - 14 - 4 or bytes(data[end - S - 4:end - S]) != _MAGIC_VALUE_SEP:
+        if S < parity_section_bytes([0, 0, 0]) or S > end - 14 - 4 or bytes(data[end - S - 4:end - S]) != _MAGIC_VALUE_SEP:
             raise ValueError("invalid file: seal parity section does not start behind the file's last scale separator")
         section_at, end = end - S, end - S
-        rs = bytes(data[section_at:section_at + 4]) == PARITY_RS_SIGNATURE
-        if not rs and bytes(data[section_at:section_at + 4]) != PARITY_SIGNATURE:
+        signature = bytes(data[section_at:section_at + 4])
+        if signature not in _SECTION_KINDS:
             raise ValueError("invalid file: seal parity section without its 'L3CP' signature")
         G, m = struct.unpack('<HH', bytes(data[section_at + 4:section_at + 8]))
-        fields_at, R = (12 if rs else 8), 1                              # where plen starts inside the section
+        fields_at, rs, R = _SECTION_KINDS[signature], signature == PARITY_RS_SIGNATURE, 1
         if m < 1 or fields_at + 8 + 12 * m > S:
             raise ValueError('invalid file: seal parity section is too short for its {} x 3 length fields'.format(m))
         if rs:
@@ -872,10 +862,9 @@ def split_seal(data, view=False):
             if reserved:
                 raise ValueError('invalid file: seal parity section with a non-zero reserved field')
         plen = np.frombuffer(bytes(data[section_at + fields_at:section_at + fields_at + 12 * m]), dtype='<u4').astype(np.int64).reshape(3, m)
-        if not rs and S != 16 + 12 * m + int(plen.sum()):
-            raise ValueError('invalid file: seal parity section length is not 16 + 12 m + the sum of its payload lengths')
-        if rs and S != 20 + 12 * m + R * int(plen.sum()):
-            raise ValueError('invalid file: seal parity section length is not 20 + 12 m + R times the sum of its payload lengths')
+        if S != parity_section_bytes(plen, R):
+            raise ValueError('invalid file: seal parity section length is not 20 + 12 m + R times the sum of its payload lengths' if rs else
+                             'invalid file: seal parity section length is not 16 + 12 m + the sum of its payload lengths')
         checked = bytes(data[section_at:section_at + fields_at + 12 * m]) + bytes(data[section_at + S - 8:section_at + S])
     if flags:
         raise ValueError('invalid file: seal with non-zero flags')
@@ -907,7 +896,7 @@ def split_seal(data, view=False):
         rows.append([])
         for g in range(m):
             k = int(plen[c, g])
-            rows[c].append(view[at:at + k] if R == 1 else [view[at + r * k:at + (r + 1) * k] for r in range(R)])
+            rows[c].append([view[at + r * k:at + (r + 1) * k] for r in range(R)])
             at += R * k
     return body, Seal(generation, frame_crc, model_id, L, crcs, G, rows, R)
 

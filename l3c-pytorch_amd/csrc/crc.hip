@@ -595,11 +595,38 @@ int l3c_seal_write_bands(const l3c_seal *seal_host, const uint8_t *padding8_host
     return L3C_OK;
 }
 
-int64_t l3c_seal_parity_bytes(int n, int m, int64_t payload_bytes) {
-    if (n < 1 || n > l3c_sealing::MAX_BANDS || m < 1 || m > n || payload_bytes < 0 || payload_bytes > (int64_t)UINT32_MAX - 16 - 12 * m)
-        return l3c::fail(L3C_ERR_INVALID_ARG, "%s", "n must be in 1..1024, m in 1..n, and the section must stay below 2^32 bytes");
-    return l3c_sealing::section_bytes(m, payload_bytes) + l3c_sealing::table_bytes(n) + L3C_SEAL_BYTES;
+// l3c_seal_parity_bytes and l3c_seal_parity_rs_bytes: payload_bytes = R times the sum of plen; `what`: the caller's message
+static int64_t parity_tail_bytes(int n, int m, int R, int64_t payload_bytes, const char *what) {
+    if (n < 1 || n > l3c_sealing::MAX_BANDS || m < 1 || m > n || R < 1 || R > l3c_sealing::MAX_PARITY_STREAMS || payload_bytes < 0 ||
+        payload_bytes % R != 0 || payload_bytes > (int64_t)UINT32_MAX - l3c_sealing::parity_section_bytes(m, R, 0))
+        return l3c::fail(L3C_ERR_INVALID_ARG, "%s", what);
+    return l3c_sealing::parity_section_bytes(m, R, payload_bytes / R) + l3c_sealing::table_bytes(n) + L3C_SEAL_BYTES;
 }
+
+// l3c_seal_write_parity (R = 1) and l3c_seal_write_parity_rs
+static int write_parity_tail(const l3c_seal *seal_host, const uint8_t *padding8_host, const uint32_t *band_crc_host, int n, uint32_t band_len, int G,
+                             int R, const uint32_t *plen_host, const uint8_t *payloads_host, uint8_t *dst_host) {
+    L3C_REQUIRE(seal_host && padding8_host && band_crc_host && plen_host && dst_host, "null pointer");
+    L3C_REQUIRE(n >= 1 && n <= l3c_sealing::MAX_BANDS && band_len > 0, "n must be in 1..1024 and band_len positive");
+    L3C_REQUIRE(R >= 1 && R <= l3c_sealing::MAX_PARITY_STREAMS, "R must be in 1..4");
+    L3C_REQUIRE(G >= 1 && G <= n, "G must be in 1..n");
+    L3C_REQUIRE(R == 1 || G <= l3c_sealing::MAX_RS_GROUP, "more than one parity stream needs groups of at most 255 bands");
+    const int m = (n + G - 1) / G;
+    int64_t sum = 0;
+    for (int i = 0; i < 3 * m; ++i) sum += plen_host[i];
+    L3C_REQUIRE(sum == 0 || payloads_host, "null pointer (payloads_host)");
+    L3C_REQUIRE(R * sum <= (int64_t)UINT32_MAX - l3c_sealing::parity_section_bytes(m, R, 0), "the section must stay below 2^32 bytes");
+    uint8_t *crc = dst_host + l3c_sealing::parity_section_bytes(m, R, sum) + 12;   // the table's words, little-endian, where write_tail puts them
+    for (int i = 0; i < 3 * n; ++i) l3c_sealing::put(crc + 4 * i, band_crc_host[i], 4);
+    l3c_sealing::write_parity_rs(*seal_host, padding8_host, crc, n, band_len, G, m, R, plen_host, payloads_host, dst_host);
+    return L3C_OK;
+}
+
+static const char PARITY_BYTES_WHAT[] = "n must be in 1..1024, m in 1..n, and the section must stay below 2^32 bytes";
+static const char PARITY_RS_BYTES_WHAT[] =
+    "n must be in 1..1024, m in 1..n, R in 1..4, payload_bytes a multiple of R, and the section must stay below 2^32 bytes";
+
+int64_t l3c_seal_parity_bytes(int n, int m, int64_t payload_bytes) { return parity_tail_bytes(n, m, 1, payload_bytes, PARITY_BYTES_WHAT); }
 
 int l3c_seal_find_parity(const uint8_t *file_host, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
                          l3c_seal_parity *parity_out) {
@@ -609,26 +636,11 @@ int l3c_seal_find_parity(const uint8_t *file_host, int64_t file_bytes, int64_t *
 
 int l3c_seal_write_parity(const l3c_seal *seal_host, const uint8_t *padding8_host, const uint32_t *band_crc_host, int n, uint32_t band_len, int G,
                           const uint32_t *plen_host, const uint8_t *payloads_host, uint8_t *dst_host) {
-    L3C_REQUIRE(seal_host && padding8_host && band_crc_host && plen_host && dst_host, "null pointer");
-    L3C_REQUIRE(n >= 1 && n <= l3c_sealing::MAX_BANDS && band_len > 0, "n must be in 1..1024 and band_len positive");
-    L3C_REQUIRE(G >= 1 && G <= n, "G must be in 1..n");
-    const int m = (n + G - 1) / G;
-    int64_t sum = 0;
-    for (int i = 0; i < 3 * m; ++i) sum += plen_host[i];
-    L3C_REQUIRE(sum == 0 || payloads_host, "null pointer (payloads_host)");
-    L3C_REQUIRE(sum <= (int64_t)UINT32_MAX - 16 - 12 * m, "the section must stay below 2^32 bytes");
-    uint8_t *crc = dst_host + l3c_sealing::section_bytes(m, sum) + 12;       // the table's words, little-endian, where write_parity puts them
-    for (int i = 0; i < 3 * n; ++i) l3c_sealing::put(crc + 4 * i, band_crc_host[i], 4);
-    l3c_sealing::write_parity(*seal_host, padding8_host, crc, n, band_len, G, m, plen_host, payloads_host, dst_host);
-    return L3C_OK;
+    return write_parity_tail(seal_host, padding8_host, band_crc_host, n, band_len, G, 1, plen_host, payloads_host, dst_host);
 }
 
 int64_t l3c_seal_parity_rs_bytes(int n, int m, int R, int64_t payload_bytes) {
-    if (R == 1) return l3c_seal_parity_bytes(n, m, payload_bytes);
-    if (n < 1 || n > l3c_sealing::MAX_BANDS || m < 1 || m > n || R < 1 || R > l3c_sealing::MAX_PARITY_STREAMS || payload_bytes < 0 ||
-        payload_bytes % R != 0 || payload_bytes > (int64_t)UINT32_MAX - 20 - 12 * m)
-        return l3c::fail(L3C_ERR_INVALID_ARG, "%s", "n must be in 1..1024, m in 1..n, R in 1..4, payload_bytes a multiple of R, and the section must stay below 2^32 bytes");
-    return l3c_sealing::rs_section_bytes(m, 1, payload_bytes) + l3c_sealing::table_bytes(n) + L3C_SEAL_BYTES;
+    return parity_tail_bytes(n, m, R, payload_bytes, R == 1 ? PARITY_BYTES_WHAT : PARITY_RS_BYTES_WHAT);
 }
 
 int l3c_seal_find_parity_rs(const uint8_t *file_host, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
@@ -639,21 +651,7 @@ int l3c_seal_find_parity_rs(const uint8_t *file_host, int64_t file_bytes, int64_
 
 int l3c_seal_write_parity_rs(const l3c_seal *seal_host, const uint8_t *padding8_host, const uint32_t *band_crc_host, int n, uint32_t band_len, int G,
                              int R, const uint32_t *plen_host, const uint8_t *payloads_host, uint8_t *dst_host) {
-    if (R == 1) return l3c_seal_write_parity(seal_host, padding8_host, band_crc_host, n, band_len, G, plen_host, payloads_host, dst_host);
-    L3C_REQUIRE(seal_host && padding8_host && band_crc_host && plen_host && dst_host, "null pointer");
-    L3C_REQUIRE(n >= 1 && n <= l3c_sealing::MAX_BANDS && band_len > 0, "n must be in 1..1024 and band_len positive");
-    L3C_REQUIRE(R >= 1 && R <= l3c_sealing::MAX_PARITY_STREAMS, "R must be in 1..4");
-    L3C_REQUIRE(G >= 1 && G <= n, "G must be in 1..n");
-    L3C_REQUIRE(G <= l3c_sealing::MAX_RS_GROUP, "more than one parity stream needs groups of at most 255 bands");
-    const int m = (n + G - 1) / G;
-    int64_t sum = 0;
-    for (int i = 0; i < 3 * m; ++i) sum += plen_host[i];
-    L3C_REQUIRE(sum == 0 || payloads_host, "null pointer (payloads_host)");
-    L3C_REQUIRE(R * sum <= (int64_t)UINT32_MAX - 20 - 12 * m, "the section must stay below 2^32 bytes");
-    uint8_t *crc = dst_host + l3c_sealing::rs_section_bytes(m, R, sum) + 12;  // the table's words, little-endian, where write_parity_rs puts them
-    for (int i = 0; i < 3 * n; ++i) l3c_sealing::put(crc + 4 * i, band_crc_host[i], 4);
-    l3c_sealing::write_parity_rs(*seal_host, padding8_host, crc, n, band_len, G, m, R, plen_host, payloads_host, dst_host);
-    return L3C_OK;
+    return write_parity_tail(seal_host, padding8_host, band_crc_host, n, band_len, G, R, plen_host, payloads_host, dst_host);
 }
 
 namespace {

@@ -13,6 +13,10 @@
 // csrc/seal.h), with the same loads, masks and stores.  The only field operation is "times alpha" on four packed bytes (xtime: 5 VALU
 // instructions per dword): the encoder keeps R accumulators and applies Horner's rule over the members, so a member is loaded once for all
 // rows; the repair side multiplies each member by a coefficient that is uniform over the block, by shift and add under scalar branches.
+//
+// XOR is the R = 1 / every-coefficient-1 case of the GF(2^8) kernels and could be their instantiation; it keeps kernels of its own because
+// that instantiation measured 8 to 10 % slower (profiles/r23_parity_one_path_latency.log).  The host side is one path: the entry points of a
+// family share their argument checks (check_band_parity, u8_spans).
 #include "l3c_common.h"
 #include "parity_plan.h"
 
@@ -297,39 +301,39 @@ int l3c_band_parity_rs(const l3c_banded_scale *scale_host, int64_t B, int G, int
     return l3c::check_launch("band_parity_rs_kernel");
 }
 
-int l3c_u8_xor_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, int64_t n_spans,
-                     const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups, const l3c_u8_span *out_spans_host,
-                     const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream) {
-    L3C_REQUIRE(n_groups >= 0, "n_groups must not be negative");
-    if (n_groups == 0) return L3C_OK;
-    const int64_t tiles = check_xor_spans(spans_host, n_spans, group_first_host, n_groups, out_spans_host, data_bytes, out_bytes, l3c::error_buffer(), 512);
-    if (tiles < 0) return (int)tiles;
-    L3C_REQUIRE(out && group_first && out_spans && (n_spans == 0 || (data && spans)), "null pointer");
-    L3C_REQUIRE((reinterpret_cast<uintptr_t>(data) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0, "data and out must be 4-byte aligned");
-    L3C_REQUIRE((reinterpret_cast<uintptr_t>(spans) & 7) == 0 && (reinterpret_cast<uintptr_t>(group_first) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(out_spans) & 7) == 0,
-                "spans, group_first and out_spans (the device tables) must be 8-byte aligned");
-    L3C_REQUIRE(n_spans == 0 || out + out_bytes <= data || data + data_bytes <= out, "out must not overlap data");
-    hipLaunchKernelGGL(u8_xor_spans_kernel, dim3((unsigned)tiles, (unsigned)n_groups), dim3(THREADS), 0, l3c::as_stream(stream), data, spans,
-                       group_first, out_spans, out);
-    return l3c::check_launch("u8_xor_spans_kernel");
-}
-
-int l3c_u8_gf_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, const uint8_t *coef_host,
+// l3c_u8_xor_spans (gf false: no coefficients, the XOR kernel) and l3c_u8_gf_spans: the argument checks, all before the launch, and the launch
+static int u8_spans(bool gf, const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, const uint8_t *coef_host,
                     const uint8_t *coef, int64_t n_spans, const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups,
                     const l3c_u8_span *out_spans_host, const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream) {
     L3C_REQUIRE(n_groups >= 0, "n_groups must not be negative");
     if (n_groups == 0) return L3C_OK;
     const int64_t tiles = check_xor_spans(spans_host, n_spans, group_first_host, n_groups, out_spans_host, data_bytes, out_bytes, l3c::error_buffer(), 512);
     if (tiles < 0) return (int)tiles;
-    L3C_REQUIRE(out && group_first && out_spans && (n_spans == 0 || (data && spans && coef_host && coef)), "null pointer");
+    L3C_REQUIRE(out && group_first && out_spans && (n_spans == 0 || (data && spans && (!gf || (coef_host && coef)))), "null pointer");
     L3C_REQUIRE((reinterpret_cast<uintptr_t>(data) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0, "data and out must be 4-byte aligned");
     L3C_REQUIRE((reinterpret_cast<uintptr_t>(spans) & 7) == 0 && (reinterpret_cast<uintptr_t>(group_first) & 7) == 0 &&
                     (reinterpret_cast<uintptr_t>(out_spans) & 7) == 0,
                 "spans, group_first and out_spans (the device tables) must be 8-byte aligned");
     L3C_REQUIRE(n_spans == 0 || out + out_bytes <= data || data + data_bytes <= out, "out must not overlap data");
-    hipLaunchKernelGGL(u8_gf_spans_kernel, dim3((unsigned)tiles, (unsigned)n_groups), dim3(THREADS), 0, l3c::as_stream(stream), data, spans, coef,
-                       group_first, out_spans, out);
-    return l3c::check_launch("u8_gf_spans_kernel");
+    const dim3 grid((unsigned)tiles, (unsigned)n_groups);
+    if (gf)
+        hipLaunchKernelGGL(u8_gf_spans_kernel, grid, dim3(THREADS), 0, l3c::as_stream(stream), data, spans, coef, group_first, out_spans, out);
+    else
+        hipLaunchKernelGGL(u8_xor_spans_kernel, grid, dim3(THREADS), 0, l3c::as_stream(stream), data, spans, group_first, out_spans, out);
+    return l3c::check_launch(gf ? "u8_gf_spans_kernel" : "u8_xor_spans_kernel");
+}
+
+int l3c_u8_xor_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, int64_t n_spans,
+                     const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups, const l3c_u8_span *out_spans_host,
+                     const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream) {
+    return u8_spans(false, data, data_bytes, spans_host, spans, nullptr, nullptr, n_spans, group_first_host, group_first, n_groups, out_spans_host,
+                    out_spans, out, out_bytes, stream);
+}
+
+int l3c_u8_gf_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, const uint8_t *coef_host,
+                    const uint8_t *coef, int64_t n_spans, const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups,
+                    const l3c_u8_span *out_spans_host, const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream) {
+    return u8_spans(true, data, data_bytes, spans_host, spans, coef_host, coef, n_spans, group_first_host, group_first, n_groups, out_spans_host,
+                    out_spans, out, out_bytes, stream);
 }
 }

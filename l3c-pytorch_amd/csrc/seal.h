@@ -36,6 +36,10 @@
 // 'L3CP' payload.  G <= 255 so that the points alpha^k of a group are distinct.  check covers section bytes [0, 12 + 12 m) and the last 8.
 // R = 1 is always written as 'L3CP'.  find_parity reports an 'L3CQ' section as m = 0 (the band-sealed file it contains); find_parity_rs
 // reports both kinds, 'L3CP' as R = 1.
+//
+// ONE writer (write_tail) lays down every tail -- [section] [table] seal, whatever is present -- and ONE reader (find_parity_rs) takes it
+// apart; the two sections are one layout whose signature and head length (section_head_bytes) depend on R.  write, write_bands,
+// write_parity, write_parity_rs and find, find_bands, find_parity are those two under the names of the format's versions.
 #ifndef L3C_SEAL_H_
 #define L3C_SEAL_H_
 
@@ -91,19 +95,15 @@ inline int fail_d(char *err, size_t cap, const char *what, int d) {
     return L3C_ERR_INVALID_ARG;
 }
 
-// seal bytes 0..19 of `s`, then the check word over padding8 | those bytes
-inline void write(const l3c_seal &s, const uint8_t *padding8, uint8_t *dst) {
-    memcpy(dst, SIGNATURE, 4);
-    dst[4] = VERSION;
-    dst[5] = 0;
-    put(dst + 6, s.generation, 2);
-    put(dst + 8, s.frame_crc, 4);
-    put(dst + 12, s.model_id, 8);
-    put(dst + 20, crc32(crc32(0, padding8, 8), dst, 20), 4);
-}
-
-// band table + seal of a band-sealed file: table_bytes(n) + L3C_SEAL_BYTES bytes behind the body
+// the tail of a file behind its body: [parity section] [band table] the 24 seal bytes.  table_bytes(n): the table of n bands per channel;
+// section_head_bytes(R): the section's bytes in front of its plen fields, 8 ('L3CP', R = 1) or 12 ('L3CQ', R = 2..4) -- with the signature
+// the only difference between the two sections; parity_section_bytes(m, R, sum of plen): a section of m groups per channel and R rows per group
 constexpr int64_t table_bytes(int64_t n) { return 20 + 12 * n; }
+constexpr int64_t section_head_bytes(int64_t R) { return R == 1 ? 8 : 12; }
+constexpr int64_t parity_section_bytes(int64_t m, int64_t R, int64_t plen_sum) { return section_head_bytes(R) + 12 * m + R * plen_sum + 8; }
+// (the names the two sections' sizes had before there was one function)
+constexpr int64_t section_bytes(int64_t m, int64_t payload_bytes) { return parity_section_bytes(m, 1, payload_bytes); }
+constexpr int64_t rs_section_bytes(int64_t m, int64_t R, int64_t plen_sum) { return parity_section_bytes(m, R, plen_sum); }
 
 // zlib's crc32_combine over the bands of a frame of 3 planes of hw bytes: crc(A | B) = crc(A) x^(8 |B|) + crc(B), from crc() = 0.
 // crc: 12 n bytes, [3][n] little-endian words, unaligned
@@ -146,98 +146,81 @@ inline bool finest_record(const uint8_t *f, int64_t body, int64_t *hw_out, uint3
     return found;
 }
 
-// the band table for n bands per channel of length band_len and the seal of version 2 behind it: table_bytes(n) + 24 bytes at dst.
-// band_crc: 12 n bytes, [3][n] little-endian words (unaligned is fine)
+// The band table of a tail: band_crc, 12 n bytes, [3][n] little-endian words (unaligned is fine; may already lie where the table puts them)
+struct TailTable {
+    const uint8_t *band_crc;
+    int n;
+    uint32_t band_len;
+};
+
+// The parity section of a tail: m groups per channel, R rows per group; plen: [3][m] host words; payloads: the 3 m R payloads back to back,
+// (c, g, r) order, plen[c][g] bytes each.  R == 1 is the 'L3CP' section, R in 2..4 the 'L3CQ' one.
+struct TailSection {
+    int G, m, R;
+    const uint32_t *plen;
+    const uint8_t *payloads;
+};
+
+// THE writer of every tail: [section] [table] seal at dst, of the version that what is present makes (1: neither, 2: a table, 3: both; a
+// section needs a table).  check = CRC-32 of padding8, the section's head and its last 8 bytes, the table, seal bytes 0..19.  dst must not
+// overlap the payloads; the band CRCs may lie at their place in dst already.
+inline void write_tail(const l3c_seal &s, const uint8_t *padding8, const TailTable *table, const TailSection *section, uint8_t *dst) {
+    uint32_t check = crc32(0, padding8, 8);
+    if (section) {
+        const int64_t m = section->m, R = section->R, fields_at = section_head_bytes(R), head = fields_at + 12 * m;
+        int64_t sum = 0;
+        for (int i = 0; i < 3 * m; ++i) sum += section->plen[i];
+        const int64_t S = parity_section_bytes(m, R, sum);
+        memcpy(dst, R == 1 ? PARITY_SIGNATURE : PARITY_RS_SIGNATURE, 4);
+        put(dst + 4, (uint64_t)section->G, 2);
+        put(dst + 6, (uint64_t)m, 2);
+        if (R != 1) put(dst + 8, (uint64_t)R, 4);                     // u16 R | u16 0
+        for (int i = 0; i < 3 * m; ++i) put(dst + fields_at + 4 * i, section->plen[i], 4);
+        if (sum) memcpy(dst + head, section->payloads, (size_t)(R * sum));
+        put(dst + S - 8, (uint64_t)S, 4);
+        memcpy(dst + S - 4, SEPARATOR, 4);
+        check = crc32(crc32(check, dst, head), dst + S - 8, 8);
+        dst += S;
+    }
+    if (table) {
+        const int64_t n = table->n, T = table_bytes(n);
+        memcpy(dst, TABLE_SIGNATURE, 4);
+        put(dst + 4, (uint64_t)n, 2);
+        put(dst + 6, 0, 2);
+        put(dst + 8, table->band_len, 4);
+        memmove(dst + 12, table->band_crc, 12 * (size_t)n);
+        put(dst + 12 + 12 * n, (uint64_t)T, 4);
+        memcpy(dst + 16 + 12 * n, SEPARATOR, 4);
+        check = crc32(check, dst, T);
+        dst += T;
+    }
+    memcpy(dst, SIGNATURE, 4);
+    dst[4] = section ? VERSION_PARITY : table ? VERSION_BANDS : VERSION;
+    dst[5] = 0;
+    put(dst + 6, s.generation, 2);
+    put(dst + 8, s.frame_crc, 4);
+    put(dst + 12, s.model_id, 8);
+    put(dst + 20, crc32(check, dst, 20), 4);
+}
+
+// the four tails by name: the 24 seal bytes; table_bytes(n) + 24 bytes; parity_section_bytes(m, R, sum of plen) + table_bytes(n) + 24 bytes
+inline void write(const l3c_seal &s, const uint8_t *padding8, uint8_t *dst) { write_tail(s, padding8, nullptr, nullptr, dst); }
+
 inline void write_bands(const l3c_seal &s, const uint8_t *padding8, const uint8_t *band_crc, int n, uint32_t band_len, uint8_t *dst) {
-    const int64_t T = table_bytes(n);
-    memcpy(dst, TABLE_SIGNATURE, 4);
-    put(dst + 4, (uint64_t)n, 2);
-    put(dst + 6, 0, 2);
-    put(dst + 8, band_len, 4);
-    memmove(dst + 12, band_crc, 12 * (size_t)n);
-    put(dst + 12 + 12 * n, (uint64_t)T, 4);
-    memcpy(dst + 16 + 12 * n, SEPARATOR, 4);
-    uint8_t *seal = dst + T;
-    memcpy(seal, SIGNATURE, 4);
-    seal[4] = VERSION_BANDS;
-    seal[5] = 0;
-    put(seal + 6, s.generation, 2);
-    put(seal + 8, s.frame_crc, 4);
-    put(seal + 12, s.model_id, 8);
-    put(seal + 20, crc32(crc32(0, padding8, 8), dst, T + 20), 4);
+    const TailTable table{band_crc, n, band_len};
+    write_tail(s, padding8, &table, nullptr, dst);
 }
 
-// parity section + band table + seal of a version-3 file: section_bytes(m, payload bytes) + table_bytes(n) + L3C_SEAL_BYTES bytes behind the body
-constexpr int64_t section_bytes(int64_t m, int64_t payload_bytes) { return 16 + 12 * m + payload_bytes; }
-
-// The section for m groups per channel (plen: [3][m] host words, payloads: the 3 m parity payloads back to back, (c, g) order), the band
-// table and the seal of version 3 behind it, at dst.  dst must not overlap band_crc or payloads.
-inline void write_parity(const l3c_seal &s, const uint8_t *padding8, const uint8_t *band_crc, int n, uint32_t band_len, int G, int m,
-                         const uint32_t *plen, const uint8_t *payloads, uint8_t *dst) {
-    int64_t sum = 0;
-    for (int i = 0; i < 3 * m; ++i) sum += plen[i];
-    const int64_t S = section_bytes(m, sum), T = table_bytes(n), head = 8 + 12 * (int64_t)m;
-    memcpy(dst, PARITY_SIGNATURE, 4);
-    put(dst + 4, (uint64_t)G, 2);
-    put(dst + 6, (uint64_t)m, 2);
-    for (int i = 0; i < 3 * m; ++i) put(dst + 8 + 4 * i, plen[i], 4);
-    if (sum) memcpy(dst + head, payloads, (size_t)sum);
-    put(dst + S - 8, (uint64_t)S, 4);
-    memcpy(dst + S - 4, SEPARATOR, 4);
-    uint8_t *t = dst + S;
-    memcpy(t, TABLE_SIGNATURE, 4);
-    put(t + 4, (uint64_t)n, 2);
-    put(t + 6, 0, 2);
-    put(t + 8, band_len, 4);
-    memmove(t + 12, band_crc, 12 * (size_t)n);
-    put(t + 12 + 12 * n, (uint64_t)T, 4);
-    memcpy(t + 16 + 12 * n, SEPARATOR, 4);
-    uint8_t *seal = t + T;
-    memcpy(seal, SIGNATURE, 4);
-    seal[4] = VERSION_PARITY;
-    seal[5] = 0;
-    put(seal + 6, s.generation, 2);
-    put(seal + 8, s.frame_crc, 4);
-    put(seal + 12, s.model_id, 8);
-    put(seal + 20, crc32(crc32(crc32(crc32(0, padding8, 8), dst, head), dst + S - 8, 8), t, T + 20), 4);
-}
-
-// an 'L3CQ' section of R streams: rs_section_bytes(m, R, sum of plen)
-constexpr int64_t rs_section_bytes(int64_t m, int64_t R, int64_t plen_sum) { return 20 + 12 * m + R * plen_sum; }
-
-// write_parity for R parity streams per group (payloads: (c, g, r) order, plen[c][g] bytes each).  R == 1 writes the 'L3CP' section of
-// write_parity, R in 2..4 the 'L3CQ' one.
 inline void write_parity_rs(const l3c_seal &s, const uint8_t *padding8, const uint8_t *band_crc, int n, uint32_t band_len, int G, int m, int R,
                             const uint32_t *plen, const uint8_t *payloads, uint8_t *dst) {
-    if (R == 1) return write_parity(s, padding8, band_crc, n, band_len, G, m, plen, payloads, dst);
-    int64_t sum = 0;
-    for (int i = 0; i < 3 * m; ++i) sum += plen[i];
-    const int64_t S = rs_section_bytes(m, R, sum), T = table_bytes(n), head = 12 + 12 * (int64_t)m;
-    memcpy(dst, PARITY_RS_SIGNATURE, 4);
-    put(dst + 4, (uint64_t)G, 2);
-    put(dst + 6, (uint64_t)m, 2);
-    put(dst + 8, (uint64_t)R, 2);
-    put(dst + 10, 0, 2);
-    for (int i = 0; i < 3 * m; ++i) put(dst + 12 + 4 * i, plen[i], 4);
-    if (sum) memcpy(dst + head, payloads, (size_t)(R * sum));
-    put(dst + S - 8, (uint64_t)S, 4);
-    memcpy(dst + S - 4, SEPARATOR, 4);
-    uint8_t *t = dst + S;
-    memcpy(t, TABLE_SIGNATURE, 4);
-    put(t + 4, (uint64_t)n, 2);
-    put(t + 6, 0, 2);
-    put(t + 8, band_len, 4);
-    memmove(t + 12, band_crc, 12 * (size_t)n);
-    put(t + 12 + 12 * n, (uint64_t)T, 4);
-    memcpy(t + 16 + 12 * n, SEPARATOR, 4);
-    uint8_t *seal = t + T;
-    memcpy(seal, SIGNATURE, 4);
-    seal[4] = VERSION_PARITY;
-    seal[5] = 0;
-    put(seal + 6, s.generation, 2);
-    put(seal + 8, s.frame_crc, 4);
-    put(seal + 12, s.model_id, 8);
-    put(seal + 20, crc32(crc32(crc32(crc32(0, padding8, 8), dst, head), dst + S - 8, 8), t, T + 20), 4);
+    const TailTable table{band_crc, n, band_len};
+    const TailSection section{G, m, R, plen, payloads};
+    write_tail(s, padding8, &table, &section, dst);
+}
+
+inline void write_parity(const l3c_seal &s, const uint8_t *padding8, const uint8_t *band_crc, int n, uint32_t band_len, int G, int m,
+                         const uint32_t *plen, const uint8_t *payloads, uint8_t *dst) {
+    write_parity_rs(s, padding8, band_crc, n, band_len, G, m, 1, plen, payloads, dst);
 }
 
 // 1: sealed, 0: unsealed, L3C_ERR_INVALID_ARG (message in err): a recognised seal that is damaged.  *body_bytes_out: the bytes in front of
@@ -257,7 +240,7 @@ inline int find_parity_rs(const uint8_t *file, int64_t file_bytes, int64_t *body
     const int64_t padding_at = banded ? 6 : 0;
     const int version = s[4];
     if (version != VERSION && version != VERSION_BANDS && version != VERSION_PARITY) return fail(err, cap, "of an unknown version");
-    int64_t T = 0, n = 0, S = 0, m = 0, G = 0, R = 0, fields_at = 8, table_at = 0;      // fields_at: where plen starts inside the section
+    int64_t T = 0, n = 0, S = 0, m = 0, G = 0, R = 0, fields_at = section_head_bytes(1), table_at = 0;      // fields_at: where plen starts inside the section
     if (version != VERSION) {
         if (!banded)
             return fail(err, cap, version == VERSION_BANDS ? "of an unknown version for a legacy file (version 2, the band seal, needs a banded file)"
@@ -277,14 +260,14 @@ inline int find_parity_rs(const uint8_t *file, int64_t file_bytes, int64_t *body
     }
     if (version == VERSION_PARITY) {
         S = (int64_t)get(file + body - 8, 4);                  // (the separator at [body - 4, body) is the one the table starts behind)
-        if (S < 16 + 12 || S > body - 14 - 4 || memcmp(file + body - S - 4, SEPARATOR, 4) != 0)
+        if (S < parity_section_bytes(1, 1, 0) || S > body - 14 - 4 || memcmp(file + body - S - 4, SEPARATOR, 4) != 0)
             return fail(err, cap, "parity section does not start behind the file's last scale separator");
         body -= S;
         const uint8_t *p = file + body;
         const bool rs = memcmp(p, PARITY_RS_SIGNATURE, 4) == 0;
         if (!rs && memcmp(p, PARITY_SIGNATURE, 4) != 0) return fail(err, cap, "parity section without its 'L3CP' signature");
         G = (int64_t)get(p + 4, 2), m = (int64_t)get(p + 6, 2), R = 1;
-        if (rs) fields_at = 12;
+        if (rs) fields_at = section_head_bytes(2);
         if (m < 1 || fields_at + 8 + 12 * m > S) return fail_d(err, cap, "parity section is too short for its %d x 3 length fields", (int)m);
         if (rs) {
             R = (int64_t)get(p + 8, 2);
@@ -293,9 +276,9 @@ inline int find_parity_rs(const uint8_t *file, int64_t file_bytes, int64_t *body
         }
         int64_t sum = 0;
         for (int64_t i = 0; i < 3 * m; ++i) sum += (int64_t)get(p + fields_at + 4 * i, 4);
-        if (!rs && S != section_bytes(m, sum)) return fail(err, cap, "parity section length is not 16 + 12 m + the sum of its payload lengths");
-        if (rs && S != rs_section_bytes(m, R, sum))
-            return fail(err, cap, "parity section length is not 20 + 12 m + R times the sum of its payload lengths");
+        if (S != parity_section_bytes(m, R, sum))
+            return fail(err, cap, rs ? "parity section length is not 20 + 12 m + R times the sum of its payload lengths"
+                                     : "parity section length is not 16 + 12 m + the sum of its payload lengths");
     }
     if (s[5] != 0) return fail(err, cap, "with non-zero flags");
     if (padding_at + 8 > body) return fail(err, cap, "on a file too short for its padding fields");

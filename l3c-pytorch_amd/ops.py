@@ -933,26 +933,72 @@ def banded_scale_desc(C, H, W, L, groups):
                             ptr(out_l, torch.uint8), ptr(nb_l, torch.int32), out_l.shape[1], C, H, W, L)
 
 
+def _band_parity(name, B, H, W, L, groups, G, R, out):
+    """band_parity (R None: l3c_band_parity, slots (B, 3, m, stride)) and band_parity_rs (l3c_band_parity_rs, slots (B, 3, m, R, stride))."""
+    n = -(-(H * W) // L)
+    m = _lib.load().l3c_band_parity_groups(n, int(G))
+    _lib.check(min(m, 0))
+    lead = (B, 3, m) if R is None else (B, 3, m, int(R))
+    dev = groups[-1][0].device
+    if out is None:
+        stride = -(-max(g[0].shape[1] for g in groups) // 16) * 16
+        out = (torch.empty(lead + (stride,), dtype=torch.uint8, device=dev), torch.empty((B, 3, m), dtype=torch.int32, device=dev))
+    parity, nbytes = out
+    if tuple(parity.shape[:-1]) != lead or tuple(nbytes.shape) != (B, 3, m):
+        if R is None:
+            raise ValueError('band_parity: out must be (B, 3, m, stride) and (B, 3, m) with m = {}, got {} and {}'.format(
+                m, tuple(parity.shape), tuple(nbytes.shape)))
+        raise ValueError('band_parity_rs: out must be (B, 3, m, R, stride) and (B, 3, m) with m = {}, R = {}, got {} and {}'.format(
+            m, int(R), tuple(parity.shape), tuple(nbytes.shape)))
+    desc = banded_scale_desc(3, H, W, L, groups)
+    call(name, ctypes.byref(desc), B, int(G), *(() if R is None else (int(R),)), ptr(parity, torch.uint8), parity.shape[-1], ptr(nbytes, torch.int32),
+         stream())
+    return parity, nbytes
+
+
 def band_parity(B, H, W, L, groups, G, out=None):
     """l3c_band_parity: the XOR parity of the finest record's band payloads (3 channels; `groups` as banded_scale_desc takes them), bands
     { j : j % m == g } of a channel in group g, m = ceil(n / G) -> (parity uint8 (B, 3, m, stride), nbytes int32 (B, 3, m)) on the device:
     bytes [0, nbytes) of a slot are the parity payload (the bytes behind its 4-byte-rounded length are not written), nbytes -1 where a
     member overran.  out: (parity, nbytes) tensors of the caller's instead of new ones.  No host synchronisation."""
-    n = -(-(H * W) // L)
-    m = _lib.load().l3c_band_parity_groups(n, int(G))
-    _lib.check(min(m, 0))
-    dev = groups[-1][0].device
-    if out is None:
-        stride = -(-max(g[0].shape[1] for g in groups) // 16) * 16
-        out = (torch.empty((B, 3, m, stride), dtype=torch.uint8, device=dev), torch.empty((B, 3, m), dtype=torch.int32, device=dev))
-    parity, nbytes = out
-    if tuple(parity.shape[:3]) != (B, 3, m) or tuple(nbytes.shape) != (B, 3, m):
-        raise ValueError('band_parity: out must be (B, 3, m, stride) and (B, 3, m) with m = {}, got {} and {}'.format(
-            m, tuple(parity.shape), tuple(nbytes.shape)))
-    stride = parity.shape[3]
-    desc = banded_scale_desc(3, H, W, L, groups)
-    call('l3c_band_parity', ctypes.byref(desc), B, int(G), ptr(parity, torch.uint8), stride, ptr(nbytes, torch.int32), stream())
-    return parity, nbytes
+    return _band_parity('l3c_band_parity', B, H, W, L, groups, G, None, out)
+
+
+def band_parity_rs(B, H, W, L, groups, G, R, out=None):
+    """l3c_band_parity_rs: band_parity with R rows per group over GF(2^8) (container.rs_parity is the reference; row 0 is band_parity's
+    payload) -> (parity uint8 (B, 3, m, R, stride), nbytes int32 (B, 3, m)) on the device: one length for the R rows of a group, -1 where a
+    member overran (none of the group's slots is written then).  R in 1..4; G <= 255 when R > 1.  No host synchronisation."""
+    return _band_parity('l3c_band_parity_rs', B, H, W, L, groups, G, R, out)
+
+
+def _u8_spans(name, data, offsets, lengths, coefs, group_first, out, out_offsets, out_lengths):
+    """u8_xor_spans (coefs None: l3c_u8_xor_spans) and u8_gf_spans (l3c_u8_gf_spans): the span, slot and group tables, and the coefficients
+    where there are any, checked and uploaded as ONE table, then the call."""
+    group_first = np.ascontiguousarray(group_first, dtype=np.int64)
+    n_groups = group_first.shape[0] - 1
+    if n_groups <= 0:
+        return out
+    spans = np.zeros(len(offsets), dtype=SPAN_DTYPE)
+    spans['offset'], spans['bytes'] = offsets, lengths
+    slots = np.zeros(n_groups, dtype=SPAN_DTYPE)
+    slots['offset'], slots['bytes'] = out_offsets, out_lengths
+    parts = [spans.view(np.int64), slots.view(np.int64), group_first]            # the 8-byte tables in front, each 8-byte aligned
+    if coefs is not None:
+        coef = np.asarray(coefs, dtype=np.int64).reshape(-1)
+        if coef.shape[0] != spans.shape[0] or (coef.size and (coef.min() < 0 or coef.max() > 255)):
+            raise ValueError('u8_gf_spans: one coefficient in 0..255 per span')
+        coef8 = np.zeros(-(-coef.shape[0] // 8) * 8, dtype=np.uint8)              # padded to whole words
+        coef8[:coef.shape[0]] = coef
+        parts.append(coef8.view(np.int64))
+    if data.dtype != torch.uint8 or out.dtype != torch.uint8 or not data.is_contiguous() or not out.is_contiguous():
+        raise ValueError('{}: data and out must be contiguous uint8 tensors'.format(name[4:]))
+    table_d = upload_small(np.concatenate(parts))
+    a, b, c = 2 * spans.shape[0], 2 * spans.shape[0] + 2 * n_groups, 2 * spans.shape[0] + 3 * n_groups + 1
+    coef_args = () if coefs is None else (coef8.ctypes.data, ptr(table_d[c:], torch.int64) if a else None)
+    call(name, ptr(data, torch.uint8), data.numel(), spans.ctypes.data, ptr(table_d[:a], torch.int64) if a else None, *coef_args, spans.shape[0],
+         group_first.ctypes.data, ptr(table_d[b:c], torch.int64), n_groups, slots.ctypes.data, ptr(table_d[a:b], torch.int64),
+         ptr(out, torch.uint8), out.numel(), stream())
+    return out
 
 
 def u8_xor_spans(data, offsets, lengths, group_first, out, out_offsets, out_lengths):
@@ -960,71 +1006,11 @@ def u8_xor_spans(data, offsets, lengths, group_first, out, out_offsets, out_leng
     lengths[k]], k in [group_first[g], group_first[g + 1]), each cut or zero-extended to out_lengths[g], then zero bytes up to
     ((out_lengths[g] + 3) // 4) * 4 + 4.  data, out: contiguous uint8 device tensors that do not overlap; the tables: host integer sequences
     (offsets multiples of 4), checked on the host, uploaded through upload_small.  No groups: nothing is launched.  No host synchronisation."""
-    group_first = np.ascontiguousarray(group_first, dtype=np.int64)
-    n_groups = group_first.shape[0] - 1
-    if n_groups <= 0:
-        return out
-    spans = np.zeros(len(offsets), dtype=SPAN_DTYPE)
-    spans['offset'], spans['bytes'] = offsets, lengths
-    slots = np.zeros(n_groups, dtype=SPAN_DTYPE)
-    slots['offset'], slots['bytes'] = out_offsets, out_lengths
-    if data.dtype != torch.uint8 or out.dtype != torch.uint8 or not data.is_contiguous() or not out.is_contiguous():
-        raise ValueError('u8_xor_spans: data and out must be contiguous uint8 tensors')
-    # ONE upload for the three tables, each 8-byte aligned
-    table = np.concatenate([spans.view(np.int64), slots.view(np.int64), group_first])
-    table_d = upload_small(table)
-    a, b = 2 * spans.shape[0], 2 * spans.shape[0] + 2 * n_groups
-    call('l3c_u8_xor_spans', ptr(data, torch.uint8), data.numel(), spans.ctypes.data, ptr(table_d[:a], torch.int64) if a else None, spans.shape[0],
-         group_first.ctypes.data, ptr(table_d[b:], torch.int64), n_groups, slots.ctypes.data, ptr(table_d[a:b], torch.int64),
-         ptr(out, torch.uint8), out.numel(), stream())
-    return out
-
-
-def band_parity_rs(B, H, W, L, groups, G, R, out=None):
-    """l3c_band_parity_rs: band_parity with R rows per group over GF(2^8) (container.rs_parity is the reference; row 0 is band_parity's
-    payload) -> (parity uint8 (B, 3, m, R, stride), nbytes int32 (B, 3, m)) on the device: one length for the R rows of a group, -1 where a
-    member overran (none of the group's slots is written then).  R in 1..4; G <= 255 when R > 1.  No host synchronisation."""
-    n = -(-(H * W) // L)
-    m = _lib.load().l3c_band_parity_groups(n, int(G))
-    _lib.check(min(m, 0))
-    R = int(R)
-    dev = groups[-1][0].device
-    if out is None:
-        stride = -(-max(g[0].shape[1] for g in groups) // 16) * 16
-        out = (torch.empty((B, 3, m, R, stride), dtype=torch.uint8, device=dev), torch.empty((B, 3, m), dtype=torch.int32, device=dev))
-    parity, nbytes = out
-    if tuple(parity.shape[:4]) != (B, 3, m, R) or tuple(nbytes.shape) != (B, 3, m):
-        raise ValueError('band_parity_rs: out must be (B, 3, m, R, stride) and (B, 3, m) with m = {}, R = {}, got {} and {}'.format(
-            m, R, tuple(parity.shape), tuple(nbytes.shape)))
-    desc = banded_scale_desc(3, H, W, L, groups)
-    call('l3c_band_parity_rs', ctypes.byref(desc), B, int(G), R, ptr(parity, torch.uint8), parity.shape[4], ptr(nbytes, torch.int32), stream())
-    return parity, nbytes
+    return _u8_spans('l3c_u8_xor_spans', data, offsets, lengths, None, group_first, out, out_offsets, out_lengths)
 
 
 def u8_gf_spans(data, offsets, lengths, coefs, group_first, out, out_offsets, out_lengths):
     """l3c_u8_gf_spans: u8_xor_spans with one GF(2^8) coefficient per span (polynomial 0x11D): slot g receives the XOR over its spans k of
     coefs[k] * data[offsets[k]:offsets[k] + lengths[k]], cut or zero-extended and zero-padded as u8_xor_spans does.  coefs: host integers
     0..255, one per span; a span with coefficient 0 is not read.  No groups: nothing is launched.  No host synchronisation."""
-    group_first = np.ascontiguousarray(group_first, dtype=np.int64)
-    n_groups = group_first.shape[0] - 1
-    if n_groups <= 0:
-        return out
-    spans = np.zeros(len(offsets), dtype=SPAN_DTYPE)
-    spans['offset'], spans['bytes'] = offsets, lengths
-    slots = np.zeros(n_groups, dtype=SPAN_DTYPE)
-    slots['offset'], slots['bytes'] = out_offsets, out_lengths
-    coef = np.asarray(coefs, dtype=np.int64).reshape(-1)
-    if coef.shape[0] != spans.shape[0] or (coef.size and (coef.min() < 0 or coef.max() > 255)):
-        raise ValueError('u8_gf_spans: one coefficient in 0..255 per span')
-    if data.dtype != torch.uint8 or out.dtype != torch.uint8 or not data.is_contiguous() or not out.is_contiguous():
-        raise ValueError('u8_gf_spans: data and out must be contiguous uint8 tensors')
-    # ONE upload for the four tables, the 8-byte ones in front; the coefficients padded to whole words
-    coef8 = np.zeros(-(-coef.shape[0] // 8) * 8, dtype=np.uint8)
-    coef8[:coef.shape[0]] = coef
-    table = np.concatenate([spans.view(np.int64), slots.view(np.int64), group_first, coef8.view(np.int64)])
-    table_d = upload_small(table)
-    a, b, c = 2 * spans.shape[0], 2 * spans.shape[0] + 2 * n_groups, 2 * spans.shape[0] + 3 * n_groups + 1
-    call('l3c_u8_gf_spans', ptr(data, torch.uint8), data.numel(), spans.ctypes.data, ptr(table_d[:a], torch.int64) if a else None,
-         coef8.ctypes.data, ptr(table_d[c:], torch.int64) if a else None, spans.shape[0], group_first.ctypes.data, ptr(table_d[b:c], torch.int64),
-         n_groups, slots.ctypes.data, ptr(table_d[a:b], torch.int64), ptr(out, torch.uint8), out.numel(), stream())
-    return out
+    return _u8_spans('l3c_u8_gf_spans', data, offsets, lengths, coefs, group_first, out, out_offsets, out_lengths)

@@ -16,19 +16,21 @@ GUARD = 0xA5
 _CASES = {}
 
 
-def coder_output(B, stride_full, stride_last, seed, overrun=None):
+def coder_output(B, stride_full, stride_last, seed, overrun=None, N=N):
     """Synthetic coder output of the finest record of B images, random bytes everywhere (behind the lengths too), lengths from LENS.
     Stream (b, c) = (0, 0): the longest member of group 0 at G = 3 (bands 0, 6, 12) comes first, of group 1 (1, 7, 13) last, of group 2
-    (2, 8, 14) in the middle, 4097 bytes beside 64.  overrun: a (b, c, j) that reports L3C_AC_OVERRUN.
+    (2, 8, 14) in the middle, 4097 bytes beside 64.  overrun: a (b, c, j) that reports L3C_AC_OVERRUN.  N: another band count than 16 (then
+    without the three arranged groups).
     -> (groups on the device, lens (B, 3, N), payloads[b][c][j] bytes)."""
-    key = (B, stride_full, stride_last, seed, overrun)
+    key = (B, stride_full, stride_last, seed, overrun, N)
     if key in _CASES:
         return _CASES[key]
     rng = np.random.RandomState(seed)
     lens = np.asarray([[[LENS[(5 * j + 3 * c + 7 * b + seed) % len(LENS)] for j in range(N)] for c in range(3)] for b in range(B)], dtype=np.int64)
-    lens[0, 0, [0, 6, 12]] = (4097, 64, 5)
-    lens[0, 0, [1, 7, 13]] = (64, 5, 4097)
-    lens[0, 0, [2, 8, 14]] = (64, 4097, 255)
+    if N == 16:
+        lens[0, 0, [0, 6, 12]] = (4097, 64, 5)
+        lens[0, 0, [1, 7, 13]] = (64, 5, 4097)
+        lens[0, 0, [2, 8, 14]] = (64, 4097, 255)
     full = rng.randint(0, 256, (B * 3 * (N - 1), stride_full)).astype(np.uint8)
     last = rng.randint(0, 256, (B * 3, stride_last)).astype(np.uint8)
     payloads = [[[(full[(b * 3 + c) * (N - 1) + j, :lens[b, c, j]] if j + 1 < N else last[b * 3 + c, :lens[b, c, j]]).tobytes() for j in range(N)]
@@ -43,11 +45,11 @@ def coder_output(B, stride_full, stride_last, seed, overrun=None):
     return _CASES[key]
 
 
-def run_band_parity(groups, B, G, stride):
-    m = container.parity_groups(N, G)
+def run_band_parity(groups, B, G, stride, n=N, hw=(H, W)):
+    m = container.parity_groups(n, G)
     parity = torch.full((B, 3, m, stride), GUARD, dtype=torch.uint8, device='cuda')
     nbytes = torch.full((B, 3, m), 0x5A5A5A5A, dtype=torch.int32, device='cuda')
-    ops.band_parity(B, H, W, L, groups, G, out=(parity, nbytes))
+    ops.band_parity(B, hw[0], hw[1], L, groups, G, out=(parity, nbytes))
     torch.cuda.synchronize()
     return parity.cpu().numpy(), nbytes.cpu().numpy()
 
@@ -80,6 +82,16 @@ def test_band_parity_matches_the_reference(G, stride_full, stride_last, stride):
     check_band_parity(parity, nbytes, payloads, G)
     if G == 3:                                                          # the groups of (0, 0): longest first, last, in the middle
         assert list(nbytes[0, 0, :3]) == [4097, 4097, 4097]
+
+
+@pytest.mark.parametrize('G', [12, 9])
+def test_band_parity_of_more_members_than_one_batch(G):
+    """A 32 x 24 plane, n = 12 bands.  G = 12: one group of 12 members, more than the eight the kernel takes at a time: a whole batch and a
+    partly filled one; G = 9: m = 2 groups of 6."""
+    groups, lens, payloads = coder_output(2, 4100, 4104, 5, N=12)
+    parity, nbytes = run_band_parity(groups, 2, G, 4112, n=12, hw=(32, 24))
+    assert parity.shape[2] == {12: 1, 9: 2}[G]
+    check_band_parity(parity, nbytes, payloads, G)
 
 
 def test_band_parity_of_one_image_and_of_one_band():

@@ -65,6 +65,17 @@ def test_band_parity_rs_of_one_and_three_rows(R):
     check_band_parity_rs(parity, nbytes, payloads, 4, R)
 
 
+@pytest.mark.parametrize('R', [2, 4])
+@pytest.mark.parametrize('G', [12, 9])
+def test_band_parity_rs_of_more_members_than_one_batch(G, R):
+    """The case of tests/test_gpu_parity_kernels.py (n = 12 bands: a group of 12 members, a batch of eight and four on top; two groups of 6),
+    where Horner's rule has to run through the empty members above the last one."""
+    groups, lens, payloads = coder_output(2, 4100, 4104, 5, N=12)
+    parity, nbytes = run_band_parity_rs(groups, 2, G, R, 4112, n=12, hw=(32, 24))
+    assert parity.shape[2] == {12: 1, 9: 2}[G]
+    check_band_parity_rs(parity, nbytes, payloads, G, R)
+
+
 def test_band_parity_rs_of_one_band():
     # n == 1: no full-band group, every band its own group of one member: every row is a copy, cut at its length
     last = torch.from_numpy(np.random.RandomState(3).randint(0, 256, (3, 136)).astype(np.uint8)).cuda()
