@@ -1415,6 +1415,54 @@ int l3c_u8_gf_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *
                     const uint8_t *coef, int64_t n_spans, const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups,
                     const l3c_u8_span *out_spans_host, const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream);
 
+/*
+ * HEAD PARITY (Bitcoding(parity=G, parity_head=True)): the parity above covers the band payloads of the finest record; the HEAD of a file
+ * is everything else in its body -- the 14-byte file header, every coarser record whole, and the header, length fields and separator of
+ * the finest record.  The seal version stays 3; the section is of a third kind, 'L3CH': an 'L3CQ' section (R = 1 is allowed and written in
+ * this shape too) with a HEAD PART between the finest record's rows and the section's last 8 bytes:
+ *       0 'L3CH' | 4 u16 G | 6 u16 m | 8 u16 R (1..4) | 10 u16 0 | 12 u32 plen[3][m] | 12 + 12 m the 3 m R finest rows, (c, g, r) order |
+ *       A = 12 + 12 m + R sum(plen): HEAD PART | S - 8 u32 S | S - 4 separator
+ *   HEAD PART    u16 n_records (all scale records, the finest included) | u16 0
+ *                FRAMING COPY: body[0:14]; per record, coarsest first: its 9 header bytes (u8 C, u16 H, u16 W, u32 L) and u32 nbytes[C][n]
+ *                u32 head_crc: CRC-32 of body[0, P0), P0 where the finest record's header starts
+ *                per head record k (every record but the finest): u32 crc[C][n_k], the CRC-32 of each band PAYLOAD | u16 G_k = min(G, n_k) |
+ *                    u16 m_k = ceil(n_k / G_k) | u32 hplen[C][m_k], the longest member of each group
+ *                the rows: per head record, (c, g, r) order, hplen[k][c][g] bytes each; groups, points and zero extension as above
+ *                u32 head_check: CRC-32 of the head part from A up to the first row byte
+ *   check        what it covers for 'L3CQ': the padding bytes, section bytes [0, 12 + 12 m), the section's last 8 bytes, the band table, seal
+ *                bytes 0..19 -- the head part is guarded by head_check alone
+ * A DAMAGED head part (one that cannot be walked, or whose head_check fails) never makes a file unreadable: every l3c_seal_find* reads
+ * the file as the 'L3CQ' file it contains (l3c_seal_find_parity: m = 0, l3c_seal_find_parity_rs: the finest rows).  A head part whose
+ * head_check holds but whose content contradicts itself, the band table or the body's size is "invalid file: seal head ...".
+ * l3c_seal_find_head: 1 for a sealed file with an 'L3CH' section, 0 for every other file, L3C_ERR_INVALID_ARG as l3c_seal_find.  Writing the
+ * section and healing a file from it are the Python side's (container.make_seal(head=...), container.heal_head).
+ */
+typedef struct {
+    int64_t at, bytes;              /* the head part: file bytes [at, at + bytes), head_check in its last 4 */
+    int32_t check_ok;               /* 1: head_check holds */
+    int32_t n_records;              /* the scale records it states (0 where check_ok is 0) */
+} l3c_seal_head;
+int l3c_seal_find_head(const uint8_t *file_host, int64_t file_bytes, l3c_seal_head *head_out);
+
+/*
+ * The encoder side of the head part, both over ALL head records of a batch in ONE launch each, lengths known on the device alone;
+ * scales_host: n_scales in 1..8 records of any C >= 1 as l3c_container_write_banded takes them.  Integer only, no atomics, no allocation,
+ * no host synchronisation.
+ *
+ * l3c_head_parity: l3c_band_parity_rs per record with G_k = min(G, n_k), m_k = ceil(n_k / G_k).  grid.y runs over (record, b, c, g).
+ *   parity          record k's slots uint8 [B][C_k][m_k][R][parity_stride] at parity + parity_offset_host[k] (multiples of 16; the caller sizes
+ *                   the buffer); what is read of a member and written of a slot is as in l3c_band_parity
+ *   parity_nbytes   uint32, record-major, [B][C_k][m_k] per record: one length for the R rows of a group, or L3C_AC_OVERRUN
+ *   parity_stride   % 16 == 0 and >= every coder stride; the sum of B C_k m_k over the records <= 65535
+ *
+ * l3c_band_payload_crc32: zlib's CRC-32 of every band payload, crc_out uint32 record-major, [B][C_k][n_k] per record.  A wavefront per
+ * payload; the word does not depend on the launch geometry.  Length 0 gives 0; a band that reported L3C_AC_OVERRUN gives 0 (its file is
+ * refused anyway).  Nothing at or behind a payload's 4-byte-rounded end is read, the bytes of its last dword behind its length are masked.
+ */
+int l3c_head_parity(const l3c_banded_scale *scales_host, int n_scales, int64_t B, int G, int R, uint8_t *parity, const int64_t *parity_offset_host,
+                    int64_t parity_stride, uint32_t *parity_nbytes, l3c_stream_t stream);
+int l3c_band_payload_crc32(const l3c_banded_scale *scales_host, int n_scales, int64_t B, uint32_t *crc_out, l3c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,11 @@ class SealParityRS(ctypes.Structure):
                 ('payload_bytes', c_i64)]
 
 
+class SealHead(ctypes.Structure):
+    """l3c_seal_head (include/l3c_hip.h): where the head part of an 'L3CH' section lies in its file."""
+    _fields_ = [('at', c_i64), ('bytes', c_i64), ('check_ok', ctypes.c_int32), ('n_records', ctypes.c_int32)]
+
+
 SEAL_BYTES = 24      # include/l3c_hip.h: L3C_SEAL_BYTES
 EPI_RELU, EPI_RESIDUAL, EPI_PIXEL_SHUFFLE = 1, 2, 4
 ABI_VERSION = 4      # include/l3c_hip.h: L3C_ABI_VERSION (4: grouped tables, l3c_decode_rgb, l3c_container_read; no canvas batches)
@@ -360,6 +365,9 @@ PROTOTYPES = {
     'l3c_u8_xor_spans': (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'l3c_band_parity_rs': (c_int, [ctypes.POINTER(BandedScale), c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp]),
     'l3c_u8_gf_spans': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'l3c_seal_find_head': (c_int, [c_vp, c_i64, ctypes.POINTER(SealHead)]),
+    'l3c_head_parity': (c_int, [ctypes.POINTER(BandedScale), c_int, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    'l3c_band_payload_crc32': (c_int, [ctypes.POINTER(BandedScale), c_int, c_i64, c_vp, c_vp]),
 }
 
 # include/l3c_xcheck.h: the TEST-ONLY cross-check library (round-1/2 Winograd F(2x2,3x3) kernel); see load_xcheck()

@@ -106,6 +106,9 @@ class EncodedBatch(object):
         self.parity_group = 0                # Bitcoding(parity=G): the group size asked for (the seal states min(G, n)) ...
         self.parity = None                   # ... and (uint8 (B, 3, m, R, stride), int32 (B, 3, m)) on the finest record's coder output: of
         self.parity_streams = 1              # ops.band_parity_rs for Bitcoding(parity_streams=R) above 1, a view of ops.band_parity's slots for R = 1
+        self.parity_head = False             # Bitcoding(parity_head=True): the 'L3CH' section ...
+        self.head = None                     # ... and (int32 payload CRCs, uint8 slots, int32 lengths) of ops.band_payload_crc32 / ops.head_parity
+                                             # over every record but the finest (ops.head_parity_layout)
 
     def _coder_outputs(self):
         """(C, H, W, out, nbytes) of every coder group, nbytes reshaped to (B, streams per image of that group)."""
@@ -129,6 +132,9 @@ class EncodedBatch(object):
             self.band_crc.record_stream(cur)
         if self.parity is not None:
             for t in self.parity:
+                t.record_stream(cur)
+        if self.head is not None:
+            for t in self.head:
                 t.record_stream(cur)
         return self
 
@@ -202,10 +208,11 @@ class EncodedBatch(object):
         return EncodedBatch.many_to_host_buffer([self], [padding_tuples])
 
     @staticmethod
-    def _seals(encs, bodies):
+    def _seals(encs, bodies, host_head=False):
         """The seal of every file of `encs` (b'' for a batch encoded without): ONE D2H of the frame CRCs (and the band CRCs of
-        seal='bands' batches, and the parity lengths and slots of parity=G batches), the band tables, parity sections and check words on
-        the host."""
+        seal='bands' batches, the parity lengths and slots of parity=G batches, the payload CRCs, lengths and slots of parity_head=True
+        batches), the band tables, parity sections and check words on the host.  host_head: the head parts come from the numpy references
+        on the bodies (container.head_from_body) instead of the device's words."""
         sealed = [e for e in encs if e.seal is not None]
         if not sealed:
             return [[b''] * len(files) for files in bodies]
@@ -216,7 +223,10 @@ class EncodedBatch(object):
                 return (e.frame_crc,)
             if e.parity is None:
                 return (e.frame_crc, e.band_crc)
-            return (e.frame_crc, e.band_crc, e.parity[1], e.parity[0].view(torch.int32))      # (the slots' stride is a multiple of 16)
+            main = (e.frame_crc, e.band_crc, e.parity[1], e.parity[0].view(torch.int32))      # (the slots' stride is a multiple of 16)
+            if e.head is None or host_head:
+                return main
+            return main + (e.head[0], e.head[2], e.head[1].view(torch.int32)) + tuple(nb for s in e.banded_scales for _, nb in s[4])
         words = torch.cat([t.reshape(-1) for e in sealed for t in parts(e)])
         words, at, res = words.cpu().numpy().view(np.uint32), 0, []
         for e, files in zip(encs, bodies):
@@ -242,7 +252,37 @@ class EncodedBatch(object):
                 G = min(e.parity_group, bands[0].shape[1])
                 parity = [(G, [[[host[b, c, g, r, :nb[b, c, g]].tobytes() for r in range(R)] for g in range(m)] for c in range(3)])
                           for b in range(e.B)]
-            res.append([container.make_seal(body, e.seal[0], frame[b], e.seal[1], bands[b], e.band_len, parity=parity[b])
+            head, framing = [None] * e.B, [None] * e.B
+            if e.head is not None and host_head:
+                head = [container.head_from_body(body, e.parity_group, e.parity_streams) for body in files]
+            elif e.head is not None:
+                crc_d, slots, lens = e.head
+                R, scales = e.parity_streams, list(e.banded_scales[:-1])
+                shapes, offsets, stride, _, first = ops.head_parity_layout(e.B, scales, e.parity_group, R)
+                crc_h = words[at:at + crc_d.numel()]
+                at += crc_d.numel()
+                nb = EncodedBatch._checked_nbytes(words[at:at + lens.numel()].view(np.int32))
+                at += lens.numel()
+                host = words[at:at + slots.numel() // 4].view(np.uint8)
+                at += slots.numel() // 4
+                head, crc_at = [[] for _ in range(e.B)], 0
+                for (C, n, m), off, f in zip(shapes, offsets, first):
+                    crcs = crc_h[crc_at:crc_at + e.B * C * n].reshape(e.B, C, n)
+                    crc_at += e.B * C * n
+                    rows = host[off:off + e.B * C * m * R * stride].reshape(e.B, C, m, R, stride)
+                    lk = nb[f:f + e.B * C * m].reshape(e.B, C, m)
+                    for b in range(e.B):
+                        head[b].append((crcs[b], [[[rows[b, c, g, r, :lk[b, c, g]].tobytes() for r in range(R)] for g in range(m)]
+                                                  for c in range(C)]))
+                lengths = []                                     # every record's (B, C, n) length fields: the framing copy needs no walk of the files
+                for C, Hs, Ws, Ls, groups in e.banded_scales:
+                    per = []
+                    for _, nb_d in groups:                       # the full bands (B C (n - 1)), then the last bands (B C)
+                        per.append(EncodedBatch._checked_nbytes(words[at:at + nb_d.numel()].view(np.int32)).reshape(e.B, C, -1))
+                        at += nb_d.numel()
+                    lengths.append(np.concatenate(per, axis=2))
+                framing = [([s[:4] for s in e.banded_scales], [nb[b] for nb in lengths]) for b in range(e.B)]
+            res.append([container.make_seal(body, e.seal[0], frame[b], e.seal[1], bands[b], e.band_len, parity=parity[b], head=head[b], head_framing=framing[b])
                         for b, body in enumerate(files)])
         return res
 
@@ -312,17 +352,19 @@ class EncodedBatch(object):
         return res
 
     def to_bytes_host_assembled(self, padding_tuples=None):
-        """Reference implementation of `to_bytes` on the host (per-scale copies + Python joins); kept for the tests."""
+        """Reference implementation of `to_bytes` on the host (per-scale copies + Python joins; the head part of a parity_head=True batch from
+        container.rs_parity and zlib.crc32 on the payloads); kept for the tests."""
         pl = self.payloads()
         scales = [s[:4] for s in self.banded_scales] if self.bands else [s[:3] for s in self.scales]
         files = [container.write_file(padding_tuples[b] if padding_tuples else (0, 0, 0, 0), scales, [p[b] for p in pl], bool(self.bands))
                  for b in range(self.B)]
-        return [f + s for f, s in zip(files, EncodedBatch._seals([self], [files])[0])]
+        return [f + s for f, s in zip(files, EncodedBatch._seals([self], [files], host_head=True)[0])]
 
 
 class Bitcoding(object):
     def __init__(self, blueprint, times=None, compare_with_theory=False, coder_cus=0, auto_recurse=0, file_writer=None,
-                 coder_streams=4, forward_streams=3, decode_overlap=None, rgb_window='auto', bands=0, seal=False, parity=0, parity_streams=1):
+                 coder_streams=4, forward_streams=3, decode_overlap=None, rgb_window='auto', bands=0, seal=False, parity=0, parity_streams=1,
+                 parity_head=False):
         """coder_streams: side streams the range-coder launches rotate over; forward_streams: streams `encode_many` spreads the forward
         passes of a heterogeneous set over (used when the HIP runtime runs with >= 8 hardware queues -- helpers/runtime.py; the package
         does NOT ask for them on import: applications that code image sets call l3c_pytorch_amd.configure_hip_queues() before their
@@ -356,7 +398,15 @@ class Bitcoding(object):
         written is the band-sealed file's.
         parity_streams=R (1..4; R > 1 needs parity=G, and min(G, bands) <= 255: ValueError otherwise): R parity rows per group over GF(2^8)
         (ops.band_parity_rs; container.rs_parity), the 'L3CQ' section, about R / G of the file's size.  decode_repair then rebuilds up to R
-        damaged bands per group, and a damaged parity row still leaves R - 1 usable.  1: every byte written is today's 'L3CP' file's."""
+        damaged bands per group, and a damaged parity row still leaves R - 1 usable.  1: every byte written is today's 'L3CP' file's.
+        parity_head=True (needs parity=G: ValueError otherwise; INTEGRATION.md "Head parity"): the section becomes an 'L3CH' section, which
+        also protects the HEAD of the file -- the file header, every coarser record, and the finest record's header, length fields and
+        separator: a copy of the framing, a CRC-32 per coarse band payload (ops.band_payload_crc32) and R parity rows per group of
+        min(G, n_k) of them (ops.head_parity), both one launch over all coarser records behind the coder.  decode_repair heals the head
+        first (container.heal_head); every other reader reads the file as the band-sealed file it contains.  The model must write 1..8
+        scale records in front of the finest (ops.HEAD_MAX_RECORDS, what one launch takes; the format itself allows 16): prepare_batch
+        raises ValueError otherwise, before anything is coded.  False: every byte written and every library call made is the 'L3CP' /
+        'L3CQ' file's."""
         if seal not in (False, True, 'bands'):
             raise ValueError("seal must be False, True or 'bands', got {!r}".format(seal))
         if isinstance(parity, bool) or not isinstance(parity, int) or parity < 0:
@@ -371,6 +421,11 @@ class Bitcoding(object):
         if parity_streams > 1:
             container.check_parity_streams(parity_streams, parity, int(bands))
         self.parity_streams = parity_streams
+        if not isinstance(parity_head, bool):
+            raise ValueError('parity_head must be True or False, got {!r}'.format(parity_head))
+        if parity_head and not parity:
+            raise ValueError('parity_head needs parity=G: the head rows are computed over groups of min(G, n) bands with its parity_streams')
+        self.parity_head = parity_head
         if seal == 'bands' and not bands:
             raise ValueError("seal='bands' needs banded files: a band seal holds a CRC per band of the finest record (bands=K, K >= 1)")
         if bands and not 1 <= int(bands) <= MAX_BANDS:
@@ -488,7 +543,7 @@ class Bitcoding(object):
             enc.band_len = band_len(H * W, self.bands)
             enc.band_crc, enc.frame_crc = ops.u8_crc32_bands(imgs.to('cuda').to(torch.uint8).contiguous().view(-1), B, H * W, enc.band_len)
             enc.seal = (self.generation(), self.model_id())
-            enc.parity_group, enc.parity_streams = self.parity, self.parity_streams
+            enc.parity_group, enc.parity_streams, enc.parity_head = self.parity, self.parity_streams, self.parity_head
         elif self.seal:
             enc.frame_crc = ops.u8_crc32(imgs.to('cuda').to(torch.uint8).contiguous().view(-1), B, 3 * H * W)
             enc.seal = (self.generation(), self.model_id())
@@ -501,6 +556,9 @@ class Bitcoding(object):
             else:
                 iv = ops.dmll_encode_intervals(raw.P[scale], sym.contiguous(), self._targets(dmll), C, K, dmll.rgb_scale)
             enc.pending.append((C, Hs, Ws, iv))
+        if enc.parity_head and not 1 <= len(enc.pending) - 1 <= ops.HEAD_MAX_RECORDS:
+            raise ValueError('parity_head needs 1..{} scale records in front of the finest (one l3c_head_parity launch takes that many), this '
+                             'model writes {} record(s)'.format(ops.HEAD_MAX_RECORDS, len(enc.pending)))
         return enc
 
     def code(self, batches):
@@ -529,8 +587,10 @@ class Bitcoding(object):
                         owners.append((enc, (C, Hs, Ws), 1))
                         groups.append((iv, enc.B * C, Hs * Ws))
             results, ws = ops.ac_encode_groups(groups)
-            g, finest = 0, {}
+            g, finest, coarser = 0, {}, {}
             for enc, shape, n_groups in owners:                 # (coarse -> fine: the last record of a batch is its finest)
+                if id(enc) in finest and enc.parity_head:
+                    coarser.setdefault(id(enc), []).append(finest[id(enc)][1] + (finest[id(enc)][2],))
                 finest[id(enc)] = (enc, shape, results[g:g + n_groups])
                 g += n_groups
             for enc, shape, coded in finest.values():
@@ -543,6 +603,9 @@ class Bitcoding(object):
                     else:
                         slots, nb = ops.band_parity(enc.B, Hs, Ws, L, coded, G)
                         enc.parity = (slots.unsqueeze(3), nb)
+                    if enc.parity_head:                          # all coarser records at once: two launches, whatever their count
+                        scales = coarser[id(enc)]
+                        enc.head = (ops.band_payload_crc32(enc.B, scales),) + ops.head_parity(enc.B, scales, enc.parity_group, enc.parity_streams)
             done = torch.cuda.Event()
             done.record(side)
         g = 0
@@ -702,11 +765,12 @@ class Bitcoding(object):
                                      (dmll.x_min, dmll.x_max, dmll.L))
         return pixels.to(out_dtype), framing.padding, info
 
-    def _decode_keeping_finest(self, files):
+    def _decode_keeping_finest(self, files, heads=None):
         """What decode_salvage and decode_repair open with: the seals split off and checked (SealError 'generation' / 'model'), the files
         parsed and uploaded, decode_batch's walk with the finest scale's P and mixture kept
         -> (seals, records, framing, streams, int16 symbols (B, 3, H, W), P, dmll)."""
-        split = [container.split_seal(f, view=True) for f in files]
+        parts = [None if h is None else h.part for h in heads or [None] * len(files)]      # (decode_repair: what heal_head has read already)
+        split = [container.split_seal(f, view=True, head=p) for f, p in zip(files, parts)]
         files, seals = [b for b, _ in split], [s for _, s in split]
         if any(s is not None for s in seals):
             container.check_seals(seals, self.generation(), self.model_id)
@@ -782,8 +846,14 @@ class Bitcoding(object):
         ops.u8_xor_spans call).  r0 = 0 first; where the group's positions still fail and t < R, a later round takes r0 = 1 .. R - t -- what
         survives a damaged parity row.  No (group, erasure set, window) is tried twice.
         info.files: per file the HEALED file -- the rebuilt payloads spliced in at their framing offsets, the same length, section, table
-        and seal --, None where nothing was repaired.  Files without parity, intact files and unsealed files: decode_salvage."""
-        seals, records, framing, streams, sym, P, dmll = self._decode_keeping_finest(files)
+        and seal --, None where nothing was repaired.  Files without parity, intact files and unsealed files: decode_salvage.
+        Files with an 'L3CH' section (Bitcoding(parity_head=True)): container.heal_head runs on every file BEFORE anything else, on the host
+        -- it rewrites damaged framing fields from the section's copy and rebuilds damaged payloads of the coarser records --, so everything
+        above sees a file with valid framing and coarse records; info.head says per file what it did, info.files holds the healed file.
+        An intact file costs one zlib.crc32 over its coarser records and makes exactly the library calls of the 'L3CQ' file."""
+        mended = [container.heal_head(f) for f in files]          # host only; an intact file comes back as the object it is
+        given, files, heads = files, [f for f, _ in mended], [h for _, h in mended]
+        seals, records, framing, streams, sym, P, dmll = self._decode_keeping_finest(files, heads)
         K = self.blueprint.net.config_ms.prob.K
         pixels, B = sym.to(torch.uint8), len(files)
         band_lens = {s.band_len for s in seals if s is not None and s.band_crcs is not None}
@@ -796,7 +866,8 @@ class Bitcoding(object):
         pixels, salvage = self._salvage(seals, pixels, sym, P, framing.padding, K, (dmll.x_min, dmll.x_max, dmll.L), words)
         rows = {i: container.band_rows(sorted({j for _, j in got}), seals[i].band_len, records[-1][1:3], framing.padding[i])
                 for i, got in repaired.items()}
-        return pixels.to(out_dtype), framing.padding, container.RepairInfo(repaired, rows, salvage, healed, rounds)
+        healed = [f if h is None and f is not g else h for h, f, g in zip(healed, files, given)]       # a head fix alone heals a file too
+        return pixels.to(out_dtype), framing.padding, container.RepairInfo(repaired, rows, salvage, healed, rounds, head=heads)
 
     def _repair(self, raw, seals, record, framing, streams, pixels, sym, P, dmll, K, words):
         """The rounds of decode_repair on the finest record (C, H, W, L) of B decoded files; `words` (_band_words) is updated in place

@@ -360,6 +360,18 @@ def image_entry_table(hws, pixbase0=0):
 # The code below knows ONE section of R rows per group: 'L3CP' is R = 1, and differs in its signature and the length of its head
 # (_SECTION_KINDS) alone.  A Seal keeps the rows as [c][g][r]; band_parity is rs_parity with one row.
 
+#
+# HEAD PARITY (Bitcoding(parity=G, parity_head=True); INTEGRATION.md "Head parity"): the same seal version with a section of a third kind,
+# 'L3CH' -- an 'L3CQ' section (R = 1..4, all written in this shape) with a HEAD PART between the finest record's rows and the last 8 bytes:
+#     'L3CH' | u16 G | u16 m | u16 R | u16 0 | u32 plen[3][m] | the 3 m R finest rows | A = 12 + 12 m + R sum(plen): HEAD PART | u32 S | separator
+#     HEAD PART: u16 n_records | u16 0 | FRAMING COPY: body[0:14], per record (coarsest first) its 9 header bytes and u32 nbytes[C][n] |
+#         u32 head_crc = crc32(body[0:P0)), P0 where the finest record's header starts |
+#         per head record k (all but the finest): u32 crc[C][n_k] of the band payloads | u16 G_k = min(G, n_k) | u16 m_k | u32 hplen[C][m_k] |
+#         the rows: per head record, (c, g, r) order, hplen[k][c][g] bytes each (rs_parity per channel) |
+#         u32 head_check = crc32 of the head part up to the first row byte
+# The seal's check word covers what it covers for 'L3CQ'; the head part is guarded by head_check alone, and a damaged one never makes a
+# file unreadable: split_seal returns a Seal with head=None, head_damaged=True.  heal_head restores a file's head from it.
+
 SEAL_SIGNATURE = b'L3CS'
 SEAL_VERSION = 1
 SEAL_VERSION_BANDS = 2
@@ -368,7 +380,9 @@ SEAL_BYTES = 24
 TABLE_SIGNATURE = b'L3CT'
 PARITY_SIGNATURE = b'L3CP'
 PARITY_RS_SIGNATURE = b'L3CQ'
-_SECTION_KINDS = {PARITY_SIGNATURE: 8, PARITY_RS_SIGNATURE: 12}        # signature -> where plen starts inside the section
+HEAD_SIGNATURE = b'L3CH'
+_SECTION_KINDS = {PARITY_SIGNATURE: 8, PARITY_RS_SIGNATURE: 12, HEAD_SIGNATURE: 12}        # signature -> where plen starts inside the section
+MAX_HEAD_RECORDS = 16
 
 
 def _section_signature(R):
@@ -385,9 +399,13 @@ class Seal(object):
     parity_group, parity: None but for a version-3 seal: G, and parity[c][g] the parity payload of group g of channel c (m = ceil(n / G)
     groups per channel; bytes, or views of the file split_seal read them from).
     parity_streams: None without parity, 1 for an 'L3CP' section, R = 2..4 for an 'L3CQ' section -- then parity[c][g] is the LIST of the
-    group's R row payloads (rs_parity), all plen[c][g] bytes long.  rows(c, g): the group's row payloads as a list in either case."""
+    group's R row payloads (rs_parity), all plen[c][g] bytes long.  rows(c, g): the group's row payloads as a list in either case.
+    head: the HeadPart of an 'L3CH' section whose head_check holds, else None; head_damaged: True for an 'L3CH' section whose head part
+    could not be read (such a file reads as the 'L3CQ' file it contains).  Neither takes part in ==: the seal is the same seal."""
 
-    def __init__(self, generation, frame_crc, model_id, band_len=None, band_crcs=None, parity_group=None, parity=None, parity_streams=None):
+    def __init__(self, generation, frame_crc, model_id, band_len=None, band_crcs=None, parity_group=None, parity=None, parity_streams=None,
+                 head=None, head_damaged=False):
+        self.head, self.head_damaged = head, bool(head_damaged)
         self.generation, self.frame_crc, self.model_id = int(generation), int(frame_crc), int(model_id)
         self.band_len = None if band_crcs is None else int(band_len)
         self.band_crcs = None if band_crcs is None else np.array(band_crcs, dtype=np.uint32).reshape(3, -1)
@@ -500,10 +518,13 @@ class RepairInfo(object):
     bit for bit.  rows: {file: (y0, y1) or None} their hull in rows of the UNPADDED image (band_rows).  salvage: the SalvageInfo of what
     was left after the repair -- decode_salvage's own when nothing was repairable.  files: per file the healed file's bytes (the rebuilt
     payloads spliced in at their framing offsets; the same length, parity section, table and seal), None where nothing was repaired.
-    rounds: the repair rounds that ran (0: no parity was uploaded, no XOR kernel launched)."""
+    rounds: the repair rounds that ran (0: no parity was uploaded, no XOR kernel launched).
+    head: per file what heal_head did before the decode -- None for a file without an 'L3CH' section, else a HeadInfo -- (None: built by a
+    caller that ran no heal_head); a file whose head was fixed is in `files` as well."""
 
-    def __init__(self, repaired, rows, salvage, files, rounds=0):
+    def __init__(self, repaired, rows, salvage, files, rounds=0, head=None):
         self.repaired, self.rows, self.salvage, self.files, self.rounds = repaired, rows, salvage, list(files), int(rounds)
+        self.head = None if head is None else list(head)
 
     def __repr__(self):
         return 'RepairInfo(repaired={!r}, rows={!r}, rounds={}, healed files={}, salvage={!r})'.format(
@@ -767,14 +788,70 @@ def _band_lengths_of_finest(body, first, C, n):
     return lens
 
 
-def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=None, parity=None):
+def head_from_body(body, G, R):
+    """What make_seal(head=...) takes, from the numpy references: per head record of the banded file `body` (every record but the
+    finest, coarsest first) a pair (crc (C, n) uint32: zlib.crc32 of every band payload, rows[c][g][r]: rs_parity(payloads of channel c,
+    min(G, n), R))."""
+    import zlib
+    p, res = parse_banded(body), []
+    for (C, H, W, L), off, nb in list(zip(p.scales, p.offset, p.nbytes))[:-1]:
+        n = off.shape[1]
+        payloads = [[bytes(body[int(off[c, j]):int(off[c, j] + nb[c, j])]) for j in range(n)] for c in range(C)]
+        crc = np.array([[zlib.crc32(q) & 0xffffffff for q in row] for row in payloads], dtype=np.uint32).reshape(C, n)
+        res.append((crc, [rs_parity(row, min(int(G), n), R) for row in payloads]))
+    return res
+
+
+def _head_part(body, G, R, head, framing=None):
+    """The HEAD PART of an 'L3CH' section for the banded file `body`: the framing copy and head_crc from the body itself, the payload CRCs
+    and rows from `head` (head_from_body's shape).  framing: (scales, nbytes) as parse_banded(body) has them, from a caller that holds them
+    already (the encoder: walking the length fields of a file is a millisecond per thousand bands in Python)."""
+    import zlib
+    p = parse_banded(body) if framing is None else ParsedFraming(None, list(framing[0]), None, [np.asarray(nb, dtype=np.int64) for nb in framing[1]])
+    if len(head) != len(p.scales) - 1:
+        raise ValueError('make_seal: head needs one (crc, rows) pair per record but the finest, {} for {} records'.format(len(head), len(p.scales)))
+    if len(p.scales) > MAX_HEAD_RECORDS:
+        raise ValueError('make_seal: a head section holds at most {} records'.format(MAX_HEAD_RECORDS))
+    meta, at = [struct.pack('<HH', len(p.scales), 0), bytes(body[:14])], 14
+    for k, (header, nb) in enumerate(zip(p.scales, p.nbytes)):
+        if k == len(p.scales) - 1:
+            P0 = at
+        meta += [struct.pack('<BHHI', *header), nb.astype('<u4').tobytes()]
+        at += 9 + 4 * nb.size + int(nb.sum()) + 4
+    if at != len(body):
+        raise ValueError('make_seal: the framing given for the head adds up to {} bytes, the body has {}'.format(at, len(body)))
+    meta.append(struct.pack('<I', zlib.crc32(memoryview(body)[:P0]) & 0xffffffff))
+    rows_out = []
+    for (C, H, W, L), nb, (crc, rows) in zip(p.scales, p.nbytes, head):
+        n = nb.shape[1]
+        Gk = min(int(G), n)
+        m = parity_groups(n, Gk)
+        crc = np.ascontiguousarray(np.asarray(crc).astype(np.int64) & 0xffffffff, dtype='<u4')
+        if crc.shape != (C, n) or len(rows) != C or any(len(row) != m for row in rows) or \
+                any(len(q) != R or len({len(r) for r in q}) != 1 for row in rows for q in row):
+            raise ValueError('make_seal: head needs ({}, {}) payload CRCs and {} x {} x {} rows of one length per group for a record of {} x {} bands'
+                             .format(C, n, C, m, R, C, n))
+        hplen = np.array([[len(q[0]) for q in row] for row in rows], dtype='<u4')
+        meta += [crc.tobytes(), struct.pack('<HH', Gk, m), hplen.tobytes()]
+        rows_out += [bytes(r) for row in rows for q in row for r in q]
+    meta = b''.join(meta)
+    return meta + b''.join(rows_out) + struct.pack('<I', zlib.crc32(meta) & 0xffffffff)
+
+
+def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=None, parity=None, head=None, head_framing=None):
     """The seal bytes for the unsealed file `body` (its padding fields go into the check word): 24 bytes, or with band_crcs ((3, n) words)
     and band_len (the finest record's) the band table and the version-2 seal, seal_bands_bytes(n) bytes.
     parity = (G, payloads) on top of a band seal, payloads[c][g] the parity payload of group g of channel c (band_parity per channel): the
     parity section in front of the table and the version-3 seal.  payloads[c][g] a LIST of R payloads of one length (rs_parity per channel):
-    the 'L3CQ' section for R = 2..4; a list of one is written as the 'L3CP' section of its payload."""
+    the 'L3CQ' section for R = 2..4; a list of one is written as the 'L3CP' section of its payload.
+    head (needs parity): per head record of `body` (every record but the finest, coarsest first) a pair (crc (C, n) words of its band
+    payloads, rows[c][g][r] = rs_parity(payloads of channel c, min(G, n), R)) -- head_from_body's shape: the 'L3CH' section, for every R in
+    1..4; its framing copy and head_crc are taken from `body` (head_framing: the (scales, nbytes) of parse_banded(body), where the caller
+    holds them already)."""
     import zlib
     table, section, checked = b'', b'', b''
+    if head is not None and parity is None:
+        raise ValueError('make_seal: head needs parity (the head rows use its G and R)')
     if parity is not None:
         if band_crcs is None:
             raise ValueError('make_seal: parity needs a band seal (band_crcs and band_len)')
@@ -788,14 +865,17 @@ def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=
         if listed and any(not isinstance(p, (list, tuple)) or len(p) != R or len({len(q) for q in p}) != 1 for row in rows for p in row):
             raise ValueError('make_seal: parity needs {} row payloads of one length in every group'.format(R))
         rows = [[[bytes(q) for q in (p if listed else [p])] for p in row] for row in rows]                # [c][g][r]
-        fields = (int(G), m) if R == 1 else (int(G), m, R, 0)
-        head = _section_signature(R) + struct.pack('<{}H'.format(len(fields)), *fields) + b''.join(struct.pack('<I', len(p[0])) for row in rows for p in row)
+        fields = (int(G), m) if R == 1 and head is None else (int(G), m, R, 0)
+        front = (_section_signature(R) if head is None else HEAD_SIGNATURE) + struct.pack('<{}H'.format(len(fields)), *fields) + \
+            b''.join(struct.pack('<I', len(p[0])) for row in rows for p in row)
         payload = b''.join(q for row in rows for p in row for q in p)
-        S = len(head) + len(payload) + 8
+        if head is not None:
+            payload += _head_part(body, int(G), R, head, head_framing)
+        S = len(front) + len(payload) + 8
         if S >= 1 << 32:
             raise ValueError('make_seal: parity section of {} bytes'.format(S))
         tail = struct.pack('<I', S) + _MAGIC_VALUE_SEP
-        section, checked = head + payload + tail, head + tail
+        section, checked = front + payload + tail, front + tail
     if band_crcs is not None:
         crcs = np.ascontiguousarray(np.asarray(band_crcs).astype(np.int64) & 0xffffffff, dtype='<u4').reshape(3, -1)
         n = crcs.shape[1]
@@ -806,27 +886,29 @@ def make_seal(body, generation, frame_crc, model_id=0, band_crcs=None, band_len=
         T = 20 + 12 * n
         table = TABLE_SIGNATURE + struct.pack('<HHI', n, 0, int(band_len)) + crcs.tobytes() + struct.pack('<I', T) + _MAGIC_VALUE_SEP
     version = SEAL_VERSION_PARITY if section else SEAL_VERSION_BANDS if table else SEAL_VERSION
-    head = SEAL_SIGNATURE + struct.pack('<BBHIQ', version, 0, generation, frame_crc & 0xffffffff, model_id)
-    return section + table + head + struct.pack('<I', zlib.crc32(_padding_bytes(body) + checked + table + head) & 0xffffffff)
+    seal20 = SEAL_SIGNATURE + struct.pack('<BBHIQ', version, 0, generation, frame_crc & 0xffffffff, model_id)
+    return section + table + seal20 + struct.pack('<I', zlib.crc32(_padding_bytes(body) + checked + table + seal20) & 0xffffffff)
 
 
-def split_seal(data, view=False):
-    """-> (body, Seal or None): the file without its seal (and band table), as the parsers above expect it.
-    ValueError('invalid file: seal ...') for a recognised seal with an unknown version, non-zero flags or a wrong check word, and for a band
-    seal whose table is not where its length field says, lacks its signature, has a non-zero reserved field, sits on a legacy file, states
-    another n or L than the finest record's header, or whose frame CRC is not the combination of its band CRCs: never silently treated as
-    absent.  view=True: the body of a sealed file is a memoryview of `data`, not a copy (the decoders: a copy of every file is a
-    millisecond per 10 MB on the host, more than the hash costs on the device); everything above reads either."""
-    import zlib
-    if not is_sealed(data):
-        return data, None
-    end, s = len(data) - SEAL_BYTES, bytes(data[-SEAL_BYTES:])
-    version, flags, generation, frame_crc, model_id, check = struct.unpack('<BBHIQI', s[4:])
-    if version not in (SEAL_VERSION, SEAL_VERSION_BANDS, SEAL_VERSION_PARITY):
+class _Tail(object):
+    """What lies behind a sealed file's body, located from the file's end WITHOUT walking the body: the 24 seal bytes `s` and their
+    fields, the band table (`table`, n), the parity section (section_at, S, signature, G, m, R, fields_at, plen) and `end`, where the body
+    ends.  checked: the section bytes under the seal's check word."""
+
+
+def _tail(data, heal=False):
+    """The tail of a SEALED file (is_sealed) -> _Tail; raises what split_seal raises for a tail whose structure is broken.  The check
+    word, the flags and everything that needs the body's records are split_seal's.  heal (heal_head): the file's signature and the
+    separator the section starts behind -- the finest record's -- are not asked for: they are among the things heal_head restores."""
+    t = _Tail()
+    t.end, t.s = len(data) - SEAL_BYTES, bytes(data[-SEAL_BYTES:])
+    t.version, t.flags, t.generation, t.frame_crc, t.model_id, t.check = struct.unpack('<BBHIQI', t.s[4:])
+    if t.version not in (SEAL_VERSION, SEAL_VERSION_BANDS, SEAL_VERSION_PARITY):
         raise ValueError('invalid file: seal of an unknown version')
-    table, checked, section_at, m = b'', b'', None, 0
+    t.table, t.checked, t.section_at, t.m, t.n, t.signature = b'', b'', None, 0, 0, None
+    version, end = t.version, t.end
     if version != SEAL_VERSION:
-        if not is_banded(data):
+        if not (heal or is_banded(data)):
             raise ValueError('invalid file: seal of an unknown version for a legacy file (version {}, needs a banded file)'.format(
                 '2, the band seal' if version == SEAL_VERSION_BANDS else '3, the parity seal'))
         if end < 20 + 12 + 4:
@@ -838,38 +920,160 @@ def split_seal(data, view=False):
                              '1 <= n <= 1024'.format(version))
         if T > end - 14 - 4 or bytes(data[end - T - 4:end - T]) != _MAGIC_VALUE_SEP:
             raise ValueError("invalid file: seal band table does not start behind the file's last scale separator")
-        table, end = bytes(data[end - T:end]), end - T
-        if table[:4] != TABLE_SIGNATURE:
+        t.table, end, t.n = bytes(data[end - T:end]), end - T, n
+        if t.table[:4] != TABLE_SIGNATURE:
             raise ValueError("invalid file: seal band table without its 'L3CT' signature")
-        if table[6:8] != b'\0\0':
+        if t.table[6:8] != b'\0\0':
             raise ValueError('invalid file: seal band table with a non-zero reserved field')
     if version == SEAL_VERSION_PARITY:
         S, = struct.unpack('<I', bytes(data[end - 8:end - 4]))           # (the separator at [end - 4, end) is the one the table starts behind)
-        if S < parity_section_bytes([0, 0, 0]) or S > end - 14 - 4 or bytes(data[end - S - 4:end - S]) != _MAGIC_VALUE_SEP:
+        if S < parity_section_bytes([0, 0, 0]) or S > end - 14 - 4 or not (heal or bytes(data[end - S - 4:end - S]) == _MAGIC_VALUE_SEP):
             raise ValueError("invalid file: seal parity section does not start behind the file's last scale separator")
         section_at, end = end - S, end - S
         signature = bytes(data[section_at:section_at + 4])
         if signature not in _SECTION_KINDS:
             raise ValueError("invalid file: seal parity section without its 'L3CP' signature")
         G, m = struct.unpack('<HH', bytes(data[section_at + 4:section_at + 8]))
-        fields_at, rs, R = _SECTION_KINDS[signature], signature == PARITY_RS_SIGNATURE, 1
+        fields_at, rs, hd, R = _SECTION_KINDS[signature], signature != PARITY_SIGNATURE, signature == HEAD_SIGNATURE, 1
         if m < 1 or fields_at + 8 + 12 * m > S:
             raise ValueError('invalid file: seal parity section is too short for its {} x 3 length fields'.format(m))
         if rs:
             R, reserved = struct.unpack('<HH', bytes(data[section_at + 8:section_at + 12]))
-            if not 2 <= R <= MAX_PARITY_STREAMS:
+            if hd and not 1 <= R <= MAX_PARITY_STREAMS:
+                raise ValueError("invalid file: seal parity section states {} parity streams, an 'L3CH' section holds 1..4".format(R))
+            if not hd and not 2 <= R <= MAX_PARITY_STREAMS:
                 raise ValueError("invalid file: seal parity section states {} parity streams, an 'L3CQ' section holds 2..4".format(R))
             if reserved:
                 raise ValueError('invalid file: seal parity section with a non-zero reserved field')
         plen = np.frombuffer(bytes(data[section_at + fields_at:section_at + fields_at + 12 * m]), dtype='<u4').astype(np.int64).reshape(3, m)
-        if S != parity_section_bytes(plen, R):
+        if hd and S < parity_section_bytes(plen, R):
+            raise ValueError('invalid file: seal parity section length is less than 20 + 12 m + R times the sum of its payload lengths')
+        if not hd and S != parity_section_bytes(plen, R):
             raise ValueError('invalid file: seal parity section length is not 20 + 12 m + R times the sum of its payload lengths' if rs else
                              'invalid file: seal parity section length is not 16 + 12 m + the sum of its payload lengths')
-        checked = bytes(data[section_at:section_at + fields_at + 12 * m]) + bytes(data[section_at + S - 8:section_at + S])
-    if flags:
+        t.checked = bytes(data[section_at:section_at + fields_at + 12 * m]) + bytes(data[section_at + S - 8:section_at + S])
+        t.section_at, t.S, t.signature, t.G, t.m, t.R, t.fields_at, t.plen = section_at, S, signature, G, m, R, fields_at, plen
+        t.head_at = section_at + fields_at + 12 * m + R * int(plen.sum())                   # A: the head part is file bytes [head_at, head_end)
+        t.head_end = section_at + S - 8
+    t.end = end
+    return t
+
+
+class HeadPart(object):
+    """The head part of an 'L3CH' section whose head_check holds (Seal.head), as _parse_head read it.  records: every scale record's
+    (C, H, W, L), coarsest first, the finest included; nbytes[k]: its (C, n_k) int64 length fields; file_header: the copy of body[0:14];
+    head_crc; for every head record k (all but the finest) crcs[k] (C, n_k) uint32, groups[k] = (G_k, m_k), hplen[k] (C, m_k) int64 and
+    rows[k][c][g][r], views of the file.  reserved, meta_bytes, size: what _check_head checks."""
+
+    def positions(self, k):
+        """Where record k lies in the body by the COPY's lengths -> (header position, (C, n) length field positions, the separator's)."""
+        at = 14 + sum(9 + 4 * nb.size + int(nb.sum()) + 4 for nb in self.nbytes[:k])
+        nb = self.nbytes[k]
+        flat = nb.reshape(-1)
+        fields = at + 9 + 4 * np.arange(flat.shape[0], dtype=np.int64) + np.cumsum(flat) - flat
+        return at, fields.reshape(nb.shape), at + 9 + 4 * nb.size + int(nb.sum())
+
+
+def _parse_head(hp, R):
+    """The head part `hp` (a bytes-like view of section bytes [A, S - 8)) of a section with R rows per group -> HeadPart, or None where it
+    cannot be walked -- a count or a header no writer produces, a field past its end -- or its head_check does not hold: damaged."""
+    import zlib
+    end, pos = len(hp) - 4, 4 + 14
+    if pos > end:
+        return None
+    h = HeadPart()
+    n_records, h.reserved = struct.unpack('<HH', bytes(hp[:4]))
+    if not 1 <= n_records <= MAX_HEAD_RECORDS:
+        return None
+    h.file_header, h.records, h.nbytes = bytes(hp[4:18]), [], []
+    for _ in range(n_records):
+        if pos + 9 > end:
+            return None
+        C, H, W, L = struct.unpack('<BHHI', bytes(hp[pos:pos + 9]))
+        if C == 0 or H * W == 0 or L == 0 or L % 64 or n_bands(H * W, L) > MAX_BANDS:
+            return None
+        n = n_bands(H * W, L)
+        pos += 9
+        if 4 * C * n > end - pos:
+            return None
+        h.records.append((C, H, W, L))
+        h.nbytes.append(np.frombuffer(bytes(hp[pos:pos + 4 * C * n]), dtype='<u4').astype(np.int64).reshape(C, n))
+        pos += 4 * C * n
+    h.head_crc, = struct.unpack('<I', bytes(hp[pos:pos + 4]))
+    pos += 4
+    h.crcs, h.groups, h.hplen = [], [], []
+    for (C, H, W, L), nb in zip(h.records[:-1], h.nbytes[:-1]):
+        n = nb.shape[1]
+        if 4 * C * n + 4 > end - pos:
+            return None
+        h.crcs.append(np.frombuffer(bytes(hp[pos:pos + 4 * C * n]), dtype='<u4').reshape(C, n))
+        pos += 4 * C * n
+        Gk, m = struct.unpack('<HH', bytes(hp[pos:pos + 4]))
+        pos += 4
+        if not 1 <= m <= n or 4 * C * m > end - pos:
+            return None
+        h.groups.append((Gk, m))
+        h.hplen.append(np.frombuffer(bytes(hp[pos:pos + 4 * C * m]), dtype='<u4').astype(np.int64).reshape(C, m))
+        pos += 4 * C * m
+    if pos > end or zlib.crc32(bytes(hp[:pos])) & 0xffffffff != struct.unpack('<I', bytes(hp[end:end + 4]))[0]:
+        return None
+    h.meta_bytes, h.size = pos, len(hp)
+    h.rows, view = [], memoryview(hp)
+    if pos + R * sum(int(p.sum()) for p in h.hplen) == end:             # (else _check_head refuses the file)
+        for (C, _, _, _), (_, m), hplen in zip(h.records, h.groups, h.hplen):
+            rec = []
+            for c in range(C):
+                rec.append([])
+                for g in range(m):
+                    k = int(hplen[c, g])
+                    rec[c].append([view[pos + r * k:pos + (r + 1) * k] for r in range(R)])
+                    pos += R * k
+            h.rows.append(rec)
+    return h
+
+
+def _check_head(h, body_bytes, G, R, n, L):
+    """A head part whose head_check holds against itself, the band table (n, L) and the body's size: ValueError('invalid file: seal head
+    ...') where they contradict one another (csrc/seal.h: check_head, the same checks in the same order)."""
+    if h.reserved:
+        raise ValueError('invalid file: seal head with a non-zero reserved field')
+    if len(h.records) < 2:
+        raise ValueError('invalid file: seal head states {} scale record(s)'.format(len(h.records)))
+    if h.meta_bytes + R * sum(int(p.sum()) for p in h.hplen) + 4 != h.size:
+        raise ValueError('invalid file: seal head length is not the one its fields add up to')
+    C, H, W, Lf = h.records[-1]
+    if C != 3 or n_bands(H * W, Lf) != n or Lf != L:
+        raise ValueError('invalid file: seal head copy of the finest record does not match the band table')
+    if 14 + sum(9 + 4 * nb.size + int(nb.sum()) + 4 for nb in h.nbytes) != body_bytes:
+        raise ValueError('invalid file: seal head copy adds up to another body length')
+    for nb, (Gk, m), hplen in zip(h.nbytes, h.groups, h.hplen):
+        nk = nb.shape[1]
+        if Gk != min(G, nk) or m != -(-nk // Gk):
+            raise ValueError('invalid file: seal head states a group size or count that is not min(G, n) and ceil(n / G)')
+        if any(int(hplen[c, g]) != int(nb[c, g::m].max()) for c in range(nb.shape[0]) for g in range(m)):
+            raise ValueError("invalid file: seal head states a payload length that is not its longest member's")
+
+
+def split_seal(data, view=False, head=None):
+    """-> (body, Seal or None): the file without its seal (and band table), as the parsers above expect it.
+    ValueError('invalid file: seal ...') for a recognised seal with an unknown version, non-zero flags or a wrong check word, and for a band
+    seal whose table is not where its length field says, lacks its signature, has a non-zero reserved field, sits on a legacy file, states
+    another n or L than the finest record's header, or whose frame CRC is not the combination of its band CRCs: never silently treated as
+    absent.  view=True: the body of a sealed file is a memoryview of `data`, not a copy (the decoders: a copy of every file is a
+    millisecond per 10 MB on the host, more than the hash costs on the device); everything above reads either.
+    An 'L3CH' section (head parity) reads as the 'L3CQ' section it contains, R = 1 included; Seal.head is its head part, or None with
+    Seal.head_damaged where that part is damaged -- never an error.  A head part that is intact but contradicts itself, the table or the body's
+    size is ValueError('invalid file: seal head ...').  head: the HeadPart heal_head has read and checked in this very file (HeadInfo.part):
+    it is taken as it is, not read and checked a second time."""
+    import zlib
+    if not is_sealed(data):
+        return data, None
+    t = _tail(data)
+    s, table, end, n, section_at, generation, frame_crc, model_id = t.s, t.table, t.end, t.n, t.section_at, t.generation, t.frame_crc, t.model_id
+    if t.flags:
         raise ValueError('invalid file: seal with non-zero flags')
     body = (memoryview(data) if view else data)[:end]
-    if check != zlib.crc32(_padding_bytes(body) + checked + table + s[:20]) & 0xffffffff:
+    if t.check != zlib.crc32(_padding_bytes(body) + t.checked + table + s[:20]) & 0xffffffff:
         raise ValueError('invalid file: seal check word does not match (damaged seal or padding fields)')
     if not table:
         return body, Seal(generation, frame_crc, model_id)
@@ -884,6 +1088,7 @@ def split_seal(data, view=False):
         raise ValueError('invalid file: seal frame CRC is not the combination of its band CRCs')
     if section_at is None:
         return body, Seal(generation, frame_crc, model_id, L, crcs)
+    G, m, R, plen, fields_at = t.G, t.m, t.R, t.plen, t.fields_at
     if finest[0] != 3 or not 1 <= G <= n or m != -(-n // G):
         raise ValueError("invalid file: seal parity section does not match the bands of the file's finest scale record")
     if R > 1 and G > MAX_RS_GROUP:
@@ -898,7 +1103,156 @@ def split_seal(data, view=False):
             k = int(plen[c, g])
             rows[c].append([view[at + r * k:at + (r + 1) * k] for r in range(R)])
             at += R * k
-    return body, Seal(generation, frame_crc, model_id, L, crcs, G, rows, R)
+    is_head = t.signature == HEAD_SIGNATURE
+    if not is_head:
+        head = None
+    elif head is None:
+        head = _parse_head(view[t.head_at:t.head_end], R)
+        if head is not None:
+            _check_head(head, end, G, R, n, L)
+    return body, Seal(generation, frame_crc, model_id, L, crcs, G, rows, R, head=head, head_damaged=is_head and head is None)
+
+
+class HeadInfo(object):
+    """What heal_head did to one file with an 'L3CH' section.  framing_fixed: the framing fields rewritten from the section's copy (the
+    file header's first 6 bytes, each of the 4 padding fields, each record header, length field and separator count as one field),
+    framing: the same by kind; repaired, failed: [(record, channel, band)] the payloads of the coarser records (record 0: the coarsest) that
+    did not hash to their CRC and were / were not rebuilt from the head rows; section_damaged: the head part itself is damaged (its
+    head_check fails): nothing was checked, nothing done.  part: the HeadPart as heal_head read and checked it (None where damaged), for
+    the split_seal that follows."""
+
+    KINDS = ('file header', 'padding field', 'record header', 'length field', 'separator')
+
+    def __init__(self, framing=None, repaired=(), failed=(), section_damaged=False, part=None):
+        self.part = part
+        self.framing = dict(framing or {})
+        self.framing_fixed = sum(self.framing.values())
+        self.repaired, self.failed, self.section_damaged = list(repaired), list(failed), bool(section_damaged)
+
+    def __bool__(self):
+        return bool(self.framing_fixed or self.repaired or self.failed or self.section_damaged)
+
+    __nonzero__ = __bool__
+
+    def __repr__(self):
+        return 'HeadInfo(framing_fixed={}, repaired={!r}, failed={!r}, section_damaged={})'.format(
+            self.framing_fixed, self.repaired, self.failed, self.section_damaged)
+
+    def line(self):
+        """One line for people (l3c.py dec --repair), e.g. 'head: 2 length fields and 1 coarse payload restored'."""
+        if self.section_damaged:
+            return 'head: the head section is damaged, nothing of the head could be checked'
+        plural = lambda k, what: '{} {}{}'.format(k, what, '' if k == 1 else 's')                    # noqa: E731
+        done = [plural(self.framing[kind], kind) for kind in self.KINDS if self.framing.get(kind)]
+        if self.repaired:
+            done.append(plural(len(self.repaired), 'coarse payload'))
+        said = ', '.join(done[:-1]) + (' and ' if len(done) > 1 else '') + done[-1] + ' restored' if done else ''
+        if self.failed:
+            said += ('; ' if said else '') + plural(len(self.failed), 'coarse payload') + ' NOT restored (record, channel, band) {}'.format(self.failed[:6])
+        return 'head: ' + (said or 'ok')
+
+
+def heal_head(data):
+    """The pre-pass of Bitcoding.decode_repair: -> (data', HeadInfo or None).  None: the file has no 'L3CH' section (or its seal is damaged
+    where the check word covers it: split_seal then raises as ever).  The tail is found from the file's END and the body is never walked by
+    its own length fields: every position comes from the section's framing copy.
+    Fast path: head_crc matches body[0:P0) and the finest record's header, length fields and separator equal the copy -> `data` itself,
+    nothing copied, no payload hashed.  Slow path: every framing byte that differs from the copy is rewritten (file header, padding
+    fields, record headers, length fields, separators), then every payload of the coarser records is hashed against its CRC; the failures
+    of a group (record, c, g) are its erasures: t = 1..R of them are rebuilt from the head rows r0 .. r0 + t - 1 and the present members
+    (rs_repair_coefficients), r0 = 0 first, later windows while a rebuilt payload still fails its CRC -- the CRC is the arbiter.  data' is
+    then a new bytes object of the same length, section, table and seal.  Band payloads of the finest record are not touched: they are
+    decode_repair's.  A file whose length changed, or whose table, seal or checked section header is damaged, is not healed."""
+    import zlib
+    if not is_sealed(data):
+        return data, None
+    try:
+        t = _tail(data, heal=True)
+    except ValueError:
+        return data, None                                     # (split_seal raises the same error to the caller)
+    if t.signature != HEAD_SIGNATURE:
+        return data, None
+    R = t.R
+    h = _parse_head(memoryview(data)[t.head_at:t.head_end], R)
+    if h is None:
+        return data, HeadInfo(section_damaged=True)
+    # the seal's check word with the COPY's padding fields: a failure is damage to the table, the seal or the section's checked header
+    if t.flags or t.check != zlib.crc32(h.file_header[6:14] + t.checked + t.table + t.s[:20]) & 0xffffffff:
+        return data, None
+    n_stated, _, L = struct.unpack('<HHI', t.table[4:12])
+    if n_stated != t.n or not 1 <= t.G <= t.n or t.m != -(-t.n // t.G):
+        return data, None                                     # (a table or section that split_seal refuses)
+    _check_head(h, t.end, t.G, R, t.n, L)
+    K = len(h.records) - 1
+    P0, fields0, sep0 = h.positions(K)
+    arr = np.frombuffer(data, dtype=np.uint8)
+    want = h.nbytes[K].astype('<u4').reshape(-1).view(np.uint8).reshape(-1, 4)
+    if zlib.crc32(memoryview(data)[:P0]) & 0xffffffff == h.head_crc and bytes(data[P0:P0 + 9]) == struct.pack('<BHHI', *h.records[K]) and \
+            bytes(data[sep0:sep0 + 4]) == _MAGIC_VALUE_SEP and np.array_equal(arr[fields0.reshape(-1, 1) + np.arange(4)], want):
+        return data, HeadInfo(part=h)
+    buf, framing = bytearray(data), {}
+
+    def restore(kind, at, good):
+        if buf[at:at + len(good)] != good:
+            buf[at:at + len(good)] = good
+            framing[kind] = framing.get(kind, 0) + 1
+    restore('file header', 0, h.file_header[:6])
+    for i in range(4):
+        restore('padding field', 6 + 2 * i, h.file_header[6 + 2 * i:8 + 2 * i])
+    where = []
+    for k in range(K + 1):
+        at, fields, sep = h.positions(k)
+        restore('record header', at, struct.pack('<BHHI', *h.records[k]))
+        for f, nb in zip(fields.reshape(-1).tolist(), h.nbytes[k].reshape(-1).tolist()):
+            restore('length field', f, struct.pack('<I', nb))
+        restore('separator', sep, _MAGIC_VALUE_SEP)
+        where.append(fields + 4)
+    repaired, failed, mv = [], [], memoryview(buf)
+    for k in range(K):
+        C, n = h.nbytes[k].shape
+        m = h.groups[k][1]
+        payload = lambda c, j: mv[int(where[k][c, j]):int(where[k][c, j] + h.nbytes[k][c, j])]      # noqa: E731
+        for c in range(C):
+            bad = [j for j in range(n) if zlib.crc32(payload(c, j)) & 0xffffffff != int(h.crcs[k][c, j])]
+            for g in sorted({j % m for j in bad}):
+                erased = [j // m for j in bad if j % m == g]
+                members, size, fixed = list(range(g, n, m)), int(h.hplen[k][c, g]), None
+                for r0 in range(R - len(erased) + 1):                    # (no window at all for more than R erasures)
+                    fixed = _rebuild_members(erased, members, m, r0, size, h.rows[k][c][g], payload, c, h.nbytes[k][c], h.crcs[k][c])
+                    if fixed is not None:
+                        break
+                if fixed is None:
+                    failed += [(k, c, g + e * m) for e in erased]
+                    continue
+                for e, got in zip(erased, fixed):
+                    j = g + e * m
+                    buf[int(where[k][c, j]):int(where[k][c, j]) + len(got)] = got
+                    repaired.append((k, c, j))
+    del mv
+    return bytes(buf), HeadInfo(framing, repaired, failed, part=h)
+
+
+def _rebuild_members(erased, members, m, r0, size, rows, payload, c, nbytes, crcs):
+    """The erased members (indices k: band members[k]) of one group from its rows r0 .. r0 + t - 1 and its present members, on the host
+    -> the rebuilt payloads in erased's order, or None when one of them does not hash to its CRC.  size: the rows' length."""
+    import zlib
+    present = [k for k in range(len(members)) if k not in erased]
+
+    def extended(p):
+        a = np.zeros(size, dtype=np.uint8)
+        a[:len(p)] = np.frombuffer(p, dtype=np.uint8)
+        return a
+    have, parity, res = [extended(payload(c, members[k])) for k in present], [extended(rows[r0 + i]) for i in range(len(erased))], []
+    for e, (row_coefs, member_coefs) in zip(erased, rs_repair_coefficients(erased, present, r0)):
+        d = np.zeros(size, dtype=np.uint8)
+        for a, w in list(zip(parity, row_coefs)) + list(zip(have, member_coefs)):
+            if w:
+                d ^= gf_mul(a, np.uint8(w))
+        got = d[:int(nbytes[members[e]])].tobytes()
+        if zlib.crc32(got) & 0xffffffff != int(crcs[members[e]]):
+            return None
+        res.append(got)
+    return res
 
 
 def band_rows(j, L, frame_hw, padding):

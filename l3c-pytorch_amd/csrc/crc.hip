@@ -1,5 +1,6 @@
 // crc.hip -- sealed files (include/l3c_hip.h: l3c_u8_crc32, l3c_seal_append, l3c_seal_find / l3c_seal_write; the format is csrc/seal.h) and band
-// seals (l3c_u8_crc32_bands, l3c_seal_append_bands, l3c_seal_find_bands / l3c_seal_write_bands: the second half of this file).
+// seals (l3c_u8_crc32_bands, l3c_seal_append_bands, l3c_seal_find_bands / l3c_seal_write_bands: the second half of this file); the CRC-32
+// of every band PAYLOAD of a banded encode's coarser records (l3c_band_payload_crc32, for the head part of the 'L3CH' section).
 //
 // l3c_u8_crc32: zlib's CRC-32 of n_items byte runs, integer only, the same words whatever the launch geometry, no atomics.
 //
@@ -29,6 +30,8 @@
 #include "l3c_common.h"
 #include "crc_spans.h"
 #include "seal.h"
+#include "parity_plan.h"
+#include "banded_rows.h"
 
 namespace {
 
@@ -469,9 +472,134 @@ __global__ __launch_bounds__(64) void seal_append_bands_kernel(uint8_t *__restri
     }
 }
 
+// ---- l3c_band_payload_crc32: every band PAYLOAD of the coder output of several records, lengths known on the device alone ----------------
+//
+// A wavefront per payload (tens of bytes to a few KiB: the coarser records), the rows of WROW bytes and the MULW step of the band chunks
+// above; the four waves of a block never meet.  A payload's slot is only 4-byte aligned and holds garbage behind its length: dword loads
+// in front of the 4-byte-rounded end (one 16-byte load where the address allows it), the bytes of the last dword behind the length masked.
+// The length's two constants, x^(8 len) for Z and x^(-8 fill) for the zero fill of the last row, are products over the set bits of len and
+// fill: lanes 0..31 and 32..63 each hold one factor (X8_POW2) and a five-step butterfly multiplies them.
+struct Pow2Table {
+    uint32_t v[64];      // [i]: x^(8 2^i), [32 + i]: x^(-8 2^i)
+};
+constexpr Pow2Table make_pow2() {
+    Pow2Table t{};
+    uint32_t a = X8, b = X8_INV;
+    for (int i = 0; i < 32; ++i) {
+        t.v[i] = a, t.v[32 + i] = b;
+        a = mulmod(a, a), b = mulmod(b, b);
+    }
+    return t;
+}
+__device__ const Pow2Table g_pow2 = make_pow2();
+
+struct PayloadRecords {
+    l3c_banded_scale sc[l3c_parity::HEAD_MAX_RECORDS];
+    int64_t first[l3c_parity::HEAD_MAX_RECORDS + 1];      // payloads (b, c, j) in front of the record; [count]: all
+    int32_t n[l3c_parity::HEAD_MAX_RECORDS];
+    int32_t count;
+};
+
+// bytes [off, off + 16) of the payload at p (4-byte aligned) of len bytes, zero from byte len on; nothing at or behind its 4-byte-rounded end is read
+__device__ __forceinline__ u32x4 load16_masked(const uint8_t *p, int64_t len, int64_t off) {
+    const int64_t end4 = (len + 3) & ~(int64_t)3;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (off + 16 <= end4 && (reinterpret_cast<uintptr_t>(p + off) & 15) == 0) {
+        const u32x4 q = *reinterpret_cast<const u32x4 *>(p + off);
+        w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (off + 4 * i < end4) w[i] = *reinterpret_cast<const uint32_t *>(p + off + 4 * i);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int64_t keep = len - (off + 4 * i);
+        if (keep < 4) w[i] = keep <= 0 ? 0u : w[i] & (0xFFFFFFFFu >> (8 * (4 - (int)keep)));
+    }
+    return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+__global__ __launch_bounds__(THREADS) void band_payload_crc32_kernel(PayloadRecords h, uint32_t *__restrict__ crc_out) {
+    __shared__ uint32_t lds[2 * 128 * 32];
+    const int t = threadIdx.x, lane = t & 63;
+    for (int i = 0; i < 32; ++i) {                                           // MULW, then MUL32
+        const int idx = i * THREADS + t;
+        lds[idx] = idx < 128 * 32 ? g_tables.v[2][idx >> 5] : g_tables.v[1][(idx >> 5) - 128];
+    }
+    const uint32_t shift = g_shifts.v[THREADS - 64 + lane];
+    const uint32_t *mulw = lds + (t & 31), *mul32 = lds + 128 * 32 + (t & 31);
+    __syncthreads();
+    const int64_t total = h.first[h.count];
+    for (int64_t unit = (int64_t)blockIdx.x * (THREADS / 64) + (t >> 6); unit < total; unit += (int64_t)gridDim.x * (THREADS / 64)) {
+        int k = 0;
+        while (k + 1 < h.count && unit >= h.first[k + 1]) ++k;
+        const l3c_banded_scale &sc = h.sc[k];
+        const int64_t n = h.n[k], at = unit - h.first[k], s = at / n, j = at - s * n;
+        const uint32_t stated = band_nbytes(sc, n, s, j);
+        const int64_t stride = j + 1 < n ? sc.stride_full : sc.stride_last;
+        if (stated == L3C_AC_OVERRUN || (int64_t)stated > stride) {          // (its file is refused anyway)
+            if (lane == 0) crc_out[unit] = 0u;
+            continue;
+        }
+        const uint8_t *p = band_row(sc, n, s, j);
+        const int64_t len = stated, rows = (len + WROW - 1) / WROW;
+        uint32_t a[4] = {0u, 0u, 0u, 0u};
+        for (int64_t r = 0; r < rows; r += 4) {
+            u32x4 q[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) q[u] = load16_masked(p, len, (r + u) * WROW + 16 * lane);      // (behind the last row: len masks all)
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (r + u < rows) row_step(mulw, a, q[u]);
+        }
+        uint32_t v = times(mul32, a[0]);
+        v = times(mul32, v ^ a[1]);
+        v = times(mul32, v ^ a[2]);
+        v = times(mul32, v ^ a[3]);
+        v = mulmod(v, shift);
+        // lanes 0..31: bit i of len -> x^(8 2^i); lanes 32..63: bit i of the fill -> x^(-8 2^i); the butterfly leaves both products everywhere in their half
+        const uint32_t bits = lane < 32 ? (uint32_t)len : (uint32_t)(rows * WROW - len);
+        uint32_t f = (bits >> (lane & 31)) & 1u ? g_pow2.v[lane] : ONE;
+#pragma unroll
+        for (int d = 16; d >= 1; d >>= 1) f = mulmod(f, __shfl_xor(f, d, 64));
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d, 64);
+        const uint32_t unfill = __shfl(f, 32, 64);
+        if (lane == 0) crc_out[unit] = mulmod(v, unfill) ^ mulmod(f, 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int l3c_band_payload_crc32(const l3c_banded_scale *scales_host, int n_scales, int64_t B, uint32_t *crc_out, l3c_stream_t stream) {
+    L3C_REQUIRE(scales_host && crc_out, "null pointer");
+    L3C_REQUIRE(n_scales >= 1 && n_scales <= l3c_parity::HEAD_MAX_RECORDS, "n_scales must be in 1..8");
+    L3C_REQUIRE(B >= 1 && B < 65536, "bad batch size (1 .. 65535)");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(crc_out) & 3) == 0, "crc_out must be 4-byte aligned");
+    PayloadRecords h{};
+    h.count = n_scales;
+    for (int k = 0; k < n_scales; ++k) {
+        const l3c_banded_scale &sc = scales_host[k];
+        L3C_REQUIRE(sc.C >= 1 && sc.C <= 1024 && sc.H > 0 && sc.W > 0, "C must be in 1..1024, H and W positive");
+        L3C_REQUIRE(sc.band_len > 0 && sc.band_len % 64 == 0, "band_len must be a positive multiple of 64");
+        const int64_t hw = (int64_t)sc.H * sc.W, n = (hw + sc.band_len - 1) / sc.band_len;
+        L3C_REQUIRE(n <= 1024, "more than 1024 bands per channel");
+        L3C_REQUIRE(sc.out_last && sc.nbytes_last && (n == 1 || (sc.out_full && sc.nbytes_full)), "null pointer in a scale");
+        L3C_REQUIRE(sc.stride_last > 0 && sc.stride_last % 4 == 0 && (n == 1 || (sc.stride_full > 0 && sc.stride_full % 4 == 0)),
+                    "the coder strides must be positive multiples of 4");
+        L3C_REQUIRE((reinterpret_cast<uintptr_t>(sc.out_last) & 3) == 0 && (reinterpret_cast<uintptr_t>(sc.out_full) & 3) == 0 &&
+                        (reinterpret_cast<uintptr_t>(sc.nbytes_last) & 3) == 0 && (reinterpret_cast<uintptr_t>(sc.nbytes_full) & 3) == 0,
+                    "the coder outputs and the length arrays must be 4-byte aligned");
+        h.sc[k] = sc, h.n[k] = (int32_t)n, h.first[k + 1] = h.first[k] + B * sc.C * n;
+    }
+    const int64_t blocks = (h.first[n_scales] + THREADS / 64 - 1) / (THREADS / 64);
+    hipLaunchKernelGGL(band_payload_crc32_kernel, dim3((unsigned)(blocks < BAND_GRID ? blocks : BAND_GRID)), dim3(THREADS), 0, l3c::as_stream(stream), h,
+                       crc_out);
+    return l3c::check_launch("band_payload_crc32_kernel");
+}
 
 int l3c_seal_find(const uint8_t *file_host, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out) {
     L3C_REQUIRE(file_host && file_bytes >= 0, "null pointer or negative size");
@@ -652,6 +780,14 @@ int l3c_seal_find_parity_rs(const uint8_t *file_host, int64_t file_bytes, int64_
 int l3c_seal_write_parity_rs(const l3c_seal *seal_host, const uint8_t *padding8_host, const uint32_t *band_crc_host, int n, uint32_t band_len, int G,
                              int R, const uint32_t *plen_host, const uint8_t *payloads_host, uint8_t *dst_host) {
     return write_parity_tail(seal_host, padding8_host, band_crc_host, n, band_len, G, R, plen_host, payloads_host, dst_host);
+}
+
+int l3c_seal_find_head(const uint8_t *file_host, int64_t file_bytes, l3c_seal_head *head_out) {
+    L3C_REQUIRE(file_host && file_bytes >= 0 && head_out, "null pointer or negative size");
+    l3c_sealing::HeadAt head;
+    const int rc = l3c_sealing::find_head(file_host, file_bytes, &head, l3c::error_buffer(), 512);
+    head_out->at = head.at, head_out->bytes = head.bytes, head_out->check_ok = head.check_ok, head_out->n_records = head.n_records;
+    return rc;
 }
 
 namespace {

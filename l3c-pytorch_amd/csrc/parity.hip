@@ -14,11 +14,15 @@
 // instructions per dword): the encoder keeps R accumulators and applies Horner's rule over the members, so a member is loaded once for all
 // rows; the repair side multiplies each member by a coefficient that is uniform over the block, by shift and add under scalar branches.
 //
+// l3c_head_parity (the head part of the 'L3CH' section) is l3c_band_parity_rs over SEVERAL records of any channel count in one launch:
+// grid.y runs over (record, b, c, g), the records travel by value, and a block does the work of its record's band_parity_rs block (rs_stream).
+//
 // XOR is the R = 1 / every-coefficient-1 case of the GF(2^8) kernels and could be their instantiation; it keeps kernels of its own because
 // that instantiation measured 8 to 10 % slower (profiles/r23_parity_one_path_latency.log).  The host side is one path: the entry points of a
 // family share their argument checks (check_band_parity, u8_spans).
 #include "l3c_common.h"
 #include "parity_plan.h"
+#include "banded_rows.h"
 
 namespace {
 
@@ -90,14 +94,6 @@ __device__ __forceinline__ void store16(uint8_t *dst, int64_t off, int64_t end, 
         if (off + 4 * i < end) *reinterpret_cast<uint32_t *>(dst + off + 4 * i) = w[i];
 }
 
-// band j of stream s (= b 3 + c) of the finest record's coder output
-__device__ __forceinline__ const uint8_t *band_row(const l3c_banded_scale &sc, int64_t n, int64_t s, int64_t j) {
-    return j + 1 < n ? sc.out_full + (s * (n - 1) + j) * sc.stride_full : sc.out_last + s * sc.stride_last;
-}
-__device__ __forceinline__ uint32_t band_nbytes(const l3c_banded_scale &sc, int64_t n, int64_t s, int64_t j) {
-    return j + 1 < n ? sc.nbytes_full[s * (n - 1) + j] : sc.nbytes_last[s];
-}
-
 // grid (tiles of the longest possible stream, B 3 m): block (x, y) folds tile x of parity stream y = s m + g, the bands j = g, g + m, .. < n
 __global__ __launch_bounds__(THREADS) void band_parity_kernel(l3c_banded_scale sc, int64_t n, int64_t m, uint8_t *__restrict__ parity,
                                                              int64_t parity_stride, uint32_t *__restrict__ parity_nbytes) {
@@ -160,10 +156,11 @@ __device__ __forceinline__ u32x4 gf_scale(u32x4 q, uint32_t c) {
 // acc_r = alpha^r acc_r ^ d_k -- every member is loaded once for all rows.  Members eight at a time as in fold_members, the batches taken from
 // the top; the batch that holds the last member is filled up with empty members ABOVE it, where every acc is still zero.
 // grid (tiles, B 3 m); the slot of row r of stream y is parity + (y R + r) parity_stride
+// (rs_stream: the block's work for output stream y of ONE record, shared with head_parity_kernel below)
 template <int R>
-__global__ __launch_bounds__(THREADS) void band_parity_rs_kernel(l3c_banded_scale sc, int64_t n, int64_t m, uint8_t *__restrict__ parity,
-                                                                int64_t parity_stride, uint32_t *__restrict__ parity_nbytes) {
-    const int64_t y = blockIdx.y, s = y / m, g = y - s * m;
+__device__ __forceinline__ void rs_stream(const l3c_banded_scale &sc, int64_t n, int64_t m, int64_t y, uint8_t *__restrict__ parity,
+                                          int64_t parity_stride, uint32_t *__restrict__ parity_nbytes) {
+    const int64_t s = y / m, g = y - s * m;
     const int64_t count = (n - g + m - 1) / m;
     uint32_t plen = 0;
     bool overrun = false;
@@ -203,6 +200,31 @@ __global__ __launch_bounds__(THREADS) void band_parity_rs_kernel(l3c_banded_scal
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) store16(parity + (y * R + r) * parity_stride, off, end4, acc[r]);
+}
+
+template <int R>
+__global__ __launch_bounds__(THREADS) void band_parity_rs_kernel(l3c_banded_scale sc, int64_t n, int64_t m, uint8_t *__restrict__ parity,
+                                                                int64_t parity_stride, uint32_t *__restrict__ parity_nbytes) {
+    rs_stream<R>(sc, n, m, blockIdx.y, parity, parity_stride, parity_nbytes);
+}
+
+// l3c_head_parity: rs_stream over SEVERAL records of any C in one launch.  The records travel by value; block (x, y) finds its record by
+// the first stream of each (uniform over the block: scalar compares), then is block (x, y - first) of that record's band_parity_rs launch
+// with G_k = min(G, n_k), its slots at parity + offset[k] and its lengths at parity_nbytes + first[k].
+struct HeadRecords {
+    l3c_banded_scale sc[HEAD_MAX_RECORDS];
+    int64_t offset[HEAD_MAX_RECORDS];      // of the record's slots inside `parity`, a multiple of 16
+    int32_t first[HEAD_MAX_RECORDS + 1];   // streams (b, c, g) in front of the record; [count]: all
+    int32_t n[HEAD_MAX_RECORDS], m[HEAD_MAX_RECORDS];
+    int32_t count;
+};
+template <int R>
+__global__ __launch_bounds__(THREADS) void head_parity_kernel(HeadRecords h, uint8_t *__restrict__ parity, int64_t parity_stride,
+                                                             uint32_t *__restrict__ parity_nbytes) {
+    const int y = (int)blockIdx.y;
+    int k = 0;
+    while (k + 1 < h.count && y >= h.first[k + 1]) ++k;
+    rs_stream<R>(h.sc[k], h.n[k], h.m[k], y - h.first[k], parity + h.offset[k], parity_stride, parity_nbytes + h.first[k]);
 }
 
 // u8_xor_spans_kernel with a coefficient per span: slot g = XOR of coef[k] * span k.  A span with coef 0 becomes an empty member: not read.
@@ -335,5 +357,52 @@ int l3c_u8_gf_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *
                     const l3c_u8_span *out_spans_host, const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream) {
     return u8_spans(true, data, data_bytes, spans_host, spans, coef_host, coef, n_spans, group_first_host, group_first, n_groups, out_spans_host,
                     out_spans, out, out_bytes, stream);
+}
+
+int l3c_head_parity(const l3c_banded_scale *scales_host, int n_scales, int64_t B, int G, int R, uint8_t *parity, const int64_t *parity_offset_host,
+                    int64_t parity_stride, uint32_t *parity_nbytes, l3c_stream_t stream) {
+    L3C_REQUIRE(scales_host && parity && parity_offset_host && parity_nbytes, "null pointer");
+    L3C_REQUIRE(n_scales >= 1 && n_scales <= HEAD_MAX_RECORDS, "n_scales must be in 1..8");
+    L3C_REQUIRE(G >= 1, "G must be at least 1");
+    L3C_REQUIRE(R >= 1 && R <= 4, "R must be in 1..4");
+    L3C_REQUIRE(B >= 1 && B <= MAX_STREAMS, "bad batch size");
+    L3C_REQUIRE(parity_stride > 0 && parity_stride % 16 == 0, "parity_stride must be a positive multiple of 16");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(parity) & 15) == 0 && (reinterpret_cast<uintptr_t>(parity_nbytes) & 3) == 0,
+                "parity must be 16-byte aligned, parity_nbytes 4-byte aligned");
+    HeadRecords h{};
+    h.count = n_scales;
+    int64_t streams = 0, longest = 0;
+    for (int k = 0; k < n_scales; ++k) {
+        const l3c_banded_scale &sc = scales_host[k];
+        L3C_REQUIRE(sc.C >= 1 && sc.C <= 1024 && sc.H > 0 && sc.W > 0, "C must be in 1..1024, H and W positive");
+        L3C_REQUIRE(sc.band_len > 0 && sc.band_len % 64 == 0, "band_len must be a positive multiple of 64");
+        const int64_t hw = (int64_t)sc.H * sc.W, n = (hw + sc.band_len - 1) / sc.band_len;
+        L3C_REQUIRE(n <= 1024, "more than 1024 bands per channel");
+        const int64_t Gk = G < n ? G : n, m = (n + Gk - 1) / Gk;
+        L3C_REQUIRE(R == 1 || Gk <= 255, "more than one parity stream needs groups of at most 255 bands");
+        L3C_REQUIRE(sc.out_last && sc.nbytes_last && (n == 1 || (sc.out_full && sc.nbytes_full)), "null pointer in a scale");
+        L3C_REQUIRE(sc.stride_last > 0 && sc.stride_last % 4 == 0 && (n == 1 || (sc.stride_full > 0 && sc.stride_full % 4 == 0)),
+                    "the coder strides must be positive multiples of 4");
+        L3C_REQUIRE((reinterpret_cast<uintptr_t>(sc.out_last) & 3) == 0 && (reinterpret_cast<uintptr_t>(sc.out_full) & 3) == 0 &&
+                        (reinterpret_cast<uintptr_t>(sc.nbytes_last) & 3) == 0 && (reinterpret_cast<uintptr_t>(sc.nbytes_full) & 3) == 0,
+                    "the coder outputs and the length arrays must be 4-byte aligned");
+        const int64_t stride = n > 1 && sc.stride_full > sc.stride_last ? sc.stride_full : sc.stride_last;
+        L3C_REQUIRE(parity_stride >= stride, "parity_stride must be at least the coder strides");
+        L3C_REQUIRE(parity_offset_host[k] >= 0 && parity_offset_host[k] % 16 == 0, "the parity offsets must be non-negative multiples of 16");
+        streams += B * sc.C * m;
+        L3C_REQUIRE(streams <= MAX_STREAMS, "bad sizes: the sum of B * C * m over the records must be in 1..65535");
+        longest = stride > longest ? stride : longest;
+        h.sc[k] = sc, h.offset[k] = parity_offset_host[k], h.n[k] = (int32_t)n, h.m[k] = (int32_t)m, h.first[k + 1] = (int32_t)streams;
+    }
+    L3C_REQUIRE(parity_stride <= INT64_MAX / (MAX_STREAMS * 4) && tiles_of(longest) <= 0x7fffffff, "stride out of range");
+    const dim3 grid((unsigned)tiles_of(longest), (unsigned)streams);
+    const hipStream_t st = l3c::as_stream(stream);
+    switch (R) {
+    case 1: hipLaunchKernelGGL(head_parity_kernel<1>, grid, dim3(THREADS), 0, st, h, parity, parity_stride, parity_nbytes); break;
+    case 2: hipLaunchKernelGGL(head_parity_kernel<2>, grid, dim3(THREADS), 0, st, h, parity, parity_stride, parity_nbytes); break;
+    case 3: hipLaunchKernelGGL(head_parity_kernel<3>, grid, dim3(THREADS), 0, st, h, parity, parity_stride, parity_nbytes); break;
+    default: hipLaunchKernelGGL(head_parity_kernel<4>, grid, dim3(THREADS), 0, st, h, parity, parity_stride, parity_nbytes); break;
+    }
+    return l3c::check_launch("head_parity_kernel");
 }
 }

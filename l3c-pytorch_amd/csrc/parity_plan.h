@@ -16,6 +16,7 @@ namespace l3c_parity {
 
 constexpr int THREADS = 256, TILE_BYTES = THREADS * 16;      // a block folds 4096 bytes of one output stream, 16 per thread
 constexpr int64_t MAX_STREAMS = 65535;                       // grid.y
+constexpr int HEAD_MAX_RECORDS = 8;                          // records of one l3c_head_parity / l3c_band_payload_crc32 call (they travel by value)
 
 constexpr int64_t round4(int64_t n) { return (n + 3) / 4 * 4; }
 constexpr int64_t slot_bytes(int64_t bytes) { return round4(bytes) + 4; }      // what l3c_u8_xor_spans writes of a slot of `bytes` bytes

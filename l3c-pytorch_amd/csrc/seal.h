@@ -37,9 +37,30 @@
 // R = 1 is always written as 'L3CP'.  find_parity reports an 'L3CQ' section as m = 0 (the band-sealed file it contains); find_parity_rs
 // reports both kinds, 'L3CP' as R = 1.
 //
-// ONE writer (write_tail) lays down every tail -- [section] [table] seal, whatever is present -- and ONE reader (find_parity_rs) takes it
-// apart; the two sections are one layout whose signature and head length (section_head_bytes) depend on R.  write, write_bands,
-// write_parity, write_parity_rs and find, find_bands, find_parity are those two under the names of the format's versions.
+// Version 3 with HEAD PARITY carries a section of a third kind, 'L3CH': the 'L3CQ' layout for every R in 1..4, with a HEAD PART between the
+// finest record's rows and the section's last 8 bytes.  "Head" is everything in the body that is not a band payload of the finest record.
+//
+//     0 'L3CH' | 4 u16 G | 6 u16 m | 8 u16 R (1..4) | 10 u16 0 | 12 u32 plen[3][m] | 12 + 12 m the 3 m R finest rows, (c, g, r) order |
+//     A = 12 + 12 m + R sum(plen): HEAD PART | S - 8 u32 S | S - 4 separator
+//
+//     HEAD PART:  u16 n_records (all scale records, the finest included) | u16 0
+//                 FRAMING COPY: body[0:14]; per record, coarsest first: its 9 header bytes (u8 C, u16 H, u16 W, u32 L) and u32 nbytes[C][n]
+//                 u32 head_crc = CRC-32 of body[0, P0), P0 where the finest record's header starts
+//                 per head record k (every record but the finest): u32 crc[C][n_k], the CRC-32 of each band PAYLOAD | u16 G_k = min(G, n_k) |
+//                     u16 m_k = ceil(n_k / G_k) | u32 hplen[C][m_k], the longest member of each group
+//                 the rows: per head record, (c, g, r) order, hplen[k][c][g] bytes each -- groups, points and zero extension as above
+//                 u32 head_check = CRC-32 of the head part from A up to the first row byte
+//
+// check covers what it covers for 'L3CQ' -- section bytes [0, 12 + 12 m) and the last 8 --, the head part is guarded by head_check alone.
+// A head part that cannot be walked or whose head_check fails is DAMAGED, never an error: every reader goes on as for the 'L3CQ' file
+// (find_parity: m = 0; find_parity_rs: the finest rows; find_head: check_ok = 0).  One whose check holds but whose content contradicts
+// itself, the band table or the body's size is "invalid file: seal head ..." (check_head).  This header reads the section; writing it and
+// healing a file from it are container.make_seal(head=...) and container.heal_head.
+//
+// ONE writer (write_tail) lays down every tail -- [section] [table] seal, whatever is present -- and ONE reader (find_tail) takes it
+// apart; the sections are one layout whose signature and head length (section_head_bytes) depend on the kind.  write, write_bands,
+// write_parity, write_parity_rs and find, find_bands, find_parity, find_parity_rs, find_head are those two under the names of the format's
+// versions.
 #ifndef L3C_SEAL_H_
 #define L3C_SEAL_H_
 
@@ -56,6 +77,7 @@ constexpr int VERSION = 1, VERSION_BANDS = 2, VERSION_PARITY = 3, MAX_BANDS = 10
 constexpr uint8_t TABLE_SIGNATURE[4] = {'L', '3', 'C', 'T'};
 constexpr uint8_t PARITY_SIGNATURE[4] = {'L', '3', 'C', 'P'};
 constexpr uint8_t PARITY_RS_SIGNATURE[4] = {'L', '3', 'C', 'Q'};
+constexpr uint8_t HEAD_SIGNATURE[4] = {'L', '3', 'C', 'H'};
 constexpr int MAX_PARITY_STREAMS = 4, MAX_RS_GROUP = 255;
 constexpr uint8_t SIGNATURE[4] = {'L', '3', 'C', 'S'};
 constexpr uint8_t SEPARATOR[4] = {0x46, 0xE2, 0x84, 0x92};
@@ -223,11 +245,89 @@ inline void write_parity(const l3c_seal &s, const uint8_t *padding8, const uint8
     write_parity_rs(s, padding8, band_crc, n, band_len, G, m, 1, plen, payloads, dst);
 }
 
+// The HEAD PART of an 'L3CH' section, hp[0, hbytes): walked field by field.  *check_ok = 0 (and L3C_OK) where it cannot be walked -- a
+// count or a header no writer produces, a field past its end -- or its head_check does not hold: a DAMAGED head part never makes a file
+// unreadable.  A head part whose check holds but whose content contradicts itself, the band table (n, band_len) or the body's size is
+// L3C_ERR_INVALID_ARG, "invalid file: seal head ...".  G, R: the section's.
+constexpr int MAX_HEAD_RECORDS = 16;
+inline int check_head(const uint8_t *hp, int64_t hbytes, int64_t body, int64_t G, int64_t R, int64_t n, uint32_t band_len, int *check_ok,
+                      int *n_records_out, char *err, size_t cap) {
+    *check_ok = 0;
+    if (n_records_out) *n_records_out = 0;
+    const int64_t end = hbytes - 4;                                // where head_check lies
+    int64_t pos = 4 + 14;
+    if (pos > end) return L3C_OK;
+    const int64_t records = (int64_t)get(hp, 2);
+    if (records < 1 || records > MAX_HEAD_RECORDS) return L3C_OK;
+    int64_t C[MAX_HEAD_RECORDS], bands[MAX_HEAD_RECORDS], lens_at[MAX_HEAD_RECORDS], total = 14;
+    uint32_t L_finest = 0;
+    for (int64_t k = 0; k < records; ++k) {
+        if (pos + 9 > end) return L3C_OK;
+        const int64_t hw = (int64_t)get(hp + pos + 1, 2) * (int64_t)get(hp + pos + 3, 2), L = (int64_t)get(hp + pos + 5, 4);
+        C[k] = hp[pos];
+        if (C[k] == 0 || hw == 0 || L == 0 || L % 64) return L3C_OK;
+        bands[k] = (hw + L - 1) / L;
+        if (bands[k] > MAX_BANDS) return L3C_OK;
+        pos += 9;
+        lens_at[k] = pos;
+        if (4 * C[k] * bands[k] > end - pos) return L3C_OK;
+        total += 9 + 4 * C[k] * bands[k] + 4;
+        for (int64_t i = 0; i < C[k] * bands[k]; ++i) total += (int64_t)get(hp + pos + 4 * i, 4);
+        pos += 4 * C[k] * bands[k];
+        L_finest = (uint32_t)L;
+    }
+    pos += 4;                                                      // head_crc
+    int64_t rows = 0, groups_at[MAX_HEAD_RECORDS];
+    for (int64_t k = 0; k + 1 < records; ++k) {
+        if (4 * C[k] * bands[k] + 4 > end - pos) return L3C_OK;
+        pos += 4 * C[k] * bands[k];
+        groups_at[k] = pos;
+        const int64_t m = (int64_t)get(hp + pos + 2, 2);
+        pos += 4;
+        if (m < 1 || m > bands[k] || 4 * C[k] * m > end - pos) return L3C_OK;
+        for (int64_t i = 0; i < C[k] * m; ++i) rows += R * (int64_t)get(hp + pos + 4 * i, 4);
+        pos += 4 * C[k] * m;
+    }
+    if (pos > end || crc32(0, hp, pos) != (uint32_t)get(hp + end, 4)) return L3C_OK;
+    *check_ok = 1;
+    if (n_records_out) *n_records_out = (int)records;
+    if (get(hp + 2, 2) != 0) return fail(err, cap, "head with a non-zero reserved field");
+    if (records < 2) return fail_d(err, cap, "head states %d scale record(s)", (int)records);
+    if (pos + rows != end) return fail(err, cap, "head length is not the one its fields add up to");
+    if (C[records - 1] != 3 || bands[records - 1] != n || L_finest != band_len)
+        return fail(err, cap, "head copy of the finest record does not match the band table");
+    if (total != body) return fail(err, cap, "head copy adds up to another body length");
+    for (int64_t k = 0; k + 1 < records; ++k) {
+        const int64_t Gk = G < bands[k] ? G : bands[k], m = (bands[k] + Gk - 1) / Gk;
+        if ((int64_t)get(hp + groups_at[k], 2) != Gk || (int64_t)get(hp + groups_at[k] + 2, 2) != m)
+            return fail(err, cap, "head states a group size or count that is not min(G, n) and ceil(n / G)");
+        for (int64_t c = 0; c < C[k]; ++c)
+            for (int64_t g = 0; g < m; ++g) {
+                uint32_t longest = 0;
+                for (int64_t j = g; j < bands[k]; j += m) {
+                    const uint32_t len = (uint32_t)get(hp + lens_at[k] + 4 * (c * bands[k] + j), 4);
+                    if (len > longest) longest = len;
+                }
+                if ((uint32_t)get(hp + groups_at[k] + 4 + 4 * (c * m + g), 4) != longest)
+                    return fail(err, cap, "head states a payload length that is not its longest member's");
+            }
+    }
+    return L3C_OK;
+}
+
+// where the head part of an 'L3CH' section lies in its file; at = 0: the file has none
+struct HeadAt {
+    int64_t at, bytes;
+    int check_ok, n_records;
+};
+
 // 1: sealed, 0: unsealed, L3C_ERR_INVALID_ARG (message in err): a recognised seal that is damaged.  *body_bytes_out: the bytes in front of
 // the seal, in front of the band table where the seal has one, in front of the parity section where it has one.  bands_out (may be null):
-// n = 0 for a version-1 seal.  parity_out (may be null): m = 0 unless the seal is of version 3; R = 1 for an 'L3CP' section, 2..4 for 'L3CQ'.
-inline int find_parity_rs(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
-                          l3c_seal_parity_rs *parity_out, char *err, size_t cap) {
+// n = 0 for a version-1 seal.  parity_out (may be null): m = 0 unless the seal is of version 3; R = 1 for an 'L3CP' section, 2..4 for 'L3CQ',
+// 1..4 for 'L3CH' (the finest record's rows).  head_out (may be null): the head part of an 'L3CH' section.
+inline int find_tail(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
+                     l3c_seal_parity_rs *parity_out, HeadAt *head_out, char *err, size_t cap) {
+    if (head_out) head_out->at = 0, head_out->bytes = 0, head_out->check_ok = 0, head_out->n_records = 0;
     if (body_bytes_out) *body_bytes_out = file_bytes;
     if (bands_out) bands_out->n = 0, bands_out->band_len = 0, bands_out->crc = nullptr;
     if (parity_out)
@@ -241,6 +341,8 @@ inline int find_parity_rs(const uint8_t *file, int64_t file_bytes, int64_t *body
     const int version = s[4];
     if (version != VERSION && version != VERSION_BANDS && version != VERSION_PARITY) return fail(err, cap, "of an unknown version");
     int64_t T = 0, n = 0, S = 0, m = 0, G = 0, R = 0, fields_at = section_head_bytes(1), table_at = 0;      // fields_at: where plen starts inside the section
+    int64_t plen_sum = 0;
+    bool hd = false;                                           // an 'L3CH' section: a head part follows the finest record's rows
     if (version != VERSION) {
         if (!banded)
             return fail(err, cap, version == VERSION_BANDS ? "of an unknown version for a legacy file (version 2, the band seal, needs a banded file)"
@@ -264,19 +366,24 @@ inline int find_parity_rs(const uint8_t *file, int64_t file_bytes, int64_t *body
             return fail(err, cap, "parity section does not start behind the file's last scale separator");
         body -= S;
         const uint8_t *p = file + body;
-        const bool rs = memcmp(p, PARITY_RS_SIGNATURE, 4) == 0;
+        hd = memcmp(p, HEAD_SIGNATURE, 4) == 0;
+        const bool rs = hd || memcmp(p, PARITY_RS_SIGNATURE, 4) == 0;
         if (!rs && memcmp(p, PARITY_SIGNATURE, 4) != 0) return fail(err, cap, "parity section without its 'L3CP' signature");
         G = (int64_t)get(p + 4, 2), m = (int64_t)get(p + 6, 2), R = 1;
         if (rs) fields_at = section_head_bytes(2);
         if (m < 1 || fields_at + 8 + 12 * m > S) return fail_d(err, cap, "parity section is too short for its %d x 3 length fields", (int)m);
         if (rs) {
             R = (int64_t)get(p + 8, 2);
-            if (R < 2 || R > MAX_PARITY_STREAMS) return fail_d(err, cap, "parity section states %d parity streams, an 'L3CQ' section holds 2..4", (int)R);
+            if (hd && (R < 1 || R > MAX_PARITY_STREAMS))
+                return fail_d(err, cap, "parity section states %d parity streams, an 'L3CH' section holds 1..4", (int)R);
+            if (!hd && (R < 2 || R > MAX_PARITY_STREAMS))
+                return fail_d(err, cap, "parity section states %d parity streams, an 'L3CQ' section holds 2..4", (int)R);
             if (get(p + 10, 2) != 0) return fail(err, cap, "parity section with a non-zero reserved field");
         }
-        int64_t sum = 0;
-        for (int64_t i = 0; i < 3 * m; ++i) sum += (int64_t)get(p + fields_at + 4 * i, 4);
-        if (S != parity_section_bytes(m, R, sum))
+        for (int64_t i = 0; i < 3 * m; ++i) plen_sum += (int64_t)get(p + fields_at + 4 * i, 4);
+        if (hd && S < parity_section_bytes(m, R, plen_sum))
+            return fail(err, cap, "parity section length is less than 20 + 12 m + R times the sum of its payload lengths");
+        if (!hd && S != parity_section_bytes(m, R, plen_sum))
             return fail(err, cap, rs ? "parity section length is not 20 + 12 m + R times the sum of its payload lengths"
                                      : "parity section length is not 16 + 12 m + the sum of its payload lengths");
     }
@@ -315,9 +422,16 @@ inline int find_parity_rs(const uint8_t *file, int64_t file_bytes, int64_t *body
                     if ((uint32_t)get(p + fields_at + 4 * (c * m + g), 4) != longest[g])
                         return fail(err, cap, "parity section states a payload length that is not its longest member's");
             }
+            if (hd) {
+                const int64_t A = fields_at + 12 * m + R * plen_sum;              // the head part: section bytes [A, S - 8)
+                int ok = 0, records = 0;
+                const int rc = check_head(p + A, S - 8 - A, body, G, R, n, rec_len, &ok, &records, err, cap);
+                if (rc != L3C_OK) return rc;
+                if (head_out) head_out->at = body + A, head_out->bytes = S - 8 - A, head_out->check_ok = ok, head_out->n_records = records;
+            }
             if (parity_out)
                 parity_out->G = (int32_t)G, parity_out->m = (int32_t)m, parity_out->R = (int32_t)R, parity_out->plen = p + fields_at,
-                parity_out->payloads = p + fields_at + 12 * m, parity_out->payload_bytes = S - fields_at - 8 - 12 * m;
+                parity_out->payloads = p + fields_at + 12 * m, parity_out->payload_bytes = R * plen_sum;
         }
         if (bands_out) bands_out->n = (int32_t)n, bands_out->band_len = rec_len, bands_out->crc = t + 12;
     }
@@ -330,14 +444,29 @@ inline int find_parity_rs(const uint8_t *file, int64_t file_bytes, int64_t *body
     return 1;
 }
 
-// find_parity_rs for callers that know the 'L3CP' section alone: an 'L3CQ' file reads as the band-sealed file it contains, m = 0
+// find_tail without the head part: the finest record's rows of every section kind
+inline int find_parity_rs(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
+                          l3c_seal_parity_rs *parity_out, char *err, size_t cap) {
+    return find_tail(file, file_bytes, body_bytes_out, seal_out, bands_out, parity_out, nullptr, err, cap);
+}
+
+// 1: a sealed file with an 'L3CH' section (head_out: its head part), 0: any other file, L3C_ERR_INVALID_ARG: as find_tail
+inline int find_head(const uint8_t *file, int64_t file_bytes, HeadAt *head_out, char *err, size_t cap) {
+    HeadAt head;
+    const int rc = find_tail(file, file_bytes, nullptr, nullptr, nullptr, nullptr, &head, err, cap);
+    if (head_out) *head_out = head;
+    return rc == 1 ? (head.at != 0 ? 1 : 0) : rc;
+}
+
+// find_tail for callers that know the 'L3CP' section alone: an 'L3CQ' or 'L3CH' file reads as the band-sealed file it contains, m = 0
 inline int find_parity(const uint8_t *file, int64_t file_bytes, int64_t *body_bytes_out, l3c_seal *seal_out, l3c_seal_bands *bands_out,
                        l3c_seal_parity *parity_out, char *err, size_t cap) {
     l3c_seal_parity_rs rs;
-    const int rc = find_parity_rs(file, file_bytes, body_bytes_out, seal_out, bands_out, &rs, err, cap);
+    HeadAt head;
+    const int rc = find_tail(file, file_bytes, body_bytes_out, seal_out, bands_out, &rs, &head, err, cap);
     if (parity_out) {
         parity_out->G = 0, parity_out->m = 0, parity_out->plen = nullptr, parity_out->payloads = nullptr, parity_out->payload_bytes = 0;
-        if (rc == 1 && rs.R == 1)
+        if (rc == 1 && rs.R == 1 && head.at == 0)
             parity_out->G = rs.G, parity_out->m = rs.m, parity_out->plen = rs.plen, parity_out->payloads = rs.payloads,
             parity_out->payload_bytes = rs.payload_bytes;
     }

@@ -971,6 +971,66 @@ def band_parity_rs(B, H, W, L, groups, G, R, out=None):
     return _band_parity('l3c_band_parity_rs', B, H, W, L, groups, G, R, out)
 
 
+HEAD_MAX_RECORDS = 8      # csrc/parity_plan.h: the records of one l3c_head_parity / l3c_band_payload_crc32 call
+
+
+def _banded_scale_array(scales):
+    """scales: [(C, H, W, L, groups)] records of a banded encode (groups as banded_scale_desc takes them) -> the l3c_banded_scale array."""
+    arr = (_lib.BandedScale * len(scales))()
+    for k, (C, H, W, L, groups) in enumerate(scales):
+        arr[k] = banded_scale_desc(C, H, W, L, groups)
+    return arr
+
+
+def head_parity_layout(B, scales, G, R):
+    """The slots of head_parity for those records -> (per record (C, n, m), per record its byte offset in the slot buffer, stride, bytes of
+    the buffer, lengths in front of every record + their total): record k's slots are uint8 (B, C_k, m_k, R, stride) at its offset, its
+    lengths int32 (B, C_k, m_k) at its place in the length array; G_k = min(G, n_k), m_k = ceil(n_k / G_k)."""
+    shapes, offsets, first, at = [], [], [0], 0
+    stride = -(-max(g[0].shape[1] for s in scales for g in s[4]) // 16) * 16
+    for C, H, W, L, groups in scales:
+        n = -(-(H * W) // L)
+        m = -(-n // min(int(G), n))
+        shapes.append((C, n, m))
+        offsets.append(at)
+        at += B * C * m * int(R) * stride
+        first.append(first[-1] + B * C * m)
+    return shapes, offsets, stride, at, first
+
+
+def head_parity(B, scales, G, R, out=None):
+    """l3c_head_parity: band_parity_rs over SEVERAL records of any C in ONE launch (the head records of a batch: every record but the
+    finest).  scales: [(C, H, W, L, groups)], at most 8 -> (parity uint8 (bytes,), nbytes int32 (total,)) on the device, laid out as
+    head_parity_layout says; nbytes -1 where a member overran (none of the group's slots is written then).  out: (parity, nbytes) tensors
+    of the caller's, parity 16-byte aligned.  No host synchronisation."""
+    shapes, offsets, stride, total, first = head_parity_layout(B, scales, G, R)
+    dev = scales[0][4][-1][0].device
+    if out is None:
+        out = (torch.empty(total, dtype=torch.uint8, device=dev), torch.empty(first[-1], dtype=torch.int32, device=dev))
+    parity, nbytes = out
+    if parity.dtype != torch.uint8 or nbytes.dtype != torch.int32 or parity.numel() != total or nbytes.numel() != first[-1] \
+            or not parity.is_contiguous() or not nbytes.is_contiguous():
+        raise ValueError('head_parity: out must be contiguous uint8 ({},) and int32 ({},) tensors, got {} and {}'.format(
+            total, first[-1], tuple(parity.shape), tuple(nbytes.shape)))
+    arr = _banded_scale_array(scales)
+    offs = (ctypes.c_int64 * len(scales))(*offsets)
+    call('l3c_head_parity', arr, len(scales), B, int(G), int(R), ptr(parity, torch.uint8), offs, stride, ptr(nbytes, torch.int32), stream())
+    return parity, nbytes
+
+
+def band_payload_crc32(B, scales, out=None):
+    """l3c_band_payload_crc32: zlib.crc32 of every band payload of those records (scales as head_parity takes them), the lengths read on the
+    device -> int32 (sum of B C_k n_k,) device tensor, record-major then (b, c, j); view it as uint32 on the host.  A payload of length 0 gives
+    0, and so does an overrun band.  No host synchronisation."""
+    total = sum(B * C * -(-(H * W) // L) for C, H, W, L, _ in scales)
+    dev = scales[0][4][-1][0].device
+    out = torch.empty(total, dtype=torch.int32, device=dev) if out is None else out
+    if out.dtype != torch.int32 or out.numel() != total or not out.is_contiguous():
+        raise ValueError('band_payload_crc32: out must be a contiguous int32 tensor of {} elements'.format(total))
+    call('l3c_band_payload_crc32', _banded_scale_array(scales), len(scales), B, ptr(out, torch.int32), stream())
+    return out
+
+
 def _u8_spans(name, data, offsets, lengths, coefs, group_first, out, out_offsets, out_lengths):
     """u8_xor_spans (coefs None: l3c_u8_xor_spans) and u8_gf_spans (l3c_u8_gf_spans): the span, slot and group tables, and the coefficients
     where there are any, checked and uploaded as ONE table, then the call."""

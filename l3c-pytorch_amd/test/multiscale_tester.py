@@ -196,11 +196,14 @@ class MultiscaleTester(object):
             raise ValueError('--seal-bands needs --bands: a band seal holds a CRC per band of a banded file')
         if getattr(flags, 'parity', 0) and not getattr(flags, 'seal_bands', False):
             raise ValueError('--parity needs --bands --seal-bands: the band seal is what locates the damage the parity repairs')
+        if getattr(flags, 'parity_head', False) and not getattr(flags, 'parity', 0):
+            raise ValueError('--parity-head needs --parity: the head rows use its groups and streams')
         self.bc = Bitcoding(self.blueprint, times=self.times if getattr(flags, 'write_to_files', None) else None,
                             compare_with_theory=bool(getattr(flags, 'compare_theory', False)), auto_recurse=self.recursive,
                             file_writer=self.file_writer, bands=int(getattr(flags, 'bands', 0) or 0),
                             seal='bands' if getattr(flags, 'seal_bands', False) else bool(getattr(flags, 'seal', False)),
-                            parity=int(getattr(flags, 'parity', 0) or 0), parity_streams=int(getattr(flags, 'parity_streams', 1) or 1))
+                            parity=int(getattr(flags, 'parity', 0) or 0), parity_streams=int(getattr(flags, 'parity_streams', 1) or 1),
+                            parity_head=bool(getattr(flags, 'parity_head', False)))
         self.max_batch = int(getattr(flags, 'batch', None) or 8)
         self.io_threads = int(getattr(flags, 'io_threads', None) or 4)
         exp_name = os.path.basename(experiment_dir)
@@ -524,7 +527,7 @@ class MultiscaleTester(object):
         """region: a box (y0, y1) or (y0, y1, x0, x1) of the image -- only that box is decoded (Bitcoding.decode_region) and written.
         salvage: Bitcoding.decode_salvage -- the picture is written whatever the pixel CRCs say, and SalvageInfo.line() is printed.
         repair: Bitcoding.decode_repair -- salvage that first rebuilds what the file's parity bands can rebuild; RepairInfo.line() is
-        printed, and the healed file goes to write_repaired when something was repaired."""
+        printed (behind HeadInfo.line() for a file with a head section), and the healed file goes to write_repaired when something was repaired."""
         pout_dir = os.path.dirname(os.path.abspath(png_out_p))
         if not os.path.isdir(pout_dir):
             raise DecodeError('png_out_p directory ({}) does not exists!'.format(pout_dir))
@@ -546,6 +549,8 @@ class MultiscaleTester(object):
                 from ..helpers import pad
                 decoded = pad.undo_pad(decoded, *padding[0])
             self._write_img(decoded, png_out_p)
+            if repair and info.head and info.head[0] is not None:
+                print(info.head[0].line())
             print(info.line())
             if repair:
                 if write_repaired and info.files[0] is not None:

@@ -79,6 +79,10 @@ def main(argv=None):
     enc.add_argument('--parity-streams', dest='parity_streams', type=int, default=1, choices=(1, 2, 3, 4), metavar='R',
                      help='with --parity: R parity streams per group over GF(2^8) instead of one (about R / G more bytes): dec --repair then '
                           'rebuilds up to R damaged bands per group, and a damaged parity stream leaves R - 1 usable')
+    enc.add_argument('--parity-head', dest='parity_head', action='store_true',
+                     help='with --parity: protect the HEAD of the file as well -- the file header, the coarser records and every length field '
+                          '(a copy of the framing, a CRC-32 per coarse payload and the same R streams per group over them): dec --repair then '
+                          'heals damaged framing and coarse payloads before it decodes')
     dec.add_argument('img_p')
     dec.add_argument('out_p_png')
     dec.add_argument('--no-verify', dest='no_verify', action='store_true', help='do not check the seal of a sealed file')
