@@ -1310,8 +1310,8 @@ int l3c_seal_append_bands(uint8_t *files, int64_t file_stride, int64_t *file_byt
  * them against the kept P, l3c_sym_to_u8, and ONE l3c_u8_crc32_spans hashes their bands again.  Rounds repeat while one verified a band
  * more; a payload counts as repaired only when all three channels of its position verify, and what still fails is concealed
  * (l3c_dmll_conceal).
- * NOT BUILT: the encoder side and the repair in l3c_encode_batch_banded / l3c_decode_batch_banded callers (NativeCodec), repair in the set
- * readers and in the region decode, protection of the coarser records and of the framing (a damaged length field is an invalid file),
+ * The encoder side behind the C ABI is l3c_encode_batch_banded_parity (NativeCodec(parity=G)), at the end of this header.
+ * NOT BUILT: the repair in l3c_decode_batch_banded callers (NativeCodec.decode_repair), repair in the set readers and in the region decode,
  * verification of parity payloads that were never needed.
  */
 typedef struct {
@@ -1434,8 +1434,9 @@ int l3c_u8_gf_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *
  * A DAMAGED head part (one that cannot be walked, or whose head_check fails) never makes a file unreadable: every l3c_seal_find* reads
  * the file as the 'L3CQ' file it contains (l3c_seal_find_parity: m = 0, l3c_seal_find_parity_rs: the finest rows).  A head part whose
  * head_check holds but whose content contradicts itself, the band table or the body's size is "invalid file: seal head ...".
- * l3c_seal_find_head: 1 for a sealed file with an 'L3CH' section, 0 for every other file, L3C_ERR_INVALID_ARG as l3c_seal_find.  Writing the
- * section and healing a file from it are the Python side's (container.make_seal(head=...), container.heal_head).
+ * l3c_seal_find_head: 1 for a sealed file with an 'L3CH' section, 0 for every other file, L3C_ERR_INVALID_ARG as l3c_seal_find.  The section
+ * is written on the device by l3c_seal_append_parity (below) and on the host by container.make_seal(head=...); healing a file from it is the
+ * Python side's (container.heal_head).
  */
 typedef struct {
     int64_t at, bytes;              /* the head part: file bytes [at, at + bytes), head_check in its last 4 */
@@ -1462,6 +1463,86 @@ int l3c_seal_find_head(const uint8_t *file_host, int64_t file_bytes, l3c_seal_he
 int l3c_head_parity(const l3c_banded_scale *scales_host, int n_scales, int64_t B, int G, int R, uint8_t *parity, const int64_t *parity_offset_host,
                     int64_t parity_stride, uint32_t *parity_nbytes, l3c_stream_t stream);
 int l3c_band_payload_crc32(const l3c_banded_scale *scales_host, int n_scales, int64_t B, uint32_t *crc_out, l3c_stream_t stream);
+
+/*
+ * l3c_seal_append_parity: l3c_seal_append_bands for seal version 3 (csrc/seal_parity.hip): behind every file of a banded encode, at files +
+ * b * file_stride + file_bytes[b], exactly what container.make_seal(body, ..., parity=(G, rows), head=..., head_framing=...) returns --
+ * [section][band table][the 24 seal bytes, version 3] -- and file_bytes[b] grows by as much.  All inputs are on the device, where alone
+ * the lengths are known; two launches, no host round trip:
+ *   a block per file   prefix sums over the file's 3 m (and head) group lengths give every row's place and S; the block writes the
+ *                      section's front and last 8 bytes, the table, the seal and the check word (a wavefront shares the words, as
+ *                      l3c_seal_append_bands), and with `head` stages the head part's meta bytes in the workspace: the framing copy
+ *                      (rebuilt from the records and the padding -- the bytes l3c_container_write_banded wrote; the body's size is
+ *                      checked against them), head_crc over body[0, P0), the payload CRC words, G_k, m_k, hplen, then head_check over them
+ *   grid (tiles x R, groups + 1, B)   a block copies a tile of ONE row from its 16-byte aligned slot to its place in the file, which has any
+ *                      byte alignment: dword stores inside the row, byte stores for the up to three bytes at either edge
+ * Section kinds: R == 1 && !head 'L3CP' (8-byte front, no R field), R > 1 && !head 'L3CQ', head 'L3CH' for every R; G as stated in the file is
+ * min(G, n), plen[c][g] is parity_nbytes.
+ *   scales_host     the records of the encode as l3c_container_write_banded took them, coarsest first, the finest (C == 3) last; without
+ *                   `head` only the finest one's C, H, W and band_len are read
+ *   frame_crc, band_crc     uint32 [B], uint32 [B][3][n]: the outputs of l3c_u8_crc32_bands on the padded frames
+ *   parity, parity_stride, parity_nbytes     the slots [B][3][m][R][parity_stride] and lengths [B][3][m] of l3c_band_parity_rs on the finest
+ *                   record with the same G and R (G > n there: pass min(G, n))
+ *   head_parity, head_parity_offset_host, head_parity_stride, head_parity_nbytes, payload_crc     with `head`: the slots, offsets and lengths
+ *                   of l3c_head_parity and the words of l3c_band_payload_crc32, both over scales_host[0 .. n_scales - 2]; else ignored
+ *   padding, model_id     as for l3c_seal_append           G >= 1, R in 1..4, head 0 or 1, reserved 0
+ *   workspace       l3c_seal_append_parity_workspace_bytes(...) bytes, 16-byte aligned; garbage on entry
+ * file_bytes[b] == -1 stays -1.  A file becomes -1, and nothing of its slot is written, when a group length is L3C_AC_OVERRUN (or exceeds
+ * its slot's stride), when -- with `head` -- a band length does or the body is not 14 + sum (9 + 4 C n + 4) + its payload bytes long, when
+ * the section would reach 2^32 bytes, and when the slot has no room.  Nothing is stored outside [old end, new end) of a slot.
+ * Limits: B * 3 * m <= 65535, with `head` the sum of B C_k m_k over the coarser records <= 65535 (beyond: L3C_ERR_UNSUPPORTED, "slice the
+ * batch"), n_scales <= 8 (L3C_ERR_UNSUPPORTED) and >= 2 with `head`, min(G, n_k) <= 255 when R > 1; with `head` files and file_stride are
+ * multiples of 4.  Every argument is checked before the first launch.
+ */
+typedef struct {
+    uint8_t *files;                         /* [B][file_stride] */
+    int64_t file_stride;
+    int64_t *file_bytes;                    /* int64 [B], 8-byte aligned */
+    int64_t B;
+    const l3c_banded_scale *scales_host;
+    int32_t n_scales;
+    int32_t G, R, head, reserved;
+    const uint16_t *padding;                /* uint16 [B][4] or NULL: zeros */
+    uint64_t model_id;
+    const uint32_t *frame_crc, *band_crc;
+    const uint8_t *parity;
+    int64_t parity_stride;
+    const uint32_t *parity_nbytes;
+    const uint8_t *head_parity;
+    const int64_t *head_parity_offset_host;
+    int64_t head_parity_stride;
+    const uint32_t *head_parity_nbytes, *payload_crc;
+    void *workspace;
+    int64_t workspace_bytes;
+} l3c_seal_parity_desc;
+int64_t l3c_seal_append_parity_workspace_bytes(const l3c_banded_scale *scales_host, int n_scales, int64_t B, int G, int R, int head);
+int l3c_seal_append_parity(const l3c_seal_parity_desc *desc_host, l3c_stream_t stream);
+
+/*
+ * The parity-sealed encode as ONE library call (the files of Bitcoding(bp, bands=K, seal='bands', parity=G, parity_streams=R,
+ * parity_head=head) byte for byte): l3c_encode_batch_banded's schedule unchanged, then on the same stream l3c_u8_crc32_bands on desc.img,
+ * l3c_band_parity_rs on the finest record, with `head` l3c_head_parity and l3c_band_payload_crc32 on the coarser ones, and
+ * l3c_seal_append_parity -- the coder's outputs are still live in the workspace behind l3c_container_write_banded, which is why this is one
+ * entry and not a recipe of calls.  l3c_encode_batch_desc as for l3c_encode_batch_banded; opts_host: G >= 1 (the files state min(G, n)),
+ * R in 1..4, head 0 or 1, reserved 0, model_id as for l3c_seal_append.  Refusals as l3c_seal_append_parity's, before anything is enqueued.
+ *   l3c_encode_banded_parity_file_stride   l3c_encode_banded_file_stride(...) + TAIL rounded up to 32, where with P_s = max(l3c_ac_max_bytes(L_s),
+ *       l3c_ac_max_bytes(last band of scale s)), n_s bands per channel, G_s = min(G, n_s), m_s = ceil(n_s / G_s), C_s channels (3 at scale 0):
+ *       TAIL = F + 12 m_0 + 3 m_0 R P_0 + 8 + (20 + 12 n_0) + 24,  F = 8 for R == 1 without head, else 12; and with head
+ *            + META + sum over s >= 1 of C_s m_s R P_s + 4,  META = 4 + 14 + sum over all s of (9 + 4 C_s n_s) + 4 + sum over s >= 1 of
+ *              (4 C_s n_s + 4 + 4 C_s m_s)
+ *   l3c_encode_batch_banded_parity_workspace_bytes   l3c_encode_batch_banded_workspace_bytes(...) plus, each rounded up to 256: 4 B (frame
+ *       CRCs), 12 B n_0 (band CRCs), l3c_u8_crc32_bands_workspace_bytes(B, 3, H W, L_0), 3 B m_0 R S_0 with S_0 = P_0 rounded up to 16 (the finest
+ *       slots), 12 B m_0 (their lengths), l3c_seal_append_parity_workspace_bytes(...), and with head  sum over s >= 1 of B C_s m_s R S_h with
+ *       S_h = the largest P_s, s >= 1, rounded up to 16 (the head slots), 4 sum B C_s m_s (their lengths), 4 sum B C_s n_s (the payload CRCs)
+ */
+typedef struct {
+    int32_t G, R, head, reserved;
+    uint64_t model_id;
+} l3c_parity_opts;
+int64_t l3c_encode_banded_parity_file_stride(const l3c_net_config *cfg_host, int H, int W, int bands, const l3c_parity_opts *opts_host);
+int64_t l3c_encode_batch_banded_parity_workspace_bytes(const l3c_net_config *cfg_host, int64_t B, int H, int W, int bands,
+                                                       const l3c_parity_opts *opts_host);
+int l3c_encode_batch_banded_parity(const l3c_encode_batch_desc *desc_host, int bands, const l3c_parity_opts *opts_host, l3c_stream_t stream);
 
 #ifdef __cplusplus
 }

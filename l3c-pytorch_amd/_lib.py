@@ -223,6 +223,20 @@ class SealHead(ctypes.Structure):
     _fields_ = [('at', c_i64), ('bytes', c_i64), ('check_ok', ctypes.c_int32), ('n_records', ctypes.c_int32)]
 
 
+class SealParityDesc(ctypes.Structure):
+    """l3c_seal_parity_desc (include/l3c_hip.h): everything l3c_seal_append_parity reads, all but scales_host and the offsets on the device."""
+    _fields_ = [('files', c_vp), ('file_stride', c_i64), ('file_bytes', c_vp), ('B', c_i64), ('scales_host', ctypes.POINTER(BandedScale)),
+                ('n_scales', ctypes.c_int32), ('G', ctypes.c_int32), ('R', ctypes.c_int32), ('head', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('padding', c_vp), ('model_id', ctypes.c_uint64), ('frame_crc', c_vp), ('band_crc', c_vp), ('parity', c_vp),
+                ('parity_stride', c_i64), ('parity_nbytes', c_vp), ('head_parity', c_vp), ('head_parity_offset_host', ctypes.POINTER(c_i64)),
+                ('head_parity_stride', c_i64), ('head_parity_nbytes', c_vp), ('payload_crc', c_vp), ('workspace', c_vp), ('workspace_bytes', c_i64)]
+
+
+class ParityOpts(ctypes.Structure):
+    """l3c_parity_opts (include/l3c_hip.h)."""
+    _fields_ = [('G', ctypes.c_int32), ('R', ctypes.c_int32), ('head', ctypes.c_int32), ('reserved', ctypes.c_int32), ('model_id', ctypes.c_uint64)]
+
+
 SEAL_BYTES = 24      # include/l3c_hip.h: L3C_SEAL_BYTES
 EPI_RELU, EPI_RESIDUAL, EPI_PIXEL_SHUFFLE = 1, 2, 4
 ABI_VERSION = 4      # include/l3c_hip.h: L3C_ABI_VERSION (4: grouped tables, l3c_decode_rgb, l3c_container_read; no canvas batches)
@@ -368,6 +382,11 @@ PROTOTYPES = {
     'l3c_seal_find_head': (c_int, [c_vp, c_i64, ctypes.POINTER(SealHead)]),
     'l3c_head_parity': (c_int, [ctypes.POINTER(BandedScale), c_int, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp]),
     'l3c_band_payload_crc32': (c_int, [ctypes.POINTER(BandedScale), c_int, c_i64, c_vp, c_vp]),
+    'l3c_seal_append_parity_workspace_bytes': (c_i64, [ctypes.POINTER(BandedScale), c_int, c_i64, c_int, c_int, c_int]),
+    'l3c_seal_append_parity': (c_int, [ctypes.POINTER(SealParityDesc), c_vp]),
+    'l3c_encode_banded_parity_file_stride': (c_i64, [ctypes.POINTER(NetConfig), c_int, c_int, c_int, ctypes.POINTER(ParityOpts)]),
+    'l3c_encode_batch_banded_parity_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_i64, c_int, c_int, c_int, ctypes.POINTER(ParityOpts)]),
+    'l3c_encode_batch_banded_parity': (c_int, [ctypes.POINTER(EncodeBatchDesc), c_int, ctypes.POINTER(ParityOpts), c_vp]),
 }
 
 # include/l3c_xcheck.h: the TEST-ONLY cross-check library (round-1/2 Winograd F(2x2,3x3) kernel); see load_xcheck()

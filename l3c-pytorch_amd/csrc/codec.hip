@@ -32,6 +32,7 @@
 #include "codec_plan_banded.h"
 #include "codec_plan_region.h"
 #include "l3c_common.h"
+#include "seal_parity_plan.h"
 
 #define CODEC_FAIL(code, ...) (snprintf(l3c::error_buffer(), 512, __VA_ARGS__), (code))
 #define CODEC_TRY(x)                        \
@@ -404,7 +405,8 @@ int enc_run(const l3c_encode_batch_desc *d, const EncPlan &p, l3c_stream_t strea
     return l3c_container_write(scales, S + 1, B, padding, la.file_offset, d->files, stream);
 }
 
-int enc_banded_run(const l3c_encode_batch_desc *d, const EncPlan &p, l3c_stream_t stream) {
+// scales_out (the parity entry): receives the S + 1 records the files were written from, coarsest first
+int enc_banded_run(const l3c_encode_batch_desc *d, const EncPlan &p, l3c_stream_t stream, l3c_banded_scale *scales_out = nullptr) {
     const int64_t B = d->B;
     const int S = p.S;
     char *ws = base256(d->workspace);
@@ -446,7 +448,111 @@ int enc_banded_run(const l3c_encode_batch_desc *d, const EncPlan &p, l3c_stream_
     la.framing = p.framing;
     CODEC_TRY(launch_layout_banded(la, stream));
     const uint16_t *padding = d->padding ? d->padding : reinterpret_cast<const uint16_t *>(ws + p.zero_pad);
+    if (scales_out) memcpy(scales_out, scales, sizeof(l3c_banded_scale) * (size_t)(S + 1));
     return l3c_container_write_banded(scales, S + 1, B, padding, la.file_offset, d->files, cs + p.pos, B * p.streams_per_image * 8, stream);
+}
+
+// ---- the parity-sealed banded encode (l3c_encode_batch_banded_parity): what follows enc_banded_run on the same stream ---------------------
+//
+// The buffers of the seal lie BEHIND the plan's workspace (p.bytes - ALIGN from its 256-byte aligned base): the coder's outputs, which the
+// parity kernels read, are still live in the scratch region.  The formulas are stated in include/l3c_hip.h and decided in seal_parity_plan.h.
+struct ParityPlan {
+    l3c_parity_seal::Plan seal;
+    int64_t max_payload[MAX_REC];       // per record, coarsest first: the longest band payload the coder can write
+    int64_t tail;                       // the most bytes a seal adds to a file
+    int64_t frame_crc, band_crc, crc_ws, crc_ws_bytes, slots, slot_stride, slot_nb, seal_ws;
+    int64_t head_slots, head_stride, head_offset[MAX_REC], head_nb, head_crc;
+    int64_t bytes;                      // the whole workspace of the entry
+};
+
+int parity_plan(const l3c_parity_opts *o, int64_t B, int H, int W, const EncPlan &p, ParityPlan *out) {
+    namespace sp = l3c_parity_seal;
+    ParityPlan q{};
+    sp::Shape shapes[MAX_REC];
+    const int S = p.S;
+    for (int k = 0; k <= S; ++k) {
+        const int s = S - k;
+        shapes[k] = sp::Shape{p.Cs[s], H >> s, W >> s, p.L[s]};
+        q.max_payload[k] = p.n[s] > 1 && p.stride_f[s] > p.stride_l[s] ? p.stride_f[s] : p.stride_l[s];
+    }
+    CODEC_TRY(sp::make_plan(shapes, S + 1, B, o->G, o->R, o->head, q.max_payload, &q.seal, l3c::error_buffer(), 512));
+    const sp::Plan &t = q.seal;
+    q.tail = sp::tail_bound(t, q.max_payload + (S + 1 - t.n_records));
+    const int64_t n0 = p.n[0], m0 = t.rec[t.n_records - 1].m;
+    int64_t at = p.bytes - ALIGN;
+    q.frame_crc = take(at, 4 * B);
+    q.band_crc = take(at, 12 * B * n0);
+    q.crc_ws_bytes = l3c_u8_crc32_bands_workspace_bytes(B, 3, p.hw[0], p.L[0]);
+    if (q.crc_ws_bytes < 0) return (int)q.crc_ws_bytes;
+    q.crc_ws = take(at, q.crc_ws_bytes);
+    q.slot_stride = sp::round16(q.max_payload[S]);
+    q.slots = take(at, 3 * B * m0 * t.R * q.slot_stride);
+    q.slot_nb = take(at, 12 * B * m0);
+    q.seal_ws = take(at, t.ws_bytes);
+    if (t.head) {
+        int64_t groups = 0, fields = 0;
+        for (int k = 0; k < S; ++k) q.head_stride = q.max_payload[k] > q.head_stride ? q.max_payload[k] : q.head_stride;
+        q.head_stride = sp::round16(q.head_stride);
+        for (int k = 0; k < S; ++k) {
+            q.head_offset[k] = groups * t.R * q.head_stride;
+            groups += B * t.rec[k].C * t.rec[k].m;
+            fields += B * t.rec[k].C * t.rec[k].n;
+        }
+        q.head_slots = take(at, groups * t.R * q.head_stride);
+        q.head_nb = take(at, 4 * groups);
+        q.head_crc = take(at, 4 * fields);
+    }
+    q.bytes = at + ALIGN;
+    *out = q;
+    return L3C_OK;
+}
+
+// the size functions of the parity entry: the file stride (B == 0), or the workspace of a batch
+int64_t parity_size(const l3c_net_config *cfg, int64_t B, int H, int W, int bands, const l3c_parity_opts *o) {
+    L3C_REQUIRE(o, "null pointer: opts_host");
+    CODEC_TRY(l3c_parity_seal::check_opts(o->G, o->R, o->head, o->reserved, l3c::error_buffer(), 512));
+    CODEC_TRY(codec_config(cfg));
+    CODEC_TRY(check_sides(*cfg, H, W));
+    CODEC_TRY(check_bands(bands));
+    EncPlan p;
+    CODEC_TRY(enc_plan(*cfg, B ? B : 1, H, W, bands, &p));
+    ParityPlan q;
+    CODEC_TRY(parity_plan(o, B ? B : 1, H, W, p, &q));
+    return B ? q.bytes : file_stride_of(*cfg, H, W, bands) + (q.tail + 31) / 32 * 32;
+}
+
+int enc_parity_run(const l3c_encode_batch_desc *d, const EncPlan &p, const ParityPlan &q, const l3c_parity_opts *o, l3c_stream_t stream) {
+    const int64_t B = d->B;
+    const int S = p.S;
+    l3c_banded_scale scales[MAX_REC];
+    CODEC_TRY(enc_banded_run(d, p, stream, scales));
+    char *ws = base256(d->workspace);
+    const l3c_parity_seal::Plan &t = q.seal;
+    uint32_t *frame_crc = reinterpret_cast<uint32_t *>(ws + q.frame_crc), *band_crc = reinterpret_cast<uint32_t *>(ws + q.band_crc);
+    uint8_t *slots = reinterpret_cast<uint8_t *>(ws + q.slots), *head_slots = reinterpret_cast<uint8_t *>(ws + q.head_slots);
+    uint32_t *slot_nb = reinterpret_cast<uint32_t *>(ws + q.slot_nb), *head_nb = reinterpret_cast<uint32_t *>(ws + q.head_nb);
+    uint32_t *head_crc = reinterpret_cast<uint32_t *>(ws + q.head_crc);
+    CODEC_TRY(l3c_u8_crc32_bands(d->img, B, 3, p.hw[0], p.L[0], 3 * p.hw[0], band_crc, frame_crc, ws + q.crc_ws, q.crc_ws_bytes, stream));
+    CODEC_TRY(l3c_band_parity_rs(&scales[S], B, t.rec[t.n_records - 1].G, t.R, slots, q.slot_stride, slot_nb, stream));
+    if (t.head) {
+        CODEC_TRY(l3c_head_parity(scales, S, B, o->G, t.R, head_slots, q.head_offset, q.head_stride, head_nb, stream));
+        CODEC_TRY(l3c_band_payload_crc32(scales, S, B, head_crc, stream));
+    }
+    l3c_seal_parity_desc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.files = d->files, sd.file_stride = d->file_stride, sd.file_bytes = d->file_bytes, sd.B = B;
+    sd.scales_host = scales, sd.n_scales = S + 1;
+    sd.G = o->G, sd.R = o->R, sd.head = o->head;
+    sd.padding = d->padding ? d->padding : reinterpret_cast<const uint16_t *>(ws + p.zero_pad);
+    sd.model_id = o->model_id;
+    sd.frame_crc = frame_crc, sd.band_crc = band_crc;
+    sd.parity = slots, sd.parity_stride = q.slot_stride, sd.parity_nbytes = slot_nb;
+    if (t.head) {
+        sd.head_parity = head_slots, sd.head_parity_offset_host = q.head_offset, sd.head_parity_stride = q.head_stride;
+        sd.head_parity_nbytes = head_nb, sd.payload_crc = head_crc;
+    }
+    sd.workspace = ws + q.seal_ws, sd.workspace_bytes = t.ws_bytes;
+    return l3c_seal_append_parity(&sd, stream);
 }
 
 // ---- decode: one plan, one check and one walk over either plan header --------------------------------------------------------------
@@ -1100,6 +1206,33 @@ int l3c_encode_batch_banded(const l3c_encode_batch_desc *d, int bands, l3c_strea
     EncPlan p;
     CODEC_TRY(enc_check_desc(d, true, bands, &p));
     return enc_banded_run(d, p, stream);     // everything checked: enqueue
+}
+
+int64_t l3c_encode_banded_parity_file_stride(const l3c_net_config *cfg, int H, int W, int bands, const l3c_parity_opts *opts_host) {
+    return parity_size(cfg, 0, H, W, bands, opts_host);
+}
+
+int64_t l3c_encode_batch_banded_parity_workspace_bytes(const l3c_net_config *cfg, int64_t B, int H, int W, int bands,
+                                                       const l3c_parity_opts *opts_host) {
+    if (B < 1 || B >= 65536) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "bad batch size: B = %lld, must be 1 .. 65535", (long long)B);
+    return parity_size(cfg, B, H, W, bands, opts_host);
+}
+
+int l3c_encode_batch_banded_parity(const l3c_encode_batch_desc *d, int bands, const l3c_parity_opts *o, l3c_stream_t stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    L3C_REQUIRE(o, "null pointer: opts_host");
+    CODEC_TRY(l3c_parity_seal::check_opts(o->G, o->R, o->head, o->reserved, l3c::error_buffer(), 512));
+    EncPlan p;
+    CODEC_TRY(enc_check_desc(d, true, bands, &p));
+    ParityPlan q;
+    CODEC_TRY(parity_plan(o, d->B, d->H, d->W, p, &q));
+    const int64_t stride = file_stride_of(*d->model_host->cfg_host, d->H, d->W, bands) + (q.tail + 31) / 32 * 32;
+    if (d->file_stride < stride)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "file_stride %lld: must be at least l3c_encode_banded_parity_file_stride = %lld",
+                          (long long)d->file_stride, (long long)stride);
+    if (d->workspace_bytes < q.bytes)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld", (long long)d->workspace_bytes, (long long)q.bytes);
+    return enc_parity_run(d, p, q, o, stream);     // everything checked: enqueue
 }
 
 int64_t l3c_decode_plan_banded_bytes(const l3c_net_config *cfg, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B) {

@@ -29,6 +29,7 @@
 // table's validator, HIP-free), and the tile launch bisects a prefix of tile counts.
 #include "l3c_common.h"
 #include "crc_spans.h"
+#include "crc_wave.h"
 #include "seal.h"
 #include "parity_plan.h"
 #include "banded_rows.h"
@@ -39,38 +40,8 @@ using namespace l3c_crc;      // crc_spans.h: mulmod, powmod, the tile geometry,
 constexpr int MAX_GRID = 4096, DEPTH = 8;
 constexpr int BAND_GRID = 1024;      // blocks of the band chunk launch: four a CU, each stages the tables once for many chunks
 
-// [0]: MULK, [1]: MUL32, [2]: MULW (a wavefront's row, l3c_u8_crc32_bands) -- entry 16 k + n is (n << 4 k) times the constant
-struct NibbleTables {
-    uint32_t v[3][128];
-};
-constexpr NibbleTables make_tables() {
-    NibbleTables t{};
-    for (int k = 0; k < 8; ++k)
-        for (uint32_t n = 0; n < 16; ++n) {
-            t.v[0][16 * k + n] = mulmod(n << (4 * k), K_ROW);
-            t.v[1][16 * k + n] = mulmod(n << (4 * k), POLY);
-            t.v[2][16 * k + n] = mulmod(n << (4 * k), K_WROW);
-        }
-    return t;
-}
-// SHIFT[t] = x^(8 * 16 (255 - t)): the bytes of a row behind thread t's 16
-struct ShiftTable {
-    uint32_t v[THREADS];
-};
-constexpr ShiftTable make_shifts() {
-    ShiftTable s{};
-    const uint32_t step = powmod(X8, 16);
-    uint32_t c = ONE;
-    for (int t = THREADS - 1; t >= 0; --t) {
-        s.v[t] = c;
-        c = mulmod(c, step);
-    }
-    return s;
-}
-__device__ const NibbleTables g_tables = make_tables();
-__device__ const ShiftTable g_shifts = make_shifts();
+using namespace l3c_crc_wave;   // crc_wave.h: the nibble tables, times, row_step, and a wavefront on one byte run (wave_crc32)
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((aligned(4))) Quad {      // a 16-byte load that needs no more than the data's 4-byte alignment
     uint32_t d[4];
 };
@@ -90,27 +61,6 @@ __device__ __forceinline__ u32x4 load16(const uint8_t *item, int64_t off, int64_
         r = u32x4{w[0], w[1], w[2], w[3]};
     }
     return r;
-}
-
-// v times the table's constant; tab: the lane's column of one table in LDS
-__device__ __forceinline__ uint32_t times(const uint32_t *tab, uint32_t v) {
-    uint32_t r = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r ^= tab[(16 * k + ((v >> (4 * k)) & 15u)) * 32];
-    return r;
-}
-
-// one row: a_j = a_j K + d_j for the four remainders.  All 32 lookups are issued before the first is used: the four chains are independent,
-// and one LDS round trip per row instead of four is what the loop's time is made of
-__device__ __forceinline__ void row_step(const uint32_t *tab, uint32_t (&a)[4], u32x4 d) {
-    uint32_t r[4][8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[j][k] = tab[(16 * k + ((a[j] >> (4 * k)) & 15u)) * 32];
-    const uint32_t in[4] = {d.x, d.y, d.z, d.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] = ((r[j][0] ^ r[j][1] ^ r[j][2]) ^ (r[j][3] ^ r[j][4] ^ r[j][5])) ^ (r[j][6] ^ r[j][7] ^ in[j]);
 }
 
 __device__ __forceinline__ u32x4 load_quad(const uint8_t *p) {
@@ -479,20 +429,6 @@ __global__ __launch_bounds__(64) void seal_append_bands_kernel(uint8_t *__restri
 // in front of the 4-byte-rounded end (one 16-byte load where the address allows it), the bytes of the last dword behind the length masked.
 // The length's two constants, x^(8 len) for Z and x^(-8 fill) for the zero fill of the last row, are products over the set bits of len and
 // fill: lanes 0..31 and 32..63 each hold one factor (X8_POW2) and a five-step butterfly multiplies them.
-struct Pow2Table {
-    uint32_t v[64];      // [i]: x^(8 2^i), [32 + i]: x^(-8 2^i)
-};
-constexpr Pow2Table make_pow2() {
-    Pow2Table t{};
-    uint32_t a = X8, b = X8_INV;
-    for (int i = 0; i < 32; ++i) {
-        t.v[i] = a, t.v[32 + i] = b;
-        a = mulmod(a, a), b = mulmod(b, b);
-    }
-    return t;
-}
-__device__ const Pow2Table g_pow2 = make_pow2();
-
 struct PayloadRecords {
     l3c_banded_scale sc[l3c_parity::HEAD_MAX_RECORDS];
     int64_t first[l3c_parity::HEAD_MAX_RECORDS + 1];      // payloads (b, c, j) in front of the record; [count]: all
@@ -500,35 +436,10 @@ struct PayloadRecords {
     int32_t count;
 };
 
-// bytes [off, off + 16) of the payload at p (4-byte aligned) of len bytes, zero from byte len on; nothing at or behind its 4-byte-rounded end is read
-__device__ __forceinline__ u32x4 load16_masked(const uint8_t *p, int64_t len, int64_t off) {
-    const int64_t end4 = (len + 3) & ~(int64_t)3;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    if (off + 16 <= end4 && (reinterpret_cast<uintptr_t>(p + off) & 15) == 0) {
-        const u32x4 q = *reinterpret_cast<const u32x4 *>(p + off);
-        w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (off + 4 * i < end4) w[i] = *reinterpret_cast<const uint32_t *>(p + off + 4 * i);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int64_t keep = len - (off + 4 * i);
-        if (keep < 4) w[i] = keep <= 0 ? 0u : w[i] & (0xFFFFFFFFu >> (8 * (4 - (int)keep)));
-    }
-    return u32x4{w[0], w[1], w[2], w[3]};
-}
-
 __global__ __launch_bounds__(THREADS) void band_payload_crc32_kernel(PayloadRecords h, uint32_t *__restrict__ crc_out) {
-    __shared__ uint32_t lds[2 * 128 * 32];
+    __shared__ uint32_t lds[WAVE_TABLE_WORDS];
     const int t = threadIdx.x, lane = t & 63;
-    for (int i = 0; i < 32; ++i) {                                           // MULW, then MUL32
-        const int idx = i * THREADS + t;
-        lds[idx] = idx < 128 * 32 ? g_tables.v[2][idx >> 5] : g_tables.v[1][(idx >> 5) - 128];
-    }
-    const uint32_t shift = g_shifts.v[THREADS - 64 + lane];
-    const uint32_t *mulw = lds + (t & 31), *mul32 = lds + 128 * 32 + (t & 31);
+    stage_wave_tables(lds, t);
     __syncthreads();
     const int64_t total = h.first[h.count];
     for (int64_t unit = (int64_t)blockIdx.x * (THREADS / 64) + (t >> 6); unit < total; unit += (int64_t)gridDim.x * (THREADS / 64)) {
@@ -543,30 +454,8 @@ __global__ __launch_bounds__(THREADS) void band_payload_crc32_kernel(PayloadReco
             continue;
         }
         const uint8_t *p = band_row(sc, n, s, j);
-        const int64_t len = stated, rows = (len + WROW - 1) / WROW;
-        uint32_t a[4] = {0u, 0u, 0u, 0u};
-        for (int64_t r = 0; r < rows; r += 4) {
-            u32x4 q[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) q[u] = load16_masked(p, len, (r + u) * WROW + 16 * lane);      // (behind the last row: len masks all)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (r + u < rows) row_step(mulw, a, q[u]);
-        }
-        uint32_t v = times(mul32, a[0]);
-        v = times(mul32, v ^ a[1]);
-        v = times(mul32, v ^ a[2]);
-        v = times(mul32, v ^ a[3]);
-        v = mulmod(v, shift);
-        // lanes 0..31: bit i of len -> x^(8 2^i); lanes 32..63: bit i of the fill -> x^(-8 2^i); the butterfly leaves both products everywhere in their half
-        const uint32_t bits = lane < 32 ? (uint32_t)len : (uint32_t)(rows * WROW - len);
-        uint32_t f = (bits >> (lane & 31)) & 1u ? g_pow2.v[lane] : ONE;
-#pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) f = mulmod(f, __shfl_xor(f, d, 64));
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d, 64);
-        const uint32_t unfill = __shfl(f, 32, 64);
-        if (lane == 0) crc_out[unit] = mulmod(v, unfill) ^ mulmod(f, 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
+        const uint32_t crc = wave_crc32(lds, lane, p, (int64_t)stated);
+        if (lane == 0) crc_out[unit] = crc;
     }
 }
 

@@ -17,6 +17,10 @@ by a table of l3c_u8_image entries, one call per group of images that pad to one
 `NativeCodec(blueprint, seal=True)` writes SEALED files (include/l3c_hip.h "sealed files"; the files of `Bitcoding(bp, seal=True)` byte for
 byte): l3c_encode_batch(_banded), l3c_u8_crc32 on the input frames, l3c_seal_append -- one stream of work, no host round trip.  The decoders
 verify every sealed file they are given: generation and model id before anything is enqueued, l3c_u8_crc32 of the decoded frames after.
+
+`NativeCodec(blueprint, bands=K, seal='bands', parity=G[, parity_streams=R][, parity_head=True])` writes PARITY-SEALED files (seal version 3,
+include/l3c_hip.h "parity bands"; the files of `Bitcoding` with the same arguments byte for byte) in ONE call, l3c_encode_batch_banded_parity:
+the band CRCs, the parity rows and the whole tail (l3c_seal_append_parity) are enqueued behind the coder on the device.
 """
 import ctypes
 
@@ -207,17 +211,37 @@ def _check_region(rc):
 
 
 class NativeCodec(object):
-    def __init__(self, blueprint, bands=0, seal=False):
+    def __init__(self, blueprint, bands=0, seal=False, parity=0, parity_streams=1, parity_head=False):
         """bands: 0 = encode writes the legacy format; K in 1..1024 = banded files, as Bitcoding(bp, bands=K).  decode_batch reads either.
         seal: True = every file the encoders return ends with a seal, as Bitcoding(bp, seal=True); the decoders verify sealed files whatever
         this says.  seal='bands' (with bands=K; ValueError with bands=0): BAND-SEALED files, as Bitcoding(bp, bands=K, seal='bands'), byte for
-        byte: l3c_encode_batch_banded, ONE l3c_u8_crc32_bands on the input frames, l3c_seal_append_bands -- no host round trip."""
+        byte: l3c_encode_batch_banded, ONE l3c_u8_crc32_bands on the input frames, l3c_seal_append_bands -- no host round trip.
+        parity=G, parity_streams=R, parity_head (the rules and ValueErrors of Bitcoding's constructor; parity needs seal='bands'):
+        PARITY-SEALED files, seal version 3, as Bitcoding(bp, bands=K, seal='bands', parity=G, parity_streams=R, parity_head=...), byte for
+        byte, in ONE library call, l3c_encode_batch_banded_parity: the band CRCs, the parity rows, with parity_head the head rows and
+        payload CRCs, and the whole tail (l3c_seal_append_parity) are enqueued behind the coder on the device.  The decoders read these
+        files as the band-sealed files they contain; Bitcoding.decode_repair repairs them."""
         if seal not in (False, True, 'bands'):
             raise ValueError("seal must be False, True or 'bands', got {!r}".format(seal))
         if seal == 'bands' and not bands:
             raise ValueError("seal='bands' needs banded files: a band seal holds a CRC per band of the finest record (bands=K, K >= 1)")
         if bands and not 1 <= int(bands) <= container.MAX_BANDS:
             raise ValueError('bands must be 0 (legacy format) or in 1..{}, got {}'.format(container.MAX_BANDS, bands))
+        if isinstance(parity, bool) or not isinstance(parity, int) or parity < 0:
+            raise ValueError('parity must be 0 or a group size >= 1, got {!r}'.format(parity))
+        if parity and seal != 'bands':
+            raise ValueError("parity needs seal='bands': the band seal is what turns damage into erasures of known position")
+        if isinstance(parity_streams, bool) or not isinstance(parity_streams, int) or not 1 <= parity_streams <= container.MAX_PARITY_STREAMS:
+            raise ValueError('parity_streams must be in 1..{}, got {!r}'.format(container.MAX_PARITY_STREAMS, parity_streams))
+        if parity_streams > 1 and not parity:
+            raise ValueError('parity_streams > 1 needs parity=G: the rows are computed over the parity groups')
+        if parity_streams > 1:
+            container.check_parity_streams(parity_streams, parity, int(bands))
+        if not isinstance(parity_head, bool):
+            raise ValueError('parity_head must be True or False, got {!r}'.format(parity_head))
+        if parity_head and not parity:
+            raise ValueError('parity_head needs parity=G: the head rows are computed over groups of min(G, n) bands with its parity_streams')
+        self.parity, self.parity_streams, self.parity_head = parity, parity_streams, parity_head
         self.bands = int(bands)
         self.seal = bool(seal)
         self.seal_bands = seal == 'bands'
@@ -242,7 +266,9 @@ class NativeCodec(object):
 
     def file_stride(self, H, W):
         """The slot of one file: the library's stride, and with seal=True the 32 bytes more that l3c_seal_append asks for; with
-        seal='bands' l3c_seal_bands_bytes(n) rounded up to 32."""
+        seal='bands' l3c_seal_bands_bytes(n) rounded up to 32; with parity=G l3c_encode_banded_parity_file_stride."""
+        if self.parity:
+            return _size(_lib.load().l3c_encode_banded_parity_file_stride(self._cfg_ref, H, W, self.bands, ctypes.byref(self._parity_opts())))
         if self.seal_bands:
             n = container.n_bands(H * W, container.band_len(H * W, self.bands))
             return (_size(_lib.load().l3c_encode_banded_file_stride(self._cfg_ref, H, W, self.bands)) +
@@ -261,7 +287,14 @@ class NativeCodec(object):
     def generation():
         return _lib.load().l3c_bitstream_generation()
 
+    def _parity_opts(self):
+        """l3c_parity_opts of this codec (the model id is computed on first use)."""
+        return _lib.ParityOpts(self.parity, self.parity_streams, int(self.parity_head), 0, self.model_id())
+
     def encode_workspace_bytes(self, B, H, W):
+        if self.parity:
+            return _size(_lib.load().l3c_encode_batch_banded_parity_workspace_bytes(self._cfg_ref, B, H, W, self.bands,
+                                                                                    ctypes.byref(self._parity_opts())))
         if self.bands:
             return _size(_lib.load().l3c_encode_batch_banded_workspace_bytes(self._cfg_ref, B, H, W, self.bands))
         return _size(_lib.load().l3c_encode_batch_workspace_bytes(self._cfg_ref, B, H, W))
@@ -287,13 +320,16 @@ class NativeCodec(object):
 
     def _encode_frames(self, imgs, pads, workspace):
         """The batch entry on device frames (B,3,H,W) and a device padding array (int16 (B,4) or None); sealed: the frames' CRCs
-        (l3c_u8_crc32) and l3c_seal_append behind it on the same stream."""
+        (l3c_u8_crc32) and l3c_seal_append behind it on the same stream; parity-sealed: l3c_encode_batch_banded_parity alone."""
         B, _, H, W = imgs.shape
         stride = self.file_stride(H, W)
         ws = _bytes(self.encode_workspace_bytes(B, H, W)) if workspace is None else workspace
         files = torch.empty(B, stride, dtype=torch.uint8, device='cuda')
         file_bytes = torch.empty(B, dtype=torch.int64, device='cuda')
         d = EncodeBatchDesc(ctypes.pointer(self.model), ptr(imgs), B, H, W, ptr(pads), ptr(files), stride, ptr(file_bytes), ptr(ws), ws.numel())
+        if self.parity:      # the whole parity-sealed encode: one call
+            _lib.call('l3c_encode_batch_banded_parity', ctypes.byref(d), self.bands, ctypes.byref(self._parity_opts()), stream())
+            return files, file_bytes
         if self.bands:
             _lib.call('l3c_encode_batch_banded', ctypes.byref(d), self.bands, stream())
         else:

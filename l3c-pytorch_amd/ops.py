@@ -1031,6 +1031,36 @@ def band_payload_crc32(B, scales, out=None):
     return out
 
 
+def seal_append_parity(files, file_bytes, frame_crc, band_crc, scales, G, R, parity, padding=None, model_id=0, head=None, workspace=None):
+    """l3c_seal_append_parity: section ('L3CP' / 'L3CQ', with `head` 'L3CH'), band table and this build's version-3 seal behind every file
+    of a banded encode, in place -- container.make_seal's bytes, assembled on the device.  files uint8 (B, file_stride), file_bytes int64
+    (B,), frame_crc int32 (B,) and band_crc int32 (B, 3, n) (u8_crc32_bands of the padded frames); scales: [(C, H, W, L, groups)], ALL
+    records of the files, coarsest first, as head_parity takes them; parity: (slots, nbytes) of band_parity_rs on the finest record with
+    min(G, n) and R; head: None, or (band_payload_crc32, head_parity slots, head_parity nbytes) over scales[:-1] with G and R.  padding int16
+    (B, 4) device tensor or None.  No host synchronisation."""
+    B, stride = files.shape
+    slots, nbytes = parity
+    arr = _banded_scale_array(scales)
+    n_ws = _lib.load().l3c_seal_append_parity_workspace_bytes(arr, len(scales), B, int(G), int(R), int(head is not None))
+    _lib.check(min(n_ws, 0))
+    ws = torch.empty(n_ws, dtype=torch.uint8, device=files.device) if workspace is None else workspace
+    d = _lib.SealParityDesc()
+    d.files, d.file_stride, d.file_bytes, d.B = ptr(files, torch.uint8), stride, ptr(file_bytes, torch.int64), B
+    d.scales_host, d.n_scales = arr, len(scales)
+    d.G, d.R, d.head, d.reserved = int(G), int(R), int(head is not None), 0
+    d.padding, d.model_id = ptr(padding, torch.int16), int(model_id)
+    d.frame_crc, d.band_crc = ptr(frame_crc, torch.int32), ptr(band_crc, torch.int32)
+    d.parity, d.parity_stride, d.parity_nbytes = ptr(slots, torch.uint8), slots.shape[-1], ptr(nbytes, torch.int32)
+    if head is not None:
+        crcs, hslots, hnbytes = head
+        _, offsets, hstride, _, _ = head_parity_layout(B, scales[:-1], G, R)
+        offs = (ctypes.c_int64 * len(offsets))(*offsets)
+        d.head_parity, d.head_parity_offset_host, d.head_parity_stride = ptr(hslots, torch.uint8), offs, hstride
+        d.head_parity_nbytes, d.payload_crc = ptr(hnbytes, torch.int32), ptr(crcs, torch.int32)
+    d.workspace, d.workspace_bytes = ptr(ws, torch.uint8), ws.numel()
+    call('l3c_seal_append_parity', ctypes.byref(d), stream())
+
+
 def _u8_spans(name, data, offsets, lengths, coefs, group_first, out, out_offsets, out_lengths):
     """u8_xor_spans (coefs None: l3c_u8_xor_spans) and u8_gf_spans (l3c_u8_gf_spans): the span, slot and group tables, and the coefficients
     where there are any, checked and uploaded as ONE table, then the call."""
