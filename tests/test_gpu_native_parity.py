@@ -81,6 +81,30 @@ def test_one_band_per_channel_on_every_scale():
         assert (seal.parity_group, seal.parity_groups) == (1, 1) and seal.band_crcs.shape == (3, 1)
 
 
+@pytest.mark.parametrize('G,R,head', [(1, 2, True), (3, 4, True)])
+def test_many_bands_on_every_scale(G, R, head):
+    """bands = 440: L = 64 on every scale, n = 440 on the finest record -- more than 256 length fields in a file, and with G = 1 more than
+    256 copy units: the seal's plan kernel gives a thread several of each, on the coder's own lengths and in the encoder's own slots."""
+    bands = 440
+    hws = [(320 >> s) * (88 >> s) for s in (3, 2, 1, 0)]
+    ns = [container.n_bands(hw, container.band_len(hw, bands)) for hw in hws]
+    assert [container.band_len(hw, bands) for hw in hws] == [64, 64, 64, 64] and ns == [7, 28, 110, 440]
+    x = images(1, 320, 88).cuda()
+    want = python(G, R, head, bands=bands).encode_batch(x).to_bytes([(0, 0, 0, 0)])
+    scales = container.parse_banded(container.split_seal(want[0])[0]).scales
+    assert [tuple(s) for s in scales] == [(5, 40, 11, 64), (5, 80, 22, 64), (5, 160, 44, 64), (3, 320, 88, 64)]
+    fields = sum(C * n for (C, _, _, _), n in zip(scales, ns))
+    units = 3 * -(-ns[3] // G) + 1 + sum(C * -(-n // G) for (C, _, _, _), n in zip(scales[:3], ns[:3]))
+    assert fields == 2045 and fields > 256 and units == {1: 2046, 3: 692}[G] and units > 256
+    codec = native(G, R, head, bands=bands)
+    got = codec.encode_batch(x)
+    _same_files(got, want)
+    seal = container.split_seal(got[0])[1]
+    assert (seal.parity_group, seal.parity_groups, seal.parity_streams) == (G, -(-440 // G), R) and seal.head is not None and not seal.head_damaged
+    pixels, pads = codec.decode_batch(got)
+    assert torch.equal(pixels, x) and [tuple(p) for p in pads] == [(0, 0, 0, 0)]
+
+
 def test_the_encode_is_one_library_call_and_the_band_sealed_encode_is_unchanged(monkeypatch):
     x = images(1, 320, 88).cuda()
     codecs = [native(G, R, head) for G, R, head in CASES]

@@ -48,19 +48,25 @@ def _record(rng, B, header, length):
     return (C, H, W, L, groups), [[[payload(b, c, j) for j in range(n)] for c in range(C)] for b in range(B)]
 
 
-def _batch(coarse, B, finest=FINEST, lens=LENS):
-    """The records of a batch of B files, built once per shape: file b has b % 16 filler bytes in its first coarse payload."""
-    key = (coarse, B, finest)
+def _batch_of(key, seed, B, headers, finest, coarse_length, finest_length):
+    """The records of a batch of B files, built once per key: `headers` in front of the record `finest`; coarse_length(k, c, j) and
+    finest_length(c, j): the bytes of a payload, and file b has b % 16 filler bytes more in its first coarse payload."""
     if key not in _CACHE:
-        rng = np.random.RandomState(100 * coarse + B)
-        headers = COARSE[coarse] if finest == FINEST else [(1, 4, 4, 64)]
-        built = [_record(rng, B, h, lambda b, c, j, k=k: 1 + j + c + (b % 16 if (k, c, j) == (0, 0, 0) else 0)) for k, h in enumerate(headers)]
-        built.append(_record(rng, B, finest, lambda b, c, j: lens[c][j]))
+        rng = np.random.RandomState(seed)
+        built = [_record(rng, B, h, lambda b, c, j, k=k: coarse_length(k, c, j) + (b % 16 if (k, c, j) == (0, 0, 0) else 0))
+                 for k, h in enumerate(headers)]
+        built.append(_record(rng, B, finest, lambda b, c, j: finest_length(c, j)))
         scales, payloads = [s for s, _ in built], [p for _, p in built]
         pads = [(b, 2 * b, 65535 - b, 3) for b in range(B)]
         bodies = [container.write_file(pads[b], [s[:4] for s in scales], [p[b] for p in payloads], True) for b in range(B)]
         _CACHE[key] = (scales, payloads, pads, bodies)
     return _CACHE[key]
+
+
+def _batch(coarse, B, finest=FINEST, lens=LENS):
+    """The records of a batch of B files, built once per shape: file b has b % 16 filler bytes in its first coarse payload."""
+    headers = COARSE[coarse] if finest == FINEST else [(1, 4, 4, 64)]
+    return _batch_of((coarse, B, finest), 100 * coarse + B, B, headers, finest, lambda k, c, j: 1 + j + c, lambda c, j: lens[c][j])
 
 
 def _write_bodies(scales, pads, bodies, stride):
@@ -98,8 +104,9 @@ def _want(bodies, payloads, frame, bands, L, G, R, head):
     return res
 
 
-def _seal(scales, files, file_bytes, padding, frame, bands, G, R, head, parity_scale=None):
-    """The existing kernels on the records, then l3c_seal_append_parity.  parity_scale: the finest record as the parity kernel is to see it."""
+def _seal(scales, files, file_bytes, padding, frame, bands, G, R, head, parity_scale=None, workspace=None, between=None):
+    """The existing kernels on the records, then l3c_seal_append_parity.  parity_scale: the finest record as the parity kernel is to see it.
+    workspace: the caller's instead of a new one.  between(parity, hd): called on what the parity kernels returned, before the seal."""
     B = files.shape[0]
     C, H, W, L, groups = parity_scale or scales[-1]
     n = container.n_bands(H * W, L)
@@ -107,8 +114,10 @@ def _seal(scales, files, file_bytes, padding, frame, bands, G, R, head, parity_s
     hd = None
     if head:
         hd = (ops.band_payload_crc32(B, scales[:-1]),) + tuple(ops.head_parity(B, scales[:-1], G, R))
+    if between is not None:
+        between(parity, hd)
     ops.seal_append_parity(files, file_bytes, torch.from_numpy(frame.view(np.int32)).cuda(), torch.from_numpy(bands.view(np.int32)).cuda(), scales, G, R,
-                           parity, padding, MODEL_ID, hd)
+                           parity, padding, MODEL_ID, hd, workspace)
     torch.cuda.synchronize()
     return files.cpu().numpy(), file_bytes.cpu().numpy()
 
