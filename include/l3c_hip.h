@@ -937,12 +937,24 @@ int l3c_encode_batch_banded(const l3c_encode_batch_desc *desc_host, int bands, l
  * works from; a 256-byte aligned workspace: from the pointer).  A multiple of 256; valid until the workspace is reused.  Pure host code
  * on the plan l3c_decode_batch_banded_workspace_bytes reads; a negative status for a bad plan.  With desc.sym, the caller then holds what
  * l3c_dmll_conceal needs (INTEGRATION.md "Salvage decode").
+ *
+ * l3c_decode_batch_banded_streams_offset: the STREAM AREA of that workspace -- every band payload of the files as l3c_container_read left
+ * it, 4-byte aligned and followed by zero bytes up to ((nbytes + 3) / 4) * 4 + 4 -- as a byte offset under the base and the rules of
+ * l3c_decode_batch_banded_p_offset.  l3c_decode_plan_banded_stream: one stream of the plan without restating the blob's layout -- stream
+ * `index` of record `record` (0: the coarsest), numbered inside the record as above ((c B + b) n + j in every record but the coarsest): its
+ * first byte in `files` (src_offset), its slot inside the stream area (dst_offset, a multiple of 4) and its length.  The header is checked
+ * against the layout its own B and records imply and the entry against the size of the stream area; L3C_ERR_INVALID_ARG for a blob that is
+ * not a banded plan, a record or an index out of range, or a null pointer.  Pure host code.  Together they are what an in-place repair of
+ * the finest record's streams (l3c_band_rebuild) needs to address.
  */
 int64_t l3c_decode_plan_banded_bytes(const l3c_net_config *cfg_host, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B);
 int l3c_decode_plan_banded(const l3c_net_config *cfg_host, const uint8_t *files_host, const int64_t *file_offset_host, int64_t B,
                            void *plan_host, int64_t plan_bytes, int *H_out, int *W_out, uint16_t *padding_host_out);
 int64_t l3c_decode_batch_banded_workspace_bytes(const l3c_net_config *cfg_host, const void *plan_host);
 int64_t l3c_decode_batch_banded_p_offset(const l3c_net_config *cfg_host, const void *plan_host);
+int64_t l3c_decode_batch_banded_streams_offset(const l3c_net_config *cfg_host, const void *plan_host);
+int l3c_decode_plan_banded_stream(const void *plan_host, int record, int64_t index, int64_t *src_offset_out, int64_t *dst_offset_out,
+                                  uint32_t *nbytes_out);
 int l3c_decode_batch_banded(const l3c_decode_batch_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
 
 /* ---- pictures as they come: any size and layout, padded and cropped on the device ----------------------------------------------------- */
@@ -1311,8 +1323,8 @@ int l3c_seal_append_bands(uint8_t *files, int64_t file_stride, int64_t *file_byt
  * more; a payload counts as repaired only when all three channels of its position verify, and what still fails is concealed
  * (l3c_dmll_conceal).
  * The encoder side behind the C ABI is l3c_encode_batch_banded_parity (NativeCodec(parity=G)), at the end of this header.
- * NOT BUILT: the repair in l3c_decode_batch_banded callers (NativeCodec.decode_repair), repair in the set readers and in the region decode,
- * verification of parity payloads that were never needed.
+ * The repair behind the C ABI (NativeCodec.decode_repair) is "REPAIR THROUGH THE C ABI" below: l3c_repair_round_plan + l3c_decode_repair_round.
+ * NOT BUILT: repair in the set readers and in the region decode, verification of parity payloads that were never needed.
  */
 typedef struct {
     int32_t G, m;                   /* bands per group, groups per channel; m == 0: no parity section */
@@ -1414,6 +1426,107 @@ int l3c_band_parity_rs(const l3c_banded_scale *scale_host, int64_t B, int G, int
 int l3c_u8_gf_spans(const uint8_t *data, int64_t data_bytes, const l3c_u8_span *spans_host, const l3c_u8_span *spans, const uint8_t *coef_host,
                     const uint8_t *coef, int64_t n_spans, const int64_t *group_first_host, const int64_t *group_first, int64_t n_groups,
                     const l3c_u8_span *out_spans_host, const l3c_u8_span *out_spans, uint8_t *out, int64_t out_bytes, l3c_stream_t stream);
+
+/*
+ * l3c_band_rebuild: the repair-side counterpart of l3c_band_parity_rs -- ALL t erased members of a group in one pass, in place.  Where
+ * l3c_u8_gf_spans rebuilds one payload per output group (a group with t erasures reads its present members and its t rows t times), a block
+ * here owns a 4096-byte tile of ONE group, loads every source of the group once, eight at a time, and keeps t accumulators:
+ *     output e (e < t) of group g = XOR over the group's sources k of coef[4 k + e] * source k        GF(2^8), polynomial 0x11D
+ * every source cut or zero-extended to out[e].bytes, the output followed by zero bytes up to ((bytes + 3) / 4) * 4 + 4 (l3c_u8_gf_spans'
+ * form); the t outputs of a group may differ in length.  The powers alpha^i of a source's bytes are formed once for the t accumulators; a
+ * source whose t coefficients are all 0 is not read; coefficient 1 costs no multiply.
+ *   sources         entries [first_src, first_src + n_rows + n_members) of `src` / `coef`: the n_rows ROW sources first, then the members
+ *   row source      a span of `rows` at ANY byte offset (the rows of a parity section lie back to back in the file): the aligned dwords
+ *                   around it are read and funnel-shifted.  `rows` is 4-byte aligned and readable up to ((rows_bytes + 3) / 4) * 4 (as the
+ *                   files of l3c_container_read); no dword is read that holds no byte of the span, and the bytes of a dword outside the span
+ *                   count as zero
+ *   member source   a span of `members`, offset % 4 == 0, its 4-byte-rounded end inside members_bytes: l3c_u8_xor_spans' load rules
+ *   out[e]          a slot of the SAME `members` buffer (the stream area of a decode workspace): offset % 4 == 0, offset + ((bytes + 3) / 4)
+ *                   * 4 + 4 <= members_bytes.  A slot that overlaps a member source of ANY group of the call, or another slot, is refused
+ *                   (L3C_ERR_INVALID_ARG naming the group): the spans are sorted and swept on the host.  out[e], e >= t, is not read.
+ *                   Nothing outside the slots is stored; 16-byte stores where a slot is 16-byte aligned, dword stores otherwise
+ *   coef            uint8 [n_src][4], 4-byte aligned; coef[4 k + e], e >= t of a group that uses entry k, is not read
+ *   src_host, coef_host, groups_host    the tables on the host, validated before anything is launched (the sweep allocates host memory:
+ *                   3 words per member source and slot)
+ *   src, coef, groups                   the caller's device copies, 8-byte aligned (coef: 4-byte)
+ * n_groups <= 65535; n_groups == 0 is a success with nothing launched.  rows and members must not overlap.  No atomics, no device
+ * allocation, no host synchronisation.
+ */
+typedef struct l3c_rebuild_group {
+    int64_t first_src;                          /* sources [first_src, first_src + n_rows + n_members) of the tables: the rows first */
+    int32_t n_rows, n_members, t, reserved;     /* n_rows in 1..4; n_members >= 0; t in 1..4 outputs; reserved 0 */
+    l3c_u8_span out[4];                         /* out[e], e < t: a slot inside `members` */
+} l3c_rebuild_group;
+int l3c_band_rebuild(const uint8_t *rows, int64_t rows_bytes, uint8_t *members, int64_t members_bytes, const l3c_u8_span *src_host,
+                     const l3c_u8_span *src, const uint8_t *coef_host, const uint8_t *coef, int64_t n_src, const l3c_rebuild_group *groups_host,
+                     const l3c_rebuild_group *groups, int64_t n_groups, l3c_stream_t stream);
+
+/*
+ * REPAIR THROUGH THE C ABI (NativeCodec.decode_repair; INTEGRATION.md "Repair through the C ABI"): the rounds of THE REPAIR above as two
+ * calls per round, a host planner and ONE device call.  The caller decodes with l3c_decode_batch_banded (desc.sym set), hashes the frames
+ * with l3c_u8_crc32_bands, brings the 3 n words per file to the host, copies the parity SECTIONS of the files that have a failing band into
+ * a device buffer `rows` (a section: the file's bytes from body_bytes of l3c_seal_find_parity_rs on, at any 4-byte aligned place), and then
+ * loops { l3c_repair_round_plan; H2D of the round blob; l3c_decode_repair_round; D2H of crc_out; update the words } until a plan comes back
+ * with n_groups == 0.
+ *
+ * l3c_repair_round_plan: pure host code (csrc/repair_plan.h), Bitcoding._repair's selection word for word.  A band FAILS where its word
+ * differs from the file's table; the ERASURE of a failing position is its lowest failing channel; a group (file, c, g) is taken when it
+ * holds t = 1..R erasures and every other member verifies at c; its window is the first r0 in 0..R - t that (file, c, g, bands, r0) is not
+ * in `tried` with; groups in (file, c, g) order, the files of one row ('L3CP') first.  The coefficients are the inverse of the t x t matrix
+ * (alpha^(k_e (r0 + i))) by Gauss-Jordan -- container.rs_repair_coefficients' element for element; l3c_repair_coefficients hands them out.
+ *   plan_host        the blob of l3c_decode_plan_banded for these files' BODIES (checked again)
+ *   files_host, file_bytes_host    the B WHOLE sealed files as the caller holds them; read with l3c_seal_find_parity_rs only.  A file
+ *                    without a parity section plans nothing
+ *   band_words_host  uint32 [B][3][n]: the current words of l3c_u8_crc32_bands / l3c_u8_crc32_spans
+ *   section_at_host  int64 [B]: where file b's section starts inside `rows`, or -1; a planned group of a file at -1 is L3C_ERR_INVALID_ARG
+ *   tried_host       the l3c_repair_group entries of all earlier rounds (the caller appends every blob's list)
+ *   round_host       l3c_repair_round_plan_bytes(cfg, plan_host) bytes (an upper bound for any round), 8-byte aligned.  The blob is
+ *                    self-describing (magic word, size at word 1, the cfg words; layout: csrc/repair_plan.h); *n_groups_out == 0 is a valid
+ *                    result: nothing left to try.  l3c_repair_round_groups hands out its group list and its S positions.
+ *
+ * l3c_decode_repair_round: on main_stream  1. l3c_band_rebuild of the blob's groups, IN PLACE in the stream area of the decode's workspace
+ * (l3c_decode_batch_banded_streams_offset)  2. one launch that zeroes the S positions' symbols in the three planes  3. ONE
+ * l3c_decode_rgb_entries against the P the decode left (l3c_decode_batch_banded_p_offset), window mode 1, the blob's chunk count and lag
+ * 4. l3c_sym_to_u8 on the frames  5. ONE l3c_u8_crc32_spans of the positions' 3 S bands into crc_out (channel-major: (c, e) at c S + e,
+ * e the blob's position index).  The round blob is checked before a word of it is trusted: its header against the plan blob, then every
+ * table that follows from its groups is made again on the host and compared (that copy is the one host allocation of the call); the row
+ * spans against rows_bytes by l3c_band_rebuild.  side_stream is used only at lag 2 (16 positions or more) and must then be a stream of its
+ * own.  Nothing synchronises with the host.  A blob with n_groups == 0 is a success with nothing enqueued.
+ *   workspace        the decode's, untouched since l3c_decode_batch_banded returned (with its workspace_bytes)
+ *   round, round_host    the blob on the device (16-byte aligned) and on the host
+ *   round_workspace  l3c_decode_repair_round_workspace_bytes(cfg, plan_host, round_host) bytes, 16-byte aligned
+ * Not built: repair in the set readers and in l3c_decode_region; head healing in C (container.heal_head runs before the decode).
+ */
+typedef struct l3c_repair_group {
+    int32_t file, c, g, t, r0;      /* group g of channel c of file `file`: its t erased bands from the rows r0 .. r0 + t - 1 */
+    int32_t bands[4];               /* the erased bands, ascending; bands[e] = 0 for e >= t */
+} l3c_repair_group;
+typedef struct {
+    const l3c_codec_model *model_host;
+    const void *plan_host;
+    const void *round_host;
+    const void *round;
+    int64_t round_bytes;
+    const uint8_t *rows;
+    int64_t rows_bytes;
+    void *workspace;
+    int64_t workspace_bytes;
+    int16_t *sym;                   /* [B][3][H][W], the decode's desc.sym */
+    uint8_t *pixels;                /* [B][3][H][W] */
+    uint32_t *crc_out;              /* [3 S] */
+    void *round_workspace;
+    int64_t round_workspace_bytes;
+} l3c_decode_repair_round_desc;
+int l3c_repair_coefficients(const int32_t *erased_host, int t, int r0, const int32_t *present_host, int n_present, uint8_t *rows_out,
+                            uint8_t *members_out);     /* rows_out [t][t], members_out [t][n_present]; members k in 0..254, distinct */
+int64_t l3c_repair_round_plan_bytes(const l3c_net_config *cfg_host, const void *plan_host);
+int l3c_repair_round_plan(const l3c_net_config *cfg_host, const void *plan_host, const uint8_t *const *files_host, const int64_t *file_bytes_host,
+                          const uint32_t *band_words_host, const int64_t *section_at_host, const l3c_repair_group *tried_host, int64_t n_tried,
+                          void *round_host, int64_t round_bytes, int64_t *n_groups_out);
+int l3c_repair_round_groups(const void *round_host, const l3c_repair_group **groups_out, int64_t *n_groups_out, const int32_t **positions_out,
+                            int64_t *n_positions_out);     /* positions: int32 [S][2] = file | band, ascending; pointers into the blob */
+int64_t l3c_decode_repair_round_workspace_bytes(const l3c_net_config *cfg_host, const void *plan_host, const void *round_host);
+int l3c_decode_repair_round(const l3c_decode_repair_round_desc *desc_host, l3c_stream_t main_stream, l3c_stream_t side_stream);
 
 /*
  * HEAD PARITY (Bitcoding(parity=G, parity_head=True)): the parity above covers the band payloads of the finest record; the HEAD of a file

@@ -163,6 +163,25 @@ class U8Span(ctypes.Structure):
     _fields_ = [('offset', c_i64), ('bytes', c_i64)]
 
 
+class RebuildGroup(ctypes.Structure):
+    """l3c_rebuild_group (include/l3c_hip.h): one group of l3c_band_rebuild."""
+    _fields_ = [('first_src', c_i64), ('n_rows', ctypes.c_int32), ('n_members', ctypes.c_int32), ('t', ctypes.c_int32),
+                ('reserved', ctypes.c_int32), ('out', U8Span * 4)]
+
+
+class RepairGroup(ctypes.Structure):
+    """l3c_repair_group (include/l3c_hip.h): one group of a repair round."""
+    _fields_ = [('file', ctypes.c_int32), ('c', ctypes.c_int32), ('g', ctypes.c_int32), ('t', ctypes.c_int32), ('r0', ctypes.c_int32),
+                ('bands', ctypes.c_int32 * 4)]
+
+
+class DecodeRepairRoundDesc(ctypes.Structure):
+    """l3c_decode_repair_round_desc (include/l3c_hip.h)."""
+    _fields_ = [('model_host', ctypes.POINTER(CodecModel)), ('plan_host', c_vp), ('round_host', c_vp), ('round', c_vp), ('round_bytes', c_i64),
+                ('rows', c_vp), ('rows_bytes', c_i64), ('workspace', c_vp), ('workspace_bytes', c_i64), ('sym', c_vp), ('pixels', c_vp),
+                ('crc_out', c_vp), ('round_workspace', c_vp), ('round_workspace_bytes', c_i64)]
+
+
 class EncodeImagesDesc(ctypes.Structure):
     """l3c_encode_images_desc (include/l3c_hip.h)."""
     _fields_ = [('model_host', ctypes.POINTER(CodecModel)), ('src', c_vp), ('src_bytes', c_i64), ('images_host', c_vp), ('images', c_vp),
@@ -337,6 +356,16 @@ PROTOTYPES = {
     'l3c_decode_batch_banded_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
     'l3c_decode_batch_banded_p_offset': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
     'l3c_decode_batch_banded': (c_int, [ctypes.POINTER(DecodeBatchDesc), c_vp, c_vp]),
+    'l3c_decode_batch_banded_streams_offset': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
+    'l3c_decode_plan_banded_stream': (c_int, [c_vp, c_int, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_uint32)]),
+    'l3c_band_rebuild': (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    'l3c_repair_coefficients': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
+    'l3c_repair_round_plan_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp]),
+    'l3c_repair_round_plan': (c_int, [ctypes.POINTER(NetConfig), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i64)]),
+    'l3c_repair_round_groups': (c_int, [c_vp, ctypes.POINTER(ctypes.POINTER(RepairGroup)), ctypes.POINTER(c_i64),
+                                        ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), ctypes.POINTER(c_i64)]),
+    'l3c_decode_repair_round_workspace_bytes': (c_i64, [ctypes.POINTER(NetConfig), c_vp, c_vp]),
+    'l3c_decode_repair_round': (c_int, [ctypes.POINTER(DecodeRepairRoundDesc), c_vp, c_vp]),
     'l3c_image_padding': (c_int, [c_int, c_int, c_int, c_vp]),
     'l3c_image_table_check': (c_int, [c_vp, c_i64, c_int, c_int, c_i64]),
     'l3c_u8_gather': (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),

@@ -17,7 +17,7 @@ SOURCES = ['l3c_api.hip', 'ac_kernels.hip', 'dmll_kernels.hip', 'conv_mfma.hip',
 # encoder's interval head from before its vector fill and compile-time shapes (xcheck_iv.hip).  The
 # product library does not contain it and the package never loads it outside the tests.
 XCHECK_SOURCES = ['l3c_api.hip', 'conv_wino.hip', 'xcheck_dmll.hip', 'conv_wino4w.hip', 'xcheck_small.hip', 'xcheck_iv.hip']
-HEADERS = ['ac_core.h', 'dmll_core.h', 'l3c_common.h', 'codec_plan.h', 'codec_plan_banded.h', 'codec_plan_region.h', 'image_table.h', 'seal.h', 'crc_spans.h', 'crc_wave.h', 'parity_plan.h', 'seal_parity_plan.h', 'banded_rows.h', os.path.join('..', '..', 'include', 'l3c_hip.h'), os.path.join('..', '..', 'include', 'l3c_xcheck.h'),
+HEADERS = ['ac_core.h', 'dmll_core.h', 'l3c_common.h', 'codec_plan.h', 'codec_plan_banded.h', 'codec_plan_region.h', 'image_table.h', 'seal.h', 'crc_spans.h', 'crc_wave.h', 'parity_plan.h', 'repair_plan.h', 'seal_parity_plan.h', 'banded_rows.h', os.path.join('..', '..', 'include', 'l3c_hip.h'), os.path.join('..', '..', 'include', 'l3c_xcheck.h'),
            os.path.join('..', '..', 'include', 'l3c_xcheck_small.h')]
 LIB = os.path.join(HERE, 'libl3c_hip.so')
 XCHECK_LIB = os.path.join(HERE, 'libl3c_hip_xcheck.so')

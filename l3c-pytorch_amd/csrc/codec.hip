@@ -28,10 +28,14 @@
 // format -- a thread per legacy file, a block with a wave reduction per banded file -- and int16 symbols -> uint8 pixels.
 #include <string.h>
 
+#include <exception>
+#include <vector>
+
 #include "codec_plan.h"
 #include "codec_plan_banded.h"
 #include "codec_plan_region.h"
 #include "l3c_common.h"
+#include "repair_plan.h"
 #include "seal_parity_plan.h"
 
 #define CODEC_FAIL(code, ...) (snprintf(l3c::error_buffer(), 512, __VA_ARGS__), (code))
@@ -153,6 +157,16 @@ __global__ __launch_bounds__(256) void sym_to_u8_kernel(const int16_t *__restric
         out4[i] = make_uint4(pack4(a.x, a.y), pack4(a.z, a.w), pack4(b.x, b.y), pack4(b.z, b.w));
     }
     for (int64_t i = (n_vec << 4) + tid; i < n; i += stride) out[i] = (uint8_t)sym[i];
+}
+
+// l3c_decode_repair_round: the symbols of entry e = blockIdx.x of the table pixbase | hw | pix0 | len in the three planes of its image, two
+// per store (pix0 and len are multiples of 64 but for a frame's last band, whose end is the even H W)
+__global__ __launch_bounds__(256) void zero_entries_kernel(const int64_t *__restrict__ entries, int64_t S, int16_t *__restrict__ sym) {
+    const int64_t e = blockIdx.x, pixbase = entries[e], hw = entries[S + e], pix0 = entries[2 * S + e], len = entries[3 * S + e];
+    for (int c = 0; c < 3; ++c) {
+        uint32_t *p = reinterpret_cast<uint32_t *>(sym + 3 * pixbase + c * hw + pix0);
+        for (int64_t i = threadIdx.x; i < len / 2; i += 256) p[i] = 0u;
+    }
 }
 
 int launch_layout(const LayoutArgs &a, l3c_stream_t stream) {
@@ -1257,8 +1271,190 @@ int64_t l3c_decode_batch_banded_p_offset(const l3c_net_config *cfg, const void *
     return dec_plan_field<BandedHeader>(cfg, plan_host, &DecPlan::P);
 }
 
+// (the stream area is the first thing in the workspace; the accessor below says where a stream lies inside it)
+int64_t l3c_decode_batch_banded_streams_offset(const l3c_net_config *cfg, const void *plan_host) {
+    return dec_plan_field<BandedHeader>(cfg, plan_host, &DecPlan::streams);
+}
+
+int l3c_decode_plan_banded_stream(const void *plan_host, int record, int64_t index, int64_t *src_offset_out, int64_t *dst_offset_out,
+                                  uint32_t *nbytes_out) {
+    return l3c_plan::banded_stream(plan_host, record, index, src_offset_out, dst_offset_out, nbytes_out, l3c::error_buffer(), 512);
+}
+
 int l3c_decode_batch_banded(const l3c_decode_batch_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
     return dec_batch<BandedHeader>(d, main_stream, side_stream);
+}
+
+// ---- repair of parity-sealed files: the planner of a round (csrc/repair_plan.h) and the round on the device ----------------------------------
+
+int l3c_repair_coefficients(const int32_t *erased, int t, int r0, const int32_t *present, int n_present, uint8_t *rows_out, uint8_t *members_out) {
+    L3C_REQUIRE(erased && rows_out && (n_present == 0 || (present && members_out)), "null pointer");
+    L3C_REQUIRE(t >= 1 && t <= l3c_repair::MAX_T && r0 >= 0 && r0 <= l3c_repair::MAX_T - t && n_present >= 0, "t must be in 1..4, r0 in 0..4 - t");
+    int64_t ks[l3c_repair::MAX_T];
+    for (int e = 0; e < t; ++e) {
+        L3C_REQUIRE(erased[e] >= 0 && erased[e] < l3c_sealing::MAX_RS_GROUP, "members must be in 0..254");
+        ks[e] = erased[e];
+    }
+    for (int p = 0; p < n_present; ++p) {
+        L3C_REQUIRE(present[p] >= 0 && present[p] < l3c_sealing::MAX_RS_GROUP, "members must be in 0..254");
+        for (int e = 0; e < t; ++e) L3C_REQUIRE(present[p] != erased[e], "a member is erased or present, not both");
+    }
+    uint8_t inv[l3c_repair::MAX_T][l3c_repair::MAX_T];
+    if (!l3c_repair::rs_invert(ks, t, r0, inv)) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "singular system: the erased members must be distinct");
+    for (int e = 0; e < t; ++e) {
+        for (int i = 0; i < t; ++i) rows_out[e * t + i] = inv[e][i];
+        for (int p = 0; p < n_present; ++p) members_out[e * n_present + p] = l3c_repair::rs_member_weight(inv, e, t, r0, present[p]);
+    }
+    return L3C_OK;
+}
+
+int64_t l3c_repair_round_plan_bytes(const l3c_net_config *cfg, const void *plan_host) {
+    CODEC_TRY(codec_config(cfg));
+    BandedHeader h;
+    CODEC_TRY(check_blob_of(*cfg, plan_host, -1, &h));
+    return l3c_repair::round_bytes_bound(h);
+}
+
+int l3c_repair_round_plan(const l3c_net_config *cfg, const void *plan_host, const uint8_t *const *files_host, const int64_t *file_bytes_host,
+                          const uint32_t *band_words_host, const int64_t *section_at_host, const l3c_repair_group *tried_host, int64_t n_tried,
+                          void *round_host, int64_t round_bytes, int64_t *n_groups_out) {
+    L3C_REQUIRE(n_groups_out, "null pointer: n_groups_out");
+    CODEC_TRY(codec_config(cfg));
+    CODEC_TRY(l3c_repair::make_round_plan(cfg, plan_host, files_host, file_bytes_host, band_words_host, section_at_host, tried_host, n_tried, round_host,
+                                          round_bytes, l3c::error_buffer(), 512));
+    *n_groups_out = static_cast<const l3c_repair::RoundHeader *>(round_host)->n_groups;
+    return L3C_OK;
+}
+
+int l3c_repair_round_groups(const void *round_host, const l3c_repair_group **groups_out, int64_t *n_groups_out, const int32_t **positions_out,
+                            int64_t *n_positions_out) {
+    L3C_REQUIRE(round_host && groups_out && n_groups_out && positions_out && n_positions_out, "null pointer");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(round_host) & 7) == 0, "round_host must be 8-byte aligned");
+    l3c_repair::RoundHeader h, want;
+    memcpy(&h, round_host, sizeof(h));
+    L3C_REQUIRE(h.magic == l3c_repair::ROUND_MAGIC, "round blob: wrong magic word (not written by l3c_repair_round_plan)");
+    L3C_REQUIRE(h.B >= 1 && h.B < 65536 && h.n_groups >= 0 && h.n_groups <= 65535 && h.S >= 0 && h.S <= 65535 && h.n_src >= 0 &&
+                    h.n_src <= l3c_repair::MAX_BANDS * 65535,
+                "round blob: inconsistent header");
+    want = h;
+    l3c_repair::round_layout(want);
+    L3C_REQUIRE(memcmp(&want, &h, sizeof(h)) == 0, "round blob: inconsistent header");
+    const char *blob = static_cast<const char *>(round_host);
+    *groups_out = reinterpret_cast<const l3c_repair_group *>(blob + h.groups_off);
+    *n_groups_out = h.n_groups;
+    *positions_out = reinterpret_cast<const int32_t *>(blob + h.pos_off);
+    *n_positions_out = h.S;
+    return L3C_OK;
+}
+
+namespace {
+
+struct RoundPlan {
+    BandedHeader h;
+    DecPlan p;
+    l3c_repair::RoundHeader r;
+    int64_t entries_ws, crc_ws, bytes;
+};
+
+// both blobs -- the round blob's header against the plan; with `check` everything that follows from its groups, made again and compared --
+// and the plan of the round's workspace
+int round_blobs(const l3c_net_config *cfg, const void *plan_host, const void *round_host, int64_t round_bytes, bool check, RoundPlan *q) {
+    CODEC_TRY(codec_config(cfg));
+    L3C_REQUIRE(plan_host && round_host, "null pointer: plan_host / round_host");
+    L3C_REQUIRE(((reinterpret_cast<uintptr_t>(plan_host) | reinterpret_cast<uintptr_t>(round_host)) & 7) == 0, "plan_host and round_host must be 8-byte aligned");
+    CODEC_TRY(check_blob_of(*cfg, plan_host, -1, &q->h));
+    CODEC_TRY(dec_plan(*cfg, q->h, &q->p));
+    CODEC_TRY(l3c_repair::round_check(*cfg, q->h, plan_host, round_host, round_bytes, &q->r, nullptr, 0, l3c::error_buffer(), 512));
+    if (check) {
+        std::vector<int64_t> again;
+        try {
+            again.resize((size_t)(q->r.bytes + 7) / 8);
+        } catch (const std::exception &) {
+            return CODEC_FAIL(L3C_ERR_INVALID_ARG, "no host memory to check a round blob of %lld bytes", (long long)q->r.bytes);
+        }
+        CODEC_TRY(l3c_repair::round_check(*cfg, q->h, plan_host, round_host, round_bytes, &q->r, reinterpret_cast<uint8_t *>(again.data()), q->r.bytes,
+                                          l3c::error_buffer(), 512));
+    }
+    const l3c_repair::RoundHeader &r = q->r;
+    q->entries_ws = q->crc_ws = 0;
+    if (r.n_groups > 0) {
+        const char *blob = static_cast<const char *>(round_host);
+        L3C_REQUIRE(r.S >= 1 && r.S < 65536, "round blob: 1 .. 65535 positions");
+        q->entries_ws = l3c_decode_rgb_entries_workspace_bytes(r.S, reinterpret_cast<const int64_t *>(blob + r.entries_off) + 3 * r.S, (int)r.n_chunks, (int)r.lag);
+        if (q->entries_ws < 0) return CODEC_FAIL(L3C_ERR_INVALID_ARG, "round blob: bad entry table");
+        q->crc_ws = l3c_u8_crc32_spans_workspace_bytes(reinterpret_cast<const l3c_u8_span *>(blob + r.crc_off), 3 * r.S);
+        if (q->crc_ws < 0) return (int)q->crc_ws;
+    }
+    q->bytes = up(q->entries_ws) + up(q->crc_ws) + ALIGN;
+    return L3C_OK;
+}
+
+}  // namespace
+
+int64_t l3c_decode_repair_round_workspace_bytes(const l3c_net_config *cfg, const void *plan_host, const void *round_host) {
+    RoundPlan q;
+    CODEC_TRY(round_blobs(cfg, plan_host, round_host, -1, false, &q));
+    return q.bytes;
+}
+
+int l3c_decode_repair_round(const l3c_decode_repair_round_desc *d, l3c_stream_t main_stream, l3c_stream_t side_stream) {
+    L3C_REQUIRE(d, "null descriptor");
+    CODEC_TRY(check_model(d->model_host));
+    const l3c_codec_model &m = *d->model_host;
+    const l3c_net_config &c = *m.cfg_host;
+    L3C_REQUIRE(d->round && d->rows && d->workspace && d->sym && d->pixels && d->crc_out && d->round_workspace, "null pointer");
+    L3C_REQUIRE(aligned16(d->round) && aligned16(d->workspace) && aligned16(d->sym) && aligned16(d->pixels) && aligned16(d->crc_out) &&
+                    aligned16(d->round_workspace),
+                "every pointer but rows must be 16-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(d->rows) & 3) == 0 && d->rows_bytes >= 0, "rows must be 4-byte aligned, rows_bytes not negative");
+    RoundPlan q;
+    CODEC_TRY(round_blobs(&c, d->plan_host, d->round_host, d->round_bytes, true, &q));
+    const l3c_repair::RoundHeader &r = q.r;
+    if (d->workspace_bytes < q.p.bytes)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "workspace_bytes too small: %lld < %lld (the decode's workspace)", (long long)d->workspace_bytes,
+                          (long long)q.p.bytes);
+    if (d->round_workspace_bytes < q.bytes)
+        return CODEC_FAIL(L3C_ERR_INVALID_ARG, "round_workspace_bytes too small: %lld < %lld", (long long)d->round_workspace_bytes, (long long)q.bytes);
+    if (r.n_groups == 0) return L3C_OK;                            // nothing left to try
+    L3C_REQUIRE(r.lag == 1 || (side_stream && side_stream != main_stream),
+                "16 positions or more decode on two streams (lag 2): side_stream must be a stream of its own");
+    L3C_REQUIRE(r.HW % 2 == 0, "an odd number of pixels per plane");
+    const int64_t B = r.B, HW = r.HW, S = r.S;
+    const char *blob = static_cast<const char *>(d->round), *blob_h = static_cast<const char *>(d->round_host);
+    char *ws = base256(d->workspace), *rws = base256(d->round_workspace);
+    uint8_t *streams = reinterpret_cast<uint8_t *>(ws + q.p.streams);
+
+    // ---- everything the blobs say is checked; the calls below check their own tables (the row spans among them) before they launch
+    CODEC_TRY(l3c_band_rebuild(d->rows, d->rows_bytes, streams, r.dst_bytes, reinterpret_cast<const l3c_u8_span *>(blob_h + r.src_off),
+                               reinterpret_cast<const l3c_u8_span *>(blob + r.src_off), reinterpret_cast<const uint8_t *>(blob_h + r.coef_off),
+                               reinterpret_cast<const uint8_t *>(blob + r.coef_off), r.n_src,
+                               reinterpret_cast<const l3c_rebuild_group *>(blob_h + r.rebuild_off),
+                               reinterpret_cast<const l3c_rebuild_group *>(blob + r.rebuild_off), r.n_groups, main_stream));
+    const int64_t *entries = reinterpret_cast<const int64_t *>(blob + r.entries_off);
+    hipLaunchKernelGGL(zero_entries_kernel, dim3((unsigned)S), dim3(256), 0, l3c::as_stream(main_stream), entries, S, d->sym);
+    CODEC_TRY(l3c::check_launch("zero_entries_kernel"));
+    l3c_rgb_entries_desc e;
+    memset(&e, 0, sizeof(e));
+    e.P = reinterpret_cast<const float *>(ws + q.p.P);
+    e.targets = m.targets_rgb;
+    e.sym = d->sym;
+    e.S = S;
+    e.total_pix = B * HW;
+    e.entries_dev = entries;
+    e.entries_host = reinterpret_cast<const int64_t *>(blob_h + r.entries_off);
+    e.K = c.K;
+    e.in = streams;
+    e.in_offsets = reinterpret_cast<const int64_t *>(blob + r.in_off);
+    e.in_nbytes = reinterpret_cast<const uint32_t *>(blob + r.in_nbytes_off);
+    e.n_chunks = (int)r.n_chunks;
+    e.lag = (int)r.lag;
+    e.window_mode = 1;
+    e.workspace = rws;
+    e.workspace_bytes = q.entries_ws;
+    CODEC_TRY(l3c_decode_rgb_entries(&e, main_stream, r.lag == 2 ? side_stream : nullptr));
+    CODEC_TRY(l3c_sym_to_u8(d->sym, B * 3 * HW, d->pixels, main_stream));
+    return l3c_u8_crc32_spans(d->pixels, B * 3 * HW, reinterpret_cast<const l3c_u8_span *>(blob_h + r.crc_off),
+                              reinterpret_cast<const l3c_u8_span *>(blob + r.crc_off), 3 * S, d->crc_out, rws + up(q.entries_ws), q.crc_ws, main_stream);
 }
 
 // ---- pictures as they come: a table of views, padded and cropped on the device (csrc/images.hip) -----------------------------------

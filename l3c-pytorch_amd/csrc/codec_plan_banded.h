@@ -319,6 +319,47 @@ inline int check_blob_banded(const l3c_net_config &c, const void *plan_host, int
     return L3C_OK;
 }
 
+// One stream entry of a blob, for callers that must not restate the layout above: stream `index` of record `record` (coarsest first), numbered
+// inside the record as the blob numbers them -- band (b, c, j) of the finest record is (c B + b) n + j.  The header is checked against the layout
+// its own B and records imply before an offset of it is used, and the entry against dst_bytes.
+inline int banded_stream(const void *plan_host, int record, int64_t index, int64_t *src_out, int64_t *dst_out, uint32_t *nbytes_out, char *err,
+                         size_t cap) {
+    if (!plan_host || !src_out || !dst_out || !nbytes_out) return fail(err, cap, L3C_ERR_INVALID_ARG, "null pointer");
+    if (reinterpret_cast<uintptr_t>(plan_host) & 7) return fail(err, cap, L3C_ERR_INVALID_ARG, "plan_host must be 8-byte aligned");
+    int64_t magic;
+    memcpy(&magic, plan_host, sizeof(magic));
+    if (magic != BANDED_MAGIC) return fail(err, cap, L3C_ERR_INVALID_ARG, "plan blob: wrong magic word (not written by l3c_decode_plan_banded)");
+    BandedHeader h;
+    memcpy(&h, plan_host, sizeof(h));
+    bool ok = h.B >= 1 && h.B < 65536 && h.n_records >= 2 && h.n_records <= MAX_RECORDS && h.dst_bytes >= 0;
+    for (int k = 0; ok && k < (int)h.n_records; ++k)
+        ok = h.rec[k].C >= 1 && h.rec[k].C <= 255 && h.rec[k].n >= 1 && h.rec[k].n <= MAX_BANDS && h.B * h.rec[k].n <= MAX_BAND_STREAMS;
+    if (ok) {
+        BandedHeader want = h;
+        banded_layout(want);
+        ok = want.bytes == h.bytes && want.n_streams == h.n_streams && want.src_off == h.src_off && want.dst_off == h.dst_off &&
+             want.nbytes_off == h.nbytes_off;
+        for (int k = 0; ok && k < (int)h.n_records; ++k) ok = want.rec[k].first == h.rec[k].first && want.rec[k].n_streams == h.rec[k].n_streams;
+    }
+    if (!ok) return fail(err, cap, L3C_ERR_INVALID_ARG, "plan blob: inconsistent header");
+    if (record < 0 || record >= (int)h.n_records)
+        return fail(err, cap, L3C_ERR_INVALID_ARG, "record %lld: the plan has %lld records", (long long)record, h.n_records);
+    const BandedRecord &r = h.rec[record];
+    if (index < 0 || index >= r.n_streams)
+        return fail(err, cap, L3C_ERR_INVALID_ARG, "stream %lld: record %lld has %lld streams", index, (long long)record, r.n_streams);
+    const uint8_t *blob = static_cast<const uint8_t *>(plan_host);
+    const int64_t s = r.first + index;
+    int64_t src, dst;
+    uint32_t nb;
+    memcpy(&src, blob + h.src_off + 8 * s, 8);
+    memcpy(&dst, blob + h.dst_off + 8 * s, 8);
+    memcpy(&nb, blob + h.nbytes_off + 4 * s, 4);
+    if (src < 0 || dst < 0 || dst % 4 != 0 || dst > h.dst_bytes || ((int64_t)nb + 3) / 4 * 4 + 4 > h.dst_bytes - dst)
+        return fail(err, cap, L3C_ERR_INVALID_ARG, "plan blob: stream %lld lies outside the stream buffer", s);
+    *src_out = src, *dst_out = dst, *nbytes_out = nb;
+    return L3C_OK;
+}
+
 }  // namespace l3c_plan
 
 #endif

@@ -1,4 +1,4 @@
-// parity.hip -- parity bands (include/l3c_hip.h: l3c_band_parity, l3c_u8_xor_spans; the format is csrc/seal.h, version 3).
+// parity.hip -- parity bands (include/l3c_hip.h: l3c_band_parity, l3c_u8_xor_spans, l3c_band_rebuild; the format is csrc/seal.h, version 3).
 //
 // Both kernels are streaming XORs over byte streams of different lengths and share one fold: a block owns a TILE of 4096 bytes of ONE
 // output stream (grid.y = the stream), a thread 16 bytes of it, and walks the stream's members, eight at a time (fold_members): one 16-byte
@@ -17,9 +17,17 @@
 // l3c_head_parity (the head part of the 'L3CH' section) is l3c_band_parity_rs over SEVERAL records of any channel count in one launch:
 // grid.y runs over (record, b, c, g), the records travel by value, and a block does the work of its record's band_parity_rs block (rs_stream).
 //
+// l3c_band_rebuild is the repair-side counterpart of rs_stream: where l3c_u8_gf_spans rebuilds ONE payload per output group, a block of
+// band_rebuild_kernel loads every source of a group once and keeps an accumulator per erased member (at most four); its parity rows are
+// read where they lie in the file's section, at any byte offset (the aligned dwords around a run, funnel-shifted), and it writes IN PLACE:
+// outputs and member sources are spans of one buffer, so the host check refuses any overlap between them (parity_plan.h: check_rebuild).
+//
 // XOR is the R = 1 / every-coefficient-1 case of the GF(2^8) kernels and could be their instantiation; it keeps kernels of its own because
 // that instantiation measured 8 to 10 % slower (profiles/r23_parity_one_path_latency.log).  The host side is one path: the entry points of a
 // family share their argument checks (check_band_parity, u8_spans).
+#include <exception>
+#include <vector>
+
 #include "l3c_common.h"
 #include "parity_plan.h"
 #include "banded_rows.h"
@@ -259,9 +267,128 @@ __global__ __launch_bounds__(THREADS) void u8_gf_spans_kernel(const uint8_t *__r
     store16(out + slot.offset, off, end, acc);
 }
 
+// ---- l3c_band_rebuild: all t erased members of a group in one pass ------------------------------------------------------------------------
+
+// A source of band_rebuild_kernel: `len` bytes that start `shift` bytes (0..3) behind the 4-byte aligned p.  A member has shift 0; a parity
+// row lies where the file's section put it.
+struct Source {
+    const uint8_t *p;
+    int64_t len;
+    uint32_t shift;
+};
+
+// load16 for a source at any byte offset: bytes [off, off + 16) of it, zero at and behind the end of its last dword.  With a shift the five
+// aligned dwords around the 16 bytes are read -- none that holds no byte of the source -- and funnel-shifted by whole bytes.
+__device__ __forceinline__ u32x4 load16(const Source &s, int64_t off) {
+    if (s.shift == 0) return load16(Member{s.p, s.len}, off);
+    const int64_t end = (int64_t)s.shift + s.len;                  // of the source, in bytes from p
+    uint32_t w[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) w[i] = off + 4 * i < end ? *reinterpret_cast<const uint32_t *>(s.p + off + 4 * i) : 0u;
+    u32x4 q;
+    q.x = __builtin_amdgcn_alignbyte(w[1], w[0], s.shift);
+    q.y = __builtin_amdgcn_alignbyte(w[2], w[1], s.shift);
+    q.z = __builtin_amdgcn_alignbyte(w[3], w[2], s.shift);
+    q.w = __builtin_amdgcn_alignbyte(w[4], w[3], s.shift);
+    return q;
+}
+
+// acc[e] ^= (byte e of cw) * q for the four packed coefficients of cw, uniform over the block: the powers alpha^i q are formed once for
+// all accumulators, one uniform branch per accumulator and bit.  A coefficient of 1 takes q as it is.
+__device__ __forceinline__ void gf_scale4(u32x4 (&acc)[REBUILD_MAX], u32x4 q, uint32_t cw) {
+    while (cw) {
+        if (cw & 0x00000001u) acc[0] ^= q;
+        if (cw & 0x00000100u) acc[1] ^= q;
+        if (cw & 0x00010000u) acc[2] ^= q;
+        if (cw & 0x01000000u) acc[3] ^= q;
+        cw = (cw >> 1) & 0x7f7f7f7fu;
+        if (cw) q = xtime(q);
+    }
+}
+
+// grid (tiles of the longest slot, n_groups): block (x, g) rebuilds tile x of the t outputs of group g.  Every source is read once, cut to
+// the longest output; an output shorter than that is cut when it is stored (the field operations work byte by byte, so the cut commutes).
+__global__ __launch_bounds__(THREADS) void band_rebuild_kernel(const uint8_t *__restrict__ rows, uint8_t *members,
+                                                              const l3c_u8_span *__restrict__ src, const uint32_t *__restrict__ coef,
+                                                              const l3c_rebuild_group *__restrict__ groups) {
+    const l3c_rebuild_group &grp = groups[blockIdx.y];
+    const int t = grp.t;
+    int64_t bytes[REBUILD_MAX], longest = 0;
+#pragma unroll
+    for (int e = 0; e < REBUILD_MAX; ++e) {
+        bytes[e] = e < t ? grp.out[e].bytes : -1;
+        longest = bytes[e] > longest ? bytes[e] : longest;
+    }
+    const int64_t off = (int64_t)blockIdx.x * TILE_BYTES + 16 * threadIdx.x;
+    if (off >= slot_bytes(longest)) return;
+    const uint32_t used = 0xFFFFFFFFu >> (8 * (REBUILD_MAX - t));   // the coefficients of the outputs there are
+    const int64_t k0 = grp.first_src, n_rows = grp.n_rows, count = n_rows + grp.n_members;
+    u32x4 acc[REBUILD_MAX];
+#pragma unroll
+    for (int e = 0; e < REBUILD_MAX; ++e) acc[e] = u32x4{0u, 0u, 0u, 0u};
+    for (int64_t k = 0; k < count; k += DEPTH) {
+        Source s[DEPTH];
+        uint32_t c[DEPTH];
+        u32x4 q[DEPTH];
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) {
+            c[u] = k + u < count ? coef[k0 + k + u] & used : 0u;
+            s[u] = Source{nullptr, 0, 0u};
+            if (c[u]) {
+                const l3c_u8_span sp = src[k0 + k + u];
+                const int64_t len = sp.bytes < longest ? sp.bytes : longest;
+                if (k + u < n_rows) {
+                    const uint8_t *at = rows + sp.offset;
+                    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(at) & 3);
+                    s[u] = Source{at - shift, len, shift};
+                } else {
+                    s[u] = Source{members + sp.offset, len, 0u};
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) q[u] = load16(s[u], off);
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) gf_scale4(acc, mask16(q[u], s[u].len, off), c[u]);
+    }
+#pragma unroll
+    for (int e = 0; e < REBUILD_MAX; ++e) {
+        if (e >= t) break;
+        const int64_t end = slot_bytes(bytes[e]);
+        if (off < end) store16(members + grp.out[e].offset, off, end, mask16(acc[e], bytes[e], off));
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int l3c_band_rebuild(const uint8_t *rows, int64_t rows_bytes, uint8_t *members, int64_t members_bytes, const l3c_u8_span *src_host,
+                     const l3c_u8_span *src, const uint8_t *coef_host, const uint8_t *coef, int64_t n_src, const l3c_rebuild_group *groups_host,
+                     const l3c_rebuild_group *groups, int64_t n_groups, l3c_stream_t stream) {
+    L3C_REQUIRE(n_groups >= 0, "n_groups must not be negative");
+    if (n_groups == 0) return L3C_OK;
+    // (room for the sweep over the member sources and the slots; where the counts are bad the check itself says which)
+    const int64_t n_iv = rebuild_intervals(groups_host, n_groups);
+    std::vector<RebuildInterval> scratch;
+    try {
+        scratch.resize(n_iv > 0 ? (size_t)n_iv : 0);
+    } catch (const std::exception &) {
+        return l3c::fail(L3C_ERR_INVALID_ARG, "%s: no host memory for the overlap check of %lld spans", "l3c_band_rebuild", (long long)n_iv);
+    }
+    const int64_t tiles = check_rebuild(src_host, n_src, groups_host, n_groups, rows_bytes, members_bytes, scratch.data(), l3c::error_buffer(), 512);
+    if (tiles < 0) return (int)tiles;
+    L3C_REQUIRE(rows && members && src && coef_host && coef && groups, "null pointer");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(rows) & 3) == 0 && (reinterpret_cast<uintptr_t>(members) & 3) == 0 &&
+                    (reinterpret_cast<uintptr_t>(coef) & 3) == 0,
+                "rows, members and coef must be 4-byte aligned");
+    L3C_REQUIRE((reinterpret_cast<uintptr_t>(src) & 7) == 0 && (reinterpret_cast<uintptr_t>(groups) & 7) == 0,
+                "src and groups (the device tables) must be 8-byte aligned");
+    L3C_REQUIRE(members + members_bytes <= rows || rows + round4(rows_bytes) <= members, "members must not overlap rows");
+    hipLaunchKernelGGL(band_rebuild_kernel, dim3((unsigned)tiles, (unsigned)n_groups), dim3(THREADS), 0, l3c::as_stream(stream), rows, members, src,
+                       reinterpret_cast<const uint32_t *>(coef), groups);
+    return l3c::check_launch("band_rebuild_kernel");
+}
 
 int l3c_band_parity_groups(int n, int G) {
     L3C_REQUIRE(n >= 1 && n <= 1024 && G >= 1 && G <= n, "n must be in 1..1024 and G in 1..n");

@@ -188,6 +188,35 @@ def decode_plan_banded(cfg, files):
     return blob.tobytes(), H.value, W.value, [tuple(int(v) for v in p) for p in pads]
 
 
+ROUND_MAGIC = int.from_bytes(b'L3CROUND', 'little')
+_ROUND_NAMES = ['magic', 'bytes', 'B', 'n', 'HW', 'L', 'n_groups', 'n_src', 'S', 'n_chunks', 'lag', 'dst_bytes']
+REPAIR_GROUP_DTYPE = np.dtype([('file', '<i4'), ('c', '<i4'), ('g', '<i4'), ('t', '<i4'), ('r0', '<i4'), ('bands', '<i4', (4,))])
+
+
+def parse_round(blob):
+    """The blob l3c_repair_round_plan writes (layout: csrc/repair_plan.h) as a dict: the header's numbers, `files` (B, 2) = m | R, `groups`
+    (REPAIR_GROUP_DTYPE), the l3c_band_rebuild tables `rebuild` (ops.REBUILD_GROUP_DTYPE), `src` (ops.SPAN_DTYPE) and `coef` (n_src, 4),
+    `pos` (S, 2) = file | band, `entries` (4, S), `in_offsets` / `in_nbytes` (3, S) and `crc` (3, S) spans."""
+    raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+    w = raw[:8 * 31].view(np.int64)
+    r = {name: int(w[i]) for i, name in enumerate(_ROUND_NAMES)}
+    r['cfg'] = [int(v) for v in w[12:21]]
+    files, groups, rebuild, src, coef, pos, entries, in_off, in_nb, crc = (int(v) for v in w[21:31])
+    B, G, N, S = r['B'], r['n_groups'], r['n_src'], r['S']
+    cut = lambda at, n, dtype: raw[at:at + n * np.dtype(dtype).itemsize].view(dtype).copy()       # noqa: E731
+    r['files'] = cut(files, 2 * B, '<i4').reshape(B, 2)
+    r['groups'] = cut(groups, G, REPAIR_GROUP_DTYPE)
+    r['rebuild'] = cut(rebuild, G, ops.REBUILD_GROUP_DTYPE)
+    r['src'] = cut(src, N, ops.SPAN_DTYPE)
+    r['coef'] = cut(coef, 4 * N, np.uint8).reshape(N, 4)
+    r['pos'] = cut(pos, 2 * S, '<i4').reshape(S, 2)
+    r['entries'] = cut(entries, 4 * S, '<i8').reshape(4, S)
+    r['in_offsets'] = cut(in_off, 3 * S, '<i8').reshape(3, S)
+    r['in_nbytes'] = cut(in_nb, 3 * S, '<u4').reshape(3, S)
+    r['crc'] = cut(crc, 3 * S, ops.SPAN_DTYPE).reshape(3, S)
+    return r
+
+
 def _check_plan(rc):
     if rc == 0:
         return
@@ -393,6 +422,122 @@ class NativeCodec(object):
         pixels, info = Bitcoding._salvage(seals, pixels, kept['sym'], kept.get('P'), pads, self.cfg.K, (loss.x_min, loss.x_max, loss.L))
         return pixels, pads, info
 
+    def decode_repair(self, files, workspace=None):
+        """Bitcoding.decode_repair as library calls -> ((B,3,H,W) uint8 on the GPU, padding tuples, container.RepairInfo): the same pixels
+        and the same info.  container.heal_head on the host first, as there; then decode_salvage's decode and its ONE l3c_u8_crc32_bands
+        with its D2H.  Where a parity-sealed file has a failing band, the parity sections of those files go up in ONE H2D, each at a
+        16-byte aligned place of one buffer, and the rounds run: l3c_repair_round_plan on the host (Bitcoding._repair's selection and
+        coefficients), one small H2D of its blob, ONE l3c_decode_repair_round (l3c_band_rebuild in place in the decode workspace's stream
+        area -- every erased member of a group in one pass, the rows read where they lie in the section --, the positions' symbols zeroed,
+        one l3c_decode_rgb_entries, l3c_sym_to_u8, one l3c_u8_crc32_spans) and a D2H of its 3 S words, until a plan has nothing left to
+        try.  What still fails is concealed by Bitcoding._salvage.  info.files: the rebuilt payloads come back from their stream slots in
+        one D2H and are spliced in at their framing offsets.  An intact batch makes exactly the library calls of decode_salvage."""
+        lib = _lib.load()
+        mended = [container.heal_head(f) for f in files]          # host only; an intact file comes back as the object it is
+        given, files, heads = files, [f for f, _ in mended], [h for _, h in mended]
+        split = [self._split_seal(f) for f in files]
+        bodies, seals = [b for b, _ in split], [s for _, s in split]
+        if any(s is not None for s in seals):
+            container.check_seals(seals, self.generation(), self.model_id)
+        kept = {'plan': None}
+        pixels, pads = self._decode_bodies(bodies, workspace, None, kept)
+        sym, B, (H, W) = kept['sym'], len(files), pixels.shape[2:]
+        loss = self._losses.loss_dmol_rgb
+        band_lens = {s.band_len for s in seals if s is not None and s.band_crcs is not None}
+        words, repaired, healed, rounds = None, {}, [None] * B, 0
+        if band_lens:
+            L, = band_lens
+            n = container.n_bands(H * W, L)
+            words = Bitcoding._band_words(pixels, L)
+            band_words = words[B:].reshape(B, 3, n)                           # (a view: what _salvage reads afterwards)
+            _, failing, _ = container.failing_bands(seals, band_words, (H, W), pads)
+            if failing and kept['plan'] is not None:
+                repaired, healed, rounds = self._repair_rounds(lib, files, seals, kept, pixels, band_words, failing, pads)
+        pixels, salvage = Bitcoding._salvage(seals, pixels, sym, kept.get('P'), pads, self.cfg.K, (loss.x_min, loss.x_max, loss.L), words)
+        rows = {i: container.band_rows(sorted({j for _, j in got}), seals[i].band_len, (H, W), pads[i]) for i, got in repaired.items()}
+        healed = [f if h is None and f is not g else h for h, f, g in zip(healed, files, given)]       # a head fix alone heals a file too
+        return pixels, pads, container.RepairInfo(repaired, rows, salvage, healed, rounds, head=heads)
+
+    def _repair_rounds(self, lib, files, seals, kept, pixels, band_words, failing, pads):
+        """The rounds of decode_repair; band_words (B, 3, n) is updated in place with the words of the bands hashed again
+        -> ({file: [(c, j)]} repaired, healed files, rounds run)."""
+        B, _, H, W = pixels.shape
+        n = band_words.shape[2]
+        bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+        # the parity sections of the files with a failing band, in front of their payloads' end: ONE H2D
+        section_at, parts, at = np.full(B, -1, dtype=np.int64), [], 0
+        for i in sorted(failing):
+            body, par = ctypes.c_int64(), _lib.SealParityRS()
+            if lib.l3c_seal_find_parity_rs(bufs[i].ctypes.data, bufs[i].size, ctypes.byref(body), None, None, ctypes.byref(par)) != 1 or par.m == 0:
+                continue
+            end = par.payloads - bufs[i].ctypes.data + par.payload_bytes
+            section_at[i] = at
+            parts.append((at, bufs[i][body.value:end]))
+            at = (at + end - body.value + 15) // 16 * 16
+        if not parts:
+            return {}, [None] * B, 0
+        up = np.zeros(at, dtype=np.uint8)
+        for a, sec in parts:
+            up[a:a + sec.size] = sec
+        rows = ops.upload_small(up)
+        plan, ws, sym = kept['plan'], kept['ws'], kept['sym']
+        plan_host = plan.ctypes.data
+        cap = _size(lib.l3c_repair_round_plan_bytes(self._cfg_ref, plan_host))
+        blob = np.zeros(cap // 8 + 1, dtype=np.int64)
+        file_ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data for b in bufs])
+        sizes = np.asarray([b.size for b in bufs], dtype=np.int64)
+        tried, jobs, rounds = np.zeros(0, dtype=np.int32), [], 0
+        while True:
+            now = np.ascontiguousarray(band_words).view(np.uint32)
+            n_groups = ctypes.c_int64()
+            _check_plan(lib.l3c_repair_round_plan(self._cfg_ref, plan_host, file_ptrs, sizes.ctypes.data, now.ctypes.data, section_at.ctypes.data,
+                                                  tried.ctypes.data if tried.size else None, tried.size // 9, blob.ctypes.data, cap,
+                                                  ctypes.byref(n_groups)))
+            if n_groups.value == 0:
+                break
+            rounds += 1
+            groups_p, n_g, pos_p, S = ctypes.POINTER(_lib.RepairGroup)(), ctypes.c_int64(), ctypes.POINTER(ctypes.c_int32)(), ctypes.c_int64()
+            _lib.check(lib.l3c_repair_round_groups(blob.ctypes.data, ctypes.byref(groups_p), ctypes.byref(n_g), ctypes.byref(pos_p), ctypes.byref(S)))
+            groups = np.ctypeslib.as_array(ctypes.cast(groups_p, ctypes.POINTER(ctypes.c_int32)), shape=(n_g.value, 9)).copy()
+            spots = np.ctypeslib.as_array(pos_p, shape=(S.value, 2)).astype(np.int64)
+            tried = np.concatenate([tried.reshape(-1, 9), groups]).reshape(-1)
+            jobs += [(int(g[0]), int(g[1]), int(j)) for g in groups for j in g[5:5 + g[3]]]
+            n_blob = int(blob[1])                                             # word 1 of the header: the blob's size
+            blob_d = ops.upload_small(blob[:n_blob // 8])
+            rws = _bytes(_size(lib.l3c_decode_repair_round_workspace_bytes(self._cfg_ref, plan_host, blob.ctypes.data)))
+            again = torch.empty(3 * S.value, dtype=torch.int32, device='cuda')
+            side = self._side_stream(2 if S.value >= 16 else 1, [blob_d, rows, ws, sym, pixels, again, rws, self.targets_rgb])
+            d = _lib.DecodeRepairRoundDesc(ctypes.pointer(self.model), plan_host, blob.ctypes.data, ptr(blob_d), n_blob, ptr(rows), rows.numel(),
+                                           ptr(ws), ws.numel(), ptr(sym), ptr(pixels), ptr(again), ptr(rws), rws.numel())
+            _lib.call('l3c_decode_repair_round', ctypes.byref(d), stream(), side)
+            band_words[spots[None, :, 0], np.arange(3)[:, None], spots[None, :, 1]] = again.cpu().numpy().view(band_words.dtype).reshape(3, -1)
+        _, failing, _ = container.failing_bands(seals, band_words, (H, W), pads)
+        repaired, healed = {}, [None] * B
+        for i, c, j in sorted(set(jobs)):                                     # (a payload tried with a second window is listed twice)
+            if all((cc, j) not in failing.get(i, ()) for cc in range(3)):
+                repaired.setdefault(i, []).append((c, j))
+        # the repaired payloads from their stream slots, ONE D2H, spliced in at their framing offsets
+        area = (ws.data_ptr() + 255) // 256 * 256 - ws.data_ptr() + _size(lib.l3c_decode_batch_banded_streams_offset(self._cfg_ref, plan_host))
+        where = []
+        for i, got in sorted(repaired.items()):
+            for c, j in sorted(got):
+                src, dst, nb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_uint32()
+                _lib.check(lib.l3c_decode_plan_banded_stream(plan_host, self.cfg.num_scales, (c * B + i) * n + j, ctypes.byref(src), ctypes.byref(dst),
+                                                             ctypes.byref(nb)))
+                where.append((i, src.value - int(kept['offs'][i]), area + dst.value, nb.value))
+        if where:
+            back = torch.cat([ws[a:a + nb] for _, _, a, nb in where]).cpu().numpy()
+            out, at = {}, 0
+            for i, to, _, nb in where:
+                f = out.setdefault(i, bytearray(files[i]))
+                f[to:to + nb] = back[at:at + nb].tobytes()
+                at += nb
+            for i, f in out.items():
+                healed[i] = bytes(f)
+        for got in repaired.values():
+            got.sort()
+        return repaired, healed, rounds
+
     def _decode_bodies(self, files, workspace, sym, keep=None):
         """decode_batch behind the seals: the unsealed files -> (pixels, padding tuples), enqueued on the current stream.
         keep (decode_salvage): a dict that receives 'sym', the int16 symbols, 'ws', the workspace, and -- banded files -- 'P', the device
@@ -434,6 +579,8 @@ class NativeCodec(object):
             keep.update(sym=sym, ws=ws)
             if banded:      # (the plan is read here: its staging buffer goes back to the ring with this call)
                 keep['P'] = (ws.data_ptr() + 255) // 256 * 256 + _size(lib.l3c_decode_batch_banded_p_offset(self._cfg_ref, plan_host))
+                if 'plan' in keep:      # (decode_repair: the blob itself and where the files' bodies start in the plan's offsets)
+                    keep.update(plan=st[plan_at:plan_at + n_plan].view(np.int64).copy(), offs=offs)
         if sym is not None and (sym.dtype != torch.int16 or tuple(sym.shape) != tuple(pixels.shape) or not sym.is_contiguous()):
             raise ValueError('sym must be a contiguous int16 tensor of shape {}'.format(tuple(pixels.shape)))
         side = None

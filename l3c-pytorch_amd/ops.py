@@ -1104,3 +1104,42 @@ def u8_gf_spans(data, offsets, lengths, coefs, group_first, out, out_offsets, ou
     coefs[k] * data[offsets[k]:offsets[k] + lengths[k]], cut or zero-extended and zero-padded as u8_xor_spans does.  coefs: host integers
     0..255, one per span; a span with coefficient 0 is not read.  No groups: nothing is launched.  No host synchronisation."""
     return _u8_spans('l3c_u8_gf_spans', data, offsets, lengths, coefs, group_first, out, out_offsets, out_lengths)
+
+
+REBUILD_GROUP_DTYPE = np.dtype([('first_src', '<i8'), ('n_rows', '<i4'), ('n_members', '<i4'), ('t', '<i4'), ('reserved', '<i4'),
+                                ('out', SPAN_DTYPE, (4,))])      # l3c_rebuild_group (include/l3c_hip.h)
+
+
+def band_rebuild(rows, members, offsets, lengths, coefs, groups):
+    """l3c_band_rebuild: every erased member of a group in one pass, in place.  rows: contiguous uint8 device tensor holding the parity rows at
+    ANY byte offsets; members: contiguous uint8 device tensor that holds the member sources (offsets multiples of 4) and receives the outputs.
+    offsets, lengths: one span per source; coefs: (n_src, 4) host integers 0..255, coefs[k][e] the weight of source k in output e.  groups:
+    [(first_src, n_rows, n_members, [(out_offset, out_bytes)] * t)] -- the group's n_rows row sources first (spans of `rows`), then its
+    n_members member sources (spans of `members`); output e is the XOR over the sources k of coefs[k][e] * source k over GF(2^8), cut or
+    zero-extended to out_bytes, then zero bytes up to ((out_bytes + 3) // 4) * 4 + 4.  A slot that overlaps a member source or another slot is
+    refused.  The tables are checked on the host and go up as ONE table through upload_small.  No groups: nothing is launched.  No host
+    synchronisation."""
+    if not groups:
+        return members
+    if rows.dtype != torch.uint8 or members.dtype != torch.uint8 or not rows.is_contiguous() or not members.is_contiguous():
+        raise ValueError('band_rebuild: rows and members must be contiguous uint8 tensors')
+    src = np.zeros(len(offsets), dtype=SPAN_DTYPE)
+    src['offset'], src['bytes'] = offsets, lengths
+    coef = np.asarray(coefs, dtype=np.int64).reshape(-1, 4)
+    if coef.shape[0] != src.shape[0] or (coef.size and (coef.min() < 0 or coef.max() > 255)):
+        raise ValueError('band_rebuild: four coefficients in 0..255 per source')
+    table = np.zeros(len(groups), dtype=REBUILD_GROUP_DTYPE)
+    for g, (first, n_rows, n_members, outs) in enumerate(groups):
+        if not 1 <= len(outs) <= 4:
+            raise ValueError('band_rebuild: group {} has {} outputs, must be 1..4'.format(g, len(outs)))
+        table[g]['first_src'], table[g]['n_rows'], table[g]['n_members'], table[g]['t'] = first, n_rows, n_members, len(outs)
+        for e, (at, k) in enumerate(outs):
+            table[g]['out'][e] = (at, k)
+    coef8 = np.zeros(-(-coef.size // 8) * 8, dtype=np.uint8)                     # padded to whole words
+    coef8[:coef.size] = coef.reshape(-1)
+    a, b = 2 * src.shape[0], 2 * src.shape[0] + 11 * table.shape[0]               # the 8-byte tables in front, each 8-byte aligned
+    table_d = upload_small(np.concatenate([src.view(np.int64), table.view(np.int64), coef8.view(np.int64)]))
+    call('l3c_band_rebuild', ptr(rows, torch.uint8), rows.numel(), ptr(members, torch.uint8), members.numel(), src.ctypes.data,
+         ptr(table_d[:a], torch.int64) if a else None, coef8.ctypes.data, ptr(table_d[b:], torch.int64) if a else None, src.shape[0],
+         table.ctypes.data, ptr(table_d[a:b], torch.int64), table.shape[0], stream())
+    return members
